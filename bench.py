@@ -9,8 +9,10 @@ inputs resident in HBM.  value = generated tokens / wall time of the timed steps
 + decode), whole job over all ranks; N > 1 runs N independent replicas (generation rows are independent,
 SURVEY.md section 8e: "replicas only") plus a DP-sharded retrieval leg with ONE RCCL all-gather.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = the decode layer launch, algorithmic bytes /
-HIP-event time measured live), `cpu_baseline` (the oracle on this box's host cores, bounded sample), `phases`.
+A plain run sets up, warms up, times the steps and prints the headline line; nothing else.  With `--full` the JSON line also
+carries `phases`, `roofline` (dominant kernel = the decode layer launch, algorithmic bytes / HIP-event time measured live),
+`retrieval`, the `configs` block and `cpu_baseline` (the oracle on the host's cores, bounded sample), each measured after
+the timed steps.  `--dump-outputs DIR` writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
@@ -37,7 +39,28 @@ def parse():
     ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed profiles/ ratio instead of two rocprofv3 --pmc passes run now")
     ap.add_argument("--retrieval-proteins", type=int, default=750, help="proteins per rank in the retrieval leg (30 engine batches, ~1.2 s per pass -- a 0.4 s pass of 10 batches moved by a fifth with one host or clock event: the first batch's host packing is the only one the GPU waits for)")
     ap.add_argument("--no-configs", action="store_true", help="skip the BASELINE configs[3] / configs[4] block (batch-32 generation, pair scoring)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the phases, the roofline, the retrieval leg, the "
+                                                        "configs block and the CPU baseline (the --no-* options above apply to this mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the arrays the last timed step returned to DIR/<name>.npy")
     return ap.parse_args()
+
+
+DUMP_LOGITS_SAMPLE = 1 << 22   # elements of the logits record kept by --dump-outputs (16 MB of float32)
+
+
+def dump_outputs(path, toks, lp, logits):
+    """What `UnifiedProCyon.generate(method="greedy")` hands its caller, as .npy files: the generated token ids (float64, exact), their
+    log-probabilities (float32) and the logits record (float32).  The record is [1, 1, tokens, vocab] (131 MB at the default size), so
+    above DUMP_LOGITS_SAMPLE elements a fixed sample of them is written instead: the flat indices
+    np.sort(np.random.default_rng(0).choice(numel, DUMP_LOGITS_SAMPLE, replace=False)), the same for every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "tokens.npy"), toks.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, "log_probs.npy"), lp.float().cpu().numpy())
+    flat = logits.float().cpu().reshape(-1).numpy()
+    if flat.size > DUMP_LOGITS_SAMPLE:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_LOGITS_SAMPLE, replace=False))]
+    np.save(os.path.join(path, "logits.npy"), flat)
 
 
 def relaunch_under_torchrun(a):
@@ -185,14 +208,16 @@ def main():
             phases.update(encode_project_splice_ms=(t1 - t0) * 1e3, prefill_ms=(t2 - t1) * 1e3)
         toks, lp, logits, text = model.generate(inputs, max_len=a.tokens, method="greedy")
         assert toks.shape == (1, 1, a.tokens)
-        return toks
+        return toks, lp, logits
 
     for _ in range(a.warmup):
         one_step()
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        toks = one_step()
+        # the previous step's logits record (pinned host memory, one per call) goes back to the allocator before the next step needs one
+        result = None
+        result = one_step()
     barrier()
     dt = time.perf_counter() - t0
     if dist:
@@ -201,6 +226,21 @@ def main():
         dt = float(t)
     value = world * a.tokens * a.steps / dt
     ctx.sync()   # raises if a cross-workgroup hand-over of the fused decode launches ever hit its watchdog (results would be invalid)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, *result)
+    out = {"metric": f"phenotype-gen tokens/sec ({'ProCyon-Split' if a.geometry == 'split' else 'ProCyon-Full'} greedy generation, end to end)", "value": round(value, 2),
+           "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+           "config": {"workload": (f"configs[1]: ProCyon-Full (ESM2-650M + Llama-3-8B geometry={a.geometry}) bf16 batch=1, " if a.geometry != "split" else
+                                   "configs[0] shape on the GPU: ProCyon-Split (ESM2-150M + Llama-2-7B geometry) bf16 batch=1, ") +
+                                  f"{a.residues}-residue protein, {a.prompt}-token prompt, {a.tokens}-token greedy generation",
+                      "parallelism": f"replicas x{world}" if world > 1 else "single GPU"}}
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out))
+        if dist:
+            td.destroy_process_group()
+        return
 
     # ---- phases + decode-only rate (outside the timed region) --------------------------------------
     one_step(record=True)
@@ -401,14 +441,7 @@ def main():
             configs["config4_fp8_accuracy_damped_model"]["residual_branch_scale"] = 0.25
 
     if rank == 0:
-        out = {"metric": f"phenotype-gen tokens/sec ({'ProCyon-Split' if a.geometry == 'split' else 'ProCyon-Full'} greedy generation, end to end)", "value": round(value, 2),
-               "unit": "tokens/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-               "config": {"workload": (f"configs[1]: ProCyon-Full (ESM2-650M + Llama-3-8B geometry={a.geometry}) bf16 batch=1, " if a.geometry != "split" else
-                                       "configs[0] shape on the GPU: ProCyon-Split (ESM2-150M + Llama-2-7B geometry) bf16 batch=1, ") +
-                                      f"{a.residues}-residue protein, {a.prompt}-token prompt, {a.tokens}-token greedy generation",
-                          "parallelism": f"replicas x{world}" if world > 1 else "single GPU"},
-               "phases": {k: round(v, 3) for k, v in phases.items()}, "roofline": roofline, "retrieval": retrieval}
+        out.update(phases={k: round(v, 3) for k, v in phases.items()}, roofline=roofline, retrieval=retrieval)
         if configs is not None:
             out["configs"] = configs
         if decode_curve is not None:

@@ -669,7 +669,7 @@ def test_bench_line_contract_and_internal_consistency():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-configs", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-configs", "--no-cpu-baseline",
                           "--retrieval-proteins", "25"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -687,3 +687,35 @@ def test_bench_line_contract_and_internal_consistency():
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
     assert abs(r["achieved"] - r["bytes_per_launch"] / 1e9 / (r["avg_launch_us"] / 1e6)) < 0.01 * r["achieved"]
     assert d["retrieval"]["proteins_per_s"] > 0 and d["retrieval"]["n_proteins"] == 25
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py` without --full: the headline line alone (no phases / roofline / retrieval / configs / CPU baseline), and
+    --dump-outputs writes what the last timed step's `generate` returned -- token ids, log-probabilities, a seeded sample of the
+    logits record -- as float .npy files within 64 MB."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    tokens = 64                                            # 64 x 128263 logits: above the dump's sample size, so the sample is taken
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--tokens", str(tokens),
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "tokens/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - tokens) < 0.02 * tokens, (d["value"], d["ms_per_step"])
+    for k in ("phases", "roofline", "retrieval", "configs", "cpu_baseline"):
+        assert k not in d, k
+    files = {p.name: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert set(files) == {"tokens.npy", "log_probs.npy", "logits.npy"}, set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(p.stat().st_size for p in tmp_path.glob("*.npy")) <= 64 << 20
+    t = files["tokens.npy"]
+    assert t.shape == (1, 1, tokens) and np.array_equal(t, np.round(t)) and t.min() >= 0 and t.max() < 128263
+    assert np.isfinite(files["log_probs.npy"]).all()
+    assert files["logits.npy"].shape == (1 << 22,) and np.isfinite(files["logits.npy"]).all()

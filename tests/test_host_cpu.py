@@ -269,3 +269,27 @@ def test_bench_live_pmc_declines_without_a_profiler(monkeypatch, tmp_path):
     v = next(iter(r["kernels"].values()))
     assert v["hbm_bytes_per_launch"] == int((2 * 1000.0 + 10.0) * 1024) and v["launches"] == [4, 4]
     assert abs(v["ratio"] - (2 * 1000.0 + 10.0) * 1024 / 2_000_000) < 1e-3
+
+
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_logits_sample(tmp_path):
+    """bench.py --dump-outputs: token ids as exact float64, log-probabilities and logits as float32, and above DUMP_LOGITS_SAMPLE
+    elements the same seeded sample of the logits record on every call (two builds are compared output for output)."""
+    import importlib, os, sys
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    bench = importlib.import_module("bench")
+    toks = torch.randint(0, 128263, (1, 1, 40))
+    lp = -torch.rand(1)
+    logits = torch.randn(1, 1, 40, 128263).bfloat16()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), toks, lp, logits)
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("tokens", "log_probs", "logits")}
+    assert a["tokens"].dtype == np.float64 and np.array_equal(a["tokens"], toks.numpy())
+    assert a["log_probs"].dtype == np.float32 and np.array_equal(a["log_probs"], lp.numpy())
+    assert a["logits"].dtype == np.float32 and a["logits"].shape == (bench.DUMP_LOGITS_SAMPLE,)
+    assert np.isin(a["logits"], logits.float().numpy()).all()
+    assert np.array_equal(a["logits"], np.load(tmp_path / "b" / "logits.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+    small = torch.randn(1, 1, 4, 1000).bfloat16()                 # below the sample size: the whole record, in order
+    bench.dump_outputs(str(tmp_path / "c"), toks, lp, small)
+    assert np.array_equal(np.load(tmp_path / "c" / "logits.npy"), small.float().reshape(-1).numpy())

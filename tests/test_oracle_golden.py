@@ -1,5 +1,6 @@
 """CPU: the oracle (oracle/) against the golden fixtures produced from the reference's own
 extracted functions and the container's HF Llama/ESM (tests/golden/make_golden.py)."""
+import pytest
 import torch
 
 from conftest import assert_bf16_close, rel_err
@@ -9,6 +10,13 @@ from oracle import procyon_ref as PR
 from procyon_amd import synth
 
 TINY = dict(vocab=300, d=128, n_layers=2, n_heads=8, n_kv_heads=2, ffn=256)
+
+
+@pytest.fixture(autouse=True)
+def native_cpu_gemm(monkeypatch):
+    """The oracle on torch's own CPU GEMM, as g5 / g6 were recorded (make_golden.native_cpu_gemm): oneDNN's bf16 kernels sum in an
+    order that depends on the host's ISA and thread count, which moved the full-width layers past the 1-ulp bar on other hosts."""
+    monkeypatch.setattr(torch.backends.mkldnn, "enabled", False)
 
 
 def test_g1_split(golden):

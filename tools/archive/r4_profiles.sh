@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r4; mkdir -p $O
 cd $R
 # 1. the bench line + its kernel table
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 python tools/prof_summary.py $O/prof_bench > $O/bench_kernel_stats.csv 2>/dev/null; rm -rf $O/prof_bench
 # 2. the single-protein encoder and the single-prompt prefill: kernel tables + MFMA counters
 for t in esm1 prefill1; do

@@ -5,8 +5,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r6e; mkdir -p $O
 cd $R
 # 1. the bench line + its kernel table
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/prof_bench -o b -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 python tools/prof_summary.py $O/prof_bench > $O/bench_kernel_stats.csv 2>/dev/null; rm -rf $O/prof_bench
 # 2. the single-protein encoder and the single-prompt prefill: kernel tables + MFMA counters
 for t in esm1 prefill1; do
@@ -46,8 +46,8 @@ for pr in stream_rows stream_cus; do [ -x tools/probes/$pr ] || /opt/rocm/bin/hi
 ./tools/probes/stream_cus > $O/probe_stream_cus.log 2>&1
 ls -la $O
 # 9. round 6: ProCyon-Split (Llama-2-7B geometry) -- the bench line, its kernel table, HBM traffic of decode_step_mha_kernel, bit-identity + in-kernel stamps
-python bench.py --geometry split --steps 5 --warmup 2 > $O/bench_split.json 2> $O/bench_split.err
-rocprofv3 --kernel-trace --stats -d $O/prof_split -o b -- python bench.py --geometry split --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+python bench.py --full --geometry split --steps 5 --warmup 2 > $O/bench_split.json 2> $O/bench_split.err
+rocprofv3 --kernel-trace --stats -d $O/prof_split -o b -- python bench.py --full --geometry split --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 python tools/prof_summary.py $O/prof_split > $O/split_kernel_stats.csv 2>/dev/null; rm -rf $O/prof_split
 for c in FETCH_SIZE WRITE_SIZE; do
   GEO=split rocprofv3 --pmc $c --kernel-trace -d $O/pmc_mha_$c -o p --output-format csv -- python tools/pmc_decode.py > /dev/null 2>&1
