@@ -499,7 +499,8 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       try_layer = false;   // geometry not covered: the same for every layer
     }
     int qkv_splits = 0;   // batched: the attention adds up the K-split partial sums of ITS rows (no finish launch); PCY_DISABLE=attn_qkv_finish: separate launch
-    if (batched && sk_ws && !try_ao && !qkv_finish_launch()) g.defer_finish = &qkv_splits;
+    // (up to 32 rows: above, the GEMV runs in 32-row passes that share the workspace -- the finish is a launch per pass, same bits)
+    if (batched && B <= 32 && sk_ws && !try_ao && !qkv_finish_launch()) g.defer_finish = &qkv_splits;
     pcy_launch_gemv(s, g);
     if (qkv_splits > 1) { t.qkv_partials = sk_ws; t.qkv_splits = qkv_splits; }
     if (!(try_ao && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err,

@@ -1197,6 +1197,14 @@ void pcy_launch_gemv(hipStream_t s, const PcyGemvArgs& a00) {
   // batches from pcy_mfma_min_batch() on MFMA, 32 rows per pass over the weights (x already normalised by the caller: the fused
   // RMSNorm prologue is a feature of the streaming kernel)
   if (!a0.force_stream && (a0.B >= pcy_mfma_min_batch() || a0.force_mfma) && a0.K % 128 == 0 && a0.rms_w == nullptr && (a0.ldx % 8) == 0) {
+    // more than 32 rows: several passes, each with its own row count and the same K-split workspace.  Partial sums left for the consumer
+    // (defer_finish: laid out [split][B][N] for the WHOLE batch) would be overwritten by the next pass, and the finish + RMSNorm fusion
+    // writes next_xn from row 0 of the pass -- so the finish runs per pass and the norm is left to the caller
+    if (a0.B > 32) {
+      if (a0.defer_finish) *a0.defer_finish = 0;
+      a0.defer_finish = nullptr;
+      a0.next_rms_w = nullptr; a0.next_xn = nullptr; a0.fused_next = nullptr;
+    }
     for (int b0 = 0; b0 < a0.B; b0 += 32) {
       PcyGemvArgs a = a0;
       a.B = (a0.B - b0) < 32 ? (a0.B - b0) : 32;

@@ -224,24 +224,37 @@ def test_llama8b_full_depth_left_padded_rows_compat_mode(llama, golden):
     assert max(e_hr) < 0.12        # a wrong position / a dropped pad slot gives O(1)
 
 
-def _rows_compat_run(llama, ids, mask, toks, rows, teacher):
+def _rows_compat_run(llama, ids, mask, toks, rows, teacher, keep_rows=None, copy_of=None):
     """prefill (left-padded rows, compat mode) + teacher-forced cached steps of a B-row batch; rows in `teacher` are fed the fixture's tokens
-    (toks [nstep, len(teacher)]), every other row its own argmax.  -> logits [nstep, B, V] fp32 (CPU)"""
+    (toks [nstep, len(teacher)]), every other row its own argmax.  -> logits [nstep, B, V] fp32 (CPU); with `keep_rows` only those rows
+    [nstep, len(keep_rows), V] (the argmax of the others is taken on the device).  `copy_of` [B] (rows holding the same prompt and the same
+    tokens): the logits of every step and the whole K / V cache of row b must be BIT-identical to those of row copy_of[b] (checked on the device)."""
     from procyon_amd.engine import GenState
     B, T = ids.shape
     nstep = toks.shape[0]
     cache = llama.new_cache(B, T + nstep + 1)
     logits, _ = llama.prefill(llama.embed_tokens(ids), mask, cache, "last")
-    got = [logits.float().cpu()]
+    ksel = None if keep_rows is None else torch.tensor(keep_rows, device=logits.device)
+    csel = None if copy_of is None else torch.tensor(copy_of, device=logits.device)
+    host = lambda lg: lg.float().cpu() if ksel is None else lg[ksel].float().cpu()
+    same = lambda lg: csel is None or torch.equal(lg, lg[csel])
+    assert same(logits), "prefill logits of copies differ"
+    got = [host(logits)]
     st = GenState(B, LLAMA["vocab"], nstep + 1, "cuda")            # keep = None: compat mode (every cached slot is attended)
     tsel = torch.tensor(teacher)
     for s in range(1, nstep):
-        nxt = got[-1].argmax(-1).to(torch.int32)
+        if ksel is None:
+            nxt = got[-1].argmax(-1).to(torch.int32)
+        else:
+            nxt = (logits if s == 1 else st.logits).float().argmax(-1).cpu().to(torch.int32)
         nxt[tsel] = toks[s - 1].to(torch.int32)
         st.pos.fill_(T + s - 1)
         st.next_tok.copy_(nxt)
         llama.decode(cache, st, B)
-        got.append(st.logits.float().cpu())
+        assert same(st.logits), f"step {s}: logits of copies differ"
+        got.append(host(st.logits))
+    if csel is not None:
+        assert torch.equal(cache.k, cache.k[:, csel]) and torch.equal(cache.v, cache.v[:, csel]), "K / V rows of copies differ"
     return torch.stack(got)
 
 
@@ -279,14 +292,39 @@ def test_llama8b_full_depth_ten_ragged_rows_compat_mode(llama, golden, monkeypat
     /root/reference/procyon/evaluate/framework/procyon.py:72-76) held to the ORACLE at full depth, not only to its launch-per-stage twin:
     fixture f7 -- ten ragged left-padded rows (0 .. 27 pad slots of 64), prefill with the mask and positions arange(T), 16 teacher-forced
     cached steps with no mask at position = cache length (Q1 / Q2), bf16 oracle + the same procedure in fp32.  10 rows decode on the
-    mid-batch step (pcy_decode_mb.hip); the first 8 / 5 rows as batches of their own on the small-batch step (pcy_decode_nb.hip: so far held
-    to the oracle at 2 rows only).  Per (row, step): err(HIP, fp32) <= 1.25 x err(oracle, fp32); argmax on every clear-margin (row, step)."""
+    batched launches (skinny-MFMA GEMVs; the mid-batch step, pcy_decode_mb.hip, is opt-in through PCY_MB_MAX, unset here); the first 8 / 5
+    rows as batches of their own on the small-batch step (pcy_decode_nb.hip: so far held to the oracle at 2 rows only).  Per (row, step):
+    err(HIP, fp32) <= 1.25 x err(oracle, fp32); argmax on every clear-margin (row, step)."""
     monkeypatch.delenv("PCY_DISABLE", raising=False)
     monkeypatch.setenv("PCY_NB_MAX", "8")        # (8 rows default to the batched launches since round 6; here the fused step is what is checked)
     g = golden("f7_llama8b_rows10_T64")
     ids, mask, toks = g["ids"].long()[:nrows], g["mask"].float()[:nrows], g["tokens"].long()[:, :nrows]
     got = _rows_compat_run(llama, ids, mask, toks, nrows, list(range(nrows)))
     _rows_compat_check(f"fulldepth/llama8b_ragged_rows_compat_B{nrows}", got, g, list(range(nrows)), min_clear=nrows)
+
+
+# the f7 rows tiled into batches of more than 32 rows: row i holds f7 row (i - s) % 10, so rows [s, s + 10) -- the copies held to the oracle --
+# straddle the 31 / 32 boundary (33: f7 row 9 alone in the 1-row remainder pass; 40: f7 rows 2..9 in the 8-row remainder pass)
+_OVER_32 = {33: 23, 40: 30, 160: 27}
+
+
+@pytest.mark.parametrize("B", sorted(_OVER_32))
+def test_llama8b_full_depth_rows_over_32(llama, golden, monkeypatch, B):
+    """Decode steps above 32 rows (the evaluation plugin's default: 16 prompts x beam 10 = 160 rows) at full depth: fixture f7's ten ragged
+    rows tiled into a B-row batch, every row teacher-forced with its f7 row's tokens.  The copies in rows [s, s + 10) against the bf16 oracle
+    and the fp32 truth at the bars of the ten-row test (err(HIP, fp32) <= 1.25 x err(oracle, fp32), argmax on every clear-margin (row, step));
+    every other copy of an f7 row -- in another full 32-row pass or in the remainder pass -- BIT-identical to the first one (logits of every
+    step, the whole K / V cache): a row's bits do not depend on where in the batch it sits."""
+    monkeypatch.delenv("PCY_DISABLE", raising=False)
+    g = golden("f7_llama8b_rows10_T64")
+    s = _OVER_32[B]
+    perm = [(i - s) % 10 for i in range(B)]
+    first = {}
+    copy_of = [first.setdefault(p, i) for i, p in enumerate(perm)]
+    ids, mask, toks = g["ids"].long()[perm], g["mask"].float()[perm], g["tokens"].long()[:, perm]
+    rows = list(range(s, s + 10))
+    got = _rows_compat_run(llama, ids, mask, toks, B, list(range(B)), keep_rows=rows, copy_of=copy_of)
+    _rows_compat_check(f"fulldepth/llama8b_rows_over_32_B{B}", got, g, [perm[i] for i in rows], min_clear=10)
 
 
 def test_llama8b_full_depth_config3_ragged_batch32(llama, golden, monkeypatch):

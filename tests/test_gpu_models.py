@@ -377,7 +377,7 @@ def test_batched_decode_finish_norm_fusion_bit_identical(monkeypatch):
     kw = dict(vocab=4096, d=4096, n_layers=2, n_heads=32, n_kv_heads=8, ffn=14336)
     eng = LlamaEngine(synth.llama_state_dict(**kw), LlamaConfig(**kw, max_pos=256))
     T, N = 33, 5
-    for B in (7, 20):
+    for B in (7, 20, 40, 64):     # (above 32 rows: 32-row GEMV passes, the finish not fused with the norm)
         torch.manual_seed(B)
         emb = (torch.randn(B, T, 4096) * 0.02).to(BF).cuda()
 
@@ -404,13 +404,13 @@ def test_batched_decode_finish_norm_fusion_bit_identical(monkeypatch):
 def test_batched_decode_qkv_finish_in_attention_bit_identical(monkeypatch):
     """Batched decode: the K-split partial sums of the qkv projection are added up by the attention workgroup that needs them
     (attn_dec_splitk_kernel, default) instead of by a finish launch (PCY_DISABLE=attn_qkv_finish).  Same split order, same rounding: logits,
-    tokens and the appended K/V rows are bit-identical, eager and under graph replay; batches of 5..32 rows incl. a ragged keep mask."""
+    tokens and the appended K/V rows are bit-identical, eager and under graph replay; batches of 5..64 rows incl. a ragged keep mask."""
     from procyon_amd import synth
     from procyon_amd.engine import GenState, LlamaConfig, LlamaEngine
     kw = dict(vocab=4096, d=4096, n_layers=2, n_heads=32, n_kv_heads=8, ffn=14336)
     eng = LlamaEngine(synth.llama_state_dict(**kw), LlamaConfig(**kw, max_pos=256))
     T, N = 40, 4
-    for B in (5, 20, 32):
+    for B in (5, 20, 32, 40, 64):     # (above 32 rows: 32-row GEMV passes, the qkv finish as its own launch)
         torch.manual_seed(B)
         emb = (torch.randn(B, T, 4096) * 0.02).to(BF).cuda()
 

@@ -5,6 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from beam_oracle import assert_beam_matches_oracle
 from conftest import alt_accumulation, parity_bar, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -97,25 +98,7 @@ def test_generate_beam_matches_oracle(env):
                                           beam_size=4, beam_group_size=2, diversity_penalty=0.8, trace=trace)
     tokens, scores, logits, text = m.generate(_inputs(m, env["prot"], instr, [[0]], text_slots=[[]]), max_len=6, method="beam",
                                               beam_size=4, beam_group_size=2, diversity_penalty=0.8)
-    assert tokens.shape == t_ref.shape and scores.shape == s_ref.shape
-    # step 0 is identical up to bf16 noise: same top-2 per group from beam 0 (before any re-indexing every row of a prompt
-    # holds the same logits, so this comparison does not depend on the beams' order)
-    assert rel_err(logits[0, 0, 0], lg_ref[0, 0, 0]) < 1e-2   # ESM + pool + projector + 2 Llama layers deep
-    noise = float((logits[0, 0, 0].float() - lg_ref[0, 0, 0].float()).abs().max())
-    if torch.equal(tokens, t_ref):
-        assert torch.allclose(scores, s_ref, atol=0.3)
-    else:
-        # A divergence must come from a near-tie among the oracle's own candidate scores at the FIRST step that differs: some
-        # adjacent pair of its top-(g+1) candidates (bf16 log-softmax + fp32 running score) lies within the logits noise (x4,
-        # plus one bf16 ulp of the score, the granularity of the log-softmax) -- otherwise the engine picked a clear loser.
-        first = int((tokens != t_ref).any(0).any(0).nonzero()[0])
-        gaps = []
-        for (step, b, k, top) in trace:
-            if step == first:
-                ulp = 2.0 ** -8 * float(top.abs().max())
-                gaps += [(float(g_), ulp) for g_ in (top[:-1] - top[1:])]
-        assert gaps and any(g_ <= 4 * noise * (first + 1) + ulp for g_, ulp in gaps), (first, noise, gaps)
-        assert torch.equal(tokens[..., :first], t_ref[..., :first])
+    assert_beam_matches_oracle(tokens, scores, logits, t_ref, s_ref, lg_ref, trace)   # (tie-aware: tests/beam_oracle.py)
 
 
 @pytest.mark.parametrize("beam,group,max_len", [(4, 2, 6), (5, 1, 19), (6, 3, 9)])
