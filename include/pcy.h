@@ -37,9 +37,13 @@ enum { PCY_EPI_STORE = 0, PCY_EPI_RESID = 1, PCY_EPI_GELU_ERF = 2, PCY_EPI_GELU_
 enum { PCY_POOL_MEAN = 0, PCY_POOL_MEAN_CORRECTED = 1, PCY_POOL_MAX = 2 };
 
 int pcy_abi_version(void);
-/* Test instrumentation: number of GEMM launches that went to kernel family `kind` since the library was loaded
- * (0: 128x128 tiles, 1: 64x64, 2: 256x256, 3: 256x256 persistent (ESM fc1 + GELU), 4: split-K, 5: fp8 256x256).  Parity
- * tests use it to assert that they reach the kernel they claim to test. */
+/* Test instrumentation: number of launches that went to kernel family `kind` since the library was loaded.  GEMMs -- 0: 128x128 tiles,
+ * 1: 64x64, 2: 256x256, 3: 256x256 persistent (ESM fc1 + GELU), 4: split-K, 5: fp8 256x256, 8: mid tiles; 6: single-pass ESM attention;
+ * 9: ESM layers through a captured graph.  Decode steps, ONE count per step enqueued outside a graph replay, by what served it --
+ * 7: one row, all layers in one launch, grouped-query geometry; 10: the same, multi-head geometry; 11: one row, a launch per layer;
+ * 12: small-batch step (2..8 rows); 13: mid-batch step (9..32 rows, PCY_MB_MAX); 14: launch per stage, streaming GEMVs;
+ * 15: launch per stage, MFMA GEMVs.  A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
+ * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
 const char* pcy_last_error(void);
 /* stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for the default stream */

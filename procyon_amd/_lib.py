@@ -12,7 +12,12 @@ EPI_STORE, EPI_RESID, EPI_GELU_ERF, EPI_GELU_ESM, EPI_SWIGLU = range(5)
 POOL_MEAN, POOL_MEAN_CORRECTED, POOL_MAX = range(3)
 ABI_VERSION = 10
 # pcy_debug_dispatch_count kinds
-DISPATCH_GEMM_128, DISPATCH_GEMM_64, DISPATCH_GEMM_BIG, DISPATCH_GEMM_BIG_PERSIST, DISPATCH_GEMM_SPLITK, DISPATCH_GEMM_FP8, DISPATCH_ATTN_FAST, _DISPATCH_UNUSED_7, DISPATCH_GEMM_MID, DISPATCH_ESM_GRAPH = range(10)
+(DISPATCH_GEMM_128, DISPATCH_GEMM_64, DISPATCH_GEMM_BIG, DISPATCH_GEMM_BIG_PERSIST, DISPATCH_GEMM_SPLITK, DISPATCH_GEMM_FP8, DISPATCH_ATTN_FAST,
+ DISPATCH_DEC_STEP_GQA, DISPATCH_GEMM_MID, DISPATCH_ESM_GRAPH, DISPATCH_DEC_STEP_MHA, DISPATCH_DEC_LAYER, DISPATCH_DEC_STEP_NB, DISPATCH_DEC_STEP_MB,
+ DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA) = range(16)
+# which way a decode step was served (one count per step enqueued outside a graph replay; pcy_internal.h PCY_DISPATCH_DEC_*)
+DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STEP_MHA, layer=DISPATCH_DEC_LAYER, step_nb=DISPATCH_DEC_STEP_NB,
+                       step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
 
 vp = C.c_void_p
 i32 = C.c_int32

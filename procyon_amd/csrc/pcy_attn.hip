@@ -1184,12 +1184,14 @@ bool pcy_launch_decode_layer(hipStream_t s, const PcyDecAttnArgs& a, const PcyAt
 bool pcy_launch_decode_step(hipStream_t s, const PcyDecAttnArgs& a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc, const PcyDecodeStepArgs& st,
                             int n_cu, const unsigned* step_epoch) {
   if (a.B != 1 || a.dh != 128 || a.dbg || n_cu < 256 || st.n_layers < 1) return false;
-  if (pcy_launch_decode_mha(s, a, p, mc, &st, n_cu, step_epoch, a.xflags)) return true;
+  if (pcy_launch_decode_mha(s, a, p, mc, &st, n_cu, step_epoch, a.xflags)) { ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_MHA]; return true; }
+  bool ok = false;
   switch (a.H / a.Hkv) {
-    case 1: return launch_decode_layer<128, 1>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st);
-    case 2: return launch_decode_layer<128, 2>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st);
-    case 4: return launch_decode_layer<128, 4>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st);
-    case 8: return launch_decode_layer<128, 8>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st);
+    case 1: ok = launch_decode_layer<128, 1>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st); break;
+    case 2: ok = launch_decode_layer<128, 2>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st); break;
+    case 4: ok = launch_decode_layer<128, 4>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st); break;
+    case 8: ok = launch_decode_layer<128, 8>(s, a, p, mc, step_epoch, a.xflags, n_cu, &st); break;
   }
-  return false;
+  if (ok) ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_GQA];
+  return ok;
 }

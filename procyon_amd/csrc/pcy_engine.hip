@@ -52,7 +52,7 @@ struct pcy_ctx {
   static constexpr int GRAPH_KEY_N = 19;
   const void* graph_key[GRAPH_KEY_N] = {};
   int graph_B = 0;
-  int graph_mode = 0;
+  long long graph_mode = 0;
   int graph_kind = 0;                 // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps)
   int n_cu = 0;
   // sticky error word: a cross-workgroup hand-over inside a launch hit its watchdog.  PINNED HOST memory (device-visible): the
@@ -64,7 +64,7 @@ struct pcy_ctx {
   uint32_t* mc_tags = nullptr;
   const void* mc_tags_model = nullptr;
   size_t mc_tags_words = 0;
-  int mc_tags_mode = -1;
+  long long mc_tags_mode = -1;
   uint64_t layers_fp = 0;              // fingerprint of the weight pointers dev_layers was built from
   PcyLayerWeightsDev* dev_layers = nullptr;   // device copy of the layers' weight pointers (decode_step_kernel)
   // small-batch decode step (pcy_decode_nb.hip): hand-over slots and tag counter PER BATCH SIZE (a slot is rewritten in every step of its
@@ -222,12 +222,20 @@ int decode_xmin() {   // cached keys from which the decode attention splits its 
 // prefetch) and the flag hops.  PCY_MB_MAX=<rows> (9..32) runs it up to that batch size: tests, tools/bench_decode_mb.py.
 int decode_mb_max_rows() {
   const char* e = getenv("PCY_MB_MAX");
-  return e ? atoi(e) : 0;
+  const int v = e ? atoi(e) : 0;
+  return v < 0 ? 0 : v > 32 ? 32 : v;
 }
 int decode_nb_max_rows();
-int decode_mode() {
+int decode_mode_lo();
+// (PCY_MB_MAX clamped to 0..32 where it is read; PCY_NB_MAX in bits of its own above the 32 others: `& 3` took 2 for 6 and 3 for 7, and a test
+// that switches them inside one process would have been handed the other value's captured graph and hand-over buffers)
+long long decode_mode() {
+  const int nb = decode_nb_max_rows();
+  return ((long long)(nb < 0 ? 0 : nb) << 32) | (long long)(unsigned)decode_mode_lo();
+}
+int decode_mode_lo() {
   return (pcy_off("kv_permute") ? 2048 : 0) | (attn_o_enabled() ? 2 : 0) | (decode_layer_enabled() ? 32 : 0) | (decode_step_enabled() ? 64 : 0) | (qkv_finish_launch() ? 128 : 0) |
-         (pcy_off("lds_prefetch") ? 256 : 0) | (decode_nb_enabled() ? 512 : 0) | (decode_nb_step_enabled() ? 1024 : 0) | (decode_mb_step_enabled() ? 4096 : 0) | (decode_mb_max_rows() << 16) | ((decode_nb_max_rows() & 3) << 28) |
+         (pcy_off("lds_prefetch") ? 256 : 0) | (decode_nb_enabled() ? 512 : 0) | (decode_nb_step_enabled() ? 1024 : 0) | (decode_mb_step_enabled() ? 4096 : 0) | (decode_mb_max_rows() << 16) |
          (int)((((unsigned)decode_xmin() * 2654435761u) ^ ((unsigned)decode_xmin_nb(2) * 40503u) ^ ((unsigned)decode_xmin_nb(4) * 69069u)) & 0x3fu) << 22;
 }
 constexpr int AO_MAX_LAYERS = 128, AO_FLAGS = 64;
@@ -411,6 +419,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       bp.trace = g_mc_trace + (size_t)128 * 256 * 16;
     }
     step_done = pcy_launch_decode_step_nb(s, c->device, t, bp, mc, sa, c->n_cu, c->ao_sync, B, decode_xmin_nb(B));
+    if (step_done) ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_NB];
   }
   if (try_layer && decode_step_enabled() && c->dev_layers) {   // all layers in one launch
     PcyDecAttnArgs t{};
@@ -431,7 +440,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
       bp.trace = g_mc_trace + (size_t)128 * 256 * 16;
     }
-    step_done = pcy_launch_decode_step(s, t, bp, mc, sa, c->n_cu, c->ao_sync);
+    step_done = pcy_launch_decode_step(s, t, bp, mc, sa, c->n_cu, c->ao_sync);   // (counts its own kind: grouped-query or multi-head)
   }
   int xn_ready = 0;   // batched path: xn = RMSNorm(x) of the NEXT projection already produced by a fused finish kernel
   if (mb_step) {
@@ -449,7 +458,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       ma.trace = g_mc_trace + (size_t)128 * 256 * 16;
     }
     pcy_launch_rmsnorm(s, x, (const bf16_t*)m->layers[0].ln1, xn, B, d, m->rms_eps, m->rms_cast);
-    if (pcy_launch_decode_step_mb(s, c->device, ma, c->n_cu)) { step_done = true; xn_ready = 1; }
+    if (pcy_launch_decode_step_mb(s, c->device, ma, c->n_cu)) { step_done = true; xn_ready = 1; ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_MB]; }
   }
   for (int l = 0; l < (step_done ? 0 : m->n_layers); ++l) {
     const pcy_llama_layer& L = m->layers[l];
@@ -495,9 +504,13 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       mc.x = x; mc.x_out = x; mc.ln2 = (const bf16_t*)L.ln2; mc.wgu = (const bf16_t*)L.wgu; mc.wdown = (const bf16_t*)L.wdown;
       mc.d = d; mc.F = F; mc.rms_eps = m->rms_eps; mc.rms_cast = m->rms_cast;
       mc.act_tag = tags; mc.epoch = c->ao_sync + 1; mc.err = c->xwg_err;
-      if (pcy_launch_decode_layer(s, t, bp, mc, c->n_cu, c->ao_sync, c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS)) continue;
+      if (pcy_launch_decode_layer(s, t, bp, mc, c->n_cu, c->ao_sync, c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS)) {
+        if (l == 0) ++g_pcy_dispatch[PCY_DISPATCH_DEC_LAYER];   // (one count per step)
+        continue;
+      }
       try_layer = false;   // geometry not covered: the same for every layer
     }
+    if (l == 0) ++g_pcy_dispatch[batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
     int qkv_splits = 0;   // batched: the attention adds up the K-split partial sums of ITS rows (no finish launch); PCY_DISABLE=attn_qkv_finish: separate launch
     // (up to 32 rows: above, the GEMV runs in 32-row passes that share the workspace -- the finish is a launch per pass, same bits)
     if (batched && B <= 32 && sk_ws && !try_ao && !qkv_finish_launch()) g.defer_finish = &qkv_splits;

@@ -121,8 +121,21 @@ void pcy_launch_gemm(hipStream_t s, const PcyGemmArgs& a);
 // CAPTURE a chain of launches call it first, so that the build is not recorded into the graph
 void pcy_gemm_prepare(hipStream_t s);
 // launch counters per kernel family (pcy_debug_dispatch_count)
+// PCY_DISPATCH_DEC_*: which way enqueue_decode served a decode step -- ONE count per enqueued step, taken where the choice is final (after a
+// fused launcher returned true, or at the first layer of the per-layer loop).  Every fused step may decline at launch time (LDS size for the
+// cache length, co-residency, a missing sync buffer) and the step then runs launch by launch with the same bits: only these counters tell a
+// test which of the two it compared.  A step replayed from a captured graph does not pass through enqueue_decode (the capture counts once).
 enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BIG = 2, PCY_DISPATCH_GEMM_BIG_PERSIST = 3,
-       PCY_DISPATCH_GEMM_SPLITK = 4, PCY_DISPATCH_GEMM_FP8 = 5, PCY_DISPATCH_ATTN_FAST = 6, PCY_DISPATCH_UNUSED_7 = 7, PCY_DISPATCH_GEMM_MID = 8, PCY_DISPATCH_ESM_GRAPH = 9, PCY_DISPATCH_N = 10 };
+       PCY_DISPATCH_GEMM_SPLITK = 4, PCY_DISPATCH_GEMM_FP8 = 5, PCY_DISPATCH_ATTN_FAST = 6,
+       PCY_DISPATCH_DEC_STEP_GQA = 7,      // one row, all layers in one launch, grouped-query geometry (decode_step_kernel)
+       PCY_DISPATCH_GEMM_MID = 8, PCY_DISPATCH_ESM_GRAPH = 9,
+       PCY_DISPATCH_DEC_STEP_MHA = 10,     // one row, all layers in one launch, multi-head geometry (decode_step_mha_kernel)
+       PCY_DISPATCH_DEC_LAYER = 11,        // one row, one launch per decoder layer (either geometry)
+       PCY_DISPATCH_DEC_STEP_NB = 12,      // 2..8 rows, all layers in one launch (pcy_decode_nb.hip)
+       PCY_DISPATCH_DEC_STEP_MB = 13,      // 9..32 rows, all layers in one launch (pcy_decode_mb.hip)
+       PCY_DISPATCH_DEC_LOOP_STREAM = 14,  // launch-per-stage loop, streaming GEMVs
+       PCY_DISPATCH_DEC_LOOP_MFMA = 15,    // launch-per-stage loop, skinny-MFMA GEMVs (`batched`)
+       PCY_DISPATCH_N = 16 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
 
 // per-row symmetric e4m3 quantisation: scale[r] = smallest power of two with amax|x[r,:]| / scale <= 448 (1 for an all-zero row), q = e4m3_rne(x / scale)
@@ -246,7 +259,7 @@ bool pcy_launch_decode_step(hipStream_t s, const PcyDecAttnArgs& a, const PcyAtt
                             int n_cu, const unsigned* step_epoch);
 bool pcy_launch_decode_layer(hipStream_t s, const PcyDecAttnArgs& a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc, int n_cu,
                              const unsigned* step_epoch, unsigned* xflags);
-// The same for the multi-head geometry (pcy_decode_mha.hip: 32 kv heads of 128, d 4096, 7168 < ffn <= 14336 -- Llama-2-7B / ProCyon-Split):
+// The same for the multi-head geometry (pcy_decode_mha.hip: 32 kv heads of 128, d 4096, 8192 < ffn <= 12288, ffn % 256 == 0 -- Llama-2-7B / ProCyon-Split):
 // one layer (st == nullptr) or all layers in one launch; tried first by the two launchers above.  The launch-per-stage twin's attention must
 // cut its output into pcy_decode_mha_ds() columns per workgroup (the summation order of P.V).
 bool pcy_decode_mha_covers(int d, int H, int Hkv, int dh, int F, int n_cu);

@@ -22,7 +22,12 @@ Round 4: the same runs on DAMPED weights (`synth.damp_residual_branches`, residu
 f3_llama8b_damped_T64.npz, f4_esm650m_damped_1024.npz -- where the bf16 oracle agrees with the fp32 truth on (nearly) every argmax, so the
 GPU test can assert token agreement between the HIP path and the bf16 ORACLE itself and a bound on err(HIP, oracle_bf16).
 
-    python tests/golden/make_fulldepth.py [llama] [esm] [llama_damped] [esm_damped] [llama_leftpad] [llama256] [split] [rows10] [config3] [config4]
+ProCyon-Split's decoder (Llama-2-7B geometry) in bf16 at full depth: s1_llama2_7b_T{128,704}_N128.npz (`split1`: one row, 128 cached steps, the
+longer prompt crossing the 768-key split of the decode attention) and s2_llama2_7b_rows20_T64.npz (`split_rows20`: twenty ragged left-padded rows
+in compat mode) -- tests/test_gpu_fulldepth_split.py.  Both print their clear-margin counts (the tests need >= 16 steps / >= nrows pairs); about
+six minutes on 8 cores, 14 GB of bf16 weights + one fp32 layer.
+
+    python tests/golden/make_fulldepth.py [llama] [esm] [llama_damped] [esm_damped] [llama_leftpad] [llama256] [split] [rows10] [config3] [config4] [split1] [split_rows20]
 """
 from __future__ import annotations
 
@@ -407,6 +412,108 @@ def make_split():
          top_ids=top.indices.to(torch.int32), top_vals=top.values)
 
 
+def _clear_count(lb, lf, top_f):
+    """(row, step) pairs whose fp32 top-2 margin clears 4 x the bf16 logit noise (rms of oracle_bf16 - fp32 over ALL columns here; the tests
+    take the rms over the fixture's columns): the condition the argmax assertions of the GPU tests speak on, a property of the fixture alone."""
+    noise = (lb.float() - lf).pow(2).mean(-1).sqrt()
+    return int(((top_f.values[..., 0] - top_f.values[..., 1]) >= 4.0 * noise).sum())
+
+
+def _pack_split1(T, ids, toks, lb, lf, hb, hf, stride):
+    nstep, V = lb.shape
+    cols = set(range(0, V, stride))
+    for s in range(nstep):
+        cols |= set(lf[s].topk(8).indices.tolist()) | set(lb[s].float().topk(8).indices.tolist())
+    cols = torch.tensor(sorted(cols))
+    top_f, top_b = lf.topk(8, dim=-1), lb.float().topk(8, dim=-1)
+    err_full = torch.tensor([rel(lb[s].float(), lf[s]) for s in range(nstep)])
+    noise = (lb[:, cols].float() - lf[:, cols]).pow(2).mean(-1).sqrt()
+    clear = int(((top_f.values[:, 0] - top_f.values[:, 1]) >= 4.0 * noise).sum())
+    print(f"  split1 T={T}: bf16-vs-fp32 err mean {float(err_full.mean()):.3e} min {float(err_full.min()):.3e} max {float(err_full.max()):.3e}; "
+          f"argmax agree {int((lb.float().argmax(-1) == lf.argmax(-1)).sum())}/{nstep}; CLEAR-MARGIN steps {clear}/{nstep} "
+          f"(all columns: {_clear_count(lb, lf, top_f)}; the tests need >= 16); {cols.numel()} columns", flush=True)
+    save(f"s1_llama2_7b_T{T}_N{nstep - 1}", ids=ids.to(torch.int32), tokens=toks.to(torch.int32), cols=cols.to(torch.int32),
+         logits_bf16=lb[:, cols], logits_fp32=lf[:, cols], hidden_bf16=hb[:1], hidden_fp32=hf[:1],
+         norm_fp32=lf.double().norm(dim=-1).float(), err_bf16_full=err_full.float(),
+         top_ids_fp32=top_f.indices.to(torch.int32), top_vals_fp32=top_f.values,
+         top_ids_bf16=top_b.indices.to(torch.int32), top_vals_bf16=top_b.values)
+
+
+def make_split1(stride=127):
+    """s1: ProCyon-Split's decoder (Llama-2-7B geometry: 32 heads = 32 kv heads, ffn 11008, vocabulary 32007) at FULL depth in bf16, one row,
+    teacher-forced on the bf16 oracle's greedy tokens, bf16 oracle + fp32 truth in one causal pass (as f1): T = 128 with 128 cached steps, and
+    T = 704 with 128 cached steps -- the cache grows 704 -> 832, across the 768-key split of the decode attention in the middle of the run.
+    128 steps, not 64: at 64 only 9 / 12 of 65 steps clear 4 x the bf16 noise on this geometry.  Every 127th column (as f1) + the top-8 of either
+    run at every step (1130 columns at T = 128): with every 31st the files would be 1.5 MB each."""
+    t0 = time.time()
+    sd = synth.llama_state_dict(**SPLIT_LLAMA)
+    print(f"split llama weights generated in {time.time() - t0:.0f}s", flush=True)
+    geom = LR.LlamaGeom(**SPLIT_LLAMA)
+    for T in (128, 704):
+        g = torch.Generator().manual_seed(2727 + T)
+        ids = torch.randint(3, 32000, (1, T), generator=g)
+        t0 = time.time()
+        lb, hb, toks = llama_run(sd, geom, ids, torch.bfloat16, ndec=128)
+        print(f"  split1 T={T} bf16 oracle {time.time() - t0:.0f}s", flush=True)
+        t0 = time.time()
+        lf, hf = llama_truth(sd, geom, ids, toks)
+        print(f"  split1 T={T} fp32 truth {time.time() - t0:.0f}s", flush=True)
+        _pack_split1(T, ids, toks, lb, lf, hb, hf, stride)
+
+
+def _pack_split_rows20(ids, mask, toks, lb, lf, stride=127):
+    """Columns PER ROW (cols [B, C]; logits_* [nstep, B, C] hold row b at cols[b]): the union over all 340 (row, step) pairs of the top-8 of
+    either run is 2902 columns (5.4 MB), the top-8 of either run at the 17 steps of ONE row at most 272 -- every (row, step) keeps the top-8 of
+    either run among its own row's columns, plus every `stride`-th column; rows with fewer top columns are filled up from a second strided
+    sequence so that the arrays are rectangular."""
+    nstep, B, V = lb.shape
+    top_f, top_b = lf.topk(8, dim=-1), lb.float().topk(8, dim=-1)
+    per_row = [set(range(0, V, stride)) | set(top_f.indices[:, b].flatten().tolist()) | set(top_b.indices[:, b].flatten().tolist()) for b in range(B)]
+    C = max(len(c) for c in per_row)
+    for c in per_row:
+        fill = iter(range(stride // 2, V, stride))
+        while len(c) < C:
+            c.add(next(fill))
+    cols = torch.tensor([sorted(c) for c in per_row])                                   # [B, C]
+    gather = lambda t: torch.stack([t[:, b, cols[b]] for b in range(B)], dim=1)         # [nstep, B, C]
+    lbc, lfc = gather(lb), gather(lf)
+    err_full = torch.tensor([[rel(lb[s, b].float(), lf[s, b]) for b in range(B)] for s in range(nstep)])
+    noise = (lbc.float() - lfc).pow(2).mean(-1).sqrt()
+    clear = (top_f.values[..., 0] - top_f.values[..., 1]) >= 4.0 * noise                # [nstep, B]
+    print(f"  split_rows20: bf16-vs-fp32 err mean {float(err_full.mean()):.3e} min {float(err_full.min()):.3e} max {float(err_full.max()):.3e}; "
+          f"argmax agree {(lb.float().argmax(-1) == lf.argmax(-1)).float().mean():.3f}; {C} columns per row\n   CLEAR-MARGIN (row, step) pairs in the "
+          f"first n rows (the tests need >= n): " + ", ".join(f"n={n}: {int(clear[:, :n].sum())}" for n in (2, 3, 4, 10, 20)), flush=True)
+    save("s2_llama2_7b_rows20_T64", ids=ids.to(torch.int32), mask=mask.to(torch.int32), tokens=toks.to(torch.int32), cols=cols.to(torch.int32),
+         logits_bf16=lbc, logits_fp32=lfc, norm_fp32=lf.double().norm(dim=-1).float(), err_bf16_full=err_full.float(),
+         top_ids_fp32=top_f.indices.to(torch.int32), top_vals_fp32=top_f.values, top_ids_bf16=top_b.indices.to(torch.int32), top_vals_bf16=top_b.values)
+
+
+SPLIT_ROWS20_PADS = [0, 21, 3, 0, 11, 27, 8, 0, 16, 5, 13, 0, 25, 2, 19, 7, 0, 23, 9, 14]
+
+
+def make_split_rows20():
+    """s2: TWENTY ragged left-padded rows (pads 0 .. 27 of 64 slots, five rows unpadded) through the Split decoder at FULL depth, 16 teacher-forced
+    cached steps in the reference's compat mode as make_llama_rows10 does it (mask in the prefill only, positions arange(T), every cached slot
+    attended afterwards), bf16 oracle + the same procedure in fp32.  Twenty: the reference's callers run Split at beam 20; the first 10 rows
+    double as the beam-10 batch."""
+    sd = synth.llama_state_dict(**SPLIT_LLAMA)
+    geom = LR.LlamaGeom(**SPLIT_LLAMA)
+    B, T, ndec = 20, 64, 16
+    g = torch.Generator().manual_seed(2020)
+    ids = torch.randint(3, 32000, (B, T), generator=g)
+    mask = torch.ones(B, T)
+    for b, n in enumerate(SPLIT_ROWS20_PADS):
+        mask[b, :n] = 0
+        ids[b, :n] = 32000            # whatever sits in the pad slots is embedded and cached like any token
+    t0 = time.time()
+    lb, toks = llama_run_rows(sd, geom, ids, mask, torch.bfloat16, ndec)
+    print(f"  split_rows20 bf16 oracle {time.time() - t0:.0f}s", flush=True)
+    t0 = time.time()
+    lf, _ = llama_run_rows(sd, geom, ids, mask, torch.float32, ndec, forced=toks)
+    print(f"  split_rows20 fp32 truth {time.time() - t0:.0f}s", flush=True)
+    _pack_split_rows20(ids, mask, toks, lb, lf)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["esm", "llama"]
     torch.set_num_threads(os.cpu_count())
@@ -430,3 +537,7 @@ if __name__ == "__main__":
         make_config3_rows()
     if "config4" in what:
         make_config4_pair()
+    if "split1" in what:
+        make_split1()
+    if "split_rows20" in what:
+        make_split_rows20()

@@ -24,12 +24,14 @@ import pytest
 import torch
 
 from conftest import record_parity, rel_err
+from fulldepth_common import SLACK, served_by
+from fulldepth_common import llama_stats as _llama_stats, margin_conditioned as _margin_conditioned, rows_compat_check as _rows_compat_check
+from fulldepth_common import llama_steps, rows_compat_run
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 LLAMA = dict(vocab=128263, d=4096, n_layers=32, n_heads=32, n_kv_heads=8, ffn=14336)
 ESM = dict(d=1280, n_layers=33, n_heads=20, ffn=5120)
-SLACK = 1.25
 
 
 def _llama_engine(damped):
@@ -53,38 +55,11 @@ def llama_damped():
 
 
 def _llama_steps(eng, g, T):
-    """prefill + teacher-forced cached decode steps on the fixture's tokens -> logits [65, V] fp32 (CPU), prefill hidden row"""
-    from procyon_amd.engine import GenState
-    ids, toks = g["ids"].long(), g["tokens"].long()
-    nstep = toks.numel()                          # prefill + 64 decode steps
-    cache = eng.new_cache(1, T + nstep + 1)
-    logits, hidden = eng.prefill(eng.embed_tokens(ids), None, cache, "last", want_hidden=True)
-    got = [logits[0].cpu()]
-    st = GenState(1, LLAMA["vocab"], nstep + 1, "cuda")
-    for s in range(1, nstep):                     # teacher-forced on the bf16 oracle's greedy tokens
-        st.pos.fill_(T + s - 1)
-        st.next_tok.copy_(toks[s - 1:s].to(torch.int32))
-        eng.decode(cache, st, 1)
-        got.append(st.logits[0].cpu())
-    return torch.stack(got).float(), hidden[0, -1].cpu().float()
+    return llama_steps(eng, g, T, LLAMA["vocab"])
 
 
-def _llama_stats(got, g):
-    """per-step errors and agreement counts of HIP logits [65, V] against the fixture's bf16 oracle and fp32 truth (column subset)"""
-    cols = g["cols"].long()
-    truth, ref = g["logits_fp32"], g["logits_bf16"].float()
-    nstep = got.shape[0]
-    out = dict(nstep=nstep, e_hip_truth=[], e_ref_truth=[], e_hip_ref=[], agree_hip_truth=0, agree_ref_truth=0, agree_hip_ref=0, rows=[])
-    for s in range(nstep):
-        out["e_hip_truth"].append(rel_err(got[s, cols], truth[s]))
-        out["e_ref_truth"].append(rel_err(ref[s], truth[s]))
-        out["e_hip_ref"].append(rel_err(got[s, cols], ref[s]))
-        am, am_t, am_r = int(got[s].argmax()), int(g["top_ids_fp32"][s, 0]), int(g["top_ids_bf16"][s, 0])
-        out["agree_hip_truth"] += am == am_t
-        out["agree_ref_truth"] += am_r == am_t
-        out["agree_hip_ref"] += am == am_r
-        out["rows"].append((am, am_t, am_r, float(g["top_vals_fp32"][s, 0] - g["top_vals_fp32"][s, 1])))
-    return out
+def _rows_compat_run(llama, ids, mask, toks, rows, teacher, keep_rows=None, copy_of=None):
+    return rows_compat_run(llama, ids, mask, toks, rows, teacher, LLAMA["vocab"], keep_rows=keep_rows, copy_of=copy_of)
 
 
 @pytest.mark.parametrize("T", [64, 512])
@@ -120,21 +95,6 @@ def test_llama8b_full_depth_vs_fp32_truth(llama, golden, T):
     assert e_hip <= SLACK * e_ref
 
 
-def _margin_conditioned(st, g):
-    """Steps whose fp32 top-2 margin exceeds 4 x the per-logit noise of the bf16 pipeline (rms over the fixture's columns of
-    oracle_bf16 - fp32 at that step): there two bf16 implementations MUST pick the same token (a flip needs a 2.8-sigma event on the
-    difference of two logit errors).  Returns (n_clear, n_clear_agree_hip_oracle, n_clear_agree_hip_fp32)."""
-    truth, ref = g["logits_fp32"], g["logits_bf16"].float()
-    clear = agree_o = agree_t = 0
-    for s_, (am, am_t, am_r, margin) in enumerate(st["rows"]):
-        noise = float((ref[s_] - truth[s_]).pow(2).mean().sqrt())
-        if margin >= 4.0 * noise:
-            clear += 1
-            agree_o += am == am_r
-            agree_t += am == am_t
-    return clear, agree_o, agree_t
-
-
 @pytest.mark.parametrize("T", [64, 512])
 def test_llama8b_argmax_agrees_wherever_the_margin_clears_the_bf16_noise(llama, golden, T):
     """The falsifiable form of north_star's "bit-exact argmax ids" (/root/reference/procyon/model/model_unified.py:892-906).  Two
@@ -161,7 +121,8 @@ def test_llama8b_full_depth_256_steps(llama, golden):
     step, argmax on EVERY clear-margin step (>= 40 of them), agreement rates."""
     T = 512
     g = golden("f1_llama8b_T512_N256")
-    got, _ = _llama_steps(llama, g, T)
+    with served_by("step_gqa", 256):              # every cached step on the one-launch step (eager steps: the counters say what ran)
+        got, _ = _llama_steps(llama, g, T)
     st = _llama_stats(got, g)
     nstep = st["nstep"]
     mean = lambda v: sum(v) / len(v)
@@ -194,11 +155,12 @@ def test_llama8b_full_depth_left_padded_rows_compat_mode(llama, golden):
     logits, _ = llama.prefill(llama.embed_tokens(ids), mask, cache, "last")
     got = [logits.cpu()]
     st = GenState(2, LLAMA["vocab"], nstep + 1, "cuda")            # keep = None: compat mode
-    for s in range(1, nstep):
-        st.pos.fill_(T + s - 1)
-        st.next_tok.copy_(toks[s - 1].to(torch.int32))
-        llama.decode(cache, st, 2)
-        got.append(st.logits.cpu())
+    with served_by("step_nb", nstep - 1):                          # every cached step on the fused small-batch step, none on its fallback
+        for s in range(1, nstep):
+            st.pos.fill_(T + s - 1)
+            st.next_tok.copy_(toks[s - 1].to(torch.int32))
+            llama.decode(cache, st, 2)
+            got.append(st.logits.cpu())
     got = torch.stack(got).float()                                 # [17, 2, V]
     cols = g["cols"].long()
     truth, ref = g["logits_fp32"], g["logits_bf16"].float()
@@ -224,68 +186,6 @@ def test_llama8b_full_depth_left_padded_rows_compat_mode(llama, golden):
     assert max(e_hr) < 0.12        # a wrong position / a dropped pad slot gives O(1)
 
 
-def _rows_compat_run(llama, ids, mask, toks, rows, teacher, keep_rows=None, copy_of=None):
-    """prefill (left-padded rows, compat mode) + teacher-forced cached steps of a B-row batch; rows in `teacher` are fed the fixture's tokens
-    (toks [nstep, len(teacher)]), every other row its own argmax.  -> logits [nstep, B, V] fp32 (CPU); with `keep_rows` only those rows
-    [nstep, len(keep_rows), V] (the argmax of the others is taken on the device).  `copy_of` [B] (rows holding the same prompt and the same
-    tokens): the logits of every step and the whole K / V cache of row b must be BIT-identical to those of row copy_of[b] (checked on the device)."""
-    from procyon_amd.engine import GenState
-    B, T = ids.shape
-    nstep = toks.shape[0]
-    cache = llama.new_cache(B, T + nstep + 1)
-    logits, _ = llama.prefill(llama.embed_tokens(ids), mask, cache, "last")
-    ksel = None if keep_rows is None else torch.tensor(keep_rows, device=logits.device)
-    csel = None if copy_of is None else torch.tensor(copy_of, device=logits.device)
-    host = lambda lg: lg.float().cpu() if ksel is None else lg[ksel].float().cpu()
-    same = lambda lg: csel is None or torch.equal(lg, lg[csel])
-    assert same(logits), "prefill logits of copies differ"
-    got = [host(logits)]
-    st = GenState(B, LLAMA["vocab"], nstep + 1, "cuda")            # keep = None: compat mode (every cached slot is attended)
-    tsel = torch.tensor(teacher)
-    for s in range(1, nstep):
-        if ksel is None:
-            nxt = got[-1].argmax(-1).to(torch.int32)
-        else:
-            nxt = (logits if s == 1 else st.logits).float().argmax(-1).cpu().to(torch.int32)
-        nxt[tsel] = toks[s - 1].to(torch.int32)
-        st.pos.fill_(T + s - 1)
-        st.next_tok.copy_(nxt)
-        llama.decode(cache, st, B)
-        assert same(st.logits), f"step {s}: logits of copies differ"
-        got.append(host(st.logits))
-    if csel is not None:
-        assert torch.equal(cache.k, cache.k[:, csel]) and torch.equal(cache.v, cache.v[:, csel]), "K / V rows of copies differ"
-    return torch.stack(got)
-
-
-def _rows_compat_check(name, got, g, sel, min_clear):
-    """got [nstep, n, V] (the fixture's rows `sel` of the batch) against the fixture's bf16 oracle and fp32 truth: per (row, step) the truth
-    distance bar, argmax on every clear-margin (row, step), agreement rates; one PARITY record."""
-    cols = g["cols"].long()
-    nstep = got.shape[0]
-    e_ht, e_rt, e_hr, clear, clear_ok, agree_hr, agree_rt = [], [], [], 0, 0, 0, 0
-    for s in range(nstep):
-        for j, b in enumerate(sel):
-            truth, ref = g["logits_fp32"][s, b], g["logits_bf16"][s, b].float()
-            e_ht.append(rel_err(got[s, j, cols], truth)); e_rt.append(rel_err(ref, truth)); e_hr.append(rel_err(got[s, j, cols], ref))
-            am, am_t, am_r = int(got[s, j].argmax()), int(g["top_ids_fp32"][s, b, 0]), int(g["top_ids_bf16"][s, b, 0])
-            agree_hr += am == am_r
-            agree_rt += am_r == am_t
-            noise = float((ref - truth).pow(2).mean().sqrt())
-            if float(g["top_vals_fp32"][s, b, 0] - g["top_vals_fp32"][s, b, 1]) >= 4.0 * noise:
-                clear += 1
-                clear_ok += (am == am_r) and (am == am_t)
-    mean = lambda v: sum(v) / len(v)
-    record_parity(name, rows_x_steps=len(e_ht), err_hip_fp32_mean=mean(e_ht), err_oracle_fp32_mean=mean(e_rt), err_hip_oracle_mean=mean(e_hr),
-                  err_hip_oracle_max=max(e_hr), worst_ratio_hip_over_oracle=max(a / b for a, b in zip(e_ht, e_rt)), agree_hip_oracle=agree_hr,
-                  agree_oracle_fp32=agree_rt, clear_margin=clear, clear_agree=clear_ok)
-    for a, b in zip(e_ht, e_rt):
-        assert a <= SLACK * b, (a, b)
-    assert clear >= min_clear and clear_ok == clear, (clear, clear_ok)
-    assert agree_hr >= agree_rt - max(2, len(e_ht) // 32), (agree_hr, agree_rt)
-    assert max(e_hr) < 0.15        # a wrong position / a dropped pad slot / a stale hand-over gives O(1)
-
-
 @pytest.mark.parametrize("nrows", [10, 8, 5])
 def test_llama8b_full_depth_ten_ragged_rows_compat_mode(llama, golden, monkeypatch, nrows):
     """Round 6: the batch of the reference's beam-10 callers (/root/reference/scripts/caption_bulk.py:193-194,
@@ -299,8 +199,26 @@ def test_llama8b_full_depth_ten_ragged_rows_compat_mode(llama, golden, monkeypat
     monkeypatch.setenv("PCY_NB_MAX", "8")        # (8 rows default to the batched launches since round 6; here the fused step is what is checked)
     g = golden("f7_llama8b_rows10_T64")
     ids, mask, toks = g["ids"].long()[:nrows], g["mask"].float()[:nrows], g["tokens"].long()[:, :nrows]
-    got = _rows_compat_run(llama, ids, mask, toks, nrows, list(range(nrows)))
+    with served_by("loop_mfma" if nrows == 10 else "step_nb", toks.shape[0] - 1):      # (eager steps: the counters say what ran)
+        got = _rows_compat_run(llama, ids, mask, toks, nrows, list(range(nrows)))
     _rows_compat_check(f"fulldepth/llama8b_ragged_rows_compat_B{nrows}", got, g, list(range(nrows)), min_clear=nrows)
+
+
+def test_llama8b_full_depth_ten_ragged_rows_on_the_mid_batch_step(llama, golden, monkeypatch):
+    """decode_step_mb_kernel (opt-in: PCY_MB_MAX) had no full-depth oracle run: f7's ten rows a second time with PCY_MB_MAX=32, at the bars of the
+    default run, the logits of every step BIT-identical to the default run's (the launches), and the counter shows the mid-batch step for every
+    cached step of the second run, the MFMA launches for every step of the first."""
+    monkeypatch.delenv("PCY_DISABLE", raising=False)
+    g = golden("f7_llama8b_rows10_T64")
+    ids, mask, toks = g["ids"].long(), g["mask"].float(), g["tokens"].long()
+    monkeypatch.delenv("PCY_MB_MAX", raising=False)
+    with served_by("loop_mfma", toks.shape[0] - 1):
+        ref = _rows_compat_run(llama, ids, mask, toks, 10, list(range(10)))
+    monkeypatch.setenv("PCY_MB_MAX", "32")
+    with served_by("step_mb", toks.shape[0] - 1) as delta:
+        got = _rows_compat_run(llama, ids, mask, toks, 10, list(range(10)))
+    _rows_compat_check("fulldepth/llama8b_ragged_rows_compat_B10_mid_batch_step", got, g, list(range(10)), min_clear=10, steps_on_step_mb=delta["step_mb"])
+    assert torch.equal(got, ref)
 
 
 # the f7 rows tiled into batches of more than 32 rows: row i holds f7 row (i - s) % 10, so rows [s, s + 10) -- the copies held to the oracle --
@@ -323,7 +241,8 @@ def test_llama8b_full_depth_rows_over_32(llama, golden, monkeypatch, B):
     copy_of = [first.setdefault(p, i) for i, p in enumerate(perm)]
     ids, mask, toks = g["ids"].long()[perm], g["mask"].float()[perm], g["tokens"].long()[:, perm]
     rows = list(range(s, s + 10))
-    got = _rows_compat_run(llama, ids, mask, toks, B, list(range(B)), keep_rows=rows, copy_of=copy_of)
+    with served_by("loop_mfma", toks.shape[0] - 1):
+        got = _rows_compat_run(llama, ids, mask, toks, B, list(range(B)), keep_rows=rows, copy_of=copy_of)
     _rows_compat_check(f"fulldepth/llama8b_rows_over_32_B{B}", got, g, [perm[i] for i in rows], min_clear=10)
 
 
@@ -334,8 +253,27 @@ def test_llama8b_full_depth_config3_ragged_batch32(llama, golden, monkeypatch):
     monkeypatch.delenv("PCY_DISABLE", raising=False)
     g = golden("f8_config3_rows_T512")
     ids, mask, toks, rows = g["ids"].long(), g["mask"].float(), g["tokens"].long(), g["rows"].long().tolist()
-    got = _rows_compat_run(llama, ids, mask, toks, 32, rows)[:, rows]
+    monkeypatch.delenv("PCY_MB_MAX", raising=False)
+    with served_by("loop_mfma", toks.shape[0] - 1):
+        got = _rows_compat_run(llama, ids, mask, toks, 32, rows)[:, rows]
     _rows_compat_check("fulldepth/llama8b_config3_ragged_batch32_rows_0_13_31", got, g, [0, 1, 2], min_clear=3)
+
+
+def test_llama8b_full_depth_config3_ragged_batch32_on_the_mid_batch_step(llama, golden, monkeypatch):
+    """The same 32-row batch with PCY_MB_MAX=32: the two-tile form of decode_step_mb_kernel at full depth.  Its cache holds 522 slots (T = 512 +
+    the steps), well inside what pcy_decode_mb_fits accepts at 17 .. 32 rows (2881 slots), so every cached step must be served by the fused
+    step; bars as above on the three sampled rows, and the logits of ALL 32 rows at every step bit-identical to the default run's."""
+    monkeypatch.delenv("PCY_DISABLE", raising=False)
+    g = golden("f8_config3_rows_T512")
+    ids, mask, toks, rows = g["ids"].long(), g["mask"].float(), g["tokens"].long(), g["rows"].long().tolist()
+    monkeypatch.delenv("PCY_MB_MAX", raising=False)
+    with served_by("loop_mfma", toks.shape[0] - 1):
+        ref = _rows_compat_run(llama, ids, mask, toks, 32, rows)
+    monkeypatch.setenv("PCY_MB_MAX", "32")
+    with served_by("step_mb", toks.shape[0] - 1) as delta:
+        got = _rows_compat_run(llama, ids, mask, toks, 32, rows)
+    _rows_compat_check("fulldepth/llama8b_config3_ragged_batch32_mid_batch_step", got[:, rows], g, [0, 1, 2], min_clear=3, steps_on_step_mb=delta["step_mb"])
+    assert torch.equal(got, ref)
 
 
 def test_config4_pair_answer_row_full_depth(llama, golden):

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import alt_accumulation, assert_no_further_from_truth, assert_bf16_close, parity_bar, pcy_disable, rel_err
+from fulldepth_common import served_by
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -294,11 +295,16 @@ def test_decode_layer_launch_bit_identical(monkeypatch, T, N, n_layers, cap):
         st.logits.copy_(logits); st.pos.fill_(T)
         eng.pick(cache, st, 1, advance_pos=False)
         out = []
-        for i in range(N):
-            if i % 3 == 2:
-                continue
-            eng.greedy_steps(cache, st, 1, 2 if i % 3 == 1 else 1, use_graph=use_graph)
-            out.append(st.logits[0].clone())
+        # each side must have run what it names (dispatch counters): a fused launch that declines -- its LDS image grows with the cache capacity,
+        # 4096 slots in the last case -- falls back to the launches with the same bits; a replayed run counts its capture only
+        kind = "loop_stream" if not (layer and attn_o) else "step_gqa" if step else "layer"
+        n_eager = sum(2 if i % 3 == 1 else 1 for i in range(N) if i % 3 != 2)
+        with served_by(kind, None if use_graph else n_eager):
+            for i in range(N):
+                if i % 3 == 2:
+                    continue
+                eng.greedy_steps(cache, st, 1, 2 if i % 3 == 1 else 1, use_graph=use_graph)
+                out.append(st.logits[0].clone())
         Context.get().sync()
         return (torch.stack(out).cpu(), st.tokens_out[0, :N + 1].cpu(), st.logprob.cpu().clone(), cache.k[:, 0, :, T:T + N].cpu(),
                 cache.v[:, 0, :, T:T + N].cpu())

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import pcy_disable
+from fulldepth_common import served_by
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -43,11 +44,15 @@ def test_decode_nb_step_bit_identical(eng2, monkeypatch, B, T, N, xmin):
         st.logits.copy_(logits); st.pos.fill_(T)
         eng2.pick(cache, st, B, advance_pos=False)
         out = []
-        for i in range(N):
-            if i % 3 == 2:
-                continue
-            eng2.greedy_steps(cache, st, B, 2 if i % 3 == 1 else 1, use_graph=use_graph)
-            out.append(st.logits.clone())
+        # each side must have run what it names: every eager step on the fused kernel / on the streaming launches of its twin (the fused
+        # step may decline at launch time, and the twin would then be compared with itself; a graph run counts its capture only)
+        n_eager = sum(2 if i % 3 == 1 else 1 for i in range(N) if i % 3 != 2)
+        with served_by("step_nb" if step else "loop_stream", None if use_graph else n_eager):
+            for i in range(N):
+                if i % 3 == 2:
+                    continue
+                eng2.greedy_steps(cache, st, B, 2 if i % 3 == 1 else 1, use_graph=use_graph)
+                out.append(st.logits.clone())
         Context.get().sync()
         return torch.stack(out).cpu(), st.tokens_out[:, :N + 1].cpu(), st.logprob.cpu().clone(), cache.k[:, :, :, T:T + N].cpu(), cache.v[:, :, :, T:T + N].cpu()
 
@@ -57,6 +62,39 @@ def test_decode_nb_step_bit_identical(eng2, monkeypatch, B, T, N, xmin):
         got = run(True, use_graph)
         for x, y in zip(got, ref):
             assert torch.equal(x, y), (B, T, use_graph)
+
+
+@pytest.mark.parametrize("B", [2, 5, 8])
+def test_decode_nb_step_at_a_long_cache(eng2, monkeypatch, B):
+    """The small-batch step's LDS need grows with the cache CAPACITY (16 bytes per slot for the four heads of a kv group: 43 KB at 2048 slots,
+    76 KB at 4096 -- below the 160 KB at which the launcher declines, so there is no coverage limit up to the model's 4096 positions).  With a
+    cache of 2048 slots (what this engine allows) and 1700 cached keys the counters must show the fused step on every eager step; bits equal
+    to the launch-per-stage twin."""
+    from procyon_amd.engine import Context, GenState
+    monkeypatch.setenv("PCY_NB_MAX", "8")
+    monkeypatch.delenv("PCY_AO_XMIN", raising=False)
+    T, N, cap = 1700, 3, 2048
+    emb = (torch.randn(B, T, 4096, generator=torch.Generator().manual_seed(B)) * 0.02).to(BF).cuda()
+
+    def run(step):
+        pcy_disable(monkeypatch, "" if step else "decode_nb_step")
+        cache = eng2.new_cache(B, cap)
+        st = GenState(B, KW["vocab"], N + 2, "cuda")
+        logits, _ = eng2.prefill(emb, None, cache, "last")
+        st.logits.copy_(logits); st.pos.fill_(T)
+        eng2.pick(cache, st, B, advance_pos=False)
+        out = []
+        with served_by("step_nb" if step else "loop_stream", N):
+            for _ in range(N):
+                eng2.greedy_steps(cache, st, B, 1, use_graph=False)
+                out.append(st.logits.clone())
+        Context.get().sync()
+        return torch.stack(out).cpu(), st.tokens_out[:, :N + 1].cpu(), cache.k[:, :, :, T:T + N].cpu(), cache.v[:, :, :, T:T + N].cpu()
+
+    ref, got = run(False), run(True)
+    assert torch.isfinite(ref[0].float()).all()
+    for x, y in zip(got, ref):
+        assert torch.equal(x, y), B
 
 
 def test_decode_nb_rows_are_independent(eng2, monkeypatch):
@@ -103,12 +141,13 @@ def test_decode_nb_beam_loop_bit_identical(eng2, monkeypatch):
         st.pos, st.next_tok = bs.pos, bs.next_tok
         st.c.pos, st.c.next_tok = bs.pos.data_ptr(), bs.next_tok.data_ptr()
         lg = logits.contiguous()
-        for i in range(steps):
-            if i > 0:
-                eng2.decode_graph(cache, st, beam)
-                lg = st.logits
-            eng2.beam_step(lg, bs, 5, 0.8)
-            eng2.kv_reorder(cache, bs.src, T + i)
+        with served_by("step_nb" if step else "loop_stream"):      # (replayed steps: the capture counts)
+            for i in range(steps):
+                if i > 0:
+                    eng2.decode_graph(cache, st, beam)
+                    lg = st.logits
+                eng2.beam_step(lg, bs, 5, 0.8)
+                eng2.kv_reorder(cache, bs.src, T + i)
         out, n = bs.tokens()
         Context.get().sync()
         return out.cpu(), bs.cur.cpu().clone(), bs.anc[:n].cpu().clone()
@@ -116,6 +155,32 @@ def test_decode_nb_beam_loop_bit_identical(eng2, monkeypatch):
     ref, got = run(False), run(True)
     for x, y in zip(got, ref):
         assert torch.equal(x, y)
+
+
+def test_decode_nb_max_switch_is_part_of_the_captured_step_key(eng2, monkeypatch):
+    """PCY_NB_MAX is read per call and selects the decode step of a 5-row batch: 6 (default) and 8 put it on the small-batch step, 2 on the
+    MFMA launches.  A captured step is keyed on the switch settings; the key used to hold PCY_NB_MAX & 3, which took 2 for 6 -- after a step
+    captured at 6 the SAME cache and state at 2 replayed the stale capture.  Asserted: every change of the value captures anew (the capture
+    is what the dispatch counters count) on the step it names, and each setting keeps its own bits."""
+    from procyon_amd.engine import Context, GenState
+    pcy_disable(monkeypatch)
+    monkeypatch.delenv("PCY_AO_XMIN", raising=False)
+    B, T = 5, 90
+    emb = (torch.randn(B, T, 4096, generator=torch.Generator().manual_seed(55)) * 0.02).to(BF).cuda()
+    cache = eng2.new_cache(B, T + 8)
+    st = GenState(B, KW["vocab"], 8, "cuda")
+    out = {}
+    for nb_max, kind in ((6, "step_nb"), (2, "loop_mfma"), (6, "step_nb"), (8, "step_nb"), (2, "loop_mfma")):
+        monkeypatch.setenv("PCY_NB_MAX", str(nb_max))
+        logits, _ = eng2.prefill(emb, None, cache, "last")
+        st.logits.copy_(logits); st.pos.fill_(T)
+        eng2.pick(cache, st, B, advance_pos=False)
+        with served_by(kind, 1):                  # one capture, on the step this value names; the replays count nothing
+            eng2.greedy_steps(cache, st, B, 3, use_graph=True)
+        Context.get().sync()
+        got = st.logits.cpu().clone()
+        assert torch.equal(out.setdefault(kind, got), got), (nb_max, kind)
+    assert not torch.equal(out["step_nb"], out["loop_mfma"])      # (two arithmetics: other accumulation orders)
 
 
 def test_decode_nb_switch_restores_round4_path(eng2, monkeypatch):
@@ -134,7 +199,8 @@ def test_decode_nb_switch_restores_round4_path(eng2, monkeypatch):
         logits, _ = eng2.prefill(emb, None, cache, "last")
         st.logits.copy_(logits); st.pos.fill_(T)
         eng2.pick(cache, st, B, advance_pos=False)
-        eng2.greedy_steps(cache, st, B, N)
+        with served_by("loop_mfma" if off else "step_nb"):         # (replayed steps: the capture counts)
+            eng2.greedy_steps(cache, st, B, N)
         Context.get().sync()
         return st.logits.cpu().clone()
 

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 from conftest import pcy_disable, rel_err
+from fulldepth_common import served_by
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -41,11 +42,14 @@ def test_decode_mb_step_bit_identical(eng2, monkeypatch, B, T, N):
         st.logits.copy_(logits); st.pos.fill_(T)
         eng2.pick(cache, st, B, advance_pos=False)
         out = []
-        for i in range(N):
-            if i % 3 == 2:
-                continue
-            eng2.greedy_steps(cache, st, B, 2 if i % 3 == 1 else 1, use_graph=use_graph)
-            out.append(st.logits.clone())
+        # each side must have run what it names: every eager step on the fused kernel / on the launches (a graph run counts its capture only)
+        n_eager = sum(2 if i % 3 == 1 else 1 for i in range(N) if i % 3 != 2)
+        with served_by("step_mb" if step else "loop_mfma", None if use_graph else n_eager):
+            for i in range(N):
+                if i % 3 == 2:
+                    continue
+                eng2.greedy_steps(cache, st, B, 2 if i % 3 == 1 else 1, use_graph=use_graph)
+                out.append(st.logits.clone())
         Context.get().sync()
         return torch.stack(out).cpu(), st.tokens_out[:, :N + 1].cpu(), st.logprob.cpu().clone(), cache.k[:, :, :, T:T + N].cpu(), cache.v[:, :, :, T:T + N].cpu()
 
@@ -55,6 +59,40 @@ def test_decode_mb_step_bit_identical(eng2, monkeypatch, B, T, N):
         got = run(True, use_graph)
         for x, y in zip(got, ref):
             assert torch.equal(x, y), (B, T, use_graph)
+
+
+# cache slots the mid-batch step covers (pcy_decode_mb_fits: the attention's LDS image beside the weight rings): 2369 at 9..15 rows, 1857 at 16 rows
+# (128-column attention units in the 48 KB of the one-tile layout), 2881 at 17..32 rows (64 KB beside the shorter rings of the two-tile layout)
+@pytest.mark.parametrize("B,cap,kind", [(10, 2048, "step_mb"), (16, 1857, "step_mb"), (16, 2048, "loop_mfma"), (20, 2048, "step_mb"), (32, 2048, "step_mb")])
+def test_decode_mb_step_at_a_long_cache(eng2, monkeypatch, B, cap, kind):
+    """The fused step's LDS need grows with the cache CAPACITY (Tmax), and a step that does not fit declines at launch time in favour of the
+    launches -- silently, with the same bits.  With PCY_MB_MAX=32 and a cache of 2048 slots (what these engines allow) the counters must show
+    the fused step at 10, 20 and 32 rows; at 16 rows coverage ends at 1857 slots (fused there, the launches at 2048: asserted both ways).
+    Eager steps around a prompt of 1500 keys; logits, tokens and the appended K / V rows bit-identical to PCY_DISABLE=decode_mb_step."""
+    from procyon_amd.engine import Context, GenState
+    monkeypatch.setenv("PCY_MB_MAX", "32")
+    T, N = 1500, 3
+    emb = (torch.randn(B, T, 4096, generator=torch.Generator().manual_seed(B + cap)) * 0.02).to(BF).cuda()
+
+    def run(step):
+        pcy_disable(monkeypatch, "" if step else "decode_mb_step")
+        cache = eng2.new_cache(B, cap)
+        st = GenState(B, KW["vocab"], N + 2, "cuda")
+        logits, _ = eng2.prefill(emb, None, cache, "last")
+        st.logits.copy_(logits); st.pos.fill_(T)
+        eng2.pick(cache, st, B, advance_pos=False)
+        out = []
+        with served_by(kind if step else "loop_mfma", N):
+            for _ in range(N):
+                eng2.greedy_steps(cache, st, B, 1, use_graph=False)
+                out.append(st.logits.clone())
+        Context.get().sync()
+        return torch.stack(out).cpu(), st.tokens_out[:, :N + 1].cpu(), cache.k[:, :, :, T:T + N].cpu(), cache.v[:, :, :, T:T + N].cpu()
+
+    ref, got = run(False), run(True)
+    assert torch.isfinite(ref[0].float()).all()
+    for x, y in zip(got, ref):
+        assert torch.equal(x, y), (B, cap)
 
 
 def test_decode_mb_switches_inside_one_process(eng2, monkeypatch):
@@ -76,9 +114,15 @@ def test_decode_mb_switches_inside_one_process(eng2, monkeypatch):
         logits, _ = eng2.prefill(emb, None, cache, "last")
         st.logits.copy_(logits); st.pos.fill_(T)
         eng2.pick(cache, st, B, advance_pos=False)
-        eng2.greedy_steps(cache, st, B, 3)
+        kind = "step_mb" if mb_max is not None and B <= mb_max else "loop_mfma"
+        with served_by(kind):                           # (replayed: the capture counts)
+            eng2.greedy_steps(cache, st, B, 3)
         Context.get().sync()
-        return st.logits.cpu().clone()
+        out = st.logits.cpu().clone()
+        with served_by(kind, 1):                        # ... and one eager step more, not compared: this setting runs what the comment says
+            eng2.decode(cache, st, B)
+        Context.get().sync()
+        return out
 
     ref10, ref20, ref12 = run(10, 90, None), run(20, 60, None), run(12, 70, None)       # the launches
     for _ in range(2):
@@ -92,8 +136,10 @@ def test_decode_mb_switches_inside_one_process(eng2, monkeypatch):
 def test_decode_mb_beam10_loop_bit_identical(eng2, monkeypatch):
     """The reference's production call: diverse beam search, beam 10 in groups of 2 (scripts/caption_bulk.py:193-194, :130) = a 10-row
     decode step + pcy_beam_step + the K/V reorder of every step, as the replayed chain (pcy_llama_beam_steps).  One launch per step vs the
-    seven launches per layer: tokens, running scores, the parent chain and the logits record equal."""
+    seven launches per layer: tokens, running scores, the parent chain and the logits record equal.  (PCY_MB_MAX: since the fused step became
+    opt-in this test had compared the launches with themselves -- the dispatch counters found it.)"""
     from procyon_amd.engine import BeamState, Context, GenState
+    monkeypatch.setenv("PCY_MB_MAX", "32")
     torch.manual_seed(10)
     T, steps, beam, group = 120, 14, 10, 2
     emb = (torch.randn(1, T, 4096) * 0.02).to(BF).cuda().repeat(beam, 1, 1).contiguous()
@@ -110,7 +156,8 @@ def test_decode_mb_beam10_loop_bit_identical(eng2, monkeypatch):
         rec[0].copy_(logits)
         eng2.beam_step(logits.contiguous(), bs, group, 0.8)
         eng2.kv_reorder(cache, bs.src, T)
-        eng2.beam_steps(cache, st, bs, group, 0.8, rec, steps - 1)
+        with served_by("step_mb" if step else "loop_mfma"):      # (a replayed chain: its capture counts)
+            eng2.beam_steps(cache, st, bs, group, 0.8, rec, steps - 1)
         out, n = bs.tokens()
         Context.get().sync()
         return out.cpu(), bs.cur.cpu().clone(), bs.anc[:n].cpu().clone(), rec[:n].cpu()
@@ -233,12 +280,10 @@ def test_beam_search_reorders_only_the_suffix(monkeypatch):
                 assert torch.equal(x, y), (beam, group)
 
 
-@pytest.mark.parametrize("T,N", [(40, 6), (300, 6), (764, 8), (1100, 4)])
-def test_split_decode_step_bit_identical(monkeypatch, T, N):
-    """ProCyon-Split's decoder (Llama-2-7B geometry: 32 kv heads, ffn 11008; /root/reference/README.md:50-51) at one row: every layer of a decode
-    step in ONE launch (decode_step_mha_kernel, pcy_decode_mha.hip) against one launch per layer (PCY_DISABLE=decode_step) and against the
-    launch-per-stage step (PCY_DISABLE=decode_step,decode_layer: streaming GEMVs in the rotated k order, 64-column attention workgroups), launched
-    one by one and replayed: logits, tokens and the appended K / V rows EQUAL -- across the key-split threshold of the attention (768 keys)."""
+_SPLIT_KIND = {"": "step_mha", "decode_step": "layer", "decode_step,decode_layer": "loop_stream"}    # what serves a one-row Split step under PCY_DISABLE=<key>
+
+
+def _split_step_twins(monkeypatch, T, N, cap=0):
     from procyon_amd import synth
     from procyon_amd.engine import Context, GenState, LlamaConfig, LlamaEngine
     kw = dict(vocab=4096, d=4096, n_layers=2, n_heads=32, n_kv_heads=32, ffn=11008)
@@ -248,15 +293,18 @@ def test_split_decode_step_bit_identical(monkeypatch, T, N):
 
     def run(off, use_graph):
         pcy_disable(monkeypatch, *[o for o in off.split(",") if o])
-        cache = eng.new_cache(1, T + N + 2)
+        cache = eng.new_cache(1, cap or T + N + 2)
         st = GenState(1, kw["vocab"], N + 2, "cuda")
         logits, _ = eng.prefill(emb, None, cache, "last")
         st.logits.copy_(logits); st.pos.fill_(T)
         eng.pick(cache, st, 1, advance_pos=False)
         out = []
-        for _ in range(N):
-            eng.greedy_steps(cache, st, 1, 1, use_graph=use_graph)
-            out.append(st.logits.clone())
+        # every eager step on the kernel its side names -- the one-launch step may decline at launch time and the launches would then be
+        # compared with themselves (a replayed run counts its capture only)
+        with served_by(_SPLIT_KIND[off], None if use_graph else N):
+            for _ in range(N):
+                eng.greedy_steps(cache, st, 1, 1, use_graph=use_graph)
+                out.append(st.logits.clone())
         Context.get().sync()
         return torch.stack(out).cpu(), st.tokens_out[:, :N + 1].cpu(), cache.k[:, :, :, T:T + N].cpu(), cache.v[:, :, :, T:T + N].cpu()
 
@@ -266,6 +314,24 @@ def test_split_decode_step_bit_identical(monkeypatch, T, N):
         got = run(off, g)
         for x, y in zip(got, ref):
             assert torch.equal(x, y), (off, g)
+
+
+@pytest.mark.parametrize("T,N", [(40, 6), (300, 6), (764, 8), (1100, 4)])
+def test_split_decode_step_bit_identical(monkeypatch, T, N):
+    """ProCyon-Split's decoder (Llama-2-7B geometry: 32 kv heads, ffn 11008; /root/reference/README.md:50-51) at one row: every layer of a decode
+    step in ONE launch (decode_step_mha_kernel, pcy_decode_mha.hip) against one launch per layer (PCY_DISABLE=decode_step) and against the
+    launch-per-stage step (PCY_DISABLE=decode_step,decode_layer: streaming GEMVs in the rotated k order, 64-column attention workgroups), launched
+    one by one and replayed: logits, tokens and the appended K / V rows EQUAL -- across the key-split threshold of the attention (768 keys).
+    The dispatch counters say that each side ran what it names."""
+    _split_step_twins(monkeypatch, T, N)
+
+
+@pytest.mark.parametrize("T,cap", [(765, 2048), (1900, 2048)])
+def test_split_decode_step_at_a_long_cache(monkeypatch, T, cap):
+    """The same with a cache of 2048 slots (the attention's LDS image follows the cache CAPACITY: 4 bytes per slot beside 22 KB of MLP
+    staging, far below the 160 KB at which the launcher declines): 8 steps that walk over the key split at 768 keys inside a long cache, and
+    8 steps near its end.  The multi-head step must serve every eager step -- no coverage limit up to the 4096 positions of the model."""
+    _split_step_twins(monkeypatch, T, 8, cap)
 
 
 def test_split_decode_step_against_the_oracle(monkeypatch):
@@ -288,9 +354,10 @@ def test_split_decode_step_against_the_oracle(monkeypatch):
     st.logits.copy_(logits); st.pos.fill_(T)
     eng.pick(cache, st, 1, advance_pos=False)
     out = [logits.float().cpu()]
-    for _ in range(N):
-        eng.greedy_steps(cache, st, 1, 1)
-        out.append(st.logits.float().cpu())
+    with served_by("step_mha"):        # (replayed steps: the capture counts)
+        for _ in range(N):
+            eng.greedy_steps(cache, st, 1, 1)
+            out.append(st.logits.float().cpu())
     Context.get().sync()
     tok = st.tokens_out[:, :N + 1].cpu()
     geom = LR.LlamaGeom(**kw, max_pos=512)

@@ -293,3 +293,20 @@ def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_logits_sample(tmp_pa
     small = torch.randn(1, 1, 4, 1000).bfloat16()                 # below the sample size: the whole record, in order
     bench.dump_outputs(str(tmp_path / "c"), toks, lp, small)
     assert np.array_equal(np.load(tmp_path / "c" / "logits.npy"), small.float().reshape(-1).numpy())
+
+
+def test_dispatch_counter_kinds_mirror_the_header():
+    """procyon_amd/_lib.py restates the PCY_DISPATCH_* enum of csrc/pcy_internal.h by hand (DISPATCH_*, DISPATCH_DECODE): every kind the
+    header names must carry the same number on the Python side, and the decode-step kinds the tests read through `served_by` must all exist --
+    a counter read at a shifted index would make those tests assert on another kernel's launches."""
+    import os
+    import re
+    from procyon_amd import _lib as L
+    src = open(os.path.join(os.path.dirname(L.__file__), "csrc", "pcy_internal.h")).read()
+    enum = dict((k, int(v)) for k, v in re.findall(r"PCY_DISPATCH_(\w+) = (\d+)", src))
+    n = enum.pop("N")
+    assert sorted(enum.values()) == list(range(n))
+    for name, val in enum.items():
+        assert getattr(L, "DISPATCH_" + name) == val, name
+    dec = {k: v for k, v in enum.items() if k.startswith("DEC_")}
+    assert sorted(L.DISPATCH_DECODE.values()) == sorted(dec.values()) and len(dec) == 7
