@@ -723,14 +723,11 @@ bool launch_attn_o_rw(hipStream_t s, PcyDecAttnArgs a, const PcyGemvArgs& o, int
   const int rw = (o.N + n_o * 8 - 1) / (n_o * 8);
   if (rw > 4) return false;
   a.o_sc1 = 1;
-  // key split between the slice workgroups from PCY_AO_XMIN cached keys on (0 = never; read per call so that tests can compare):
+  // key split between the slice workgroups from a.xmin cached keys on (PCY_AO_XMIN through the caller's switch snapshot; 0 = never):
   // the exchange costs ~3 us per layer (eight gather loads per thread in flight; ~4 us with a load -> LDS store pair per
   // iteration), the K reads it saves 9 ns per key -- measured decode step at t ~ 540 / 660 / 1700 / 3100: 3.228 / 3.264 / 3.67 /
   // 4.29 ms without, 3.238 / 3.262 / 3.44 / 3.92 ms with the split; on from 768 keys
-  const char* xe = getenv("PCY_AO_XMIN");
-  const int xmin = xe ? atoi(xe) : 768;
-  a.xflags = (xmin > 0 && a.scratch) ? xflags : nullptr;
-  a.xmin = xmin;
+  a.xflags = (a.xmin > 0 && a.scratch) ? xflags : nullptr;
   a.unit_map = 1;
   // The attention issues all of its cache reads (<= 1024 keys) in its first microsecond; 33.5 MB of weight reads queued at
   // the same moment delay them (attention workgroups alone 15.2 us, beside the immediate weight stream 17.9 us).  The o
@@ -1031,10 +1028,7 @@ bool launch_decode_layer(hipStream_t s, PcyDecAttnArgs a, const PcyAttnBlockArgs
   // the MLP body: same geometry conditions as pcy_launch_mlp_chain
   if (mc.d != p.d || mc.d != 2 * 256 * 8 || mc.F != 2 * 7 * 1024) return false;
   a.o_sc1 = 0;
-  const char* xe = getenv("PCY_AO_XMIN");   // key split between the slice workgroups (see launch_attn_o_rw)
-  const int xmin = xe ? atoi(xe) : 768;
-  a.xflags = (xmin > 0 && a.scratch) ? xflags : nullptr;
-  a.xmin = xmin;
+  a.xflags = (a.xmin > 0 && a.scratch) ? xflags : nullptr;   // key split between the slice workgroups (see launch_attn_o_rw)
   a.unit_map = 1;
   const size_t stage_off = (attn_dec_smem_bytes(G, 16, DH, a.Tmax) + 15) & ~(size_t)15;
   const size_t smem_attn = stage_off + (size_t)(G + 2) * DH * 2, smem_o = (size_t)(2 * p.d + a.H * DH) * 2 + 512;

@@ -468,10 +468,7 @@ bool pcy_launch_decode_mha(hipStream_t s, PcyDecAttnArgs a, const PcyAttnBlockAr
   if (a.B != 1 || a.dbg || !pcy_decode_mha_covers(p.d, a.H, a.Hkv, a.dh, mc.F, n_cu) || mc.d != p.d || p.Nq != 3 * 4096) return false;
   if (st && st->n_layers < 1) return false;
   a.o_sc1 = 0;
-  const char* xe = getenv("PCY_AO_XMIN");   // key split between the two slice workgroups of a head (see launch_attn_o_rw)
-  const int xmin = xe ? atoi(xe) : 768;
-  a.xflags = (xmin > 0 && a.scratch) ? xflags : nullptr;
-  a.xmin = xmin;
+  a.xflags = (a.xmin > 0 && a.scratch) ? xflags : nullptr;   // key split between the two slice workgroups of a head (see launch_attn_o_rw)
   a.unit_map = 1;
   const size_t stage_off = (attn_dec_smem_bytes(1, MH_DS, MH_DH, a.Tmax) + 15) & ~(size_t)15;
   const size_t smem_attn = stage_off + (size_t)3 * MH_DH * 2, smem_o = (size_t)MH_OFF_ACT;

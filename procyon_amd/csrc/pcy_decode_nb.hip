@@ -715,13 +715,12 @@ NbLaunchCache g_nb_cache[16][9][2];   // [device][NB][UB - 1]
 
 template <int NB, int UB>
 bool launch_nb_ub(hipStream_t s, int device, PcyDecAttnArgs a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc, const PcyDecodeStepArgs& st,
-               const unsigned* step_epoch, int n_cu, int xmin) {
+               const unsigned* step_epoch, int n_cu) {
   constexpr int DH = 128, G = 4, DS = NbGeom<NB>::DS, SLICES = NbGeom<NB>::SLICES;
   constexpr int n_attn = 64;   // (units beyond SLICES x Hkv x NB idle through the attention phase)
   static_assert(SLICES * 8 * NB <= 128, "attention units");
   a.o_sc1 = 0;
-  a.xflags = (xmin > 0 && a.scratch && SLICES > 1) ? a.xflags : nullptr;
-  a.xmin = xmin;
+  a.xflags = (a.xmin > 0 && a.scratch && SLICES > 1) ? a.xflags : nullptr;
   a.unit_map = 1;
   const size_t stage_off = (attn_dec_smem_bytes(G, DS, DH, a.Tmax) + 15) & ~(size_t)15;
   const size_t smem_attn = stage_off + (size_t)(G + 2) * DH * 2, smem_body = (size_t)NB * 16384 + 4096;
@@ -747,14 +746,12 @@ bool launch_nb_ub(hipStream_t s, int device, PcyDecAttnArgs a, const PcyAttnBloc
   return true;
 }
 
-// UB = k-iterations per weight batch of the MLP streams (two batches in flight per wave: 16 or 32 KB); PCY_NB_UB=1|2 overrides (measurement)
+// ub = k-iterations per weight batch of the MLP streams (two batches in flight per wave: 16 or 32 KB); 2 unless PCY_NB_UB=1 (measurement)
 template <int NB>
 bool launch_nb(hipStream_t s, int device, PcyDecAttnArgs a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc, const PcyDecodeStepArgs& st,
-               const unsigned* step_epoch, int n_cu, int xmin) {
-  const char* e = getenv("PCY_NB_UB");
-  const int ub = e ? atoi(e) : 2;
-  if (ub == 1) return launch_nb_ub<NB, 1>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-  return launch_nb_ub<NB, 2>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
+               const unsigned* step_epoch, int n_cu, int ub) {
+  if (ub == 1) return launch_nb_ub<NB, 1>(s, device, a, p, mc, st, step_epoch, n_cu);
+  return launch_nb_ub<NB, 2>(s, device, a, p, mc, st, step_epoch, n_cu);
 }
 
 }  // namespace
@@ -766,23 +763,24 @@ int pcy_decode_nb_ds(int B) { return B <= 1 ? 16 : B == 2 ? 32 : 64; }
 
 // All decoder layers of a decode step for 2 <= B <= 8 rows in one launch.  Geometry: Llama-3-8B (d = 4096, ffn = 14336, 32 / 8 heads of
 // 128), 256 CUs.  false = not covered, nothing launched.  st.tags / st.tag_stride / st.x_lines follow pcy_decode_nb_tag_words /
-// pcy_decode_nb_line_words of B rows; p.epoch = the tag counter of THIS batch size's slots.
+// pcy_decode_nb_line_words of B rows; p.epoch = the tag counter of THIS batch size's slots; a.xmin = cache length from which the slice
+// workgroups split the keys; ub = PcySwitches::nb_ub.
 bool pcy_launch_decode_step_nb(hipStream_t s, int device, const PcyDecAttnArgs& a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc,
-                               const PcyDecodeStepArgs& st, int n_cu, const unsigned* step_epoch, int B, int xmin) {
+                               const PcyDecodeStepArgs& st, int n_cu, const unsigned* step_epoch, int B, int ub) {
   if (B < 1 || B > 8 || a.B != B || a.dh != 128 || a.H != 32 || a.Hkv != 8 || a.dbg || n_cu < 256 || st.n_layers < 0) return false;
   if (p.d != NBD || p.Nq != NBNQ || mc.d != NBD || mc.F != NBF) return false;
 #ifdef PCY_NB_ONLY   // (experiments: one instantiation)
-  return B == PCY_NB_ONLY ? launch_nb<PCY_NB_ONLY>(s, device, a, p, mc, st, step_epoch, n_cu, xmin) : false;
+  return B == PCY_NB_ONLY ? launch_nb<PCY_NB_ONLY>(s, device, a, p, mc, st, step_epoch, n_cu, ub) : false;
 #else
   switch (B) {
-    case 1: return launch_nb<1>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 2: return launch_nb<2>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 3: return launch_nb<3>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 4: return launch_nb<4>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 5: return launch_nb<5>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 6: return launch_nb<6>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    case 7: return launch_nb<7>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
-    default: return launch_nb<8>(s, device, a, p, mc, st, step_epoch, n_cu, xmin);
+    case 1: return launch_nb<1>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 2: return launch_nb<2>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 3: return launch_nb<3>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 4: return launch_nb<4>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 5: return launch_nb<5>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 6: return launch_nb<6>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    case 7: return launch_nb<7>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
+    default: return launch_nb<8>(s, device, a, p, mc, st, step_epoch, n_cu, ub);
   }
 #endif
 }
@@ -790,7 +788,7 @@ bool pcy_launch_decode_step_nb(hipStream_t s, int device, const PcyDecAttnArgs& 
 // Would pcy_launch_decode_step_nb launch for this batch size and cache capacity on this device?  (LDS of the attention phase grows with Tmax;
 // every workgroup must be resident.)  The engine asks BEFORE it commits a step to the small-batch arithmetic: an uncovered shape takes the
 // round-4 launches (MFMA GEMVs), not the twin's forced streaming kernels, and no hand-over counter is advanced for a step that never runs.
-bool pcy_decode_nb_launchable(int device, int B, int Tmax, int n_cu) {
+bool pcy_decode_nb_launchable(int device, int B, int Tmax, int n_cu, int ub) {
   PcyDecAttnArgs a{};
   a.B = B; a.dh = 128; a.H = 32; a.Hkv = 8; a.Tmax = Tmax;
   PcyAttnBlockArgs p{};
@@ -799,5 +797,5 @@ bool pcy_decode_nb_launchable(int device, int B, int Tmax, int n_cu) {
   mc.d = NBD; mc.F = NBF;
   PcyDecodeStepArgs st{};
   st.n_layers = 0;
-  return pcy_launch_decode_step_nb(nullptr, device, a, p, mc, st, n_cu, nullptr, B, 0);
+  return pcy_launch_decode_step_nb(nullptr, device, a, p, mc, st, n_cu, nullptr, B, ub);
 }

@@ -40,6 +40,27 @@ void pcy_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// EVERYTHING a captured decode step (or beam-search step) was derived from, each value in a field of its own: every pointer of the state /
+// cache / model the enqueue functions read AND the geometry (an allocator may hand a new state or a cache of another capacity the
+// addresses of the previous one while e.g. the `keep` mask or the token buffer differ -- a stale graph would then run with dangling
+// arguments), the context's buffers that are baked into the launches, and the switch snapshot the launches were chosen under.  Zero-filled
+// before it is filled in (decode_graph_key) and compared with memcmp: no packing, no hashing.
+struct DecodeGraphKey {
+  int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps)
+  int B;
+  PcySwitches sw;
+  const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
+  int Tmax, kv_B;
+  const void *ws, *mc_tags, *mb_flags, *nb_tags, *dev_layers;
+  uint64_t layers_fp;
+  const void *tokens_out, *logprob, *logits_all;   // kinds 0 and 1
+  int logits_all_ld, max_steps;
+  pcy_beam_state beam_state;                       // kind 2: every array of the beam state is baked into the chain
+  const void *logits_rec, *beam_ws;
+  int beam, group_size, kv_t0;
+  uint32_t penalty_bits;
+};
+
 struct pcy_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -49,11 +70,7 @@ struct pcy_ctx {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // captured decode step
   hipGraphExec_t graph = nullptr;
-  static constexpr int GRAPH_KEY_N = 19;
-  const void* graph_key[GRAPH_KEY_N] = {};
-  int graph_B = 0;
-  long long graph_mode = 0;
-  int graph_kind = 0;                 // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps)
+  DecodeGraphKey graph_key = {};      // what `graph` was captured for (meaningful while graph != nullptr)
   int n_cu = 0;
   // sticky error word: a cross-workgroup hand-over inside a launch hit its watchdog.  PINNED HOST memory (device-visible): the
   // kernels store it with system scope, every ABI entry looks at it without touching the stream (take_sticky_error below)
@@ -64,7 +81,7 @@ struct pcy_ctx {
   uint32_t* mc_tags = nullptr;
   const void* mc_tags_model = nullptr;
   size_t mc_tags_words = 0;
-  long long mc_tags_mode = -1;
+  PcySwitches mc_tags_sw = {};        // the switch snapshot the slots were last zeroed under
   uint64_t layers_fp = 0;              // fingerprint of the weight pointers dev_layers was built from
   PcyLayerWeightsDev* dev_layers = nullptr;   // device copy of the layers' weight pointers (decode_step_kernel)
   // small-batch decode step (pcy_decode_nb.hip): hand-over slots and tag counter PER BATCH SIZE (a slot is rewritten in every step of its
@@ -179,82 +196,38 @@ void linear(hipStream_t s, const bf16_t* A, int lda, const bf16_t* W, const bf16
 }
 
 // ------------------------------------------------------------------ decode step (enqueue only)
-struct DecodeWs { bf16_t *x, *qkv, *ao, *act; };
-
-// PCY_DISABLE=attn_o switches the fused attention + o-projection launch of the layered decode step off (default on; batch 1,
-// head_dim 128, d = 4096): 3.35 -> 3.28 ms/token.  PCY_DISABLE=attn_o: the two launches (pcy_switch.h).
-bool attn_o_enabled() { return !pcy_off("attn_o"); }
-// PCY_DISABLE=mlp_chain: pcy_decode_mlp runs the two GEMV launches instead of mlp_chain_kernel.  PCY_DISABLE=decode_layer: the batch-1
-// decode step runs launch by launch (qkv GEMV, attention + o, gate/up, down) instead of one decode_layer_kernel per layer.  Both are
-// read on every call: tests compare the paths in one process (bit-identical).
-unsigned long long* g_mc_trace = nullptr;
-bool mlp_chain_enabled() { return !pcy_off("mlp_chain"); }
-bool decode_layer_enabled() { return !pcy_off("decode_layer"); }
-// PCY_DISABLE=decode_step: one launch per decoder layer instead of one for all layers (decode_step_kernel); bit-identical
-bool decode_step_enabled() { return !pcy_off("decode_step"); }
-// (round 3 had everything of a batched-decode layer behind the attention as one launch with grid barriers: bit-identical, 133 us per
-// layer against 110 us launch by launch at batch 32 -- a grid barrier under a saturated memory system costs ~10 us, more than the kernel
-// boundary it replaces; removed in round 4, numbers in DESIGN.md)
-bool qkv_finish_launch() { return pcy_off("attn_qkv_finish"); }   // the qkv K-split finish as its own launch instead of inside the attention's
-// PCY_DISABLE=decode_nb: batches of 2..8 rows take the pre-round-5 path (streaming GEMVs below 4 rows, MFMA GEMVs from 4 on) instead of the
-// small-batch step (pcy_decode_nb.hip).  PCY_DISABLE=decode_nb_step: its launch-per-stage twin (gemv_stream_kernel + attn_dec_kernel with the
-// same column slices) instead of the one launch -- same bits, tests compare the two.
-bool decode_nb_enabled() { return !pcy_off("decode_nb"); }
-bool decode_nb_step_enabled() { return !pcy_off("decode_nb_step"); }
-// PCY_DISABLE=decode_mb_step: batches of 9..32 rows run launch by launch (seven per layer) instead of the mid-batch step (pcy_decode_mb.hip:
-// the same work items as phases of ONE launch) -- same bits, tests compare the two.
-bool decode_mb_step_enabled() { return !pcy_off("decode_mb_step"); }
-// ... for the small-batch step: the exchange costs more there than the K reads it saves until much longer caches (t ~ 800: 2 / 4 rows
-// 2.935 / 3.385 ms per step with the split, 2.868 / 3.287 without; t ~ 1540: 3.158 / 3.653 with, 3.180 / 3.632 without)
-int decode_xmin_nb(int B) {
-  const char* xe = getenv("PCY_AO_XMIN");
-  return xe ? atoi(xe) : (B == 2 ? 1536 : 4096);
-}
-int decode_xmin() {   // cached keys from which the decode attention splits its keys across the slice workgroups (read per call: tests compare)
-  const char* xe = getenv("PCY_AO_XMIN");
-  return xe ? atoi(xe) : 768;
-}
-
+// The switches a decode step depends on arrive as ONE snapshot (PcySwitches, pcy_switch.h), taken by the ABI entry; nothing below reads the
+// environment.  What each PCY_DISABLE name selects here (every twin has the same bits unless noted; tests compare them in one process):
+//   attn_o           the decode attention and the o projection as two launches instead of one (batch 1, head_dim 128, d = 4096: 3.35 -> 3.28 ms/token fused)
+//   decode_layer     the batch-1 step launch by launch (qkv GEMV, attention + o, gate/up, down) instead of one decode_layer_kernel per layer
+//   decode_step      one launch per decoder layer instead of one for all layers (decode_step_kernel)
+//   attn_qkv_finish  the qkv K-split finish as its own launch instead of inside the attention's
+//   decode_nb        batches of 2..8 rows on the pre-round-5 path (streaming GEMVs below 4 rows, MFMA GEMVs from 4 on: ANOTHER arithmetic) instead
+//                    of the small-batch step (pcy_decode_nb.hip);  decode_nb_step: its launch-per-stage twin (gemv_stream_kernel + attn_dec_kernel
+//                    with the same column slices) instead of the one launch
+//   decode_mb_step   batches of 9..32 rows launch by launch (seven per layer) instead of the mid-batch step (pcy_decode_mb.hip: the same work items
+//                    as phases of ONE launch)
+// PCY_AO_XMIN (PcySwitches::ao_xmin): the key split's exchange costs more on the small-batch step than the K reads it saves until much longer
+// caches (t ~ 800: 2 / 4 rows 2.935 / 3.385 ms per step with the split, 2.868 / 3.287 without; t ~ 1540: 3.158 / 3.653 with, 3.180 / 3.632 without).
+//
 // The mid-batch step is OFF by default (round 6): bit-identical to the launches, and -- once the launches' GEMVs walk their K ranges in rotated
 // order (pcy_gemv_kshift) -- no faster: 3.98 / 4.17 ms per step at 10 / 16 rows against 3.88 / 4.02 launch by launch, 4.8 / 5.1 against 4.1 / 4.3
 // at 20 / 32 rows (two batch tiles double the activation bytes every CU fetches per weight byte).  Its streaming phases run at the HBM rate
 // (G 6.3 TB/s, D 6.1); what it loses is the Q / O phases (16 / 8 tiles per wave against a ring of 7: two memory round trips whatever the
 // prefetch) and the flag hops.  PCY_MB_MAX=<rows> (9..32) runs it up to that batch size: tests, tools/bench_decode_mb.py.
-int decode_mb_max_rows() {
-  const char* e = getenv("PCY_MB_MAX");
-  const int v = e ? atoi(e) : 0;
-  return v < 0 ? 0 : v > 32 ? 32 : v;
-}
-int decode_nb_max_rows();
-int decode_mode_lo();
-// (PCY_MB_MAX clamped to 0..32 where it is read; PCY_NB_MAX in bits of its own above the 32 others: `& 3` took 2 for 6 and 3 for 7, and a test
-// that switches them inside one process would have been handed the other value's captured graph and hand-over buffers)
-long long decode_mode() {
-  const int nb = decode_nb_max_rows();
-  return ((long long)(nb < 0 ? 0 : nb) << 32) | (long long)(unsigned)decode_mode_lo();
-}
-int decode_mode_lo() {
-  return (pcy_off("kv_permute") ? 2048 : 0) | (attn_o_enabled() ? 2 : 0) | (decode_layer_enabled() ? 32 : 0) | (decode_step_enabled() ? 64 : 0) | (qkv_finish_launch() ? 128 : 0) |
-         (pcy_off("lds_prefetch") ? 256 : 0) | (decode_nb_enabled() ? 512 : 0) | (decode_nb_step_enabled() ? 1024 : 0) | (decode_mb_step_enabled() ? 4096 : 0) | (decode_mb_max_rows() << 16) |
-         (int)((((unsigned)decode_xmin() * 2654435761u) ^ ((unsigned)decode_xmin_nb(2) * 40503u) ^ ((unsigned)decode_xmin_nb(4) * 69069u)) & 0x3fu) << 22;
-}
+unsigned long long* g_mc_trace = nullptr;
 constexpr int AO_MAX_LAYERS = 128, AO_FLAGS = 64;
 // geometry of the small-batch step: Llama-3-8B, 256 CUs
 // (7 and 8 rows: since the batched launches walk their K ranges in rotated order, ask for their finish loads at once and cut the attention
 // into 64-column workgroups from 4 rows on, they take 3.69 / 3.70 ms per step against the fused step's 3.81 / 3.97 -- the fused step stops
 // at 6 rows (3.65 against 3.69); PCY_NB_MAX=7 / 8 runs it there all the same: tests, tools)
-int decode_nb_max_rows() {
-  const char* e = getenv("PCY_NB_MAX");
-  const int v = e ? atoi(e) : 6;
-  return v < 8 ? v : 8;
-}
-bool decode_nb_covers(const pcy_ctx* c, const pcy_llama_desc* m, int B) {
-  return B >= 2 && B <= decode_nb_max_rows() && m->d == 4096 && m->ffn == 14336 && m->n_heads == 32 && m->n_kv_heads == 8 && m->head_dim == 128 &&
+bool decode_nb_covers(const pcy_ctx* c, const pcy_llama_desc* m, int B, const PcySwitches& sw) {
+  return B >= 2 && B <= sw.nb_max && m->d == 4096 && m->ffn == 14336 && m->n_heads == 32 && m->n_kv_heads == 8 && m->head_dim == 128 &&
          c->n_cu >= 256 && m->n_layers <= AO_MAX_LAYERS / 2;   // (score-exchange flags: 2 x AO_FLAGS words per layer)
 }
 // geometry of the mid-batch step (9..32 rows): the same model and chip
-bool decode_mb_covers(const pcy_ctx* c, const pcy_llama_desc* m, int B) {
-  return B >= 9 && B <= 32 && B <= decode_mb_max_rows() && m->d == 4096 && m->ffn == 14336 && m->n_heads == 32 && m->n_kv_heads == 8 && m->head_dim == 128 && c->n_cu >= 256;
+bool decode_mb_covers(const pcy_ctx* c, const pcy_llama_desc* m, int B, const PcySwitches& sw) {
+  return B >= 9 && B <= 32 && B <= sw.mb_max && m->d == 4096 && m->ffn == 14336 && m->n_heads == 32 && m->n_kv_heads == 8 && m->head_dim == 128 && c->n_cu >= 256;
 }
 // tagged vectors of one layer: act [ffn], qkv [(H + 2 Hkv) dh], attention output [H dh], x after o [d]
 size_t tag_words_per_layer(const pcy_llama_desc* m) {
@@ -291,16 +264,16 @@ uint64_t layers_fingerprint(const pcy_llama_desc* m) {   // FNV-1a over every we
   }
   return h;
 }
-int ensure_decode_state(pcy_ctx* c, const pcy_llama_desc* m, int B = 1) {
+int ensure_decode_state(pcy_ctx* c, const pcy_llama_desc* m, int B, const PcySwitches& sw) {
   if (int r = ensure_sync_words(c)) return r;
   // A tagged word counts as delivered when its tag equals the chain epoch, so the slots must never hold anything but words of
   // earlier chain launches OF THE SAME LAYOUT: another model -> zeroed slots and a restarted epoch (next tag 1).
-  // (a change of the launch mix as well: a slot the new mix reads may not have been rewritten for a while)
+  // (a change of the switch snapshot as well: a slot the new launch mix reads may not have been rewritten for a while)
   // "Another model" is decided on the weight POINTERS, not on the descriptor's address: a new engine of the same geometry may
   // get the address of a freed descriptor, and a descriptor may be mutated in place -- either would leave dev_layers stale.
   const size_t words = (size_t)m->n_layers * (tag_words_per_layer(m) + 32 * 256);   // + the residual stream between the layers, one line per workgroup
   const uint64_t fp = layers_fingerprint(m);
-  if (c->mc_tags_model != m || c->mc_tags_words != words || c->mc_tags_mode != decode_mode() || c->layers_fp != fp) {
+  if (c->mc_tags_model != m || c->mc_tags_words != words || c->mc_tags_sw != sw || c->layers_fp != fp) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->drop_graph();   // a captured step holds mc_tags / dev_layers as kernel arguments
     if (c->mc_tags) HIP_TRY(hipFree(c->mc_tags));
@@ -318,9 +291,9 @@ int ensure_decode_state(pcy_ctx* c, const pcy_llama_desc* m, int B = 1) {
       lw[l] = {(const bf16_t*)L.ln1, (const bf16_t*)L.wqkv, (const bf16_t*)L.wo, (const bf16_t*)L.ln2, (const bf16_t*)L.wgu, (const bf16_t*)L.wdown};
     }
     HIP_TRY(hipMemcpy(c->dev_layers, lw.data(), lw.size() * sizeof(PcyLayerWeightsDev), hipMemcpyHostToDevice));
-    c->mc_tags_model = m; c->mc_tags_words = words; c->mc_tags_mode = decode_mode(); c->layers_fp = fp;
+    c->mc_tags_model = m; c->mc_tags_words = words; c->mc_tags_sw = sw; c->layers_fp = fp;
   }
-  if (decode_nb_enabled() && decode_nb_covers(c, m, B) && !c->nb_tags[B]) {
+  if (!sw.off(PCY_SW_decode_nb) && decode_nb_covers(c, m, B, sw) && !c->nb_tags[B]) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (!c->nb_sync) {
       HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->nb_sync), 16 * sizeof(unsigned)));
@@ -331,7 +304,7 @@ int ensure_decode_state(pcy_ctx* c, const pcy_llama_desc* m, int B = 1) {
     HIP_TRY(hipMemset(c->nb_tags[B], 0, nbw * 4));
     HIP_TRY(hipMemset(c->nb_sync + B, 0, 4));   // zeroed slots, next tag 1
   }
-  if (decode_mb_covers(c, m, B)) {
+  if (decode_mb_covers(c, m, B, sw)) {
     const size_t fw = (size_t)(m->n_layers + 1) * pcy_decode_mb_flag_words();
     if (!c->mb_sync) {
       HIP_TRY(hipStreamSynchronize(c->stream));
@@ -359,197 +332,231 @@ size_t decode_ws_bytes(const pcy_llama_desc* m, int B, int Tmax) {
          align_up((size_t)B * m->d * 2, 256) + (B >= pcy_mfma_min_batch() ? align_up((size_t)8 * B * qkvw * 4, 256) : 0) + 4096;
 }
 
-// layers_only (measurement, pcy_llama_decode_layers): the decoder layers without the token embedding (the residual stream is whatever
-// the workspace holds) and without lm_head; the hand-over counters are advanced by two one-thread launches instead.
-void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool layers_only = false) {
-  hipStream_t s = c->stream;
-  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
-  const int qkvw = (H + 2 * Hkv) * dh;
-  Carver cv(c->ws);
-  bf16_t* x = cv.take<bf16_t>((size_t)B * d);
-  bf16_t* qkv = cv.take<bf16_t>((size_t)B * qkvw);
-  bf16_t* ao = cv.take<bf16_t>((size_t)B * H * dh);
-  bf16_t* act = cv.take<bf16_t>((size_t)B * F);
-  float* scores = cv.take<float>((size_t)B * H * (kv->Tmax + 1));
-  cv.take<char>((size_t)B * 64 * 16);                 // pick partials (same carve as enqueue_pick)
-  bf16_t* xn = cv.take<bf16_t>((size_t)B * d);        // normalised x for the batched (MFMA) GEMV path
-  const size_t sk_bytes = B >= pcy_mfma_min_batch() ? (size_t)8 * B * qkvw * 4 : 0;   // K-split partial sums of the batched GEMVs
-  float* sk_ws = sk_bytes ? cv.take<float>(sk_bytes / 4) : nullptr;
-  const bool batched_head = B >= pcy_mfma_min_batch() && d % 128 == 0 && F % 128 == 0;   // skinny-MFMA GEMVs, 32 rows per pass over the weights
-                                                                                         // (F = 11008, Llama-2-7B / ProCyon-Split: 86 x 128)
-  // 2..8 rows: the small-batch step (pcy_decode_nb.hip) -- one launch for all layers, or its launch-per-stage twin; lm_head as before
-  const bool nb_on = decode_nb_enabled() && decode_nb_covers(c, m, B) && c->nb_tags[B] && c->nb_sync && c->dev_layers && c->ao_sync && c->xwg_err &&
-                     pcy_decode_nb_launchable(c->device, B, kv->Tmax, c->n_cu);
-  const bool batched = batched_head && !nb_on;
-  // 9..32 rows: the mid-batch step (pcy_decode_mb.hip) -- the batched path's work items as phases of one launch
-  const bool mb_step = batched && decode_mb_step_enabled() && decode_mb_covers(c, m, B) && pcy_decode_mb_fits(B, kv->Tmax) && c->mb_flags && c->mb_sync &&
+// The carve of the decode workspace (decode_ws_bytes), in ONE place: the step's launches and the pick / sampling launches behind it agree on it.
+struct DecodeWs {
+  bf16_t *x, *qkv, *ao, *act, *xn;   // (xn: normalised x for the batched (MFMA) GEMV path)
+  float* scores;
+  void* partials;                    // row partials of the greedy pick / the sampling step
+  float* sk_ws; size_t sk_bytes;     // K-split partial sums of the batched GEMVs
+};
+DecodeWs carve_decode_ws(char* base, const pcy_llama_desc* m, int B, int Tmax) {
+  const size_t qkvw = (size_t)(m->n_heads + 2 * m->n_kv_heads) * m->head_dim;
+  Carver cv(base);
+  DecodeWs w{};
+  w.x = cv.take<bf16_t>((size_t)B * m->d);
+  w.qkv = cv.take<bf16_t>((size_t)B * qkvw);
+  w.ao = cv.take<bf16_t>((size_t)B * m->n_heads * m->head_dim);
+  w.act = cv.take<bf16_t>((size_t)B * m->ffn);
+  w.scores = cv.take<float>((size_t)B * m->n_heads * (Tmax + 1));
+  w.partials = cv.take<char>((size_t)B * 64 * 16);
+  w.xn = cv.take<bf16_t>((size_t)B * m->d);
+  w.sk_bytes = B >= pcy_mfma_min_batch() ? (size_t)8 * B * qkvw * 4 : 0;
+  w.sk_ws = w.sk_bytes ? cv.take<float>(w.sk_bytes / 4) : nullptr;
+  return w;
+}
+// What the launches of one decode step share: the workspace and the call's arguments
+struct DecodeCx : DecodeWs {
+  pcy_ctx* c; const pcy_llama_desc* m; const pcy_kv_cache* kv; const pcy_gen_state* st; int B;
+  int qkvw; size_t layer_stride;     // columns of the qkv projection; elements between the K (V) caches of consecutive layers
+};
+DecodeCx decode_cx(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  return DecodeCx{carve_decode_ws(c->ws, m, B, kv->Tmax), c, m, kv, st, B, (m->n_heads + 2 * m->n_kv_heads) * m->head_dim,
+                  (size_t)kv->B * m->n_kv_heads * kv->Tmax * m->head_dim};
+}
+
+// Which launches serve a step: decided once, from the context's state, the geometry, the batch size and the switch snapshot.  `path` is the
+// FIRST path attempted; a launcher that declines at launch time (geometry, residency) hands the step on: the one-launch batch-1 step ->
+// layer launches -> the loop; the small-batch step -> the loop on forced streaming kernels (its twin); the mid-batch step -> the MFMA loop.
+enum DecodePath { DEC_STEP_GQA, DEC_STEP_MHA, DEC_LAYERS, DEC_STEP_NB, DEC_STEP_MB, DEC_LOOP_STREAM, DEC_LOOP_MFMA };
+struct DecodePlan {
+  DecodePath path;
+  bool nb_on;               // 2..8 rows on the small-batch arithmetic (the one launch or its launch-per-stage twin; lm_head as before)
+  bool batched;             // the loop's projections on the skinny-MFMA GEMVs, 32 rows per pass over the weights, fed from xn
+  bool batched_head;        // ... and lm_head (F = 11008, Llama-2-7B / ProCyon-Split: 86 x 128)
+  bool attn_o;              // loop, one row: attention and o projection in one launch (Wo rows wait in registers while the attention runs)
+  bool defer_qkv_finish;    // loop, batched: the attention adds up the K-split partial sums of ITS rows instead of a finish launch (up to 32
+                            // rows: above, the GEMV runs in 32-row passes that share the workspace -- the finish is a launch per pass, same bits)
+  int krot;                 // one row: the projections over d walk their k-iterations rotated (PcyGemvArgs::krot) -- in the streaming launches, in
+                            // the launches that fuse them (attn_o, mlp_chain) and in the one-launch steps alike: one set of bits
+  int force_ds;             // output columns per workgroup of the loop's stand-alone attention: those of the fused step it is the twin of
+  int xmin;                 // cached keys from which the fused launches split the keys across their slice workgroups
+  unsigned* epoch_word;     // sync words this step advances (the embed launch, or one-thread launches for layers_only): the step epoch ...
+  unsigned* tag_word;       // ... and the tag counter of the hand-over slots it uses
+};
+DecodePlan plan_decode(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw) {
+  DecodePlan p{};
+  p.batched_head = B >= pcy_mfma_min_batch() && m->d % 128 == 0 && m->ffn % 128 == 0;
+  p.nb_on = !sw.off(PCY_SW_decode_nb) && decode_nb_covers(c, m, B, sw) && c->nb_tags[B] && c->nb_sync && c->dev_layers && c->ao_sync && c->xwg_err &&
+            pcy_decode_nb_launchable(c->device, B, kv->Tmax, c->n_cu, sw.nb_ub);
+  p.batched = p.batched_head && !p.nb_on;
+  const bool nb_step = p.nb_on && !sw.off(PCY_SW_decode_nb_step);
+  const bool mb_step = p.batched && !sw.off(PCY_SW_decode_mb_step) && decode_mb_covers(c, m, B, sw) && pcy_decode_mb_fits(B, kv->Tmax) && c->mb_flags && c->mb_sync &&
                        c->dev_layers && c->xwg_err && (size_t)(m->n_layers + 1) * pcy_decode_mb_flag_words() <= c->mb_flags_words;
-  const bool try_ao = attn_o_enabled() && B == 1 && c->ao_sync && c->xwg_err && m->n_layers <= AO_MAX_LAYERS;
-  bool try_layer = decode_layer_enabled() && try_ao && c->mc_tags;   // one launch per decoder layer
-  const bool nb_step = nb_on && decode_nb_step_enabled();
-  if (layers_only) {
-    if (try_ao || nb_step) pcy_launch_bump(s, c->ao_sync);
-    if (try_layer) pcy_launch_bump(s, c->ao_sync + 1);
-    if (nb_step) pcy_launch_bump(s, c->nb_sync + B);
-    if (mb_step) pcy_launch_bump(s, c->mb_sync);
+  p.attn_o = !sw.off(PCY_SW_attn_o) && B == 1 && c->ao_sync && c->xwg_err && m->n_layers <= AO_MAX_LAYERS;
+  const bool try_layer = !sw.off(PCY_SW_decode_layer) && p.attn_o && c->mc_tags;
+  // (multi-head geometry, one row: the column split of the fused step's attention workgroups, whatever the launch mix -- one set of bits)
+  const bool mha1 = B == 1 && pcy_decode_mha_covers(m->d, m->n_heads, m->n_kv_heads, m->head_dim, m->ffn, c->n_cu);
+  p.path = nb_step ? DEC_STEP_NB : mb_step ? DEC_STEP_MB
+         : try_layer && !sw.off(PCY_SW_decode_step) && c->dev_layers ? (mha1 ? DEC_STEP_MHA : DEC_STEP_GQA)
+         : try_layer ? DEC_LAYERS : p.batched ? DEC_LOOP_MFMA : DEC_LOOP_STREAM;
+  p.defer_qkv_finish = p.batched && B <= 32 && !p.attn_o && !sw.off(PCY_SW_attn_qkv_finish);
+  p.krot = B == 1 ? 1 : 0;
+  p.force_ds = mha1 ? pcy_decode_mha_ds() : p.nb_on ? pcy_decode_nb_ds(B) : 0;
+  p.xmin = sw.ao_xmin(B);
+  p.epoch_word = (p.attn_o || nb_step) ? c->ao_sync : mb_step ? c->mb_sync : nullptr;
+  p.tag_word = try_layer ? c->ao_sync + 1 : nb_step ? c->nb_sync + B : nullptr;
+  return p;
+}
+
+// measurement aid (PCY_MC_TRACE, tools/bench_decode*.py): in-kernel time stamps, [layer][workgroup][16] behind a first half of the same size
+unsigned long long* mc_trace(const PcySwitches& sw, int l = 0) {
+  if (!sw.mc_trace) return nullptr;
+  if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
+  return g_mc_trace + (size_t)(128 + l) * 256 * 16;
+}
+
+// The argument structs of the decode launches, each built in ONE place.  l = decoder layer, or -1 for a launch that runs all layers (the
+// kernel then applies the per-layer strides and takes the per-layer weights from PcyDecodeStepArgs::layers).
+PcyDecAttnArgs attn_args(const DecodeCx& cx, const DecodePlan& p, int l) {
+  const pcy_llama_desc* m = cx.m;
+  PcyDecAttnArgs t{};
+  t.qkv = cx.qkv; t.ld = cx.qkvw; t.kcache = (bf16_t*)cx.kv->k + (l > 0 ? l : 0) * cx.layer_stride; t.vcache = (bf16_t*)cx.kv->v + (l > 0 ? l : 0) * cx.layer_stride;
+  t.o = cx.ao; t.ldo = m->n_heads * m->head_dim; t.pos_dev = cx.st->pos; t.cos_t = (const bf16_t*)m->rope_cos; t.sin_t = (const bf16_t*)m->rope_sin;
+  t.keep = cx.st->keep; t.ld_keep = cx.kv->Tmax; t.scratch = cx.scores; t.B = cx.B; t.H = m->n_heads; t.Hkv = m->n_kv_heads; t.dh = m->head_dim; t.Tmax = cx.kv->Tmax;
+  t.scale = 1.0f / sqrtf((float)m->head_dim);
+  t.xmin = p.xmin;
+  if (l < 0) t.xflags = cx.c->ao_sync + 64 + AO_MAX_LAYERS * AO_FLAGS;   // (per-layer launches get their flags as a launcher argument)
+  else t.force_ds = p.force_ds;
+  return t;
+}
+// L / tags: the weights and the hand-over slots of the one layer the launch runs (nullptr for all layers in one launch)
+PcyAttnBlockArgs block_args(const DecodeCx& cx, const unsigned* epoch, unsigned long long* trace, const pcy_llama_layer* L = nullptr, uint32_t* tags = nullptr) {
+  const pcy_llama_desc* m = cx.m;
+  PcyAttnBlockArgs bp{};
+  bp.x = cx.x; bp.d = m->d; bp.Nq = cx.qkvw; bp.rms_eps = m->rms_eps; bp.rms_cast = m->rms_cast; bp.epoch = epoch; bp.err = cx.c->xwg_err; bp.trace = trace;
+  if (L) {
+    bp.ln1 = (const bf16_t*)L->ln1; bp.wqkv = (const bf16_t*)L->wqkv; bp.wo = (const bf16_t*)L->wo;
+    bp.qkv_tag = tags + m->ffn; bp.ao_tag = bp.qkv_tag + cx.qkvw; bp.xo_tag = bp.ao_tag + m->n_heads * m->head_dim;
+  }
+  return bp;
+}
+PcyMlpChainArgs mlp_args(const DecodeCx& cx, const unsigned* epoch, const pcy_llama_layer* L = nullptr, uint32_t* tags = nullptr) {
+  const pcy_llama_desc* m = cx.m;
+  PcyMlpChainArgs mc{};
+  mc.x = cx.x; mc.x_out = cx.x; mc.d = m->d; mc.F = m->ffn; mc.rms_eps = m->rms_eps; mc.rms_cast = m->rms_cast; mc.epoch = epoch; mc.err = cx.c->xwg_err;
+  if (L) { mc.ln2 = (const bf16_t*)L->ln2; mc.wgu = (const bf16_t*)L->wgu; mc.wdown = (const bf16_t*)L->wdown; mc.act_tag = tags; }
+  return mc;
+}
+// tags: [n_layers][tag_stride] hand-over slots, then [n_layers][line_stride] words of the residual stream between the layers
+PcyDecodeStepArgs step_args(const DecodeCx& cx, uint32_t* tags, size_t tag_stride, size_t xflags_stride, size_t line_stride) {
+  PcyDecodeStepArgs sa{};
+  sa.layers = cx.c->dev_layers; sa.n_layers = cx.m->n_layers; sa.kv_layer_stride = cx.layer_stride;
+  sa.tags = tags; sa.tag_stride = tag_stride; sa.xflags_stride = xflags_stride;
+  sa.x_lines = tags + (size_t)cx.m->n_layers * tag_stride; sa.x_lines_stride = line_stride;
+  return sa;
+}
+// One projection of the loop: out[B][N] = epi(in[B][K] . W^T).  STORE / SWIGLU read the residual stream through RMSNorm * ln (fused into the
+// streaming launch; batched: xn, which the caller has filled); RESID adds onto the residual stream and, batched up to 32 rows, leaves
+// RMSNorm(x) * ln of the NEXT projection in xn from its K-split finish (*xn_ready = 1 where that happened).
+PcyGemvArgs proj_args(const DecodeCx& cx, const DecodePlan& p, const void* W, const void* ln, const bf16_t* in, int K, bf16_t* out, int N, int epi,
+                      bool splitk, int krot, int* xn_ready) {
+  const pcy_llama_desc* m = cx.m;
+  PcyGemvArgs g{};
+  g.W = (const bf16_t*)W; g.x = in; g.y = out; g.N = N; g.K = K; g.B = cx.B; g.ldx = K; g.ldy = N; g.epi = epi;
+  g.force_stream = p.nb_on; g.krot = krot;
+  if (splitk) { g.splitk_ws = cx.sk_ws; g.splitk_ws_bytes = cx.sk_bytes; }
+  if (epi == EPI_RESID) {
+    g.resid = out;
+    if (p.batched && cx.B <= 32) { g.next_rms_w = (const bf16_t*)ln; g.next_xn = cx.xn; g.fused_next = xn_ready; g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast; }
   } else {
-    pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, x, B, d, (try_ao || nb_step) ? c->ao_sync : (mb_step ? c->mb_sync : nullptr),
-                                try_layer ? c->ao_sync + 1 : (nb_step ? c->nb_sync + B : nullptr));
+    g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast;
+    if (p.batched) g.x = cx.xn; else g.rms_w = (const bf16_t*)ln;
+  }
+  return g;
+}
+
+// layers_only (measurement, pcy_llama_decode_layers): the decoder layers without the token embedding (the residual stream is whatever
+// the workspace holds) and without lm_head; the hand-over counters are advanced by one-thread launches instead.
+void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const PcySwitches& sw, bool layers_only = false) {
+  hipStream_t s = c->stream;
+  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
+  const DecodeCx cx = decode_cx(c, m, kv, st, B);
+  const DecodePlan p = plan_decode(c, m, kv, B, sw);
+  if (layers_only) {
+    if (p.epoch_word) pcy_launch_bump(s, p.epoch_word);
+    if (p.tag_word) pcy_launch_bump(s, p.tag_word);
+  } else {
+    pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d, p.epoch_word, p.tag_word);
   }
   const size_t tag_stride = tag_words_per_layer(m);
-  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
   bool step_done = false;
-  if (nb_step) {
-    PcyDecAttnArgs t{};
-    t.qkv = qkv; t.ld = qkvw; t.kcache = (bf16_t*)kv->k; t.vcache = (bf16_t*)kv->v;
-    t.o = ao; t.ldo = H * dh; t.pos_dev = st->pos; t.cos_t = (const bf16_t*)m->rope_cos; t.sin_t = (const bf16_t*)m->rope_sin;
-    t.keep = st->keep; t.ld_keep = kv->Tmax; t.scratch = scores; t.B = B; t.H = H; t.Hkv = Hkv; t.dh = dh; t.Tmax = kv->Tmax;
-    t.scale = 1.0f / sqrtf((float)dh);
-    t.xflags = c->ao_sync + 64 + AO_MAX_LAYERS * AO_FLAGS;
-    PcyAttnBlockArgs bp{};
-    bp.x = x; bp.d = d; bp.Nq = qkvw; bp.rms_eps = m->rms_eps; bp.rms_cast = m->rms_cast; bp.epoch = c->nb_sync + B; bp.err = c->xwg_err;
-    PcyMlpChainArgs mc{};
-    mc.x = x; mc.x_out = x; mc.d = d; mc.F = F; mc.rms_eps = m->rms_eps; mc.rms_cast = m->rms_cast; mc.epoch = c->nb_sync + B; mc.err = c->xwg_err;
-    PcyDecodeStepArgs sa{};
-    sa.layers = c->dev_layers; sa.n_layers = m->n_layers; sa.kv_layer_stride = layer_stride;
-    sa.tags = c->nb_tags[B]; sa.tag_stride = pcy_decode_nb_tag_words(B); sa.xflags_stride = 2 * AO_FLAGS;   // up to 128 attention units per layer
-    sa.x_lines = c->nb_tags[B] + (size_t)m->n_layers * sa.tag_stride; sa.x_lines_stride = pcy_decode_nb_line_words(B);
-    if (getenv("PCY_MC_TRACE")) {   // measurement aid (tools/bench_decode_nb.py): in-kernel time stamps, [layer][workgroup][16]
-      if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
-      bp.trace = g_mc_trace + (size_t)128 * 256 * 16;
-    }
-    step_done = pcy_launch_decode_step_nb(s, c->device, t, bp, mc, sa, c->n_cu, c->ao_sync, B, decode_xmin_nb(B));
-    if (step_done) ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_NB];
-  }
-  if (try_layer && decode_step_enabled() && c->dev_layers) {   // all layers in one launch
-    PcyDecAttnArgs t{};
-    t.qkv = qkv; t.ld = qkvw; t.kcache = (bf16_t*)kv->k; t.vcache = (bf16_t*)kv->v;
-    t.o = ao; t.ldo = H * dh; t.pos_dev = st->pos; t.cos_t = (const bf16_t*)m->rope_cos; t.sin_t = (const bf16_t*)m->rope_sin;
-    t.keep = st->keep; t.ld_keep = kv->Tmax; t.scratch = scores; t.B = B; t.H = H; t.Hkv = Hkv; t.dh = dh; t.Tmax = kv->Tmax;
-    t.scale = 1.0f / sqrtf((float)dh);
-    t.xflags = c->ao_sync + 64 + AO_MAX_LAYERS * AO_FLAGS;
-    PcyAttnBlockArgs bp{};
-    bp.x = x; bp.d = d; bp.Nq = qkvw; bp.rms_eps = m->rms_eps; bp.rms_cast = m->rms_cast; bp.epoch = c->ao_sync + 1; bp.err = c->xwg_err;
-    PcyMlpChainArgs mc{};
-    mc.x = x; mc.x_out = x; mc.d = d; mc.F = F; mc.rms_eps = m->rms_eps; mc.rms_cast = m->rms_cast; mc.epoch = c->ao_sync + 1; mc.err = c->xwg_err;
-    PcyDecodeStepArgs sa{};
-    sa.layers = c->dev_layers; sa.n_layers = m->n_layers; sa.kv_layer_stride = layer_stride;
-    sa.tags = c->mc_tags; sa.tag_stride = tag_stride; sa.xflags_stride = AO_FLAGS;
-    sa.x_lines = c->mc_tags + (size_t)m->n_layers * tag_stride; sa.x_lines_stride = 32 * 256;
-    if (getenv("PCY_MC_TRACE")) {   // measurement aid (tools/bench_decode.py): in-kernel time stamps, [layer][workgroup][16]
-      if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
-      bp.trace = g_mc_trace + (size_t)128 * 256 * 16;
-    }
-    step_done = pcy_launch_decode_step(s, t, bp, mc, sa, c->n_cu, c->ao_sync);   // (counts its own kind: grouped-query or multi-head)
-  }
+  bool try_layer = p.path == DEC_STEP_GQA || p.path == DEC_STEP_MHA || p.path == DEC_LAYERS;   // one launch per decoder layer (behind a step that declines, too)
   int xn_ready = 0;   // batched path: xn = RMSNorm(x) of the NEXT projection already produced by a fused finish kernel
-  if (mb_step) {
+  if (p.path == DEC_STEP_NB) {   // 2..8 rows, all layers in one launch
+    const PcyDecodeStepArgs sa = step_args(cx, c->nb_tags[B], pcy_decode_nb_tag_words(B), 2 * AO_FLAGS, pcy_decode_nb_line_words(B));   // up to 128 attention units per layer
+    step_done = pcy_launch_decode_step_nb(s, c->device, attn_args(cx, p, -1), block_args(cx, p.tag_word, mc_trace(sw)), mlp_args(cx, p.tag_word), sa, c->n_cu,
+                                          c->ao_sync, B, sw.nb_ub);
+    if (step_done) ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_NB];
+  } else if (p.path == DEC_STEP_GQA || p.path == DEC_STEP_MHA) {   // one row, all layers in one launch
+    const PcyDecodeStepArgs sa = step_args(cx, c->mc_tags, tag_stride, AO_FLAGS, 32 * 256);
+    step_done = pcy_launch_decode_step(s, attn_args(cx, p, -1), block_args(cx, p.tag_word, mc_trace(sw)), mlp_args(cx, p.tag_word), sa, c->n_cu,
+                                       c->ao_sync);   // (counts its own kind: grouped-query or multi-head)
+  } else if (p.path == DEC_STEP_MB) {   // 9..32 rows: the batched path's work items as phases of one launch
     PcyMbArgs ma{};
     ma.layers = c->dev_layers; ma.n_layers = m->n_layers; ma.final_norm = (const bf16_t*)m->final_norm;
-    ma.x = x; ma.xn = xn; ma.ao = ao; ma.act = act;
-    ma.qkv_ws = sk_ws; ma.sk_ws = sk_ws + (size_t)2 * B * qkvw;
-    ma.kcache = (bf16_t*)kv->k; ma.vcache = (bf16_t*)kv->v; ma.kv_layer_stride = layer_stride; ma.Bcache = kv->B;
+    ma.x = cx.x; ma.xn = cx.xn; ma.ao = cx.ao; ma.act = cx.act;
+    ma.qkv_ws = cx.sk_ws; ma.sk_ws = cx.sk_ws + (size_t)2 * B * cx.qkvw;
+    ma.kcache = (bf16_t*)kv->k; ma.vcache = (bf16_t*)kv->v; ma.kv_layer_stride = cx.layer_stride; ma.Bcache = kv->B;
     ma.pos_dev = st->pos; ma.cos_t = (const bf16_t*)m->rope_cos; ma.sin_t = (const bf16_t*)m->rope_sin; ma.keep = st->keep; ma.ld_keep = kv->Tmax;
     ma.B = B; ma.Tmax = kv->Tmax; ma.scale = 1.0f / sqrtf((float)dh); ma.rms_eps = m->rms_eps; ma.rms_cast = m->rms_cast;
-    ma.flags = c->mb_flags; ma.epoch = c->mb_sync; ma.err = c->xwg_err;
-    { const char* e = getenv("PCY_MB_ABL"); ma.abl = e ? atoi(e) : 0; }
-    if (getenv("PCY_MC_TRACE")) {   // measurement aid (tools/bench_decode_mb.py): in-kernel time stamps, [layer][workgroup][16]
-      if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
-      ma.trace = g_mc_trace + (size_t)128 * 256 * 16;
-    }
-    pcy_launch_rmsnorm(s, x, (const bf16_t*)m->layers[0].ln1, xn, B, d, m->rms_eps, m->rms_cast);
+    ma.flags = c->mb_flags; ma.epoch = c->mb_sync; ma.err = c->xwg_err; ma.abl = sw.mb_abl; ma.trace = mc_trace(sw);
+    pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->layers[0].ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
     if (pcy_launch_decode_step_mb(s, c->device, ma, c->n_cu)) { step_done = true; xn_ready = 1; ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_MB]; }
   }
   for (int l = 0; l < (step_done ? 0 : m->n_layers); ++l) {
     const pcy_llama_layer& L = m->layers[l];
-    PcyGemvArgs g{};
-    g.W = (const bf16_t*)L.wqkv; g.x = x; g.y = qkv; g.rms_w = (const bf16_t*)L.ln1; g.rms_eps = m->rms_eps;
-    g.rms_cast = m->rms_cast; g.N = qkvw; g.K = d; g.B = B; g.ldx = d; g.ldy = qkvw; g.epi = EPI_STORE;
-    g.splitk_ws = sk_ws; g.splitk_ws_bytes = sk_bytes; g.force_stream = nb_on;
-    if (batched) {   // (the previous layer's down projection may have written xn already, fused into its K-split finish)
-      if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln1, xn, B, d, m->rms_eps, m->rms_cast);
-      xn_ready = 0;
-      g.x = xn; g.rms_w = nullptr;
-    }
-    PcyDecAttnArgs t{};
-    t.qkv = qkv; t.ld = qkvw; t.kcache = (bf16_t*)kv->k + l * layer_stride; t.vcache = (bf16_t*)kv->v + l * layer_stride;
-    t.o = ao; t.ldo = H * dh; t.pos_dev = st->pos; t.cos_t = (const bf16_t*)m->rope_cos; t.sin_t = (const bf16_t*)m->rope_sin;
-    t.keep = st->keep; t.ld_keep = kv->Tmax; t.scratch = scores; t.B = B; t.H = H; t.Hkv = Hkv; t.dh = dh; t.Tmax = kv->Tmax;
-    t.scale = 1.0f / sqrtf((float)dh);
-    t.force_ds = nb_on ? pcy_decode_nb_ds(B) : 0;
-    // (multi-head geometry, one row: the column split of the fused step's attention workgroups, whatever the launch mix -- one set of bits)
-    const bool mha1 = B == 1 && pcy_decode_mha_covers(d, H, Hkv, dh, F, c->n_cu);
-    if (mha1) t.force_ds = pcy_decode_mha_ds();
-    // one row: the projections over d walk their k-iterations rotated (PcyGemvArgs::krot) -- in the streaming launches, in the launches that
-    // fuse them (attn_o, mlp_chain) and in the one-launch steps alike: one set of bits
-    const int krot1 = B == 1 ? 1 : 0;
-    g.krot = krot1;   // (+ the rotated k order of its projections, PcyGemvArgs::krot)
-    PcyGemvArgs o{};
-    o.W = (const bf16_t*)L.wo; o.x = ao; o.y = x; o.resid = x; o.N = d; o.K = H * dh; o.B = B; o.ldx = H * dh; o.ldy = d; o.epi = EPI_RESID;
-    o.splitk_ws = sk_ws; o.splitk_ws_bytes = sk_bytes; o.force_stream = nb_on; o.krot = krot1;
-    // attention and o projection in one launch (Wo rows wait in registers while the attention runs) where covered
-    if (batched && B <= 32) { o.next_rms_w = (const bf16_t*)L.ln2; o.next_xn = xn; o.fused_next = &xn_ready; o.rms_eps = m->rms_eps; o.rms_cast = m->rms_cast; }
+    PcyDecAttnArgs t = attn_args(cx, p, l);
+    unsigned* xflags = c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS;   // key-split flags of this layer's fused launch
     if (try_layer) {   // the whole layer as one launch
       uint32_t* tags = c->mc_tags + (size_t)l * tag_stride;
-      PcyAttnBlockArgs bp{};
-      bp.x = x; bp.ln1 = (const bf16_t*)L.ln1; bp.wqkv = (const bf16_t*)L.wqkv; bp.wo = (const bf16_t*)L.wo;
-      bp.d = d; bp.Nq = qkvw; bp.rms_eps = m->rms_eps; bp.rms_cast = m->rms_cast;
-      bp.qkv_tag = tags + F; bp.ao_tag = bp.qkv_tag + qkvw; bp.xo_tag = bp.ao_tag + H * dh;
-      bp.epoch = c->ao_sync + 1; bp.err = c->xwg_err;
-      if (getenv("PCY_MC_TRACE")) {   // measurement aid (tools/bench_decode.py): in-kernel time stamps, [layer][workgroup][16]
-        if (!g_mc_trace) { hipMalloc(&g_mc_trace, 2 * 128 * 256 * 16 * 8); hipMemset(g_mc_trace, 0, 2 * 128 * 256 * 16 * 8); }
-        bp.trace = g_mc_trace + (size_t)(128 + l) * 256 * 16;
-      }
-      PcyMlpChainArgs mc{};
-      mc.x = x; mc.x_out = x; mc.ln2 = (const bf16_t*)L.ln2; mc.wgu = (const bf16_t*)L.wgu; mc.wdown = (const bf16_t*)L.wdown;
-      mc.d = d; mc.F = F; mc.rms_eps = m->rms_eps; mc.rms_cast = m->rms_cast;
-      mc.act_tag = tags; mc.epoch = c->ao_sync + 1; mc.err = c->xwg_err;
-      if (pcy_launch_decode_layer(s, t, bp, mc, c->n_cu, c->ao_sync, c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS)) {
+      if (pcy_launch_decode_layer(s, t, block_args(cx, p.tag_word, mc_trace(sw, l), &L, tags), mlp_args(cx, p.tag_word, &L, tags), c->n_cu, c->ao_sync, xflags)) {
         if (l == 0) ++g_pcy_dispatch[PCY_DISPATCH_DEC_LAYER];   // (one count per step)
         continue;
       }
       try_layer = false;   // geometry not covered: the same for every layer
     }
-    if (l == 0) ++g_pcy_dispatch[batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
-    int qkv_splits = 0;   // batched: the attention adds up the K-split partial sums of ITS rows (no finish launch); PCY_DISABLE=attn_qkv_finish: separate launch
-    // (up to 32 rows: above, the GEMV runs in 32-row passes that share the workspace -- the finish is a launch per pass, same bits)
-    if (batched && B <= 32 && sk_ws && !try_ao && !qkv_finish_launch()) g.defer_finish = &qkv_splits;
+    if (l == 0) ++g_pcy_dispatch[p.batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
+    // (batched: the previous layer's down projection may have written xn already, fused into its K-split finish)
+    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    PcyGemvArgs g = proj_args(cx, p, L.wqkv, L.ln1, cx.x, d, cx.qkv, cx.qkvw, EPI_STORE, true, p.krot, nullptr);
+    int qkv_splits = 0;
+    if (p.defer_qkv_finish) g.defer_finish = &qkv_splits;
     pcy_launch_gemv(s, g);
-    if (qkv_splits > 1) { t.qkv_partials = sk_ws; t.qkv_splits = qkv_splits; }
-    if (!(try_ao && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err,
-                                       c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS))) {
+    if (qkv_splits > 1) { t.qkv_partials = cx.sk_ws; t.qkv_splits = qkv_splits; }
+    const PcyGemvArgs o = proj_args(cx, p, L.wo, L.ln2, cx.ao, H * dh, cx.x, d, EPI_RESID, true, p.krot, &xn_ready);
+    if (!(p.attn_o && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err, xflags))) {
+      t.xmin = 0;   // (no key split in the stand-alone attention)
       pcy_launch_attn_decode(s, t);
       pcy_launch_gemv(s, o);
     }
-    PcyGemvArgs u{};
-    u.W = (const bf16_t*)L.wgu; u.x = x; u.y = act; u.rms_w = (const bf16_t*)L.ln2; u.rms_eps = m->rms_eps; u.rms_cast = m->rms_cast;
-    u.N = F; u.K = d; u.B = B; u.ldx = d; u.ldy = F; u.epi = EPI_SWIGLU; u.force_stream = nb_on; u.krot = krot1;
-    if (batched) {
-      if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln2, xn, B, d, m->rms_eps, m->rms_cast);
-      xn_ready = 0;
-      u.x = xn; u.rms_w = nullptr;
-    }
-    pcy_launch_gemv(s, u);
-    PcyGemvArgs w{};
-    w.W = (const bf16_t*)L.wdown; w.x = act; w.y = x; w.resid = x; w.N = d; w.K = F; w.B = B; w.ldx = F; w.ldy = d; w.epi = EPI_RESID;
-    w.splitk_ws = sk_ws; w.splitk_ws_bytes = sk_bytes; w.force_stream = nb_on;
-    if (batched && B <= 32) {
-      w.next_rms_w = (const bf16_t*)(l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm);
-      w.next_xn = xn; w.fused_next = &xn_ready; w.rms_eps = m->rms_eps; w.rms_cast = m->rms_cast;
-    }
-    if (nb_on && pcy_launch_gemv_kwin4(s, w)) continue;   // (the four-way K split of the small-batch step's down projection)
+    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, B, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    pcy_launch_gemv(s, proj_args(cx, p, L.wgu, L.ln2, cx.x, d, cx.act, F, EPI_SWIGLU, false, p.krot, nullptr));
+    const PcyGemvArgs w = proj_args(cx, p, L.wdown, l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm, cx.act, F, cx.x, d, EPI_RESID, true, 0, &xn_ready);
+    if (p.nb_on && pcy_launch_gemv_kwin4(s, w)) continue;   // (the four-way K split of the small-batch step's down projection)
     pcy_launch_gemv(s, w);
   }
   if (layers_only) return;
   PcyGemvArgs h{};
-  h.W = (const bf16_t*)m->lm_head; h.x = x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
+  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
   h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = B; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
   // (4 rows on the small-batch step: the streaming kernel with the final norm fused -- one pass over the matrix for up to 4 rows -- instead of
   // norm + MFMA GEMV: 3.178 -> 3.153 ms per step; 5 and 8 rows would take two passes: 3.51 -> 3.65, 4.00 -> 4.15)
-  if (batched_head && !(nb_on && B <= 4)) {
-    if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)m->final_norm, xn, B, d, m->rms_eps, m->rms_cast);
-    h.x = xn; h.rms_w = nullptr;
-  } else if (nb_on) {
+  if (p.batched_head && !(p.nb_on && B <= 4)) {
+    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, B, d, m->rms_eps, m->rms_cast);
+    h.x = cx.xn; h.rms_w = nullptr;
+  } else if (p.nb_on) {
     h.force_stream = 1;
   }
   pcy_launch_gemv(s, h);
@@ -578,19 +585,14 @@ __global__ void store_logits_kernel(const bf16_t* __restrict__ logits, bf16_t* _
     }
   }
 }
+// the step's logits -> row (step, b) of `all` (nullptr: no record; ld <= 0: rows of V)
+void enqueue_store_logits(hipStream_t s, const void* logits, void* all, int ld, const int32_t* step_dev, int B, int V) {
+  if (all) hipLaunchKernelGGL(store_logits_kernel, dim3(B >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)logits, (bf16_t*)all, step_dev, B, V, ld > 0 ? ld : V);
+}
 void enqueue_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos, int Tmax) {
-  hipStream_t s = c->stream;
-  if (st->logits_all)
-    hipLaunchKernelGGL(store_logits_kernel, dim3(B >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)st->logits,
-                       (bf16_t*)st->logits_all, st->step, B, m->vocab, st->logits_all_ld > 0 ? st->logits_all_ld : m->vocab);
-  // partials live at the tail of the decode workspace carve (same offsets as enqueue_decode)
-  Carver cv(c->ws);
-  const int qkvw = (m->n_heads + 2 * m->n_kv_heads) * m->head_dim;
-  cv.take<bf16_t>((size_t)B * m->d); cv.take<bf16_t>((size_t)B * qkvw); cv.take<bf16_t>((size_t)B * m->n_heads * m->head_dim);
-  cv.take<bf16_t>((size_t)B * m->ffn); cv.take<float>((size_t)B * m->n_heads * (Tmax + 1));
-  void* partials = cv.take<char>((size_t)B * 64 * 16);
-  pcy_launch_greedy_pick(s, (const bf16_t*)st->logits, B, m->vocab, st->next_tok, st->tokens_out, st->max_steps,
-                         st->logprob, st->pos, st->step, advance_pos, partials);
+  enqueue_store_logits(c->stream, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab);
+  pcy_launch_greedy_pick(c->stream, (const bf16_t*)st->logits, B, m->vocab, st->next_tok, st->tokens_out, st->max_steps,
+                         st->logprob, st->pos, st->step, advance_pos, carve_decode_ws(c->ws, m, B, Tmax).partials);
 }
 
 // sampling / nucleus selection on state->logits (the non-greedy branch of `_generate_sampling`, model_unified.py:896-906)
@@ -599,14 +601,8 @@ void enqueue_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_gen_state* st
   hipStream_t s = c->stream;
   // the nucleus branch of the reference is softmax(logits) * mask -- the temperature is not applied there (model_unified.py:899-901)
   if (nucleus_p > 0.f) temperature = 1.0f;
-  if (st->logits_all)
-    hipLaunchKernelGGL(store_logits_kernel, dim3(B >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)st->logits,
-                       (bf16_t*)st->logits_all, st->step, B, m->vocab, st->logits_all_ld > 0 ? st->logits_all_ld : m->vocab);
-  Carver cv(c->ws);
-  const int qkvw = (m->n_heads + 2 * m->n_kv_heads) * m->head_dim;
-  cv.take<bf16_t>((size_t)B * m->d); cv.take<bf16_t>((size_t)B * qkvw); cv.take<bf16_t>((size_t)B * m->n_heads * m->head_dim);
-  cv.take<bf16_t>((size_t)B * m->ffn); cv.take<float>((size_t)B * m->n_heads * (Tmax + 1));
-  void* partials = cv.take<char>((size_t)B * 64 * 16);
+  enqueue_store_logits(s, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab);
+  void* partials = carve_decode_ws(c->ws, m, B, Tmax).partials;
   pcy_launch_sample_step(s, (const bf16_t*)st->logits, B, m->vocab, temperature, nucleus_p, uniforms, c->smp_hist, probs_out, st->next_tok,
                          st->tokens_out, st->max_steps, st->logprob, st->pos, st->step, advance_pos, partials, c->smp_pbits);
 }
@@ -800,7 +796,7 @@ int pcy_decode_mlp(pcy_ctx* c, void* x, const void* ln2, const void* wgu, const 
     HIP_TRY(hipMemset(c->ao_sync + 2, 0, 4));
     c->op_tags_words = words;
   }
-  if (mlp_chain_enabled()) {
+  if (!pcy_off("mlp_chain")) {   // (the two GEMV launches instead of mlp_chain_kernel: read on every call, tests compare -- bit-identical)
     PcyMlpChainArgs mc{};
     mc.x = (const bf16_t*)x; mc.x_out = (bf16_t*)x; mc.ln2 = (const bf16_t*)ln2; mc.wgu = (const bf16_t*)wgu; mc.wdown = (const bf16_t*)wdown;
     mc.d = d; mc.F = ffn; mc.rms_eps = rms_eps; mc.rms_cast = rms_cast;
@@ -1359,6 +1355,68 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   }
   return check_launch("pcy_llama_prefill");
 }
+
+PcyBeamState beam_state_args(const pcy_beam_state* st) {
+  PcyBeamState b{};
+  b.out = st->out; b.max_len = st->max_len; b.cur = st->cur; b.cur_new = st->cur_new; b.next_tok = st->next_tok; b.src = st->src;
+  b.anc = st->anc; b.has_eos = st->has_eos; b.blk_eos = st->blk_eos; b.ticket = st->ticket; b.pos = st->pos; b.step = st->step;
+  b.done = st->done; b.eos_id = st->eos_id;
+  return b;
+}
+// row-statistics partials of pcy_beam_step in an allocation of their own: never inside the decode workspace (a captured decode graph points
+// into that one, and its tail belongs to the KV-reorder scratch)
+int ensure_beam_ws(pcy_ctx* c, int B, int beam) {
+  const size_t need = align_up(pcy_beam_ws_bytes(B, beam), 256);
+  if (need <= c->beam_ws_bytes) return 0;
+  if (c->beam_ws) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->beam_ws)); c->beam_ws = nullptr; c->beam_ws_bytes = 0; }
+  c->drop_graph();   // (a captured beam step holds it as a kernel argument)
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->beam_ws), need * 2));
+  c->beam_ws_bytes = need * 2;
+  return 0;
+}
+
+// The part of a graph key that every kind shares: what enqueue_decode reads (call after ensure_decode_state: the context's buffers are final)
+// (filled in place behind a memset: the padding bytes take part in the comparison)
+void decode_graph_key(DecodeGraphKey& k, const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int kind, const PcySwitches& sw) {
+  memset(&k, 0, sizeof(k));
+  k.kind = kind; k.B = B; k.sw = sw;
+  k.model = m; k.layers = m->layers; k.embed = m->embed; k.kv_k = kv->k; k.kv_v = kv->v; k.Tmax = kv->Tmax; k.kv_B = kv->B;
+  k.pos = st->pos; k.step = st->step; k.next_tok = st->next_tok; k.logits = st->logits; k.keep = st->keep;
+  k.ws = c->ws; k.mc_tags = c->mc_tags; k.mb_flags = c->mb_flags; k.nb_tags = B <= 8 ? c->nb_tags[B] : nullptr; k.dev_layers = c->dev_layers;
+  k.layers_fp = c->layers_fp;
+}
+// capture (once per key) and replay: `enqueue` puts the launches of ONE step on c->stream
+template <typename Enqueue>
+int replay_graph(pcy_ctx* c, const DecodeGraphKey& key, int n_steps, const char* what, Enqueue&& enqueue) {
+  if (!c->graph || memcmp(&key, &c->graph_key, sizeof(key)) != 0) {
+    c->drop_graph();
+    hipGraph_t g = nullptr;
+    hipStream_t user = c->stream;
+    c->stream = c->cap_stream;
+    hipError_t e0 = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal);
+    if (e0 == hipSuccess) {
+      enqueue();
+      e0 = hipStreamEndCapture(c->cap_stream, &g);
+    }
+    c->stream = user;
+    if (e0 != hipSuccess) return fail(2, "%s graph capture failed: %s", what, hipGetErrorString(e0));
+    HIP_TRY(hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0));
+    hipGraphDestroy(g);
+    memcpy(&c->graph_key, &key, sizeof(key));
+  }
+  for (int i = 0; i < n_steps; ++i) HIP_TRY(hipGraphLaunch(c->graph, c->stream));
+  return 0;
+}
+// kind 0 = decode + greedy pick, 1 = decode only
+int replay_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps, int kind, const PcySwitches& sw) {
+  DecodeGraphKey key;
+  decode_graph_key(key, c, m, kv, st, B, kind, sw);
+  key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps;
+  return replay_graph(c, key, n_steps, "decode-step", [&] {
+    enqueue_decode(c, m, kv, st, B, sw);
+    if (kind == 0) enqueue_pick(c, m, st, B, 1, kv->Tmax);
+  });
+}
 }  // namespace
 extern "C" {
 int pcy_llama_prefill(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
@@ -1380,8 +1438,9 @@ int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode: B=%d exceeds cache rows %d", B, kv->B);
   if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  if (int r = ensure_decode_state(c, m, B)) return r;
-  enqueue_decode(c, m, kv, st, B);
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  enqueue_decode(c, m, kv, st, B, sw);
   return check_launch("pcy_llama_decode");
 }
 
@@ -1389,8 +1448,9 @@ int pcy_llama_decode_layers(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_ca
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode_layers: B=%d exceeds cache rows %d", B, kv->B);
   if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  if (int r = ensure_decode_state(c, m, B)) return r;
-  for (int i = 0; i < reps; ++i) enqueue_decode(c, m, kv, st, B, true);
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  for (int i = 0; i < reps; ++i) enqueue_decode(c, m, kv, st, B, sw, true);
   return check_launch("pcy_llama_decode_layers");
 }
 
@@ -1401,65 +1461,31 @@ int pcy_greedy_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
   return check_launch("pcy_greedy_pick");
 }
 
-namespace {
-// capture (once per model / cache / state / batch) and replay the decode step; kind 0 = decode + greedy pick, 1 = decode only
-int replay_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps, int kind) {
-  // EVERYTHING a captured kernel argument was derived from: every pointer of the state / cache / model the enqueue functions
-  // read, AND the geometry (an allocator may hand a new state or a cache of another capacity the addresses of the previous one
-  // while e.g. the `keep` mask or the token buffer differ -- a stale graph would then run with dangling arguments)
-  const void* key[pcy_ctx::GRAPH_KEY_N] = {m, m->layers, m->embed, kv->k, kv->v, st->pos, st->step, st->next_tok, st->tokens_out, st->logprob,
-                                           st->logits, st->logits_all, st->keep, c->ws,
-                                           (const void*)(intptr_t)(((int64_t)st->logits_all_ld << 32) ^ kv->Tmax),
-                                           (const void*)(intptr_t)(((int64_t)kv->B << 32) ^ st->max_steps),
-                                           (const void*)((uintptr_t)c->mc_tags ^ ((uintptr_t)c->mb_flags << 1)), c->dev_layers, (const void*)(uintptr_t)c->layers_fp};
-  if (!c->graph || memcmp(key, c->graph_key, sizeof(key)) != 0 ||
-      c->graph_B != B || c->graph_mode != decode_mode() || c->graph_kind != kind) {
-    c->drop_graph();
-    hipGraph_t g = nullptr;
-    hipStream_t user = c->stream;
-    c->stream = c->cap_stream;
-    hipError_t e0 = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e0 == hipSuccess) {
-      enqueue_decode(c, m, kv, st, B);
-      if (kind == 0) enqueue_pick(c, m, st, B, 1, kv->Tmax);
-      e0 = hipStreamEndCapture(c->cap_stream, &g);
-    }
-    c->stream = user;
-    if (e0 != hipSuccess) return fail(2, "decode-step graph capture failed: %s", hipGetErrorString(e0));
-    HIP_TRY(hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0));
-    hipGraphDestroy(g);
-    memcpy(c->graph_key, key, sizeof(key));
-    c->graph_B = B;
-    c->graph_mode = decode_mode();
-    c->graph_kind = kind;
-  }
-  for (int i = 0; i < n_steps; ++i) HIP_TRY(hipGraphLaunch(c->graph, c->stream));
-  return 0;
-}
-}  // namespace
 
 int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps,
                      int use_graph) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_greedy: B=%d exceeds cache rows %d", B, kv->B);
   if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  if (int r = ensure_decode_state(c, m, B)) return r;
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
   if (!use_graph) {
     for (int i = 0; i < n_steps; ++i) {
-      enqueue_decode(c, m, kv, st, B);
+      enqueue_decode(c, m, kv, st, B, sw);
       enqueue_pick(c, m, st, B, 1, kv->Tmax);
     }
     return check_launch("pcy_llama_greedy");
   }
-  return replay_decode_graph(c, m, kv, st, B, n_steps, 0);
+  return replay_decode_graph(c, m, kv, st, B, n_steps, 0, sw);
 }
 
 int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode_graph: B=%d exceeds cache rows %d", B, kv->B);
   if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  if (int r = ensure_decode_state(c, m, B)) return r;
-  return replay_decode_graph(c, m, kv, st, B, 1, 1);
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  return replay_decode_graph(c, m, kv, st, B, 1, 1, sw);
 }
 
 int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
@@ -1481,10 +1507,11 @@ int pcy_llama_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
   if (!(temperature > 0.f) || nucleus_prob >= 1.f) return fail(1, "pcy_llama_sample: temperature > 0 and nucleus_prob < 1 required");
   if (m->vocab > pcy_sample_max_vocab()) return fail(1, "pcy_llama_sample: vocabulary %d unsupported (<= %d)", m->vocab, pcy_sample_max_vocab());
   if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  if (int r = ensure_decode_state(c, m, B)) return r;
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
   for (int i = 0; i < n_steps; ++i) {
-    enqueue_decode(c, m, kv, st, B);
+    enqueue_decode(c, m, kv, st, B, sw);
     enqueue_sample(c, m, st, B, 1, kv->Tmax, temperature, nucleus_prob, uniforms, nullptr);
   }
   return check_launch("pcy_llama_sample");
@@ -1496,20 +1523,8 @@ int pcy_beam_step(pcy_ctx* c, const void* logits, int vocab, int B, int beam, in
   if (B <= 0 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
     return fail(1, "pcy_beam_step: beam=%d (1..32) must be a multiple of group_size=%d", beam, group_size);
   if (vocab <= 0 || vocab > 163840) return fail(1, "pcy_beam_step: vocab %d unsupported (<= 163840)", vocab);
-  PcyBeamState b{};
-  b.out = st->out; b.max_len = st->max_len; b.cur = st->cur; b.cur_new = st->cur_new; b.next_tok = st->next_tok; b.src = st->src;
-  b.anc = st->anc; b.has_eos = st->has_eos; b.blk_eos = st->blk_eos; b.ticket = st->ticket; b.pos = st->pos; b.step = st->step;
-  b.done = st->done; b.eos_id = st->eos_id;
-  // row-statistics partials in an allocation of their own: never inside the decode workspace (a captured decode graph points
-  // into that one, and its tail belongs to the KV-reorder scratch)
-  const size_t need = align_up(pcy_beam_ws_bytes(B, beam), 256);
-  if (need > c->beam_ws_bytes) {
-    if (c->beam_ws) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->beam_ws)); c->beam_ws = nullptr; c->beam_ws_bytes = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->beam_ws), need * 2));
-    c->beam_ws_bytes = need * 2;
-  }
-  void* ws = c->beam_ws;
-  pcy_launch_beam_step(c->stream, (const bf16_t*)logits, vocab, B, beam, group_size, diversity_penalty, b, ws);
+  if (int r = ensure_beam_ws(c, B, beam)) return r;
+  pcy_launch_beam_step(c->stream, (const bf16_t*)logits, vocab, B, beam, group_size, diversity_penalty, beam_state_args(st), c->beam_ws);
   return check_launch("pcy_beam_step");
 }
 
@@ -1556,69 +1571,27 @@ int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
   const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
   const size_t tmp_elems = (size_t)2 * L * BB * Hkv * kv->Tmax * dh;
   if (int r = c->reserve(decode_ws_bytes(m, BB, kv->Tmax) + align_up(tmp_elems * 2, 256) + 4096)) return r;
-  if (int r = ensure_decode_state(c, m, BB)) return r;
-  const size_t need = align_up(pcy_beam_ws_bytes(B, beam), 256);
-  if (need > c->beam_ws_bytes) {
-    if (c->beam_ws) { HIP_TRY(hipStreamSynchronize(c->stream)); HIP_TRY(hipFree(c->beam_ws)); c->beam_ws = nullptr; c->beam_ws_bytes = 0; }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c->beam_ws), need * 2));
-    c->beam_ws_bytes = need * 2;
-    c->drop_graph();
-  }
-  uint32_t pen_bits; memcpy(&pen_bits, &diversity_penalty, 4);
-  // every array of the beam state is baked into the chain: all of them go into the key (FNV-1a), not only the ones listed by name below
-  uint64_t bsh = 1469598103934665603ull;
-  {
-    const unsigned char* pb = reinterpret_cast<const unsigned char*>(bs);
-    for (size_t i = 0; i < sizeof(pcy_beam_state); ++i) bsh = (bsh ^ pb[i]) * 1099511628211ull;
-  }
-  // ... and what enqueue_decode bakes into the step besides: the key-keep mask, the hand-over slots / flags of the fused steps
-  uint64_t fold = 1469598103934665603ull;
-  for (const void* q : {(const void*)st->keep, (const void*)c->mc_tags, (const void*)c->dev_layers, (const void*)c->mb_flags,
-                        (const void*)(BB <= 8 ? c->nb_tags[BB] : nullptr)})
-    fold = (fold ^ (uint64_t)(uintptr_t)q) * 1099511628211ull;
-  const void* key[pcy_ctx::GRAPH_KEY_N] = {m, m->layers, m->embed, kv->k, kv->v, st->pos, st->step, st->next_tok, bs->out, bs->cur,
-                                           st->logits, logits_rec, bs->src, c->ws,
-                                           (const void*)(intptr_t)(((int64_t)beam << 40) ^ ((int64_t)group_size << 32) ^ kv->Tmax),
-                                           (const void*)(intptr_t)(((int64_t)kv->B << 32) ^ pen_bits ^ ((int64_t)kv_t0 << 44)),
-                                           c->beam_ws, bs->anc, (const void*)(uintptr_t)(c->layers_fp ^ bsh ^ fold)};
-  if (!c->graph || memcmp(key, c->graph_key, sizeof(key)) != 0 || c->graph_B != BB || c->graph_mode != decode_mode() || c->graph_kind != 2) {
-    c->drop_graph();
-    PcyBeamState b{};
-    b.out = bs->out; b.max_len = bs->max_len; b.cur = bs->cur; b.cur_new = bs->cur_new; b.next_tok = bs->next_tok; b.src = bs->src;
-    b.anc = bs->anc; b.has_eos = bs->has_eos; b.blk_eos = bs->blk_eos; b.ticket = bs->ticket; b.pos = bs->pos; b.step = bs->step;
-    b.done = bs->done; b.eos_id = bs->eos_id;
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, BB, sw)) return r;
+  if (int r = ensure_beam_ws(c, B, beam)) return r;
+  DecodeGraphKey key;
+  decode_graph_key(key, c, m, kv, st, BB, 2, sw);
+  memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
+  memcpy(&key.penalty_bits, &diversity_penalty, 4);
+  return replay_graph(c, key, n_steps, "beam-step", [&] {
     bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, BB, kv->Tmax), 256));
-    hipGraph_t g = nullptr;
-    hipStream_t user = c->stream;
-    c->stream = c->cap_stream;
-    hipError_t e0 = hipStreamBeginCapture(c->cap_stream, hipStreamCaptureModeThreadLocal);
-    if (e0 == hipSuccess) {
-      hipStream_t s = c->stream;
-      enqueue_decode(c, m, kv, st, BB);
-      if (logits_rec)
-        hipLaunchKernelGGL(store_logits_kernel, dim3(BB >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)st->logits, (bf16_t*)logits_rec, bs->step, BB,
-                           m->vocab, m->vocab);
-      pcy_launch_beam_step(s, (const bf16_t*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, b, c->beam_ws);
-      if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, kv_t0)) {
-        const dim3 grid(BB, Hkv, 2 * L);
-        hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 1,
-                           (const int32_t*)bs->pos, kv_t0);
-        hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 0,
-                           (const int32_t*)bs->pos, kv_t0);
-      }
-      e0 = hipStreamEndCapture(c->cap_stream, &g);
+    hipStream_t s = c->stream;
+    enqueue_decode(c, m, kv, st, BB, sw);
+    enqueue_store_logits(s, st->logits, logits_rec, 0, bs->step, BB, m->vocab);
+    pcy_launch_beam_step(s, (const bf16_t*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
+    if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, kv_t0)) {
+      const dim3 grid(BB, Hkv, 2 * L);
+      hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 1,
+                         (const int32_t*)bs->pos, kv_t0);
+      hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 0,
+                         (const int32_t*)bs->pos, kv_t0);
     }
-    c->stream = user;
-    if (e0 != hipSuccess) return fail(2, "beam-step graph capture failed: %s", hipGetErrorString(e0));
-    HIP_TRY(hipGraphInstantiate(&c->graph, g, nullptr, nullptr, 0));
-    hipGraphDestroy(g);
-    memcpy(c->graph_key, key, sizeof(key));
-    c->graph_B = BB;
-    c->graph_mode = decode_mode();
-    c->graph_kind = 2;
-  }
-  for (int i = 0; i < n_steps; ++i) HIP_TRY(hipGraphLaunch(c->graph, c->stream));
-  return 0;
+  });
 }
 
 }  // extern "C"

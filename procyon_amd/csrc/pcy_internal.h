@@ -253,7 +253,8 @@ struct PcyDecodeStepArgs {
   uint32_t* x_lines; size_t x_lines_stride;         // [n_layers - 1][32 * 256] words: the residual stream behind layer l
 };
 // false = geometry not covered (nothing launched).  xflags / step_epoch: key-split exchange of the attention workgroups
-// (as pcy_launch_attn_o).  mc: the layer's MLP (mc.x unused).
+// (as pcy_launch_attn_o).  mc: the layer's MLP (mc.x unused).  All fused launchers take the key-split threshold from a.xmin (the caller's
+// switch snapshot, PcySwitches::ao_xmin) and read no environment of their own.
 // p / mc: geometry and the per-step pointers (x, epoch, err); their per-layer fields are filled in by the kernel.
 bool pcy_launch_decode_step(hipStream_t s, const PcyDecAttnArgs& a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc, const PcyDecodeStepArgs& st,
                             int n_cu, const unsigned* step_epoch);
@@ -268,13 +269,13 @@ bool pcy_launch_decode_mha(hipStream_t s, PcyDecAttnArgs a, const PcyAttnBlockAr
                            const unsigned* step_epoch, unsigned* xflags);
 // Small-batch decode step (pcy_decode_nb.hip): every decoder layer for 2..8 rows in ONE launch, the weights streamed once.  Hand-over slots
 // per layer: pcy_decode_nb_tag_words(B) words (act | qkv | attention output | x after o, B rows each), residual stream between two layers:
-// pcy_decode_nb_line_words(B) words; p.epoch = the tag counter of THIS batch size's slots.  false = not covered, nothing launched.
+// pcy_decode_nb_line_words(B) words; p.epoch = the tag counter of THIS batch size's slots; ub = PcySwitches::nb_ub.  false = not covered, nothing launched.
 size_t pcy_decode_nb_tag_words(int B);
 size_t pcy_decode_nb_line_words(int B);
 int pcy_decode_nb_ds(int B);   // output columns per attention workgroup of the B-row step (what the launch-per-stage twin must use)
 bool pcy_launch_decode_step_nb(hipStream_t s, int device, const PcyDecAttnArgs& a, const PcyAttnBlockArgs& p, const PcyMlpChainArgs& mc,
-                               const PcyDecodeStepArgs& st, int n_cu, const unsigned* step_epoch, int B, int xmin);
-bool pcy_decode_nb_launchable(int device, int B, int Tmax, int n_cu);   // pcy_launch_decode_step_nb would launch (LDS for this Tmax, residency)
+                               const PcyDecodeStepArgs& st, int n_cu, const unsigned* step_epoch, int B, int ub);
+bool pcy_decode_nb_launchable(int device, int B, int Tmax, int n_cu, int ub);   // pcy_launch_decode_step_nb would launch (LDS for this Tmax, residency)
 // threads of the stand-alone RMS-fused GEMV launch for N output rows (the summation order of its statistic)
 int pcy_gemv_rms_threads(int N);
 

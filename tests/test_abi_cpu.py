@@ -99,3 +99,52 @@ def test_switch_list_matches_whole_names_only(tmp_path):
     assert run("decode_stepx,xattn_o,attn_o_extra", "attn_o", "decode_step") == "00"
     assert run("xattn_o,attn_o", "attn_o") == "1"          # a later whole entry still counts
     assert run("gemv_lds", "gemv_lds", "gemv_mfma4", "lds_prefetch") == "100"
+
+
+def test_switch_snapshots_compare_by_value(tmp_path):
+    """procyon_amd/csrc/pcy_switch.h: the decode path takes ONE snapshot of the switches per call (PcySwitches), and a captured decode step
+    is keyed on it by value.  Two environments give equal snapshots exactly when they resolve to the same values -- the packed 64-bit key
+    this replaces hashed PCY_AO_XMIN into six bits in which every multiple of 64 (the defaults included) gave 0."""
+    import itertools
+    import re
+    import subprocess
+    src = tmp_path / "s.cpp"
+    # argv: VAR=value pairs, "--" between the two environments; prints 1 when the snapshots are equal
+    src.write_text('#include "pcy_switch.h"\n#include <stdio.h>\n'
+                   'static const char* vars[] = {"PCY_DISABLE", "PCY_AO_XMIN", "PCY_NB_MAX", "PCY_MB_MAX", "PCY_NB_UB", "PCY_MB_ABL", "PCY_MC_TRACE"};\n'
+                   'int main(int c, char** v) {\n  PcySwitches s[2]; int k = 0;\n  for (int i = 1; i <= c; ++i) {\n'
+                   '    if (i == c || !strcmp(v[i], "--")) { s[k++] = pcy_read_switches(); for (const char* n : vars) unsetenv(n); continue; }\n'
+                   '    char* eq = strchr(v[i], \'=\'); *eq = 0; setenv(v[i], eq + 1, 1);\n  }\n'
+                   '  printf("%d", (int)(s[0] == s[1] && !(s[0] != s[1]) && !memcmp(&s[0], &s[1], sizeof(PcySwitches))));\n  return 0;\n}\n')
+    exe = tmp_path / "s"
+    subprocess.run(["g++", "-O1", "-I", os.path.join(ROOT, "procyon_amd", "csrc"), str(src), "-o", str(exe)], check=True)
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("PCY_")}
+
+    def equal(a, b):
+        """a, b: dict VAR -> value (a missing name is unset)"""
+        args = [f"{k}={v}" for k, v in a.items()] + ["--"] + [f"{k}={v}" for k, v in b.items()]
+        return subprocess.run([str(exe), *args], env=clean, capture_output=True, text=True, check=True).stdout == "1"
+
+    def pairwise_different(var, values):
+        for x, y in itertools.combinations(values, 2):
+            assert not equal({} if x is None else {var: x}, {} if y is None else {var: y}), (var, x, y)
+
+    assert equal({}, {})
+    # unset differs from 768 through the defaults for 2 rows (1536) and 3+ rows (4096)
+    pairwise_different("PCY_AO_XMIN", [None, "0", "384", "512", "768", "1024", "1536", "4096"])
+    pairwise_different("PCY_NB_MAX", ["2", "6", "7", "8"])
+    assert equal({}, {"PCY_NB_MAX": "6"})
+    pairwise_different("PCY_MB_MAX", ["0", "9", "32"])
+    assert equal({"PCY_MB_MAX": "40"}, {"PCY_MB_MAX": "32"}) and equal({"PCY_MB_MAX": "-1"}, {"PCY_MB_MAX": "0"}) and equal({}, {"PCY_MB_MAX": "0"})
+    for var in ("PCY_NB_UB", "PCY_MB_ABL", "PCY_MC_TRACE"):
+        assert not equal({}, {var: "1"}), var
+    assert equal({}, {"PCY_NB_UB": "2"})
+    # the table of PCY_DISABLE names, read from the header: the names the library and the Python side use are all in it
+    text = open(os.path.join(ROOT, "procyon_amd", "csrc", "pcy_switch.h")).read()
+    table = text[text.index("#define PCY_SWITCH_NAMES"):text.index("enum PcySwitch")]
+    names = re.findall(r"X\((\w+)\)", table)
+    assert len(names) == len(set(names)) >= 21 and {"attn_o", "decode_step", "gemv_lds", "gemv_mfma4", "finish_norm", "decode_nb", "beam_graph"} <= set(names)
+    pairwise_different("PCY_DISABLE", [None] + names)
+    assert equal({"PCY_DISABLE": "attn_o,gemv_lds"}, {"PCY_DISABLE": "gemv_lds,attn_o"})
+    assert equal({"PCY_DISABLE": "decode_stepx"}, {}) and equal({"PCY_DISABLE": ""}, {})
+    assert not equal({"PCY_DISABLE": "decode_stepx,decode_step"}, {})

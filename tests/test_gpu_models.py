@@ -244,7 +244,7 @@ def test_decode_attn_o_fused_launch_bit_identical(monkeypatch, T, N, n_layers):
     torch.manual_seed(4)
     emb = (torch.randn(1, T, 4096) * 0.02).to(BF).cuda()
 
-    monkeypatch.setenv("PCY_AO_XMIN", "384")   # key split + score exchange between the slice workgroups from 384 keys on (default 1024)
+    monkeypatch.setenv("PCY_AO_XMIN", "384")   # key split + score exchange between the slice workgroups from 384 keys on (default 768)
 
     def run(ao, use_graph):
         pcy_disable(monkeypatch, "decode_layer", "" if ao else "attn_o")     # (the per-layer / all-layer launches have their own test below)

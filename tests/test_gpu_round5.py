@@ -183,6 +183,51 @@ def test_decode_nb_max_switch_is_part_of_the_captured_step_key(eng2, monkeypatch
     assert not torch.equal(out["step_nb"], out["loop_mfma"])      # (two arithmetics: other accumulation orders)
 
 
+def _captures_on_every_change(eng2, monkeypatch, B, T, settings, kind):
+    """The SAME cache and state throughout, replayed steps: `settings` = (label, callable that sets the environment) in turn; every change
+    must capture the step anew -- exactly one step counted by the dispatch counters, on `kind` -- and equal settings must give equal logits."""
+    from procyon_amd.engine import Context, GenState
+    emb = (torch.randn(B, T, 4096, generator=torch.Generator().manual_seed(56 + B)) * 0.02).to(BF).cuda()
+    cache = eng2.new_cache(B, T + 8)
+    st = GenState(B, KW["vocab"], 8, "cuda")
+    out = {}
+    for label, apply in settings:
+        apply()
+        logits, _ = eng2.prefill(emb, None, cache, "last")
+        st.logits.copy_(logits); st.pos.fill_(T)
+        eng2.pick(cache, st, B, advance_pos=False)
+        with served_by(kind, 1):                  # one capture under this setting; the replays count nothing
+            eng2.greedy_steps(cache, st, B, 3, use_graph=True)
+        Context.get().sync()
+        got = st.logits.cpu().clone()
+        assert torch.isfinite(got.float()).all(), label
+        assert torch.equal(out.setdefault(label, got), got), label
+
+
+def test_decode_ao_xmin_is_part_of_the_captured_step_key(eng2, monkeypatch):
+    """PCY_AO_XMIN is baked into the captured one-row step as a kernel argument (the cache length from which the attention splits its keys).
+    The key of a captured step used to fold the three thresholds into six bits in which every multiple of 64 -- the defaults, 384, 512 --
+    gave 0: a change of the threshold on the same cache and state replayed the old capture.  The step is keyed on the switch snapshot by
+    value now (pcy_switch.h).  500 cached keys: between 384 (split on) and 512 / the default 768 (split off)."""
+    pcy_disable(monkeypatch)
+    for var in ("PCY_NB_MAX", "PCY_MB_MAX"):
+        monkeypatch.delenv(var, raising=False)
+    unset = ("unset", lambda: monkeypatch.delenv("PCY_AO_XMIN", raising=False))
+    _captures_on_every_change(eng2, monkeypatch, 1, 500, [unset, ("384", lambda: monkeypatch.setenv("PCY_AO_XMIN", "384")), unset,
+                                                          ("512", lambda: monkeypatch.setenv("PCY_AO_XMIN", "512"))], "step_gqa")
+
+
+def test_decode_gemv_switches_are_part_of_the_captured_step_key(eng2, monkeypatch):
+    """gemv_lds / gemv_mfma4 are read below the decode step's enqueue, by the GEMV launcher, while a step is being captured: they select the
+    kernels of a ten-row step (MFMA launches).  Their twins keep the bits, so only the capture count can tell that a change of the list is
+    honoured -- it used not to be part of the key at all."""
+    for var in ("PCY_NB_MAX", "PCY_MB_MAX", "PCY_AO_XMIN"):
+        monkeypatch.delenv(var, raising=False)
+    empty = ("", lambda: pcy_disable(monkeypatch))
+    _captures_on_every_change(eng2, monkeypatch, 10, 90, [empty, ("gemv_lds", lambda: pcy_disable(monkeypatch, "gemv_lds")), empty,
+                                                          ("gemv_mfma4", lambda: pcy_disable(monkeypatch, "gemv_mfma4"))], "loop_mfma")
+
+
 def test_decode_nb_switch_restores_round4_path(eng2, monkeypatch):
     """PCY_DISABLE=decode_nb: batches of 2..8 rows take the pre-round-5 launches (MFMA GEMVs from 4 rows on); a different arithmetic (other
     accumulation orders), so the logits agree to bf16 noise, not bit for bit -- and switching back and forth inside one process keeps every
