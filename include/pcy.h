@@ -85,7 +85,9 @@ int pcy_attention(pcy_ctx*, const void* q, int ldq, int qcol0, const void* k, in
                   int max_len, int vt_total, int H, int Hkv, int dh, int causal, float scale);
 /* Decode attention of ONE new token per row against the [B,Hkv,Tmax,dh] cache: ropes q and the new k at position
  * *pos (device scalar = cache length), appends K,V at slot *pos, attends slots [0,*pos] (keep: optional [B,Tmax]
- * key mask, NULL = the reference's unmasked decode, quirk Q1).  qkv [B,(H+2Hkv)*dh] un-roped projections. */
+ * key mask, NULL = the reference's unmasked decode, quirk Q1).  qkv [B,(H+2Hkv)*dh] un-roped projections.
+ * keep[b*Tmax + j] != 0 (any non-zero byte): row b attends cached slot j < *pos.  Slot *pos itself (the new token) is always
+ * attended; bytes at and above *pos are not read. */
 int pcy_attn_decode(pcy_ctx*, void* qkv, int ld, void* kcache, void* vcache, void* o, int ldo, const int32_t* pos,
                     const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, int Tmax);
 /* pooled[i] over the token ranges rng[2*r],rng[2*r+1] = (start,len), r in [seg[i], seg[i+1])  (esm.py:131-173) */
@@ -233,7 +235,9 @@ typedef struct {
   void* logits;              /* [B, vocab] logits of the latest step */
   void* logits_all;          /* optional record [max_steps, B, logits_all_ld] of every step's logits; may be PINNED HOST memory
                               * (hipHostMalloc): the rows then cross PCIe during the following decode steps */
-  const uint8_t* keep;       /* optional [B, Tmax] decode key mask ("clean" mode); NULL = reference quirk Q1 */
+  const uint8_t* keep;       /* optional [B, Tmax] decode key mask ("clean" mode; Tmax = the cache's), non-zero = kept; NULL = reference
+                              * quirk Q1.  Every decode step hands it to its attention as pcy_attn_decode takes it: slot *pos itself is
+                              * always attended; bytes at and above *pos are not read */
   int32_t max_steps;
   int32_t logits_all_ld;     /* row stride of logits_all in elements; 0 = vocab.  A multiple of 8 enables 16-byte stores */
 } pcy_gen_state;

@@ -1,6 +1,8 @@
 """What the full-depth GPU tests of the two decoders share (tests/test_gpu_fulldepth.py: Llama-3-8B geometry; tests/test_gpu_fulldepth_split.py:
 Llama-2-7B geometry): the teacher-forced runs, the comparison against a fixture's bf16 oracle and fp32 truth at the project's bars, and the
-decode-step dispatch counters (`served_by`) with which a test asserts WHICH decode step it compared.  Not a test module."""
+decode-step dispatch counters (`served_by`) with which a test asserts WHICH decode step it compared; and `check_oracle`, the two-layer
+oracle comparison on sampled rows of a ragged batch with the clean decode mask (tests/test_gpu_decode_wide.py, tests/test_gpu_decode_mask.py).
+Not a test module."""
 from contextlib import contextmanager
 
 import torch
@@ -151,3 +153,30 @@ def rows_compat_check(name, got, g, sel, min_clear, **extra):
     assert clear >= min_clear and clear_ok == clear, (clear, clear_ok)
     assert agree_hr >= agree_rt - max(2, len(e_ht) // 32), (agree_hr, agree_rt)
     assert max(e_hr) < 0.15        # a wrong position / a dropped pad slot / a stale hand-over gives O(1)
+
+
+
+def check_oracle(sd, kw, emb, mask, got, rows, what, n_steps):
+    """prefill + the HIP greedy tokens teacher-forced through the oracle on `rows` alone (clean decode mask); per (row, step) rel. err < 2e-2,
+    and the HIP token is the oracle's argmax except on a near-tie (top-2 margin inside 4 x the logit noise of that row and step).
+    `got`: the sampled rows' logits [n_steps + 1, len(rows), V] and tokens [len(rows), n_steps + 1] on the CPU.  -> the worst rel. err."""
+    from oracle import llama_ref as LR
+    geom = LR.LlamaGeom(**kw, max_pos=512)
+    m = mask[rows]
+    r = LR.llama_forward(sd, geom, inputs_embeds=emb[rows], attn_mask=m, logits_rows="last")
+    tok = got["tokens"]
+    worst = 0.0
+    for s_ in range(n_steps + 1):
+        if s_:
+            m = torch.cat([m, torch.ones(len(rows), 1)], 1)
+            r = LR.llama_forward(sd, geom, input_ids=tok[:, s_ - 1:s_].long(), attn_mask=m, past_kv=past, logits_rows="last")
+        past = r["past_kv"]
+        ref = r["logits"][:, -1].float()
+        for j, b in enumerate(rows):
+            hip = got["logits"][s_, j].float()
+            worst = max(worst, rel_err(hip, ref[j]))
+            assert rel_err(hip, ref[j]) < 2e-2, (what, b, s_, rel_err(hip, ref[j]))
+            if int(tok[j, s_]) != int(ref[j].argmax()):
+                top2 = ref[j].topk(2).values
+                assert float(top2[0] - top2[1]) <= 4 * float((hip - ref[j]).abs().max()), (what, b, s_)
+    return worst

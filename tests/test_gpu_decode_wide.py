@@ -12,6 +12,7 @@ import torch
 
 from beam_oracle import assert_beam_matches_oracle
 from conftest import pcy_disable, rel_err
+from fulldepth_common import check_oracle
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
@@ -89,28 +90,6 @@ def _sampled_rows(B):
     return sorted(r for r in rows if r < B)
 
 
-def _check_oracle(sd, kw, emb, mask, got, rows, what):
-    """prefill + the HIP greedy tokens teacher-forced through the oracle on `rows` alone (clean decode mask); per (row, step) rel. err < 2e-2,
-    and the HIP token is the oracle's argmax except on a near-tie (top-2 margin inside 4 x the logit noise of that row and step)."""
-    from oracle import llama_ref as LR
-    geom = LR.LlamaGeom(**kw, max_pos=512)
-    m = mask[rows]
-    r = LR.llama_forward(sd, geom, inputs_embeds=emb[rows], attn_mask=m, logits_rows="last")
-    tok = got["tokens"]
-    for s_ in range(N + 1):
-        if s_:
-            m = torch.cat([m, torch.ones(len(rows), 1)], 1)
-            r = LR.llama_forward(sd, geom, input_ids=tok[:, s_ - 1:s_].long(), attn_mask=m, past_kv=past, logits_rows="last")
-        past = r["past_kv"]
-        ref = r["logits"][:, -1].float()
-        for j, b in enumerate(rows):
-            hip = got["logits"][s_, j].float()
-            assert rel_err(hip, ref[j]) < 2e-2, (what, b, s_, rel_err(hip, ref[j]))
-            if int(tok[j, s_]) != int(ref[j].argmax()):
-                top2 = ref[j].topk(2).values
-                assert float(top2[0] - top2[1]) <= 4 * float((hip - ref[j]).abs().max()), (what, b, s_)
-
-
 @pytest.mark.parametrize("B,T", CASES)
 def test_wide_decode_step_vs_oracle_and_32_row_chunks(geo, monkeypatch, B, T):
     """A B-row greedy step (B > 32), eager and replayed: (a) the sampled rows against the oracle; (b) every full 32-row pass against the same
@@ -128,7 +107,7 @@ def test_wide_decode_step_vs_oracle_and_32_row_chunks(geo, monkeypatch, B, T):
         assert torch.equal(out[key], rep[key]), (name, B, "replay", key)
     # (a) the oracle on the sampled rows
     rows = _sampled_rows(B)
-    _check_oracle(sd, kw, emb, mask, _rows(out, rows), rows, (name, B))
+    check_oracle(sd, kw, emb, mask, _rows(out, rows), rows, (name, B), N)
     # (c) copies in other passes
     for dst, src in ((32, 1), (B - 1, 2)) if B > 33 else ((32, 2),):
         a, b_ = _rows(out, [dst]), _rows(out, [src])

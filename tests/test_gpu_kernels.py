@@ -287,6 +287,84 @@ def test_attn_decode(ctx, H, Hkv, dh, t, B):
     assert torch.equal(kcd.cpu()[:, :, :t], kc[:, :, :t])
 
 
+ATTN_DECODE_SHAPES = [(32, 8, 128, 600, 2), (8, 2, 64, 37, 2), (4, 4, 32, 5, 2), (8, 1, 128, 0, 2), (32, 8, 128, 333, 9), (32, 8, 128, 1030, 20),
+                      (16, 8, 128, 65, 16), (32, 8, 128, 0, 20), (32, 8, 128, 2500, 2)]     # (the shape list of test_attn_decode)
+_ATTN_DECODE_PADS = lambda t: [0, t - 1, 1, t // 2, t // 3, 2, t - 2, t // 8]                # left-pad lengths, row b takes entry b % 8
+
+
+def _attn_decode_mask(mode, B, t, seed):
+    """[B, t] of 0 / 1 over the cached slots, another one for every row of the batch"""
+    m = torch.ones(B, t, dtype=torch.uint8)
+    g = torch.Generator().manual_seed(seed)
+    for b in range(B):
+        if mode == "leftpad":
+            m[b, :max(0, min(t, _ATTN_DECODE_PADS(t)[b % 8]))] = 0
+        elif mode == "half":
+            m[b, torch.randperm(t, generator=g)[:t // 2 + b % 2]] = 0
+        elif mode == "all_masked":
+            m[b] = 0
+    return m
+
+
+@pytest.mark.parametrize("mode", ["leftpad", "half", "all_masked", "ones"])
+@pytest.mark.parametrize("H,Hkv,dh,t,B", ATTN_DECODE_SHAPES)
+def test_attn_decode_key_mask(ctx, H, Hkv, dh, t, B, mode):
+    """pcy_attn_decode with `keep` (the [B, Tmax] decode key mask of the "clean" mode) against the oracle's eager formulas with
+    finfo(bf16).min added to the masked scores (llama_ref.build_additive_mask / layer_forward), over the shapes of test_attn_decode and, per
+    row of the batch, another mask over the cached slots [0, t): a left pad of another length (incl. 0 and t - 1), a random half, every
+    cached slot masked, all ones.  Bars of test_attn_decode.  Pinned besides:
+      * every cached slot masked: the softmax is one-hot on the new token, o[b, h] == v_new[b, kv(h)] BIT for bit (t = 0: trivially);
+      * all ones: the bits of keep = NULL;
+      * a non-zero byte other than 1 (2, 255) counts as kept;
+      * slot t (the new token's own) is attended whatever keep[b][t] holds, and the bytes at and above t are not read: zeros there give
+        the same bits (include/pcy.h states it)."""
+    from oracle import llama_ref as LR
+    from procyon_amd.engine import rope_tables
+    Tmax, G = t + 3, H // Hkv
+    qkv = rnd(B, (H + 2 * Hkv) * dh, seed=1)
+    kc, vc = rnd(B, Hkv, Tmax, dh, seed=2), rnd(B, Hkv, Tmax, dh, seed=3)
+    cos, sin = rope_tables(dh, 10000.0, Tmax + 1, "cpu")
+    mask = _attn_decode_mask(mode, B, t, seed=H * 1000 + t + B)
+    assert mode != "leftpad" or t < 2 or (len({int(x) for x in mask.sum(1)}) > 1 and int(mask.sum(1).min()) == 1 and int(mask.sum(1).max()) == t)
+    q = qkv[:, :H * dh].view(B, 1, H, dh).transpose(1, 2)
+    k = qkv[:, H * dh:(H + Hkv) * dh].view(B, 1, Hkv, dh).transpose(1, 2)
+    v = qkv[:, (H + Hkv) * dh:].view(B, 1, Hkv, dh).transpose(1, 2)
+    qr, kr = LR.apply_rope(q, k, cos[t][None, None].expand(B, 1, dh), sin[t][None, None].expand(B, 1, dh))
+    K = torch.cat([kc[:, :, :t], kr], 2).repeat_interleave(G, 1)
+    V = torch.cat([vc[:, :, :t], v], 2).repeat_interleave(G, 1)
+    s = torch.matmul(qr, K.transpose(2, 3)) * dh ** -0.5
+    # the additive mask of the one query row at position t: [B, 1, 1, t + 1], the new token's slot kept
+    add = LR.build_additive_mask(torch.cat([mask, torch.ones(B, 1, dtype=torch.uint8)], 1), B, 1, t, BF)
+    p = F.softmax(s + add, dim=-1, dtype=torch.float32).to(BF)
+    ref = torch.matmul(p, V).transpose(1, 2).reshape(B, H * dh)
+    pos = torch.tensor([t], dtype=torch.int32).cuda()
+
+    def run(keep):
+        kcd, vcd = kc.cuda(), vc.cuda()
+        o = ctx.attn_decode(qkv.cuda(), kcd, vcd, pos, cos.cuda(), sin.cuda(), H, Hkv, dh, keep=None if keep is None else keep.cuda().contiguous())
+        return o.cpu(), kcd.cpu(), vcd.cpu()
+
+    keep = torch.ones(B, Tmax, dtype=torch.uint8)
+    keep[:, :t] = mask
+    out, kcd, vcd = run(keep)
+    assert rel_err(out, ref) < 1e-3
+    assert_bf16_close(out, ref, f"attn decode, mask {mode}", max_frac=0.03, inter=torch.full_like(ref, 0.05))
+    assert torch.equal(kcd[:, :, t], kr[:, :, 0]) and torch.equal(vcd[:, :, t], v[:, :, 0])
+    assert torch.equal(kcd[:, :, :t], kc[:, :, :t]) and torch.equal(vcd[:, :, :t], vc[:, :, :t])
+    if mode == "all_masked" or t == 0:
+        assert torch.equal(out.view(B, H, dh), v[:, :, 0].repeat_interleave(G, 1)), "one-hot softmax: o must be the new token's V row"
+    if mode == "ones":
+        assert torch.equal(out, run(None)[0]), "all ones differs from keep = NULL"
+    # bytes 2 / 255 for "kept", and zeros at and above slot t: the same bits
+    other = keep.clone()
+    other[:, 0::2] *= 2
+    other[:, 1::2] *= 255
+    assert torch.equal(run(other)[0], out), "a non-zero byte other than 1 does not count as kept"
+    tail0 = keep.clone()
+    tail0[:, t:] = 0
+    assert torch.equal(run(tail0)[0], out), "keep[b][t:] is read"
+
+
 @pytest.mark.parametrize("Q,N,D", [(3, 1000, 1280), (40, 513, 2560)])
 def test_retrieval_scores(ctx, Q, N, D):
     from oracle.procyon_ref import retrieval_scores
