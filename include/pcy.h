@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PCY_ABI_VERSION 10
+#define PCY_ABI_VERSION 11
 
 typedef struct pcy_ctx pcy_ctx;
 
@@ -42,7 +42,8 @@ int pcy_abi_version(void);
  * 9: ESM layers through a captured graph.  Decode steps, ONE count per step enqueued outside a graph replay, by what served it --
  * 7: one row, all layers in one launch, grouped-query geometry; 10: the same, multi-head geometry; 11: one row, a launch per layer;
  * 12: small-batch step (2..8 rows); 13: mid-batch step (9..32 rows, PCY_MB_MAX); 14: launch per stage, streaming GEMVs;
- * 15: launch per stage, MFMA GEMVs.  A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
+ * 15: launch per stage, MFMA GEMVs; 16: a step served from a shared-prefix cache (pcy_kv_cache.prefix_k), counted in addition to 14 / 15.
+ * A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
  * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
 const char* pcy_last_error(void);
@@ -207,6 +208,17 @@ typedef struct {
   void* k;                   /* [L,B,Hkv,Tmax,dh] bf16: layer l rows = past_key_values[l][0] */
   void* v;                   /* same for values */
   int32_t B, Tmax;
+  /* Optional shared prefix (all zero = the plain cache above, exactly).  prefix_k / prefix_v [L,prefix_B,Hkv,prefix_T,dh] bf16: an ordinary
+   * prefill cache of prefix_B prompts with Tmax == prefix_T.  Row b of the decode batch reads prefix row b / rows_per_prefix (the beams of a
+   * prompt share ONE copy of its K/V), and k / v above then hold only the SUFFIX: logical key slot j < prefix_T of row b is
+   * prefix[b / rows_per_prefix][j], slot j >= prefix_T is k[b][j - prefix_T]; the logical capacity is prefix_T + Tmax.  *pos, the rotary
+   * position and the `keep` mask (row stride = the logical capacity) stay in logical slots; a decode step appends at k[b][*pos - prefix_T] and
+   * never writes the prefix.  Served by the launch-per-stage batched decode loop only (pcy_llama_decode / _decode_graph / _beam_steps /
+   * _greedy / _sample with >= 4 rows on a geometry that loop covers): anything else is an argument error, never a fallback.
+   * pcy_kv_reorder* move suffix slots only; the prefill entries reject such a cache. */
+  void* prefix_k;
+  void* prefix_v;
+  int32_t prefix_B, prefix_T, rows_per_prefix;
 } pcy_kv_cache;
 /* Prefill: embeds [B,T,d]; keep [B*T] uint8 attention_mask or NULL; pos[B*T] rotary positions
  * (reference: arange(T) per row, Q2); cu/vt_cu [B+1] = b*T / b*roundup(T,32).

@@ -10,11 +10,11 @@ LIB_PATH = os.environ.get("PCY_LIB") or os.path.join(_HERE, "libpcy.so")   # PCY
 
 EPI_STORE, EPI_RESID, EPI_GELU_ERF, EPI_GELU_ESM, EPI_SWIGLU = range(5)
 POOL_MEAN, POOL_MEAN_CORRECTED, POOL_MAX = range(3)
-ABI_VERSION = 10
+ABI_VERSION = 11
 # pcy_debug_dispatch_count kinds
 (DISPATCH_GEMM_128, DISPATCH_GEMM_64, DISPATCH_GEMM_BIG, DISPATCH_GEMM_BIG_PERSIST, DISPATCH_GEMM_SPLITK, DISPATCH_GEMM_FP8, DISPATCH_ATTN_FAST,
  DISPATCH_DEC_STEP_GQA, DISPATCH_GEMM_MID, DISPATCH_ESM_GRAPH, DISPATCH_DEC_STEP_MHA, DISPATCH_DEC_LAYER, DISPATCH_DEC_STEP_NB, DISPATCH_DEC_STEP_MB,
- DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA) = range(16)
+ DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA, DISPATCH_SHARED_PREFIX) = range(17)
 # which way a decode step was served (one count per step enqueued outside a graph replay; pcy_internal.h PCY_DISPATCH_DEC_*)
 DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STEP_MHA, layer=DISPATCH_DEC_LAYER, step_nb=DISPATCH_DEC_STEP_NB,
                        step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
@@ -54,7 +54,9 @@ class LlamaDesc(C.Structure):
 
 
 class KvCache(C.Structure):
-    _fields_ = [("k", vp), ("v", vp), ("B", i32), ("Tmax", i32)]
+    # (the trailing fields: an optional shared prefix, all zero = a plain cache -- include/pcy.h)
+    _fields_ = [("k", vp), ("v", vp), ("B", i32), ("Tmax", i32), ("prefix_k", vp), ("prefix_v", vp), ("prefix_B", i32), ("prefix_T", i32),
+                ("rows_per_prefix", i32)]
 
 
 class GenState(C.Structure):

@@ -520,15 +520,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void a
 #include "pcy_attn_dec.h"
 #include "pcy_attn_fast.h"
 
-template <int DH, int G, int DS>
+// SHARED: the cache has a shared prefix (see attn_dec_body); the plain instantiations are what they were
+template <int DH, int G, int DS, bool SHARED = false>
 __global__ __launch_bounds__(512) void attn_dec_kernel(PcyDecAttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  attn_dec_body<DH, G, DS>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
+  attn_dec_body<DH, G, DS, AttnDecNoHook, SHARED>(a, smem, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // The same with the new token's q / k / v taken from the K-split partial sums of the batched qkv projection (a.qkv_partials):
 // the cache rows are requested first, then 192 threads add the splits of the kv head's G + 2 rows in split order into LDS.
-template <int DH, int G, int DS>
+template <int DH, int G, int DS, bool SHARED = false>
 __global__ __launch_bounds__(512) void attn_dec_splitk_kernel(PcyDecAttnArgs a, int stage_off) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16_t* stage = reinterpret_cast<bf16_t*>(smem + stage_off);   // [G + 2][DH]
@@ -561,23 +562,30 @@ __global__ __launch_bounds__(512) void attn_dec_splitk_kernel(PcyDecAttnArgs a, 
     }
     lds_barrier();
   };
-  attn_dec_body<DH, G, DS>(a, smem, blockIdx.x, kvh, b, hook);
+  attn_dec_body<DH, G, DS, decltype(hook), SHARED>(a, smem, blockIdx.x, kvh, b, hook);
 }
 
-template <int DH, int G, int DS>
-void launch_dec_ds(hipStream_t s, const PcyDecAttnArgs& a) {
+template <int DH, int G, int DS, bool SHARED>
+void launch_dec_ds_cache(hipStream_t s, const PcyDecAttnArgs& a) {
   if (a.qkv_partials) {
     const int stage_off = (int)((attn_dec_smem_bytes(G, DS, DH, a.Tmax) + 15) & ~(size_t)15);
     const size_t smem = (size_t)stage_off + (size_t)(G + 2) * DH * 2;
     static PcyLdsAttr lds;
-    lds.ensure(&attn_dec_splitk_kernel<DH, G, DS>, smem);
-    hipLaunchKernelGGL((attn_dec_splitk_kernel<DH, G, DS>), dim3(DH / DS, a.Hkv, a.B), dim3(512), smem, s, a, stage_off);
+    lds.ensure(&attn_dec_splitk_kernel<DH, G, DS, SHARED>, smem);
+    hipLaunchKernelGGL((attn_dec_splitk_kernel<DH, G, DS, SHARED>), dim3(DH / DS, a.Hkv, a.B), dim3(512), smem, s, a, stage_off);
     return;
   }
   const size_t smem = attn_dec_smem_bytes(G, DS, DH, a.Tmax);
   static PcyLdsAttr lds;
-  lds.ensure(&attn_dec_kernel<DH, G, DS>, smem);
-  hipLaunchKernelGGL((attn_dec_kernel<DH, G, DS>), dim3(DH / DS, a.Hkv, a.B), dim3(512), smem, s, a);
+  lds.ensure(&attn_dec_kernel<DH, G, DS, SHARED>, smem);
+  hipLaunchKernelGGL((attn_dec_kernel<DH, G, DS, SHARED>), dim3(DH / DS, a.Hkv, a.B), dim3(512), smem, s, a);
+}
+// (the column split DS has been chosen by launch_dec before the cache layout is looked at: a shared-prefix cache gets the one a plain
+// cache of the same rows gets)
+template <int DH, int G, int DS>
+void launch_dec_ds(hipStream_t s, const PcyDecAttnArgs& a) {
+  if (a.prefix_k) launch_dec_ds_cache<DH, G, DS, true>(s, a);
+  else launch_dec_ds_cache<DH, G, DS, false>(s, a);
 }
 
 // ------------------------------------------------------------------------------------------------

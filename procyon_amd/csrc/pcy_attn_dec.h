@@ -105,7 +105,11 @@ struct AttnDecNoHook { __device__ __forceinline__ void operator()() const {} };
 
 // `inputs_ready` runs after the cache rows of the first passes have been requested and before anything of the new
 // token's q/k/v is read: the persistent decode kernel waits there for the projections of this layer.
-template <int DH, int G, int DS, typename Hook = AttnDecNoHook>
+// SHARED (stand-alone launches only): the cache has a shared prefix (pcy_kv_cache.prefix_k) -- logical key slot j < a.Tp of row b lives in the
+// prefix panel of prompt b / a.rows_per_prefix, slot j >= a.Tp in the row's own suffix panel at j - a.Tp (a.Tmax = the LOGICAL capacity, the
+// suffix panels hold a.Tmax - a.Tp slots).  Only the ADDRESS of a cached K / V row changes: the same loads feed the same MFMAs and sums over
+// the same logical j, so the output has the bits of the plain cache holding the same rows.
+template <int DH, int G, int DS, typename Hook = AttnDecNoHook, bool SHARED = false>
 __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* smem, const int bx, const int kvh, const int b,
                                               Hook inputs_ready = Hook()) {
   constexpr int NT = 512, NWV = NT / 64;
@@ -122,10 +126,21 @@ __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* sme
   const int fr = lane & 15, fq = lane >> 4;
   const int t = a.t_plus1 ? a.t_plus1 - 1 : *a.pos_dev;
   const int nk = t + 1;
+  // (a position outside the suffix would append outside the row's panel: the whole workgroup leaves, nothing is written)
+  if constexpr (SHARED) { if (t < a.Tp || t >= a.Tmax) return; }
   if (a.dbg == 1) { if (tid == 0) a.o[(size_t)b * a.ldo + kvh * G * DH + c0] = (bf16_t)t; return; }
   const bf16_t* row = a.qkv + (size_t)b * a.ld;
-  bf16_t* kc = a.kcache + ((size_t)b * a.Hkv + kvh) * a.Tmax * DH;
-  bf16_t* vc = a.vcache + ((size_t)b * a.Hkv + kvh) * a.Tmax * DH;
+  const int Tp = SHARED ? a.Tp : 0;                        // logical slots below Tp: the prompt's prefix panel
+  const int Tsfx = SHARED ? a.Tmax - a.Tp : a.Tmax;        // slots of the row's own panel
+  bf16_t* kc = a.kcache + ((size_t)b * a.Hkv + kvh) * Tsfx * DH;
+  bf16_t* vc = a.vcache + ((size_t)b * a.Hkv + kvh) * Tsfx * DH;
+  const bf16_t* pkc = nullptr;
+  const bf16_t* pvc = nullptr;
+  if constexpr (SHARED) {
+    const size_t prow = ((size_t)(b / a.rows_per_prefix) * a.Hkv + kvh) * Tp * DH;
+    pkc = a.prefix_k + prow;
+    pvc = a.prefix_v + prow;
+  }
   const bf16_t* cs = a.cos_t + (size_t)t * DH;
   const bf16_t* sn = a.sin_t + (size_t)t * DH;
   const uint8_t* keep = a.keep ? a.keep + (size_t)b * a.ld_keep : nullptr;
@@ -156,11 +171,16 @@ __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* sme
   const bf16_t* vrow = a.staged ? a.staged + (G + 1) * DH : row + (a.H + a.Hkv + kvh) * DH;
   const bf16_t* vnew = vrow + c0 + sub * 8;
   const bf16_t* vsl = vc + c0 + sub * 8;
+  // the 16-byte slice of cached V row j (j < t) this lane reads
+  auto v_slice = [&](int j) -> const bf16_t* {
+    if constexpr (SHARED) return j < Tp ? pvc + c0 + sub * 8 + (size_t)j * DH : vsl + (size_t)(j - Tp) * DH;
+    else return vsl + (size_t)j * DH;
+  };
   uint4 vpre[UV];
 #pragma unroll
   for (int u = 0; u < UV; ++u) {
     const int j = grp + u * NGV;
-    vpre[u] = *reinterpret_cast<const uint4*>(vsl + (size_t)(j < t ? j : (t > 0 ? t - 1 : 0)) * DH);   // slot t: see phase C
+    vpre[u] = *reinterpret_cast<const uint4*>(v_slice(j < t ? j : (t > 0 ? t - 1 : 0)));   // slot t: see phase C
   }
 
   // ---- phase A ----
@@ -181,7 +201,9 @@ __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* sme
     auto load_tile = [&](int j, bf16x8 (&f)[KB]) {
       const int jc = j < t ? j : (t > 0 ? t - 1 : 0);   // (requesting the tiles before the position load returns, i.e. clamping
                                                        // to Tmax instead of t, measured slower: 3.41 vs 3.38 ms/token)
-      const bf16_t* p = kc + (size_t)jc * DH + fq * 8;
+      const bf16_t* p;
+      if constexpr (SHARED) p = (jc < Tp ? pkc + (size_t)jc * DH : kc + (size_t)(jc - Tp) * DH) + fq * 8;
+      else p = kc + (size_t)jc * DH + fq * 8;
 #pragma unroll
       for (int kb = 0; kb < KB; ++kb) f[kb] = *reinterpret_cast<const bf16x8*>(p + kb * 32);
     };
@@ -212,11 +234,11 @@ __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* sme
       *reinterpret_cast<uint4*>(qk + hh * DH + ch * 8) =
           make_uint4(pack_bf(tmp[0], tmp[1]), pack_bf(tmp[2], tmp[3]), pack_bf(tmp[4], tmp[5]), pack_bf(tmp[6], tmp[7]));
       if (hh == G && bx == 0)   // append the new token's K
-        *reinterpret_cast<uint4*>(kc + (size_t)t * DH + ch * 8) = *reinterpret_cast<const uint4*>(qk + hh * DH + ch * 8);
+        *reinterpret_cast<uint4*>(kc + (size_t)(t - Tp) * DH + ch * 8) = *reinterpret_cast<const uint4*>(qk + hh * DH + ch * 8);
     }
     if (bx == 0 && tid >= NT - DH / 8) {  // ... and its V
       const int ch = tid - (NT - DH / 8);
-      *reinterpret_cast<uint4*>(vc + (size_t)t * DH + ch * 8) = *reinterpret_cast<const uint4*>(vrow + ch * 8);
+      *reinterpret_cast<uint4*>(vc + (size_t)(t - Tp) * DH + ch * 8) = *reinterpret_cast<const uint4*>(vrow + ch * 8);
     }
     lds_barrier();
     // A operand: roped q of head `fr` (zero rows for fr >= G); new key in B-fragment layout
@@ -361,14 +383,14 @@ __device__ __forceinline__ void attn_dec_body(const PcyDecAttnArgs& a, char* sme
       }
       if (PCY_ATTN_DEC_VPF) { vv[u] = vnx[u]; continue; }
       const int j = j0 + grp + u * NGV;
-      const bf16_t* src = (j < t) ? vsl + (size_t)j * DH : vnew;   // slot t comes straight from the projection
+      const bf16_t* src = (j < t) ? v_slice(j) : vnew;   // slot t comes straight from the projection
       vv[u] = *reinterpret_cast<const uint4*>(src);
     }
     if (PCY_ATTN_DEC_VPF && j0 + UV * NGV < nk) {
 #pragma unroll
       for (int u = 0; u < UV; ++u) {
         const int j = j0 + UV * NGV + grp + u * NGV;
-        const bf16_t* src = (j < t) ? vsl + (size_t)j * DH : vnew;
+        const bf16_t* src = (j < t) ? v_slice(j) : vnew;
         vnx[u] = *reinterpret_cast<const uint4*>(src);
       }
     }

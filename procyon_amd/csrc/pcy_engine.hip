@@ -30,6 +30,11 @@ int fail(int code, const char* fmt, ...) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A cache with a shared prefix (pcy.h, pcy_kv_cache): k / v hold the suffix slots only and the LOGICAL capacity -- what *pos, the keep mask
+// and the score rows count in -- is prefix_T + Tmax.  A plain cache has all-zero prefix fields: kv_cap == Tmax.
+inline bool kv_shared(const pcy_kv_cache* kv) { return kv->prefix_k != nullptr || kv->prefix_v != nullptr || kv->prefix_T != 0; }
+inline int kv_cap(const pcy_kv_cache* kv) { return kv->Tmax + (kv_shared(kv) ? kv->prefix_T : 0); }
+
 }  // namespace
 
 // for the other translation units of the library (pcy_f32.hip): the thread-local error text behind pcy_last_error
@@ -51,6 +56,8 @@ struct DecodeGraphKey {
   PcySwitches sw;
   const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
   int Tmax, kv_B;
+  const void *kv_prefix_k, *kv_prefix_v;           // shared-prefix cache: a captured step is never replayed on another prefix
+  int kv_prefix_T, kv_prefix_B, kv_rows_per_prefix;
   const void *ws, *mc_tags, *mb_flags, *nb_tags, *dev_layers;
   uint64_t layers_fp;
   const void *tokens_out, *logprob, *logits_all;   // kinds 0 and 1
@@ -358,10 +365,12 @@ DecodeWs carve_decode_ws(char* base, const pcy_llama_desc* m, int B, int Tmax) {
 struct DecodeCx : DecodeWs {
   pcy_ctx* c; const pcy_llama_desc* m; const pcy_kv_cache* kv; const pcy_gen_state* st; int B;
   int qkvw; size_t layer_stride;     // columns of the qkv projection; elements between the K (V) caches of consecutive layers
+  size_t prefix_layer_stride;        // ... and between the layers of the shared prefix arrays (0: a plain cache)
 };
 DecodeCx decode_cx(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
-  return DecodeCx{carve_decode_ws(c->ws, m, B, kv->Tmax), c, m, kv, st, B, (m->n_heads + 2 * m->n_kv_heads) * m->head_dim,
-                  (size_t)kv->B * m->n_kv_heads * kv->Tmax * m->head_dim};
+  return DecodeCx{carve_decode_ws(c->ws, m, B, kv_cap(kv)), c, m, kv, st, B, (m->n_heads + 2 * m->n_kv_heads) * m->head_dim,
+                  (size_t)kv->B * m->n_kv_heads * kv->Tmax * m->head_dim,
+                  kv_shared(kv) ? (size_t)kv->prefix_B * m->n_kv_heads * kv->prefix_T * m->head_dim : 0};
 }
 
 // Which launches serve a step: decided once, from the context's state, the geometry, the batch size and the switch snapshot.  `path` is the
@@ -386,11 +395,14 @@ struct DecodePlan {
 DecodePlan plan_decode(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw) {
   DecodePlan p{};
   p.batched_head = B >= pcy_mfma_min_batch() && m->d % 128 == 0 && m->ffn % 128 == 0;
-  p.nb_on = !sw.off(PCY_SW_decode_nb) && decode_nb_covers(c, m, B, sw) && c->nb_tags[B] && c->nb_sync && c->dev_layers && c->ao_sync && c->xwg_err &&
-            pcy_decode_nb_launchable(c->device, B, kv->Tmax, c->n_cu, sw.nb_ub);
+  // a cache with a shared prefix is read by the stand-alone attention launches of the batched loop only: never by a one-launch step
+  // (check_decode_cache turns every other outcome into an argument error)
+  const bool shared = kv_shared(kv);
+  p.nb_on = !shared && !sw.off(PCY_SW_decode_nb) && decode_nb_covers(c, m, B, sw) && c->nb_tags[B] && c->nb_sync && c->dev_layers && c->ao_sync && c->xwg_err &&
+            pcy_decode_nb_launchable(c->device, B, kv_cap(kv), c->n_cu, sw.nb_ub);
   p.batched = p.batched_head && !p.nb_on;
   const bool nb_step = p.nb_on && !sw.off(PCY_SW_decode_nb_step);
-  const bool mb_step = p.batched && !sw.off(PCY_SW_decode_mb_step) && decode_mb_covers(c, m, B, sw) && pcy_decode_mb_fits(B, kv->Tmax) && c->mb_flags && c->mb_sync &&
+  const bool mb_step = !shared && p.batched && !sw.off(PCY_SW_decode_mb_step) && decode_mb_covers(c, m, B, sw) && pcy_decode_mb_fits(B, kv->Tmax) && c->mb_flags && c->mb_sync &&
                        c->dev_layers && c->xwg_err && (size_t)(m->n_layers + 1) * pcy_decode_mb_flag_words() <= c->mb_flags_words;
   p.attn_o = !sw.off(PCY_SW_attn_o) && B == 1 && c->ao_sync && c->xwg_err && m->n_layers <= AO_MAX_LAYERS;
   const bool try_layer = !sw.off(PCY_SW_decode_layer) && p.attn_o && c->mc_tags;
@@ -407,6 +419,18 @@ DecodePlan plan_decode(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_c
   p.tag_word = try_layer ? c->ao_sync + 1 : nb_step ? c->nb_sync + B : nullptr;
   return p;
 }
+// A cache with a shared prefix must be well formed and must take the batched loop: anything else is the caller's error, not a fallback.
+int check_decode_cache(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw, const char* what) {
+  if (!kv_shared(kv)) return 0;
+  if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
+    return fail(1, "%s: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0", what);
+  if (B < 1 || (B - 1) / kv->rows_per_prefix >= kv->prefix_B)
+    return fail(1, "%s: %d rows of %d per prefix need more than the %d prefix rows of the cache", what, B, kv->rows_per_prefix, kv->prefix_B);
+  if (plan_decode(c, m, kv, B, sw).path == DEC_LOOP_MFMA) return 0;
+  if (B < pcy_mfma_min_batch())
+    return fail(1, "%s: a shared-prefix cache is served by the batched decode loop only (>= %d rows), not %d row%s", what, pcy_mfma_min_batch(), B, B == 1 ? "" : "s");
+  return fail(1, "%s: a shared-prefix cache is served by the batched decode loop only, which does not cover this geometry (d %% 128, ffn %% 128)", what);
+}
 
 // measurement aid (PCY_MC_TRACE, tools/bench_decode*.py): in-kernel time stamps, [layer][workgroup][16] behind a first half of the same size
 unsigned long long* mc_trace(const PcySwitches& sw, int l = 0) {
@@ -422,7 +446,12 @@ PcyDecAttnArgs attn_args(const DecodeCx& cx, const DecodePlan& p, int l) {
   PcyDecAttnArgs t{};
   t.qkv = cx.qkv; t.ld = cx.qkvw; t.kcache = (bf16_t*)cx.kv->k + (l > 0 ? l : 0) * cx.layer_stride; t.vcache = (bf16_t*)cx.kv->v + (l > 0 ? l : 0) * cx.layer_stride;
   t.o = cx.ao; t.ldo = m->n_heads * m->head_dim; t.pos_dev = cx.st->pos; t.cos_t = (const bf16_t*)m->rope_cos; t.sin_t = (const bf16_t*)m->rope_sin;
-  t.keep = cx.st->keep; t.ld_keep = cx.kv->Tmax; t.scratch = cx.scores; t.B = cx.B; t.H = m->n_heads; t.Hkv = m->n_kv_heads; t.dh = m->head_dim; t.Tmax = cx.kv->Tmax;
+  t.keep = cx.st->keep; t.ld_keep = kv_cap(cx.kv); t.scratch = cx.scores; t.B = cx.B; t.H = m->n_heads; t.Hkv = m->n_kv_heads; t.dh = m->head_dim; t.Tmax = kv_cap(cx.kv);
+  if (kv_shared(cx.kv)) {   // (per-layer strides of BOTH arrays: the suffix above, the prefix here)
+    t.prefix_k = (const bf16_t*)cx.kv->prefix_k + (l > 0 ? l : 0) * cx.prefix_layer_stride;
+    t.prefix_v = (const bf16_t*)cx.kv->prefix_v + (l > 0 ? l : 0) * cx.prefix_layer_stride;
+    t.Tp = cx.kv->prefix_T; t.rows_per_prefix = cx.kv->rows_per_prefix;
+  }
   t.scale = 1.0f / sqrtf((float)m->head_dim);
   t.xmin = p.xmin;
   if (l < 0) t.xflags = cx.c->ao_sync + 64 + AO_MAX_LAYERS * AO_FLAGS;   // (per-layer launches get their flags as a launcher argument)
@@ -526,6 +555,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
       try_layer = false;   // geometry not covered: the same for every layer
     }
     if (l == 0) ++g_pcy_dispatch[p.batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
+    if (l == 0 && kv_shared(kv)) ++g_pcy_dispatch[PCY_DISPATCH_SHARED_PREFIX];
     // (batched: the previous layer's down projection may have written xn already, fused into its K-split finish)
     if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
     xn_ready = 0;
@@ -631,7 +661,7 @@ int ensure_sample_state(pcy_ctx* c, int B, int V) {
 // re-ranks most rows at every step: 3.87 -> see DESIGN.md ms per beam-5 step at a 570-token cache.
 template <int MAXB>
 __global__ __launch_bounds__(128) void kv_permute_kernel(bf16_t* __restrict__ kbase, bf16_t* __restrict__ vbase, const int32_t* __restrict__ rows, int B,
-                                                         int Bcache, int Hkv, int Tmax, int t, int dh, const int32_t* __restrict__ t_dev, int t0) {
+                                                         int Bcache, int Hkv, int Tmax, int t, int dh, const int32_t* __restrict__ t_dev, int t0, int t_off) {
   __shared__ uint4 stage[MAXB * 128];
   const int h = blockIdx.x, lw = blockIdx.y, l = lw >> 1;
   unsigned need = 0;                                       // rows some OTHER row takes its contents from (uniform)
@@ -641,7 +671,8 @@ __global__ __launch_bounds__(128) void kv_permute_kernel(bf16_t* __restrict__ kb
     if (sb != b) { moves = true; if (sb >= 0 && sb < B) need |= 1u << sb; }
   }
   if (!moves) return;                                      // no row moves
-  if (t_dev) { t = *t_dev; t = t < Tmax ? t : Tmax; }
+  // (t_off: the slots of a shared-prefix cache's suffix panels start at logical slot t_off = prefix_T; 0 for a plain cache)
+  if (t_dev) { t = *t_dev - t_off; t = t < Tmax ? t : Tmax; t = t > 0 ? t : 0; }
   bf16_t* cache = ((lw & 1) ? vbase : kbase) + (size_t)l * Bcache * Hkv * Tmax * dh + (size_t)h * Tmax * dh;
   const size_t rstride = (size_t)Hkv * Tmax * dh;          // elements between two rows of the slab
   const size_t n8 = (size_t)t * dh / 8;
@@ -662,13 +693,13 @@ __global__ __launch_bounds__(128) void kv_permute_kernel(bf16_t* __restrict__ kb
 }
 // enqueue: the one-pass form for <= 32 rows (PCY_DISABLE=kv_permute: the two launches through the scratch copy; same result)
 static bool enqueue_kv_permute(hipStream_t s, const pcy_llama_desc* m, const pcy_kv_cache* kv, const int32_t* src_rows, int B, int t, const int32_t* t_dev,
-                               int t0 = 0) {
+                               int t0, int t_off) {
   if (B > 32 || pcy_off("kv_permute")) return false;
   const dim3 grid(m->n_kv_heads, 2 * m->n_layers, 4);
   if (B <= 8)
-    hipLaunchKernelGGL(kv_permute_kernel<8>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0);
+    hipLaunchKernelGGL(kv_permute_kernel<8>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0, t_off);
   else
-    hipLaunchKernelGGL(kv_permute_kernel<32>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0);
+    hipLaunchKernelGGL(kv_permute_kernel<32>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0, t_off);
   return true;
 }
 
@@ -676,12 +707,12 @@ static bool enqueue_kv_permute(hipStream_t s, const pcy_llama_desc* m, const pcy
 // advanced) and the scratch rows are Tmax slots apart -- nothing in the launch depends on the step.
 __global__ void kv_gather_kernel(bf16_t* __restrict__ kbase, bf16_t* __restrict__ vbase, bf16_t* __restrict__ tmp,
                                  const int32_t* __restrict__ rows, int B, int Bcache, int Hkv, int Tmax, int t, int dh, int to_tmp,
-                                 const int32_t* __restrict__ t_dev, int t0) {
+                                 const int32_t* __restrict__ t_dev, int t0, int t_off) {
   const int b = blockIdx.x, h = blockIdx.y, lw = blockIdx.z, l = lw >> 1;
   const int src_b = rows[b];
   if (src_b == b) return;
   int ts = t;                 // slots between two scratch rows
-  if (t_dev) { t = *t_dev; t = t < Tmax ? t : Tmax; ts = Tmax; }
+  if (t_dev) { t = *t_dev - t_off; t = t < Tmax ? t : Tmax; t = t > 0 ? t : 0; ts = Tmax; }   // (t_off: see kv_permute_kernel)
   bf16_t* cache = ((lw & 1) ? vbase : kbase) + (size_t)l * Bcache * Hkv * Tmax * dh;
   bf16_t* scratch = tmp + (size_t)lw * B * Hkv * ts * dh;
   const size_t n8 = (size_t)t * dh / 8;
@@ -1219,6 +1250,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
   if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "pcy_llama_prefill: d, ffn, H*dh, Hkv*dh must be multiples of 64");
   if (F % 16) return fail(1, "pcy_llama_prefill: ffn %% 16");
+  if (kv_shared(kv)) return fail(1, "pcy_llama_prefill: a cache with a shared prefix cannot be prefilled (prefill the prefix cache itself)");
   if (B > kv->B || T > kv->Tmax) return fail(1, "pcy_llama_prefill: B=%d T=%d exceed cache (%d,%d)", B, T, kv->B, kv->Tmax);
   if (T > m->max_pos) return fail(1, "pcy_llama_prefill: T=%d exceeds rope table %d", T, m->max_pos);
   const int M = B * T, qkvw = (H + 2 * Hkv) * dh, Tp = (T + 31) / 32 * 32;
@@ -1381,6 +1413,7 @@ void decode_graph_key(DecodeGraphKey& k, const pcy_ctx* c, const pcy_llama_desc*
   memset(&k, 0, sizeof(k));
   k.kind = kind; k.B = B; k.sw = sw;
   k.model = m; k.layers = m->layers; k.embed = m->embed; k.kv_k = kv->k; k.kv_v = kv->v; k.Tmax = kv->Tmax; k.kv_B = kv->B;
+  if (kv_shared(kv)) { k.kv_prefix_k = kv->prefix_k; k.kv_prefix_v = kv->prefix_v; k.kv_prefix_T = kv->prefix_T; k.kv_prefix_B = kv->prefix_B; k.kv_rows_per_prefix = kv->rows_per_prefix; }
   k.pos = st->pos; k.step = st->step; k.next_tok = st->next_tok; k.logits = st->logits; k.keep = st->keep;
   k.ws = c->ws; k.mc_tags = c->mc_tags; k.mb_flags = c->mb_flags; k.nb_tags = B <= 8 ? c->nb_tags[B] : nullptr; k.dev_layers = c->dev_layers;
   k.layers_fp = c->layers_fp;
@@ -1414,7 +1447,7 @@ int replay_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache*
   key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps;
   return replay_graph(c, key, n_steps, "decode-step", [&] {
     enqueue_decode(c, m, kv, st, B, sw);
-    if (kind == 0) enqueue_pick(c, m, st, B, 1, kv->Tmax);
+    if (kind == 0) enqueue_pick(c, m, st, B, 1, kv_cap(kv));
   });
 }
 }  // namespace
@@ -1437,9 +1470,10 @@ int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cach
 int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode")) return r;
   enqueue_decode(c, m, kv, st, B, sw);
   return check_launch("pcy_llama_decode");
 }
@@ -1447,17 +1481,18 @@ int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
 int pcy_llama_decode_layers(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int reps) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode_layers: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode_layers")) return r;
   for (int i = 0; i < reps; ++i) enqueue_decode(c, m, kv, st, B, sw, true);
   return check_launch("pcy_llama_decode_layers");
 }
 
 int pcy_greedy_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos) {
   PCY_STICKY(c);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
-  enqueue_pick(c, m, st, B, advance_pos, kv->Tmax);
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
+  enqueue_pick(c, m, st, B, advance_pos, kv_cap(kv));
   return check_launch("pcy_greedy_pick");
 }
 
@@ -1466,13 +1501,14 @@ int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
                      int use_graph) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_greedy: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_greedy")) return r;
   if (!use_graph) {
     for (int i = 0; i < n_steps; ++i) {
       enqueue_decode(c, m, kv, st, B, sw);
-      enqueue_pick(c, m, st, B, 1, kv->Tmax);
+      enqueue_pick(c, m, st, B, 1, kv_cap(kv));
     }
     return check_launch("pcy_llama_greedy");
   }
@@ -1482,9 +1518,10 @@ int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
 int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
   if (B > kv->B) return fail(1, "pcy_llama_decode_graph: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode_graph")) return r;
   return replay_decode_graph(c, m, kv, st, B, 1, 1, sw);
 }
 
@@ -1494,9 +1531,9 @@ int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
   if (!(temperature > 0.f)) return fail(1, "pcy_sample_pick: temperature must be > 0 (greedy: pcy_greedy_pick)");
   if (nucleus_prob >= 1.f) return fail(1, "pcy_sample_pick: nucleus_prob must be < 1 (<= 0 switches the nucleus mask off)");
   if (m->vocab > pcy_sample_max_vocab()) return fail(1, "pcy_sample_pick: vocabulary %d unsupported (<= %d)", m->vocab, pcy_sample_max_vocab());
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
-  enqueue_sample(c, m, st, B, advance_pos, kv->Tmax, temperature, nucleus_prob, uniforms, (bf16_t*)probs_out);
+  enqueue_sample(c, m, st, B, advance_pos, kv_cap(kv), temperature, nucleus_prob, uniforms, (bf16_t*)probs_out);
   return check_launch("pcy_sample_pick");
 }
 
@@ -1506,13 +1543,14 @@ int pcy_llama_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
   if (B > kv->B) return fail(1, "pcy_llama_sample: B=%d exceeds cache rows %d", B, kv->B);
   if (!(temperature > 0.f) || nucleus_prob >= 1.f) return fail(1, "pcy_llama_sample: temperature > 0 and nucleus_prob < 1 required");
   if (m->vocab > pcy_sample_max_vocab()) return fail(1, "pcy_llama_sample: vocabulary %d unsupported (<= %d)", m->vocab, pcy_sample_max_vocab());
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax))) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_sample")) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
   for (int i = 0; i < n_steps; ++i) {
     enqueue_decode(c, m, kv, st, B, sw);
-    enqueue_sample(c, m, st, B, 1, kv->Tmax, temperature, nucleus_prob, uniforms, nullptr);
+    enqueue_sample(c, m, st, B, 1, kv_cap(kv), temperature, nucleus_prob, uniforms, nullptr);
   }
   return check_launch("pcy_llama_sample");
 }
@@ -1534,20 +1572,28 @@ int pcy_kv_reorder(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, 
 int pcy_kv_reorder_range(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const int32_t* src_rows, int B, int t0, int t) {
   PCY_STICKY(c);
   const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
-  if (t <= 0 || t0 >= t) return 0;
+  if (!kv_shared(kv) && (t <= 0 || t0 >= t)) return 0;
   if (t0 < 0) return fail(1, "pcy_kv_reorder_range: t0 < 0");
+  if (kv_shared(kv)) {   // the rows own their suffix slots only: logical [max(t0, Tp), t) = suffix [max(t0, Tp) - Tp, t - Tp)
+    if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0) return fail(1, "pcy_kv_reorder: malformed shared-prefix cache");
+    const int Tp = kv->prefix_T;
+    t0 = (t0 > Tp ? t0 : Tp) - Tp;
+    t -= Tp;
+    if (t > kv->Tmax) return fail(1, "pcy_kv_reorder: %d suffix slots exceed the cache's %d", t, kv->Tmax);
+  }
+  if (t <= 0 || t0 >= t) return 0;
   if ((t * dh) % 8 || (t0 * dh) % 8) return fail(1, "pcy_kv_reorder: t * head_dim (and t0 * head_dim) must be multiples of 8");
   // scratch sized for the cache capacity, not for t: a workspace that grows step by step would be re-allocated (and the
   // captured decode graph dropped) several times per beam search
   const size_t tmp_elems = (size_t)2 * L * B * Hkv * kv->Tmax * dh;
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv->Tmax) + align_up(tmp_elems * 2, 256) + 4096)) return r;
-  bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, B, kv->Tmax), 256));
-  if (enqueue_kv_permute(c->stream, m, kv, src_rows, B, t, nullptr, t0)) return check_launch("pcy_kv_reorder");
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
+  bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256));
+  if (enqueue_kv_permute(c->stream, m, kv, src_rows, B, t, nullptr, t0, 0)) return check_launch("pcy_kv_reorder");
   const dim3 grid(B, Hkv, 2 * L);
   hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, c->stream, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, src_rows, B, kv->B, Hkv,
-                     kv->Tmax, t, dh, 1, (const int32_t*)nullptr, t0);
+                     kv->Tmax, t, dh, 1, (const int32_t*)nullptr, t0, 0);
   hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, c->stream, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, src_rows, B, kv->B, Hkv,
-                     kv->Tmax, t, dh, 0, (const int32_t*)nullptr, t0);
+                     kv->Tmax, t, dh, 0, (const int32_t*)nullptr, t0, 0);
   return check_launch("pcy_kv_reorder");
 }
 
@@ -1570,26 +1616,30 @@ int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
   // everything the chain allocates, before the capture: decode workspace + the reorder scratch behind it, beam scratch, decode state
   const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
   const size_t tmp_elems = (size_t)2 * L * BB * Hkv * kv->Tmax * dh;
-  if (int r = c->reserve(decode_ws_bytes(m, BB, kv->Tmax) + align_up(tmp_elems * 2, 256) + 4096)) return r;
+  if (int r = c->reserve(decode_ws_bytes(m, BB, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, BB, sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, BB, sw, "pcy_llama_beam_steps")) return r;
+  // (a shared-prefix cache: the rows own their suffix slots only -- the reorder starts at the first of them, and counts them from prefix_T)
+  const int t_off = kv_shared(kv) ? kv->prefix_T : 0;
+  const int sfx_t0 = (kv_t0 > t_off ? kv_t0 : t_off) - t_off;
   if (int r = ensure_beam_ws(c, B, beam)) return r;
   DecodeGraphKey key;
   decode_graph_key(key, c, m, kv, st, BB, 2, sw);
   memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
   memcpy(&key.penalty_bits, &diversity_penalty, 4);
   return replay_graph(c, key, n_steps, "beam-step", [&] {
-    bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, BB, kv->Tmax), 256));
+    bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, BB, kv_cap(kv)), 256));
     hipStream_t s = c->stream;
     enqueue_decode(c, m, kv, st, BB, sw);
     enqueue_store_logits(s, st->logits, logits_rec, 0, bs->step, BB, m->vocab);
     pcy_launch_beam_step(s, (const bf16_t*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
-    if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, kv_t0)) {
+    if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, sfx_t0, t_off)) {
       const dim3 grid(BB, Hkv, 2 * L);
       hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 1,
-                         (const int32_t*)bs->pos, kv_t0);
+                         (const int32_t*)bs->pos, sfx_t0, t_off);
       hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 0,
-                         (const int32_t*)bs->pos, kv_t0);
+                         (const int32_t*)bs->pos, sfx_t0, t_off);
     }
   });
 }

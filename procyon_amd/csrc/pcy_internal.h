@@ -135,7 +135,8 @@ enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BI
        PCY_DISPATCH_DEC_STEP_MB = 13,      // 9..32 rows, all layers in one launch (pcy_decode_mb.hip)
        PCY_DISPATCH_DEC_LOOP_STREAM = 14,  // launch-per-stage loop, streaming GEMVs
        PCY_DISPATCH_DEC_LOOP_MFMA = 15,    // launch-per-stage loop, skinny-MFMA GEMVs (`batched`)
-       PCY_DISPATCH_N = 16 };
+       PCY_DISPATCH_SHARED_PREFIX = 16,   // a step served from a shared-prefix cache (in addition to the loop's own count)
+       PCY_DISPATCH_N = 17 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
 
 // per-row symmetric e4m3 quantisation: scale[r] = smallest power of two with amax|x[r,:]| / scale <= 448 (1 for an all-zero row), q = e4m3_rne(x / scale)
@@ -217,6 +218,11 @@ struct PcyDecAttnArgs {
   // stand-alone launch only: output columns per workgroup (16 / 32 / 64 / 128; 0 = the launcher's choice) -- the summation order of P.V
   // depends on it, and the launch-per-stage twin of the small-batch decode step must use the fused launch's
   int force_ds;
+  // stand-alone launch only: a cache with a shared prefix (pcy_kv_cache.prefix_k; nullptr = a plain cache, the fields below are not read).
+  // prefix_k / prefix_v [prefix_B, Hkv, Tp, dh] of THIS layer; row b reads prefix row b / rows_per_prefix for logical slots < Tp; kcache /
+  // vcache are then the suffix panels [B, Hkv, Tmax - Tp, dh] and Tmax (ld_keep, the score rows) is the LOGICAL capacity.  The launcher takes
+  // the column split it takes for a plain cache of the same rows (it depends on B, Hkv and force_ds only): same order of the P.V sums.
+  const bf16_t* prefix_k; const bf16_t* prefix_v; int Tp; int rows_per_prefix;
 };
 void pcy_launch_attn_decode(hipStream_t s, const PcyDecAttnArgs& a);
 struct PcyGemvArgs;

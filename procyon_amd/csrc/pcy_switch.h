@@ -27,7 +27,7 @@
 #define PCY_SWITCH_NAMES(X)                                                                                                                \
   X(attn_o) X(mlp_chain) X(decode_layer) X(decode_step) X(attn_qkv_finish) X(finish_norm) X(fp8_fused_norm) X(prefill_post_qkv) X(gemv_lds) \
   X(gemv_mfma4) X(fa_vrow) X(gelu_fast) X(esm_graph) X(lds_prefetch) X(decode_nb) X(decode_nb_step) X(beam_graph) X(kv_permute)             \
-  X(decode_mb_step) X(beam_prefill_once) X(beam_kv_suffix)
+  X(decode_mb_step) X(beam_prefill_once) X(beam_kv_suffix) X(beam_kv_shared)
 enum PcySwitch {
 #define X(n) PCY_SW_##n,
   PCY_SWITCH_NAMES(X)

@@ -384,16 +384,66 @@ def _h2d_many(arrays, dev, into=None):
 
 
 class KVCache:
-    """[L,B,Hkv,Tmax,dh] x2; `layer(l)` gives the reference's past_key_values[l] views."""
+    """[L,B,Hkv,Tmax,dh] x2; `layer(l)` gives the reference's past_key_values[l] views.
 
-    def __init__(self, cfg: LlamaConfig, B, Tmax, device):
+    With `prefix` (a B'-row prefill cache whose Tmax is the prompt length T, see LlamaEngine.new_beam_cache) the B rows share its K / V:
+    row b reads prefix row b // rows_per_prefix for logical slots [0, T) and owns only the suffix slots [T, T + Tmax) held in k / v
+    (include/pcy.h, pcy_kv_cache).  `Tmax` is then the suffix capacity and `capacity` the logical one."""
+
+    def __init__(self, cfg: LlamaConfig, B, Tmax, device, prefix: "KVCache" = None, rows_per_prefix=0):
         self.k = torch.zeros(cfg.n_layers, B, cfg.n_kv_heads, Tmax, cfg.head_dim, dtype=BF16, device=device)
         self.v = torch.zeros_like(self.k)
         self.B, self.Tmax = B, Tmax
-        self.c = L.KvCache(self.k.data_ptr(), self.v.data_ptr(), B, Tmax)
+        self.prefix, self.rows_per_prefix = prefix, int(rows_per_prefix)
+        if prefix is None:
+            self.c = L.KvCache(self.k.data_ptr(), self.v.data_ptr(), B, Tmax)
+        else:
+            if prefix.prefix is not None or self.rows_per_prefix < 1 or B > prefix.B * self.rows_per_prefix:
+                raise ValueError(f"shared-prefix cache: {B} rows of {rows_per_prefix} per prefix row on a {prefix.B}-row plain prefix cache")
+            self.c = L.KvCache(self.k.data_ptr(), self.v.data_ptr(), B, Tmax, prefix.k.data_ptr(), prefix.v.data_ptr(), prefix.B, prefix.Tmax,
+                               self.rows_per_prefix)
+
+    @property
+    def prefix_T(self):
+        return 0 if self.prefix is None else self.prefix.Tmax
+
+    @property
+    def capacity(self):
+        """logical key slots per row: what the position counter and the keep mask count in"""
+        return self.prefix_T + self.Tmax
 
     def layer(self, l, t):
-        return self.k[l, :, :, :t], self.v[l, :, :, :t]
+        if self.prefix is None:
+            return self.k[l, :, :, :t], self.v[l, :, :, :t]
+        # (tests / debugging only: the logical [B, Hkv, t, dh] rows materialised, prefix rows repeated + suffix)
+        Tp = self.prefix_T
+        rows = torch.arange(self.B, device=self.k.device) // self.rows_per_prefix
+        pk, pv = self.prefix.k[l][rows, :, :min(t, Tp)], self.prefix.v[l][rows, :, :min(t, Tp)]
+        if t <= Tp:
+            return pk, pv
+        return torch.cat([pk, self.k[l, :, :, :t - Tp]], 2), torch.cat([pv, self.v[l, :, :, :t - Tp]], 2)
+
+
+# The beams of a prompt share ONE copy of its K / V (KVCache with a prefix) when the plan below says so.  A pure function of the call's shape
+# and the PCY_DISABLE names: the rule lives here and nowhere else.
+#   beam > 1                     -- one row per prompt has nothing to share
+#   B * beam > BEAM_SHARED_MIN_ROWS_ABOVE (8 = the upper clamp of PCY_NB_MAX) -- the small-batch one-launch step serves up to that many rows and
+#                                   reads plain caches only: it is never displaced, whatever the switches say
+#   none of beam_kv_shared / beam_prefill_once / beam_kv_suffix in PCY_DISABLE -- the shared cache IS "prefill once" and "reorder the suffix
+#                                   only"; with either twin asked for, the plain cache serves it
+BEAM_SHARED_MIN_ROWS_ABOVE = 8
+
+
+def beam_cache_plan(B, beam, T, max_new, disabled_names=()):
+    """-> dict(shared, rows, prefix_rows, prefix_slots, suffix_slots, slots_shared, slots_plain): whether a beam search of B prompts x beam
+    beams over T prompt tokens and max_new generated ones runs on a shared-prefix cache, and the K (= V) slots per layer and kv head of
+    the two layouts: B*T + B*beam*max_new against B*beam*(T + max_new)."""
+    B, beam, T, max_new = int(B), int(beam), int(T), int(max_new)
+    off = set(disabled_names)
+    rows = B * beam
+    shared = beam > 1 and rows > BEAM_SHARED_MIN_ROWS_ABOVE and not (off & {"beam_kv_shared", "beam_prefill_once", "beam_kv_suffix"})
+    return dict(shared=bool(shared), rows=rows, prefix_rows=B, prefix_slots=T, suffix_slots=max_new,
+                slots_shared=B * T + rows * max_new, slots_plain=rows * (T + max_new))
 
 
 class GenState:
@@ -505,6 +555,11 @@ class LlamaEngine:
 
     def new_cache(self, B, Tmax):
         return KVCache(self.cfg, B, Tmax, self.device)
+
+    def new_beam_cache(self, prefix_cache: KVCache, beam, max_new):
+        """The cache of a beam search over the prompts prefilled into `prefix_cache` (B rows, Tmax == the prompt length): B * beam rows that
+        share the prompts' K / V and own [L, B*beam, Hkv, max_new, dh] suffix slots.  Row r belongs to prompt r // beam."""
+        return KVCache(self.cfg, prefix_cache.B * int(beam), int(max_new), self.device, prefix=prefix_cache, rows_per_prefix=int(beam))
 
     def embed_tokens(self, ids, soft=None, soft_map=None):
         """ids [B,T] int -> [B,T,d]; soft-token splice of `_prepare_input_embeddings` if soft_map given."""

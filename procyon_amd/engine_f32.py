@@ -197,6 +197,12 @@ class EsmEngineF32:
         return out
 
 
+def _no_shared_prefix(cache):
+    """the fp32 family reads plain caches only (a shared-prefix cache, engine.KVCache with a prefix, belongs to the bf16 batched decode loop)"""
+    if getattr(cache, "prefix", None) is not None:
+        raise ValueError("the fp32 decoder does not take a cache with a shared prefix")
+
+
 class KVCacheF32:
     """token-major fp32 K (roped) / V caches [L, B, Tmax, Hkv*dh]"""
 
@@ -257,6 +263,7 @@ class LlamaEngineF32:
         ops, cfg = self.ops, self.cfg
         H, Hkv, dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
         B = ids.numel()
+        _no_shared_prefix(cache)
         if t + 1 > cache.Tmax:
             raise ValueError(f"KV cache capacity {cache.Tmax} exhausted; raise max_new_tokens")
         ids_d, = _h2d_many([ids.reshape(-1).to(torch.int32).cpu()], self.device)
@@ -282,6 +289,7 @@ class LlamaEngineF32:
         L+1 hidden states at `sum_rows` (flat b*T+t) [n,d]]) -- the return contract of `LlamaEngine.prefill`"""
         ops, cfg = self.ops, self.cfg
         B, T, d = embeds.shape
+        _no_shared_prefix(cache)
         if T > cfg.max_pos:
             raise ValueError(f"T={T} exceeds the rotary table ({cfg.max_pos})")
         H, Hkv, dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim

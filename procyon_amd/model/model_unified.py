@@ -575,7 +575,7 @@ class UnifiedProCyon:
             enc.max_new_tokens = keep_new
 
     def _beam_search_body(self, input_embeds, attn_mask, B, BB, V, T, max_len, beam_size, beam_group_size, diversity_penalty):
-        from ..engine import BeamState, GenState
+        from ..engine import BeamState, GenState, beam_cache_plan
         dev = self.device
         enc = self.text_encoder
         eng = enc.engine
@@ -589,7 +589,17 @@ class UnifiedProCyon:
         # Here each prompt is prefilled ONCE into row b of a BB-row cache; its K / V rows are then copied to the rows of its beams (one
         # pcy_kv_reorder with the constant source map r -> r // beam) and its last-row logits repeated.  PCY_DISABLE=beam_prefill_once: the
         # reference's replicated prefill (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise, tests).
-        if beam_size > 1 and "beam_prefill_once" not in os.environ.get("PCY_DISABLE", "").split(","):
+        # Where beam_cache_plan says so (more than 8 rows, default switches) the beams do not even get copies: the prompts are prefilled into a
+        # B-row cache of exactly T slots and the BB rows share it, owning only their max_new suffix slots (engine.KVCache with a prefix; DESIGN.md
+        # 4.3b) -- B*T + BB*max_new slots instead of BB*(T + max_new), no replicating copy, and the same bits: PCY_DISABLE=beam_kv_shared is the twin.
+        disabled = os.environ.get("PCY_DISABLE", "").split(",")
+        plan = beam_cache_plan(B, beam_size, T, enc.max_new_tokens, disabled)
+        if plan["shared"]:
+            prefix = eng.new_cache(B, T)
+            lg_b, _ = eng.prefill(input_embeds.to(eng.device), attn_mask, prefix, "last")
+            cache = eng.new_beam_cache(prefix, beam_size, enc.max_new_tokens)
+            logits = lg_b.repeat_interleave(beam_size, dim=0).contiguous()
+        elif beam_size > 1 and "beam_prefill_once" not in disabled:
             cache = eng.new_cache(BB, T + enc.max_new_tokens)
             lg_b, _ = eng.prefill(input_embeds.to(eng.device), attn_mask, cache, "last")
             eng.kv_reorder(cache, torch.arange(BB, dtype=torch.int32) // beam_size, T)
@@ -615,8 +625,8 @@ class UnifiedProCyon:
         if "beam_graph" in os.environ.get("PCY_DISABLE", "").split(","):   # the four calls per step (same kernels, same bits; tests)
             for i in range(max_len):
                 if i > 0:
-                    if T + i > cache.Tmax:
-                        raise ValueError(f"KV cache capacity {cache.Tmax} exhausted; raise max_new_tokens")
+                    if T + i > cache.capacity:
+                        raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
                     eng.decode_graph(cache, st, BB)
                     logits = st.logits
                 rec[i].copy_(logits)
@@ -632,9 +642,9 @@ class UnifiedProCyon:
             eng.kv_reorder(cache, bs.src, T, t0=kv_t0)
             i = 1
             while i < max_len:
-                if T + i > cache.Tmax:
-                    raise ValueError(f"KV cache capacity {cache.Tmax} exhausted; raise max_new_tokens")
-                n = min(8 - (i & 7), max_len - i, cache.Tmax - T - i + 1)
+                if T + i > cache.capacity:
+                    raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
+                n = min(8 - (i & 7), max_len - i, cache.capacity - T - i + 1)
                 eng.beam_steps(cache, st, bs, beam_group_size, diversity_penalty, rec, n, kv_t0=kv_t0)
                 i += n
                 if (i & 7) == 0 and int(bs.done):
