@@ -446,11 +446,16 @@ def beam_cache_plan(B, beam, T, max_new, disabled_names=()):
                 slots_shared=B * T + rows * max_new, slots_plain=rows * (T + max_new))
 
 
+def disabled_switches():
+    """The names in PCY_DISABLE (procyon_amd/csrc/pcy_switch.h: comma separated, whole names), read now: the one reader on the Python side."""
+    return frozenset(n.strip() for n in os.environ.get("PCY_DISABLE", "").split(",") if n.strip())
+
+
 class GenState:
-    def __init__(self, B, vocab, max_steps, device, keep_logits=False, keep=None):
-        self.pos = torch.zeros(1, dtype=torch.int32, device=device)
+    def __init__(self, B, vocab, max_steps, device, keep_logits=False, keep=None, pos=None, next_tok=None):   # pos, next_tok: see BeamState.gen_state
+        self.pos = torch.zeros(1, dtype=torch.int32, device=device) if pos is None else pos
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
-        self.next_tok = torch.zeros(B, dtype=torch.int32, device=device)
+        self.next_tok = torch.zeros(B, dtype=torch.int32, device=device) if next_tok is None else next_tok
         self.tokens_out = torch.zeros(B, max_steps, dtype=torch.int32, device=device)
         self.logprob = torch.zeros(B, dtype=torch.float32, device=device)
         self.logits = torch.empty(B, vocab, dtype=BF16, device=device)
@@ -490,6 +495,10 @@ class BeamState:
         self.c = L.BeamState(self.out.data_ptr(), max_len, self.cur.data_ptr(), self.cur_new.data_ptr(), self.next_tok.data_ptr(),
                              self.src.data_ptr(), self.anc.data_ptr(), self.has_eos.data_ptr(), self.blk_eos.data_ptr(),
                              self.ticket.data_ptr(), self.pos.data_ptr(), self.step.data_ptr(), self.done.data_ptr(), int(eos_id))
+
+    def gen_state(self, vocab):
+        """The decode state of the BB rows on this state's own position and next-token arrays: the decode step reads what the beam step writes."""
+        return GenState(self.BB, vocab, 1, self.pos.device, pos=self.pos, next_tok=self.next_tok)
 
     def tokens(self):
         """[BB, steps] int64 histories after the steps run so far (syncs)."""
@@ -568,11 +577,10 @@ class LlamaEngine:
         sm = None if soft_map is None else soft_map.to(self.device, torch.int32).contiguous().view(-1)
         return self.ctx.embed_splice(self.embed, i32, soft, sm).view(B, T, self.cfg.d)
 
-    def prefill(self, embeds, attn_mask, cache: KVCache, logit_rows="last", want_hidden=False, sum_rows=None):
-        """embeds [B,T,d] bf16; attn_mask [B,T] (0/1) or None.  Returns (logits [n,V], hidden [B,T,d]|None), and with
-        `sum_rows` (flat token rows b*T+t) additionally the sum over all L+1 hidden states of those rows [n,d]
-        (ret_token_access='all')."""
-        B, T, d = embeds.shape
+    def _prefill_args(self, embeds, attn_mask, logit_rows, all_rows=False):
+        """What both prefill entry points hand the library -> (embeds contiguous, keep mask uint8 [B,T] | None when nothing is masked, positions,
+        cu / vt_cu offsets, flat logit rows int32, logits [n,V] to fill).  logit_rows: "last", None, flat rows b*T+t; with all_rows also "all"."""
+        B, T, _ = embeds.shape
         embeds = embeds.contiguous()
         _chk_bf16(embeds)
         dev = self.device
@@ -580,23 +588,31 @@ class LlamaEngine:
         if attn_mask is not None and not bool((attn_mask != 0).all()):
             keep = (attn_mask != 0).to(dev, torch.uint8).contiguous()
         pos = torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-        Tp = (T + 31) // 32 * 32
         cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * T
-        vt_cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * Tp
-        if isinstance(logit_rows, str) and logit_rows == "last":
+        vt_cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * ((T + 31) // 32 * 32)
+        if all_rows and isinstance(logit_rows, str) and logit_rows == "all":
+            rows = torch.arange(B * T, dtype=torch.int32, device=dev)
+        elif isinstance(logit_rows, str) and logit_rows == "last":
             rows = (torch.arange(B, dtype=torch.int32, device=dev) + 1) * T - 1
         elif logit_rows is None:
             rows = torch.zeros(0, dtype=torch.int32, device=dev)
         else:
             rows = logit_rows.to(dev, torch.int32).contiguous()
-        n = rows.numel()
-        logits = torch.empty(n, self.cfg.vocab, dtype=BF16, device=dev)
+        return embeds, keep, pos, cu, vt_cu, rows, torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
+
+    def prefill(self, embeds, attn_mask, cache: KVCache, logit_rows="last", want_hidden=False, sum_rows=None):
+        """embeds [B,T,d] bf16; attn_mask [B,T] (0/1) or None.  Returns (logits [n,V], hidden [B,T,d]|None), and with
+        `sum_rows` (flat token rows b*T+t) additionally the sum over all L+1 hidden states of those rows [n,d]
+        (ret_token_access='all')."""
+        B, T, d = embeds.shape
+        dev = self.device
+        embeds, keep, pos, cu, vt_cu, rows, logits = self._prefill_args(embeds, attn_mask, logit_rows)
         hidden = torch.empty(B, T, d, dtype=BF16, device=dev) if want_hidden else None
         srows = None if sum_rows is None else sum_rows.to(dev, torch.int32).contiguous()
         ns = 0 if srows is None else srows.numel()
         hsum = torch.empty(ns, d, dtype=BF16, device=dev) if ns else None
         L.check(self.ctx.lib.pcy_llama_prefill(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep), _p(pos),
-                                               _p(cu), _p(vt_cu), B, T, _p(rows), n, _p(logits), _p(hidden), _p(srows), ns, _p(hsum)),
+                                               _p(cu), _p(vt_cu), B, T, _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), ns, _p(hsum)),
                 "pcy_llama_prefill")
         if sum_rows is not None:
             return logits, hidden, hsum
@@ -607,29 +623,11 @@ class LlamaEngine:
         `logit_rows` ("all" = every token row, the reference's [B,T,V]; "last"; None; or flat rows), hidden_states [L+1,B,T,d] =
         embeddings, outputs of layers 0..L-2, final-normed output of layer L-1)."""
         B, T, d = embeds.shape
-        embeds = embeds.contiguous()
-        _chk_bf16(embeds)
         dev = self.device
-        keep = None
-        if attn_mask is not None and not bool((attn_mask != 0).all()):
-            keep = (attn_mask != 0).to(dev, torch.uint8).contiguous()
-        pos = torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
-        Tp = (T + 31) // 32 * 32
-        cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * T
-        vt_cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * Tp
-        if isinstance(logit_rows, str) and logit_rows == "all":
-            rows = torch.arange(B * T, dtype=torch.int32, device=dev)
-        elif isinstance(logit_rows, str) and logit_rows == "last":
-            rows = (torch.arange(B, dtype=torch.int32, device=dev) + 1) * T - 1
-        elif logit_rows is None:
-            rows = torch.zeros(0, dtype=torch.int32, device=dev)
-        else:
-            rows = logit_rows.to(dev, torch.int32).contiguous()
-        n = rows.numel()
-        logits = torch.empty(n, self.cfg.vocab, dtype=BF16, device=dev)
+        embeds, keep, pos, cu, vt_cu, rows, logits = self._prefill_args(embeds, attn_mask, logit_rows, all_rows=True)
         hidden_all = torch.empty(self.cfg.n_layers + 1, B, T, d, dtype=BF16, device=dev)
         L.check(self.ctx.lib.pcy_llama_prefill_all(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep), _p(pos),
-                                                   _p(cu), _p(vt_cu), B, T, _p(rows), n, _p(logits), _p(hidden_all)),
+                                                   _p(cu), _p(vt_cu), B, T, _p(rows), rows.numel(), _p(logits), _p(hidden_all)),
                 "pcy_llama_prefill_all")
         return logits, hidden_all
 
@@ -675,17 +673,23 @@ class LlamaEngine:
         L.check(self.ctx.lib.pcy_llama_sample(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B, n_steps, float(temperature),
                                               -1.0 if nucleus_prob is None else float(nucleus_prob), _p(uniforms)), "pcy_llama_sample")
 
+    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, keep=None):
+        """How greedy and sampling open: a cache of T + max_len slots, the state, the prompts prefilled, their last-row logits in st.logits, pos = T."""
+        B, T, _ = embeds.shape
+        cache = self.new_cache(B, T + max_len)
+        st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, keep)
+        logits, _ = self.prefill(embeds, attn_mask, cache, "last")
+        st.logits.copy_(logits)
+        st.pos.fill_(T)
+        return cache, st
+
     def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) entirely on the device: prefill, then per step the
         decode launches + the sampling kernels (pcy_llama_sample); the uniform variates of all steps are drawn up front from
         torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state)."""
-        B, T, _ = embeds.shape
-        cache = self.new_cache(B, T + max_len)
-        st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, None)
+        B = embeds.shape[0]
         u = torch.rand(max_len * B, device=self.device, dtype=torch.float32) if uniforms is None else uniforms.to(self.device, torch.float32).contiguous()
-        logits, _ = self.prefill(embeds, attn_mask, cache, "last")
-        st.logits.copy_(logits)
-        st.pos.fill_(T)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits)
         self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
         if max_len > 1:
             self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob)
@@ -703,15 +707,11 @@ class LlamaEngine:
         steps with no mask and position = cache length (Q1/Q2); no EOS stop.  Everything stays on the device;
         returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,max_len,V] bf16 | None, state)."""
         B, T, _ = embeds.shape
-        cache = self.new_cache(B, T + max_len)
         keep = None
         if clean_decode_mask and attn_mask is not None:
             keep = torch.ones(B, T + max_len, dtype=torch.uint8, device=self.device)
             keep[:, :T] = (attn_mask != 0).to(self.device, torch.uint8)
-        st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, keep)
-        logits, _ = self.prefill(embeds, attn_mask, cache, "last")
-        st.logits.copy_(logits)
-        st.pos.fill_(T)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, keep)
         self.pick(cache, st, B, advance_pos=False)
         if max_len > 1:
             self.greedy_steps(cache, st, B, max_len - 1, use_graph)
@@ -720,6 +720,76 @@ class LlamaEngine:
         self.ctx.sync()
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
         return st.tokens_out.long(), st.logprob, la, (st, cache)
+
+    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new):
+        """`_generate_beam_search` (model_unified.py:702-842): diverse beam search of B prompts x beam_size beams, at most max_len tokens, on
+        a cache with room for max_new (>= max_len) generated ones.  Returns (tokens [BB,max_len] int64 and scores [BB] on the host, logits
+        [BB,steps,V] in pinned host memory), BB = B * beam_size, row r = beam r % beam_size of prompt r // beam_size.
+        Nothing synchronises inside a step: the decode step is ONE replayed hipGraph reading the next tokens and the position from device
+        memory, the reference's per-group bookkeeping ONE launch (pcy_beam_step), the KV reorder two.  The logits record is kept per SLOT and
+        step and re-indexed once at the end along the parent chain (the reference re-indexes the whole history in every group of every step,
+        :827-829).  The EOS stop (:833) is decided on the device; the host looks at the flag every 8 steps."""
+        B, T, _ = embeds.shape
+        BB, V, dev = B * beam_size, self.cfg.vocab, self.device
+        off = disabled_switches()
+        # Three cache layouts (DESIGN.md 4.3b).  Each prompt is prefilled ONCE (the reference replicates it x beam before the prefill, :751-752)
+        # and its last-row logits repeated: where beam_cache_plan says so into a B-row cache of exactly T slots that the BB rows share, owning
+        # only their max_new suffix slots; otherwise into row b of a BB-row cache, its K / V rows then copied to the rows of its beams (one
+        # pcy_kv_reorder, source map r -> r // beam).  PCY_DISABLE=beam_prefill_once, or one beam: the reference's replicated prefill, issued
+        # as LlamaPostTokenization.forward issues it (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise).
+        shared = beam_cache_plan(B, beam_size, T, max_new, off)["shared"]
+        rep = lambda x: x.repeat_interleave(beam_size, dim=0)
+        if shared or (beam_size > 1 and "beam_prefill_once" not in off):
+            cache = self.new_cache(B, T) if shared else self.new_cache(BB, T + max_new)
+            lg_b, _ = self.prefill(embeds.to(dev), attn_mask, cache, "last")
+            if shared:
+                cache = self.new_beam_cache(cache, beam_size, max_new)
+            else:
+                self.kv_reorder(cache, torch.arange(BB, dtype=torch.int32) // beam_size, T)
+            logits = rep(lg_b).contiguous()
+        else:
+            cache = self.new_cache(BB, T + max_new)
+            logits, _ = self.prefill_all(rep(embeds).to(dev), rep(attn_mask), cache, (torch.arange(BB, dtype=torch.int32) + 1) * T - 1)
+        # The beams of a prompt hold the SAME K / V rows in slots [0, T), so the per-step reorder starts at slot T (at 10 beams and a 512-token
+        # prompt it was 0.4-0.6 ms of a 4.5 ms step).  PCY_DISABLE=beam_kv_suffix: every slot, as the reference (:830-832; same result).
+        kv_t0 = 0 if "beam_kv_suffix" in off or (T * self.cfg.head_dim) % 8 else T
+        bs = BeamState(B, beam_size, max_len, eos_id, prompt_len=T, device=dev)
+        st = bs.gen_state(V)
+        rec = torch.empty(max_len, BB, V, dtype=logits.dtype, device=dev)
+        # Step 0 selects on the prefill's logits.  Every later step is decode -> record -> beam step -> KV reorder: ONE replayed launch chain
+        # (pcy_llama_beam_steps), enqueued up to the next multiple of 8 steps; PCY_DISABLE=beam_graph: the four calls (same kernels and bits).
+        rec[0].copy_(logits)
+        self.beam_step(logits, bs, group_size, diversity_penalty)
+        self.kv_reorder(cache, bs.src, T, t0=kv_t0)
+        i = 1
+        while i < max_len and not ((i & 7) == 0 and int(bs.done)):
+            if T + i > cache.capacity:
+                raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
+            if "beam_graph" in off:
+                n = 1
+                self.decode_graph(cache, st, BB)
+                rec[i].copy_(st.logits)
+                self.beam_step(st.logits, bs, group_size, diversity_penalty)
+                self.kv_reorder(cache, bs.src, T + i, t0=kv_t0)
+            else:
+                n = min(8 - (i & 7), max_len - i, cache.capacity - T - i + 1)
+                self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=kv_t0)
+            i += n
+        out, steps = bs.tokens()                                   # synchronises
+        anc = bs.anc[:steps].long()
+        slot = torch.arange(BB, device=dev)
+        idx = torch.empty(steps, BB, dtype=torch.long, device=dev)
+        for s_ in range(steps - 1, -1, -1):                        # the record of step s is re-indexed by the parents of steps >= s
+            slot = anc[s_][slot]
+            idx[s_] = slot
+        # [BB, steps, V] on the device, then ONE copy into pinned host memory (a pageable destination moves the 2.5 MB per step
+        # and beam-10 record at a few GB/s: ~1 ms per generated token)
+        out_logits_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
+        out_logits = torch.empty(out_logits_dev.shape, dtype=out_logits_dev.dtype, pin_memory=True)
+        out_logits.copy_(out_logits_dev, non_blocking=True)
+        tokens, scores = torch.nn.functional.pad(out.cpu(), (0, max_len - steps)), bs.cur.cpu()      # (zeros behind an early EOS stop)
+        self.ctx.sync()      # stream complete + the sticky watchdog word of the fused launches checked (raises PcyError)
+        return tokens, scores, out_logits
 
 
 # ------------------------------------------------------------------------------------------------

@@ -8,12 +8,12 @@ SURVEY.md section 8b (scripts/, evaluate/framework/procyon.py, inference/) can s
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass
 from itertools import chain
 from types import SimpleNamespace
 from typing import List, Optional
 
-import os
 import torch
 
 from ..engine import BF16, MlpEngine
@@ -531,16 +531,10 @@ class UnifiedProCyon:
         B = len(input_embeds)
         out_list, lp_list, logit_list = [], [], []
         for _ in range(num_text_per_instance):
-            if greedy:
-                tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True)
-                out_list.append(tok.cpu())
-                lp_list.append(lp.cpu().clone())
-                logit_list.append(lg.cpu())
-                continue
-            # the whole loop on the device: decode launches + the sampling kernels (softmax, nucleus mask by histogram, inverse-CDF
+            # the whole loop on the device: decode launches + the pick (greedy: argmax; sampling: softmax, nucleus mask by histogram, inverse-CDF
             # draw with uniform variates from torch's device generator); the logits record goes to the host as it is produced
-            tok, lp, lg, _ = eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob,
-                                                   keep_logits=True)
+            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True) if greedy else \
+                eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True)
             out_list.append(tok.cpu())
             lp_list.append(lp.cpu().clone())
             logit_list.append(lg.cpu())
@@ -557,115 +551,25 @@ class UnifiedProCyon:
         fp32 running score, EOS-anywhere stop).  The transformer steps run on the engine; the per-step
         O(B x groups) bookkeeping is `pcy_beam_step` (one launch; ties between equal candidate scores go to the lowest flat
         index, where torch.topk leaves the order unspecified)."""
-        B = input_embeds.shape[0]
-        BB = B * beam_size
-        V = self.text_encoder.model.vocab_size
         if beam_size % beam_group_size != 0:
             raise ValueError("beam_group_size must evenly divide beam_size, got: "
                              f"{beam_size} % {beam_group_size} != 0")
-        enc = self.text_encoder
         if beam_size > 32:
             raise ValueError("beam_size > 32 is not supported by the device-side beam step")
-        T = input_embeds.shape[1]
-        keep_new = enc.max_new_tokens
+        enc = self.text_encoder
+        flat = enc.engine.generate_beam(input_embeds, attn_mask, max_len, beam_size, beam_group_size, diversity_penalty,
+                                        self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len))
+        return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
+
+    @contextmanager
+    def _room_for(self, max_len):
+        """the text encoder's caches hold at least max_len generated tokens inside the block (max_new_tokens raised, then put back)"""
+        enc, keep_new = self.text_encoder, self.text_encoder.max_new_tokens
         enc.max_new_tokens = max(keep_new, max_len)
         try:
-            return self._beam_search_body(input_embeds, attn_mask, B, BB, V, T, max_len, beam_size, beam_group_size, diversity_penalty)
+            yield
         finally:
             enc.max_new_tokens = keep_new
-
-    def _beam_search_body(self, input_embeds, attn_mask, B, BB, V, T, max_len, beam_size, beam_group_size, diversity_penalty):
-        from ..engine import BeamState, GenState, beam_cache_plan
-        dev = self.device
-        enc = self.text_encoder
-        eng = enc.engine
-        # Everything per step stays on the device and nothing synchronises: the decode step is ONE replayed hipGraph reading the
-        # next tokens and the position from device memory, the reference's per-group bookkeeping is ONE launch (pcy_beam_step),
-        # the KV reorder two (rows that keep their place are skipped).  The logits record is kept per SLOT and step and is
-        # re-indexed once at the end along the parent chain (the reference re-indexes the whole history on the host in every
-        # group of every step, model_unified.py:827-829).  The EOS stop (:833) is decided on the device; once it has fired the
-        # queued steps change nothing, so the host looks at the flag only every few steps.
-        # The reference replicates every prompt x beam BEFORE the prefill (model_unified.py:751-752): beam x the prefill on identical rows.
-        # Here each prompt is prefilled ONCE into row b of a BB-row cache; its K / V rows are then copied to the rows of its beams (one
-        # pcy_kv_reorder with the constant source map r -> r // beam) and its last-row logits repeated.  PCY_DISABLE=beam_prefill_once: the
-        # reference's replicated prefill (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise, tests).
-        # Where beam_cache_plan says so (more than 8 rows, default switches) the beams do not even get copies: the prompts are prefilled into a
-        # B-row cache of exactly T slots and the BB rows share it, owning only their max_new suffix slots (engine.KVCache with a prefix; DESIGN.md
-        # 4.3b) -- B*T + BB*max_new slots instead of BB*(T + max_new), no replicating copy, and the same bits: PCY_DISABLE=beam_kv_shared is the twin.
-        disabled = os.environ.get("PCY_DISABLE", "").split(",")
-        plan = beam_cache_plan(B, beam_size, T, enc.max_new_tokens, disabled)
-        if plan["shared"]:
-            prefix = eng.new_cache(B, T)
-            lg_b, _ = eng.prefill(input_embeds.to(eng.device), attn_mask, prefix, "last")
-            cache = eng.new_beam_cache(prefix, beam_size, enc.max_new_tokens)
-            logits = lg_b.repeat_interleave(beam_size, dim=0).contiguous()
-        elif beam_size > 1 and "beam_prefill_once" not in disabled:
-            cache = eng.new_cache(BB, T + enc.max_new_tokens)
-            lg_b, _ = eng.prefill(input_embeds.to(eng.device), attn_mask, cache, "last")
-            eng.kv_reorder(cache, torch.arange(BB, dtype=torch.int32) // beam_size, T)
-            logits = lg_b.repeat_interleave(beam_size, dim=0).contiguous()
-        else:
-            emb_rep = torch.repeat_interleave(input_embeds, repeats=beam_size, dim=0)
-            mask_rep = torch.repeat_interleave(attn_mask, repeats=beam_size, dim=0)
-            o = enc(input_embeds=emb_rep, attn_masks=mask_rep, use_cache=True, past_key_values=None,
-                    logit_positions=torch.full((BB,), T - 1), want_hidden=False)
-            cache = o.past_key_values.cache
-            logits = o.logits[:, -1, :].contiguous()
-        # The beams of a prompt hold the SAME K / V rows in slots [0, T): the reference re-indexes the whole history of every row in every group
-        # of every step (:830-832); moving equal bytes changes nothing, so the reorder starts at slot T (pcy_kv_reorder_range; at 10 beams and a
-        # 512-token prompt the reorder was 0.4-0.6 ms of a 4.5 ms step).  PCY_DISABLE=beam_kv_suffix: every slot, as the reference (same result).
-        kv_t0 = 0 if "beam_kv_suffix" in os.environ.get("PCY_DISABLE", "").split(",") else T
-        if (kv_t0 * self.text_encoder.cfg.head_dim) % 8:
-            kv_t0 = 0
-        bs = BeamState(B, beam_size, max_len, self.tokenizer.eos_token_id, prompt_len=T, device=dev)
-        st = GenState(BB, V, 1, dev)
-        st.pos, st.next_tok = bs.pos, bs.next_tok                  # the decode graph reads what the beam step writes
-        st.c.pos, st.c.next_tok = bs.pos.data_ptr(), bs.next_tok.data_ptr()
-        rec = torch.empty(max_len, BB, V, dtype=logits.dtype, device=dev)
-        if "beam_graph" in os.environ.get("PCY_DISABLE", "").split(","):   # the four calls per step (same kernels, same bits; tests)
-            for i in range(max_len):
-                if i > 0:
-                    if T + i > cache.capacity:
-                        raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
-                    eng.decode_graph(cache, st, BB)
-                    logits = st.logits
-                rec[i].copy_(logits)
-                eng.beam_step(logits, bs, beam_group_size, diversity_penalty)
-                eng.kv_reorder(cache, bs.src, T + i, t0=kv_t0)
-                if (i & 7) == 7 and int(bs.done):
-                    break
-        else:
-            # step 0 selects on the prefill's logits; every later step (decode -> record -> beam step -> KV reorder) is ONE replayed launch
-            # chain (pcy_llama_beam_steps), enqueued up to the next multiple of 8 steps, where the host looks at the EOS flag
-            rec[0].copy_(logits)
-            eng.beam_step(logits, bs, beam_group_size, diversity_penalty)
-            eng.kv_reorder(cache, bs.src, T, t0=kv_t0)
-            i = 1
-            while i < max_len:
-                if T + i > cache.capacity:
-                    raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
-                n = min(8 - (i & 7), max_len - i, cache.capacity - T - i + 1)
-                eng.beam_steps(cache, st, bs, beam_group_size, diversity_penalty, rec, n, kv_t0=kv_t0)
-                i += n
-                if (i & 7) == 0 and int(bs.done):
-                    break
-        out, steps = bs.tokens()                                   # synchronises
-        anc = bs.anc[:steps].long()
-        slot = torch.arange(BB, device=dev)
-        idx = torch.empty(steps, BB, dtype=torch.long, device=dev)
-        for s_ in range(steps - 1, -1, -1):                        # the record of step s is re-indexed by the parents of steps >= s
-            slot = anc[s_][slot]
-            idx[s_] = slot
-        # [BB, steps, V] on the device, then ONE copy into pinned host memory (a pageable destination moves the 2.5 MB per step
-        # and beam-10 record at a few GB/s: ~1 ms per generated token)
-        out_logits_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
-        out_logits = torch.empty(out_logits_dev.shape, dtype=out_logits_dev.dtype, pin_memory=True)
-        out_logits.copy_(out_logits_dev, non_blocking=True)
-        full = torch.zeros(BB, max_len, dtype=torch.int64)
-        full[:, :steps] = out.cpu()
-        out, cur = full, bs.cur.cpu()
-        eng.ctx.sync()      # stream complete + the sticky watchdog word of the fused launches checked (raises PcyError)
-        return (out.unflatten(0, (B, beam_size)), cur.unflatten(0, (B, beam_size)), out_logits.unflatten(0, (B, beam_size)))
 
     # ---- fp32 generation (/root/reference/scripts/caption_bulk.py:70-73 never casts the model and calls generate(method="beam")): the
     # reference's own loops over the sub-module waist, every operator on the fp32 family (procyon_amd/engine_f32.py) -- a compatibility
@@ -678,9 +582,7 @@ class UnifiedProCyon:
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
         enc = self.text_encoder
         B = len(input_embeds)
-        keep_new = enc.max_new_tokens
-        enc.max_new_tokens = max(keep_new, max_len)
-        try:
+        with self._room_for(max_len):
             outs, lps, lgs = [], [], []
             for _ in range(num_text_per_instance):
                 toks, past, rec = None, None, []
@@ -696,8 +598,6 @@ class UnifiedProCyon:
                     total += lsm.gather(1, nxt)[:, 0]
                     toks = nxt if toks is None else torch.cat([toks, nxt], -1)
                 outs.append(toks.cpu()); lps.append(total.cpu()); lgs.append(torch.stack(rec, 1))
-        finally:
-            enc.max_new_tokens = keep_new
         return torch.stack(outs, 1), torch.stack(lps).T, torch.stack(lgs, 1)
 
     @torch.no_grad()
@@ -718,9 +618,7 @@ class UnifiedProCyon:
         cur = torch.zeros(BB, device=dev)
         out = torch.zeros(BB, max_len, dtype=torch.int64, device=dev)
         rec = None
-        keep_new = enc.max_new_tokens
-        enc.max_new_tokens = max(keep_new, max_len)
-        try:
+        with self._room_for(max_len):
             past = None
             for i in range(max_len):
                 o = enc(input_embeds=emb, attn_masks=mask, use_cache=True, logit_positions=torch.full((BB,), T - 1)) if i == 0 else \
@@ -749,8 +647,6 @@ class UnifiedProCyon:
                 past.cache.reorder_(src, past.t)
                 if bool((out == self.tokenizer.eos_token_id).any(dim=1).all()):
                     break
-        finally:
-            enc.max_new_tokens = keep_new
         return (out.cpu().unflatten(0, (B, beam_size)), cur.cpu().unflatten(0, (B, beam_size)), rec.unflatten(0, (B, beam_size)))
 
     @torch.no_grad()

@@ -98,7 +98,7 @@ def batched_decode_roofline(model, rows=32, prompt=512, new_tokens=512):
     """HBM roofline of the BATCHED decode step (BASELINE configs[3] shape: `rows` prompts of `prompt` tokens, `new_tokens` greedy
     steps): HIP-event time of the hipGraph-replayed steps, algorithmic bytes per step = every weight once
     (15,009,906,688 B for Llama-3-8B) + the K/V rows read, rows * t * 131,072 B at the mean cache length."""
-    from .engine import Context, GenState
+    from .engine import Context, GenState, disabled_switches
     eng = model.text_encoder.engine
     cfg = eng.cfg
     ctx = Context.get(eng.device)
@@ -122,7 +122,7 @@ def batched_decode_roofline(model, rows=32, prompt=512, new_tokens=512):
     gbps = (w_bytes + kv_bytes) / 1e9 / (ms / 1e3)
     import os
     mb_max = int(os.environ.get("PCY_MB_MAX", "0"))
-    off = os.environ.get("PCY_DISABLE", "").split(",")
+    off = disabled_switches()
     nb_max = min(int(os.environ.get("PCY_NB_MAX", "6")), 8)
     kernel = ("small-batch decode step (hipGraph: embed, decode_step_nb_kernel = all layers in one launch, lm_head, pick)" if 2 <= rows <= nb_max else
               "mid-batch decode step (hipGraph: embed, norm, decode_step_mb_kernel = all layers in one launch, lm_head, pick)"

@@ -1,8 +1,9 @@
 """beam_cache_plan (procyon_amd/engine.py): the rule that decides whether the beams of a prompt share ONE copy of its K / V (a KVCache with a
-prefix) and the slot counts of the two layouts.  Pure arithmetic, no GPU."""
+prefix) and the slot counts of the two layouts; the names it is given (disabled_switches) and the decode state a beam search runs on
+(BeamState.gen_state).  Pure arithmetic and descriptors, no GPU."""
 import pytest
 
-from procyon_amd.engine import beam_cache_plan
+from procyon_amd.engine import BeamState, beam_cache_plan, disabled_switches
 
 SWITCHES = ("beam_kv_shared", "beam_prefill_once", "beam_kv_suffix")
 
@@ -48,3 +49,22 @@ def test_evaluation_default_saving():
     assert round(p["slots_plain"] * per_slot / 1e9) == 64
     assert round(160 * 704 * per_slot / 1e9) == 59
     assert round(p["slots_shared"] * per_slot / 1e9) == 11
+
+
+def test_gen_state_of_a_beam_state_is_built_on_its_arrays():
+    """the decode step reads the position and the next tokens where the beam step writes them: same tensors, same addresses in the descriptor"""
+    bs = BeamState(2, 3, 4, 7, prompt_len=5, device="cpu")
+    gs = bs.gen_state(11)
+    assert gs.pos is bs.pos and gs.next_tok is bs.next_tok and gs.pos.data_ptr() == bs.pos.data_ptr() and gs.next_tok.data_ptr() == bs.next_tok.data_ptr()
+    assert gs.c.pos == bs.pos.data_ptr() == bs.c.pos and gs.c.next_tok == bs.next_tok.data_ptr() == bs.c.next_tok
+    assert gs.logits.shape == (6, 11) and gs.c.max_steps == 1 and gs.tokens_out.shape == (6, 1)
+    assert gs.c.logits_all_ld == 11 and not gs.c.logits_all and not gs.c.keep and int(gs.pos) == 5
+
+
+def test_disabled_switches(monkeypatch):
+    monkeypatch.delenv("PCY_DISABLE", raising=False)
+    assert disabled_switches() == frozenset()
+    monkeypatch.setenv("PCY_DISABLE", "a,,b , a")
+    assert disabled_switches() == {"a", "b"} and isinstance(disabled_switches(), frozenset)
+    monkeypatch.setenv("PCY_DISABLE", "xbeam_graph")
+    assert "beam_graph" not in disabled_switches()

@@ -156,7 +156,7 @@ def test_shared_prefix_steps_without_the_fused_qkv_finish(geo, monkeypatch, B, b
 def test_shared_prefix_replayed_beam_chain(geo, monkeypatch, B, beam):
     """pcy_llama_beam_steps (decode -> logits record -> beam step -> K / V reorder, one replayed chain per step), n = 8: 10 rows take the
     one-pass permute, 40 rows the two-launch gather; both read the slot count from the device and must count it from the prefix length on."""
-    from procyon_amd.engine import BeamState, Context, GenState
+    from procyon_amd.engine import BeamState, Context
     name, kw, eng = geo
     T, group, V, BB = 21, 5, kw["vocab"], B * beam
     emb, mask = _prompt_batch(B, T, kw["d"], seed=77 + B, ragged=False)
@@ -165,9 +165,7 @@ def test_shared_prefix_replayed_beam_chain(geo, monkeypatch, B, beam):
 
     def run(cache):
         bs = BeamState(B, beam, N + 1, V - 1, prompt_len=T, device="cuda")
-        st = GenState(BB, V, 1, "cuda")
-        st.pos, st.next_tok = bs.pos, bs.next_tok
-        st.c.pos, st.c.next_tok = bs.pos.data_ptr(), bs.next_tok.data_ptr()
+        st = bs.gen_state(V)
         rec = torch.zeros(N + 1, BB, V, dtype=BF, device="cuda")
         rec[0].copy_(logits)
         eng.beam_step(logits, bs, group, 0.8)
@@ -266,6 +264,27 @@ def test_generate_beam_5_rows_stay_on_the_plain_cache(small, monkeypatch, beam_c
     Context.get().sync()
     assert tokens.shape[:2] == (1, 5) and torch.isfinite(logits.float()).all()
     assert _count() == n0 and not beam_caches
+
+
+@pytest.mark.parametrize("n,beam,off,layout", [(2, 6, (), "shared"), (1, 4, (), "prefill_once"), (1, 4, ("beam_prefill_once",), "replicated")])
+def test_generate_adds_nothing_to_generate_beam(small, monkeypatch, beam_caches, n, beam, off, layout):
+    """`generate(method="beam")` is LlamaEngine.generate_beam + an unflatten: the driver called directly on the model's own prompt embeddings (the
+    oracle's differ by the encoder's bf16 noise; bit-equality needs the same bits going in) gives the same tokens, scores and logits record on each
+    cache layout: 12 rows (shared prefix), 4 rows (prefill once + replicate), 4 rows under PCY_DISABLE=beam_prefill_once (replicated prefill)."""
+    from procyon_amd.engine import LlamaEngine
+    m = small["model"]
+    pcy_disable(monkeypatch, *off)
+    replicated, orig = [], LlamaEngine.prefill_all
+    monkeypatch.setattr(LlamaEngine, "prefill_all", lambda self, emb, *a, **k: replicated.append(emb.shape[0]) or orig(self, emb, *a, **k))
+    instr, slots = _prompts(n, seed=70 + n)
+    emb, _, mask, *_ = m._preprocessing(_gen_inputs(small, instr, slots), crop_off=True, no_pad=True, left_pad=True)
+    direct = m.text_encoder.engine.generate_beam(emb, mask, 10, beam, 2, 0.8, m.tokenizer.eos_token_id, 32)
+    assert direct[0].shape == (n * beam, 10) and direct[0].dtype == torch.int64 and not direct[0].is_cuda and direct[2].is_pinned()
+    res = m.generate(dict(_gen_inputs(small, instr, slots), reference_indices={"target": {"text": None}, "input": {"seq": slots}}), method="beam",
+                     max_len=10, beam_size=beam, beam_group_size=2, diversity_penalty=0.8, return_all_internals=True)
+    assert len(beam_caches) == (2 if layout == "shared" else 0) and replicated == ([n * beam] * 2 if layout == "replicated" else [])
+    for got, flat in zip((res["out_tokens"], res["out_log_probs"], res["out_logits"]), direct):
+        assert torch.equal(got, flat.unflatten(0, (n, beam)))
 
 
 # ---------------------------------------------------------------------------------------------- what a shared cache is refused for

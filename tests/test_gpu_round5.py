@@ -127,7 +127,7 @@ def test_decode_nb_rows_are_independent(eng2, monkeypatch):
 def test_decode_nb_beam_loop_bit_identical(eng2, monkeypatch):
     """The reference's production path: diverse beam search, beam 5 (scripts/caption_bulk.py:123-132) = a 5-row decode step + pcy_beam_step
     + the K/V reorder of every step.  One launch per step vs the launch-per-stage twin: tokens, running scores and the parent chain equal."""
-    from procyon_amd.engine import BeamState, Context, GenState
+    from procyon_amd.engine import BeamState, Context
     torch.manual_seed(5)
     T, steps, beam = 120, 14, 5
     emb = (torch.randn(1, T, 4096) * 0.02).to(BF).cuda().repeat(beam, 1, 1).contiguous()
@@ -137,9 +137,7 @@ def test_decode_nb_beam_loop_bit_identical(eng2, monkeypatch):
         cache = eng2.new_cache(beam, T + steps + 2)
         logits, _ = eng2.prefill(emb, None, cache, "last")
         bs = BeamState(1, beam, steps, 2, prompt_len=T, device="cuda")
-        st = GenState(beam, KW["vocab"], 1, "cuda")
-        st.pos, st.next_tok = bs.pos, bs.next_tok
-        st.c.pos, st.c.next_tok = bs.pos.data_ptr(), bs.next_tok.data_ptr()
+        st = bs.gen_state(KW["vocab"])
         lg = logits.contiguous()
         with served_by("step_nb" if step else "loop_stream"):      # (replayed steps: the capture counts)
             for i in range(steps):

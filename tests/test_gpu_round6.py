@@ -138,7 +138,7 @@ def test_decode_mb_beam10_loop_bit_identical(eng2, monkeypatch):
     decode step + pcy_beam_step + the K/V reorder of every step, as the replayed chain (pcy_llama_beam_steps).  One launch per step vs the
     seven launches per layer: tokens, running scores, the parent chain and the logits record equal.  (PCY_MB_MAX: since the fused step became
     opt-in this test had compared the launches with themselves -- the dispatch counters found it.)"""
-    from procyon_amd.engine import BeamState, Context, GenState
+    from procyon_amd.engine import BeamState, Context
     monkeypatch.setenv("PCY_MB_MAX", "32")
     torch.manual_seed(10)
     T, steps, beam, group = 120, 14, 10, 2
@@ -149,9 +149,7 @@ def test_decode_mb_beam10_loop_bit_identical(eng2, monkeypatch):
         cache = eng2.new_cache(beam, T + steps + 2)
         logits, _ = eng2.prefill(emb, None, cache, "last")
         bs = BeamState(1, beam, steps, 2, prompt_len=T, device="cuda")
-        st = GenState(beam, KW["vocab"], 1, "cuda")
-        st.pos, st.next_tok = bs.pos, bs.next_tok
-        st.c.pos, st.c.next_tok = bs.pos.data_ptr(), bs.next_tok.data_ptr()
+        st = bs.gen_state(KW["vocab"])
         rec = torch.zeros(steps, beam, KW["vocab"], dtype=BF, device="cuda")
         rec[0].copy_(logits)
         eng2.beam_step(logits.contiguous(), bs, group, 0.8)

@@ -17,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from procyon_amd import synth
-from procyon_amd.engine import BeamState, Context, GenState, LlamaConfig, LlamaEngine, beam_cache_plan
+from procyon_amd.engine import BeamState, Context, LlamaConfig, LlamaEngine, beam_cache_plan
 
 GEOMS = {"full": dict(vocab=128263, d=4096, n_layers=32, n_heads=32, n_kv_heads=8, ffn=14336),
          "split": dict(vocab=32007, d=4096, n_layers=32, n_heads=32, n_kv_heads=32, ffn=11008)}
@@ -42,9 +42,7 @@ class Side:
     def __init__(self, cache, B, beam, T, logits):
         self.cache, self.T = cache, T
         self.bs = BeamState(B, beam, max_new, -1, prompt_len=T, device="cuda")      # (eos -1: the search never stops)
-        self.st = GenState(B * beam, V, 1, "cuda")
-        self.st.pos, self.st.next_tok = self.bs.pos, self.bs.next_tok
-        self.st.c.pos, self.st.c.next_tok = self.bs.pos.data_ptr(), self.bs.next_tok.data_ptr()
+        self.st = self.bs.gen_state(V)
         eng.beam_step(logits, self.bs, args.group, 0.8)
         eng.kv_reorder(cache, self.bs.src, T, t0=T)
 
