@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PCY_ABI_VERSION 11
+#define PCY_ABI_VERSION 12
 
 typedef struct pcy_ctx pcy_ctx;
 
@@ -43,6 +43,7 @@ int pcy_abi_version(void);
  * 7: one row, all layers in one launch, grouped-query geometry; 10: the same, multi-head geometry; 11: one row, a launch per layer;
  * 12: small-batch step (2..8 rows); 13: mid-batch step (9..32 rows, PCY_MB_MAX); 14: launch per stage, streaming GEMVs;
  * 15: launch per stage, MFMA GEMVs; 16: a step served from a shared-prefix cache (pcy_kv_cache.prefix_k), counted in addition to 14 / 15.
+ * 17: calls of the fused lm_head x cross-entropy operator (pcy_lm_head_xent, also inside pcy_llama_score).
  * A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
  * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
@@ -130,6 +131,19 @@ int pcy_retrieval_topk_f32(pcy_ctx*, const float* query, int Q, const void* targ
  * probabilities, lowest index on ties. */
 int pcy_qa_probs(pcy_ctx*, const void* logits, int is_f32, int rows, int V, int yes_id, int no_id, void* probs_out, float* yes_no_out,
                  int32_t* argmax_out);
+
+/* Teacher-forced scoring: lm_head x cross-entropy WITHOUT the [M, V] logits in memory.  x [M, d] bf16 (ldx elements between rows, ldx % 8
+ * == 0), already final-normed; W [V, d] bf16 = lm_head in natural row order; targets [M] int32 in [0, V).  Per row, HF's causal-LM loss
+ * term (`logits = bf16(acc)`, `logits.float()`, fp32 cross_entropy):
+ *   nll_out[m] = lse - label,  lse = max + log(sum_n exp(l[n] - max)) in fp32 over the bf16-ROUNDED logits l[n] = bf16(x[m] . W[n]),
+ *   label = l[targets[m]].  Every l[n] is bit-equal to what pcy_gemm(x, W, EPI_STORE) stores.
+ * Optional outputs (NULL = not wanted), [M] fp32: lse_out, row_max_out, label_logit_out (the last two hold bf16 values).  A target outside
+ * [0, V) gives NaN.  Deterministic (no atomics) and row-invariant: a row's bits depend neither on M nor on the other rows.  d % 64 == 0;
+ * M == 0 returns 0 without a launch.  Scratch: pcy_lm_head_xent_ws_bytes(M, V) of the context's workspace (host arithmetic only, callable
+ * without a device): min(M, 1024) x (column blocks x 8 + 4) bytes, a few thousand times smaller than the logits it replaces. */
+int pcy_lm_head_xent(pcy_ctx*, const void* x, int ldx, const void* W, int M, int V, int d, const int32_t* targets, float* nll_out,
+                     float* lse_out, float* row_max_out, float* label_logit_out);
+size_t pcy_lm_head_xent_ws_bytes(int M, int V);
 
 /* ---- fp8 weight path (BASELINE.json configs[4]: "fp8 MFMA weight path"; the reference has no fp8 counterpart) ----
  * Per-row symmetric OCP e4m3 quantisation of a bf16 matrix x[rows,K] (ldx elements between rows, K % 8 == 0):
@@ -238,6 +252,14 @@ int pcy_llama_prefill(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, cons
 int pcy_llama_prefill_all(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep,
                           const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
                           int n_logit_rows, void* logits_out, void* hidden_all_out);
+/* The prefill of pcy_llama_prefill (same launches, K/V of slots [0,T) written) followed by teacher-forced scoring: the token rows
+ * score_rows[n_score] (flat b*T + t) are gathered, final-normed (rms_cast honoured) and handed to pcy_lm_head_xent against
+ * targets[n_score] -> nll_out [n_score] fp32.  logit_rows / logits_out as in pcy_llama_prefill (the GEMV path, same bits), so a QA batch gets
+ * its answer logits and its loss from ONE pass.  layers_fp8: the projections run fp8 as in the prefill, the lm_head stays bf16.  A cache with
+ * a shared prefix is rejected. */
+int pcy_llama_score(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep, const int32_t* pos,
+                    const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* score_rows, const int32_t* targets, int n_score,
+                    float* nll_out, const int32_t* logit_rows, int n_logit_rows, void* logits_out);
 typedef struct {
   int32_t* pos;              /* device scalar: cache length == rotary position of the next token (Q2) */
   int32_t* step;             /* device scalar: index of the next generated token */

@@ -10,11 +10,11 @@ LIB_PATH = os.environ.get("PCY_LIB") or os.path.join(_HERE, "libpcy.so")   # PCY
 
 EPI_STORE, EPI_RESID, EPI_GELU_ERF, EPI_GELU_ESM, EPI_SWIGLU = range(5)
 POOL_MEAN, POOL_MEAN_CORRECTED, POOL_MAX = range(3)
-ABI_VERSION = 11
+ABI_VERSION = 12
 # pcy_debug_dispatch_count kinds
 (DISPATCH_GEMM_128, DISPATCH_GEMM_64, DISPATCH_GEMM_BIG, DISPATCH_GEMM_BIG_PERSIST, DISPATCH_GEMM_SPLITK, DISPATCH_GEMM_FP8, DISPATCH_ATTN_FAST,
  DISPATCH_DEC_STEP_GQA, DISPATCH_GEMM_MID, DISPATCH_ESM_GRAPH, DISPATCH_DEC_STEP_MHA, DISPATCH_DEC_LAYER, DISPATCH_DEC_STEP_NB, DISPATCH_DEC_STEP_MB,
- DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA, DISPATCH_SHARED_PREFIX) = range(17)
+ DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA, DISPATCH_SHARED_PREFIX, DISPATCH_XENT) = range(18)
 # which way a decode step was served (one count per step enqueued outside a graph replay; pcy_internal.h PCY_DISPATCH_DEC_*)
 DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STEP_MHA, layer=DISPATCH_DEC_LAYER, step_nb=DISPATCH_DEC_STEP_NB,
                        step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
@@ -81,6 +81,9 @@ SIGNATURES = {
     "pcy_timer_stop": (ci, [vp, C.POINTER(C.c_float)]),
     "pcy_gemm": (ci, [vp, vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci]),
     "pcy_gemv": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, vp, C.c_float, ci, ci, ci, ci, ci]),
+    "pcy_lm_head_xent": (ci, [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "pcy_lm_head_xent_ws_bytes": (C.c_size_t, [ci, ci]),
+    "pcy_llama_score": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, vp, vp, ci, vp]),
     "pcy_decode_mlp": (ci, [vp, vp, vp, vp, vp, ci, ci, C.c_float, ci]),
     "pcy_rmsnorm": (ci, [vp, vp, vp, vp, ci, ci, C.c_float, ci]),
     "pcy_layernorm": (ci, [vp, vp, vp, vp, vp, ci, ci, C.c_float]),

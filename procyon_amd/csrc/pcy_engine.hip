@@ -801,6 +801,23 @@ int pcy_gemm(pcy_ctx* c, const void* A, int lda, const void* W, const void* bias
   return check_launch("pcy_gemm");
 }
 
+size_t pcy_lm_head_xent_ws_bytes(int M, int V) { return M > 0 && V > 0 ? pcy_xent_ws_bytes(M, V) : 0; }
+
+int pcy_lm_head_xent(pcy_ctx* c, const void* x, int ldx, const void* W, int M, int V, int d, const int32_t* targets, float* nll_out,
+                     float* lse_out, float* row_max_out, float* label_logit_out) {
+  if (M < 0 || V <= 0 || d <= 0 || d % 64 != 0) return fail(1, "pcy_lm_head_xent: M=%d V=%d d=%d (d must be a multiple of 64)", M, V, d);
+  if (M == 0) return 0;
+  if (!x || !W || !targets || !nll_out) return fail(1, "pcy_lm_head_xent: x, W, targets and nll_out are required");
+  if (ldx < d || ldx % 8 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(W) & 15))
+    return fail(1, "pcy_lm_head_xent: rows of x and W must be 16-byte aligned (ldx=%d)", ldx);
+  if (int r = c->reserve(pcy_xent_ws_bytes(M, V) + 256)) return r;
+  PcyXentArgs a{};
+  a.x = (const bf16_t*)x; a.ldx = ldx; a.W = (const bf16_t*)W; a.targets = targets; a.M = M; a.V = V; a.d = d;
+  a.nll = nll_out; a.lse = lse_out; a.row_max = row_max_out; a.label_logit = label_logit_out; a.ws = c->ws;
+  pcy_launch_lm_head_xent(c->stream, a);
+  return check_launch("pcy_lm_head_xent");
+}
+
 int pcy_gemv(pcy_ctx* c, const void* W, const void* x, int ldx, const void* bias, const void* resid, void* y, int ldy,
              const void* rms_w, float rms_eps, int rms_cast, int N, int K, int B, int epi) {
   if (K % 8 != 0 || ldx % 8 != 0) return fail(1, "pcy_gemv: K and ldx must be multiples of 8");
@@ -1241,10 +1258,12 @@ static int esm_encode_enqueue(pcy_ctx* c, const pcy_esm_desc* m, const int32_t* 
 
 }  // extern "C"
 namespace {
+// pcy_llama_score: token rows to score behind the prefill (nullptr: a plain prefill)
+struct ScoreReq { const int32_t* rows; const int32_t* targets; int n; float* nll; };
 int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
                        const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
                        int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* sum_rows, int n_sum_rows,
-                       void* hidden_sum_out, void* hidden_all_out) {
+                       void* hidden_sum_out, void* hidden_all_out, const ScoreReq* score = nullptr) {
   PCY_STICKY(c);
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
@@ -1258,7 +1277,10 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   // key block's V tile to the same few L2 channels; pad it to an odd multiple of 64 bytes
   int vt_total = B * Tp;
   if ((vt_total / 32) % 2 == 0) vt_total += 32;
-  const size_t need = align_up((size_t)M * d * 2, 256) * 2 + align_up((size_t)M * qkvw * 2, 256) + align_up((size_t)M * H * dh * 2, 256) +
+  const int n_score = score ? score->n : 0;
+  if (n_score < 0 || (n_score > 0 && (!score->rows || !score->targets || !score->nll))) return fail(1, "pcy_llama_score: score_rows / targets / nll_out missing");
+  const size_t score_need = n_score > 0 ? align_up((size_t)n_score * d * 2, 256) + align_up(pcy_xent_ws_bytes(n_score, m->vocab), 256) : 0;
+  const size_t need = score_need + align_up((size_t)M * d * 2, 256) * 2 + align_up((size_t)M * qkvw * 2, 256) + align_up((size_t)M * H * dh * 2, 256) +
                       align_up((size_t)M * F * 2, 256) + align_up((size_t)Hkv * dh * vt_total * 2, 256) +
                       align_up((size_t)(n_logit_rows + 1) * d * 2, 256) + align_up((size_t)(n_sum_rows + 1) * d * 6, 256) +
                       (M <= 1024 ? align_up((size_t)8 * M * qkvw * 4, 256) : 0) + 4096 +
@@ -1282,6 +1304,8 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   // fp8 weight path: every projection = per-token e4m3 quantisation of its bf16 input + the fp8 MFMA GEMM
   unsigned char* a8 = m->layers_fp8 ? cv.take<unsigned char>((size_t)M * (F > H * dh ? F : H * dh)) : nullptr;
   float* sa8 = m->layers_fp8 ? cv.take<float>((size_t)M) : nullptr;
+  bf16_t* score_x = n_score > 0 ? cv.take<bf16_t>((size_t)n_score * d) : nullptr;
+  char* score_ws = n_score > 0 ? cv.take<char>(pcy_xent_ws_bytes(n_score, m->vocab)) : nullptr;
   // ln != nullptr: A is the raw hidden state, RMSNorm(A) * ln is what gets quantised (one fused pass; PCY_DISABLE=fp8_fused_norm = two launches)
   auto linear8 = [&](const bf16_t* A, int K, const void* W8, const float* sw, const bf16_t* resid, bf16_t* Cout, int ldc, int N, int epi,
                      const bf16_t* ln = nullptr) {
@@ -1385,6 +1409,15 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
     }
     pcy_launch_gemv(s, h);
   }
+  if (n_score > 0) {
+    // teacher-forced scoring: final norm of the scored rows, then lm_head x cross-entropy with the logits kept in registers
+    pcy_launch_copy_rows(s, x, d, score_x, d, score->rows, n_score, d);
+    pcy_launch_rmsnorm(s, score_x, (const bf16_t*)m->final_norm, score_x, n_score, d, m->rms_eps, m->rms_cast);
+    PcyXentArgs xa{};
+    xa.x = score_x; xa.ldx = d; xa.W = (const bf16_t*)m->lm_head; xa.targets = score->targets; xa.M = n_score; xa.V = m->vocab; xa.d = d;
+    xa.nll = score->nll; xa.ws = score_ws;
+    pcy_launch_lm_head_xent(s, xa);
+  }
   return check_launch("pcy_llama_prefill");
 }
 
@@ -1459,6 +1492,14 @@ int pcy_llama_prefill(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* k
   return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, hidden_out, sum_rows,
                             n_sum_rows, hidden_sum_out, nullptr);
 }
+int pcy_llama_score(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, const int32_t* pos,
+                    const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* score_rows, const int32_t* targets, int n_score,
+                    float* nll_out, const int32_t* logit_rows, int n_logit_rows, void* logits_out) {
+  const ScoreReq sr{score_rows, targets, n_score, nll_out};
+  return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, nullptr, nullptr, 0,
+                            nullptr, nullptr, &sr);
+}
+
 int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
                           const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
                           int n_logit_rows, void* logits_out, void* hidden_all_out) {

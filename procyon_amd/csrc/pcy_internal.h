@@ -136,8 +136,21 @@ enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BI
        PCY_DISPATCH_DEC_LOOP_STREAM = 14,  // launch-per-stage loop, streaming GEMVs
        PCY_DISPATCH_DEC_LOOP_MFMA = 15,    // launch-per-stage loop, skinny-MFMA GEMVs (`batched`)
        PCY_DISPATCH_SHARED_PREFIX = 16,   // a step served from a shared-prefix cache (in addition to the loop's own count)
-       PCY_DISPATCH_N = 17 };
+       PCY_DISPATCH_XENT = 17,            // one pcy_launch_lm_head_xent call (pcy_xent.hip)
+       PCY_DISPATCH_N = 18 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
+
+// lm_head x cross-entropy without logits in memory (pcy_xent.hip): nll[m] = logsumexp_n(bf16(x[m] . W[n])) - bf16(x[m] . W[targets[m]]).
+// x [M, d] bf16 (ldx, rows 16-byte aligned), W [V, d], d % 64 == 0, targets [M] int32 in [0, V) (anything else: nll = NaN).  lse / row_max /
+// label_logit: optional [M] fp32.  ws: pcy_xent_ws_bytes(M, V) bytes, 256-byte aligned -- (max, sumexp) partials [n_col_blocks][rows]
+// + the label logits, for min(M, 1024) rows at a time.
+struct PcyXentArgs {
+  const bf16_t* x; int ldx; const bf16_t* W; const int32_t* targets; int M, V, d;
+  float* nll; float* lse; float* row_max; float* label_logit; void* ws;
+};
+int pcy_xent_col_blocks(int V);            // column blocks the vocabulary is cut into: a function of V alone
+size_t pcy_xent_ws_bytes(int M, int V);
+void pcy_launch_lm_head_xent(hipStream_t s, const PcyXentArgs& a);
 
 // per-row symmetric e4m3 quantisation: scale[r] = smallest power of two with amax|x[r,:]| / scale <= 448 (1 for an all-zero row), q = e4m3_rne(x / scale)
 void pcy_launch_quant_rows_fp8(hipStream_t s, const bf16_t* x, int ldx, int rows, int K, unsigned char* q, float* scale);

@@ -84,6 +84,20 @@ class Context:
                                   N, K, B, epi), "pcy_gemv")
         return out
 
+    def lm_head_xent(self, x, W, targets, want_parts=False):
+        """Teacher-forced scoring operator (pcy_lm_head_xent): per row m of x [M, d] (final-normed, bf16) against W [V, d] (lm_head),
+        nll[m] = logsumexp(bf16 logits of the row) - bf16 logit of targets[m], HF's causal-LM loss term -- the [M, V] logits stay in
+        registers.  -> nll [M] fp32, or with want_parts (nll, lse, row_max, label_logit), all [M] fp32."""
+        _chk_bf16(x, W)
+        M, d = x.shape
+        V = W.shape[0]
+        tg = targets.to(x.device, torch.int32).contiguous()
+        assert tg.numel() == M, (tg.shape, M)
+        nll = torch.empty(M, dtype=torch.float32, device=x.device)
+        parts = [torch.empty_like(nll) for _ in range(3)] if want_parts else [None] * 3
+        L.check(self.lib.pcy_lm_head_xent(self.h, _p(x), d, _p(W), M, V, d, _p(tg), _p(nll), *[_p(t) for t in parts]), "pcy_lm_head_xent")
+        return (nll, *parts) if want_parts else nll
+
     def decode_mlp(self, x, ln2, wgu, wdown, rms_eps=1e-5, rms_cast=0):
         """One token through a Llama MLP, in place: x[1, d] += down(SwiGLU(gate/up(RMSNorm(x) * ln2))); wgu packed like gemv(EPI_SWIGLU)."""
         _chk_bf16(x, ln2, wgu, wdown)
@@ -506,6 +520,25 @@ class BeamState:
         return self.out[steps & 1, :, :steps].long(), steps
 
 
+def score_plan(full_labels, T_real, vocab):
+    """Which token rows a teacher-forced scoring pass scores, and against what -- HF's shift (`logits[:, :-1]` against `labels[:, 1:]`,
+    ignore_index -100), on the host, no device involved.  full_labels [B, T] (-100 = not scored); the engine runs T_real columns, so row
+    (b, t) is scored against full_labels[b, t + 1] for t + 1 < T_real wherever that label is not -100.
+    -> (score_rows int32 [n] = b * T_real + t, targets int32 [n], index int64 [n, 2] of the (b, t) pairs), row-major.
+    A label outside [0, vocab) other than -100 raises ValueError."""
+    lab = torch.as_tensor(full_labels).detach().cpu().long()
+    assert lab.dim() == 2, lab.shape
+    T_real = int(T_real)
+    nxt = lab[:, 1:T_real]
+    scored = nxt != -100
+    if bool((scored & ((nxt < 0) | (nxt >= int(vocab)))).any()):
+        bad = nxt[scored & ((nxt < 0) | (nxt >= int(vocab)))]
+        raise ValueError(f"full_labels hold {int(bad[0])}: labels must lie in [0, {int(vocab)}) or be -100")
+    bt = scored.nonzero()
+    rows = (bt[:, 0] * T_real + bt[:, 1]).to(torch.int32)
+    return rows, nxt[scored].to(torch.int32), bt
+
+
 class LlamaEngine:
     """HF-Llama-architecture decoder behind `LlamaPostTokenization.forward` (pmc_llama.py:546-596)."""
 
@@ -630,6 +663,29 @@ class LlamaEngine:
                                                    _p(cu), _p(vt_cu), B, T, _p(rows), rows.numel(), _p(logits), _p(hidden_all)),
                 "pcy_llama_prefill_all")
         return logits, hidden_all
+
+    def score(self, embeds, attn_mask, full_labels, cache=None, logit_rows=None):
+        """Teacher-forced scoring in ONE prefill pass (pcy_llama_score): embeds [B,T,d] bf16, attn_mask [B,T] or None, full_labels [B,>=T]
+        (HF's `labels`: -100 = not scored; columns beyond T are not run).  -> (token_nll [B,T] fp32, n_tokens, logits | None):
+        token_nll[b, t+1] = -log p(token t+1 | tokens <= t) where full_labels[b, t+1] is a label, 0 elsewhere; n_tokens = number of scored
+        tokens; logits [n,V] for `logit_rows` (flat rows b*T+t or "last"; the bits of `prefill`) or None.  The [rows, V] logits of the scored
+        rows are never materialised.  K/V go to `cache` (a scratch one when None).  Nothing is launched when there is nothing to do."""
+        B, T, _ = embeds.shape
+        dev = self.device
+        rows_c, tg_c, bt = score_plan(full_labels, T, self.cfg.vocab)
+        n = int(rows_c.numel())
+        token_nll = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        if n == 0 and logit_rows is None:
+            return token_nll, 0, None
+        cache = self.new_cache(B, T) if cache is None else cache
+        embeds, keep, pos, cu, vt_cu, rows, logits = self._prefill_args(embeds, attn_mask, logit_rows)
+        srows, tg, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev) if n else (None, None, None)
+        nll = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(self.ctx.lib.pcy_llama_score(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep), _p(pos), _p(cu), _p(vt_cu),
+                                             B, T, _p(srows), _p(tg), n, _p(nll), _p(rows), rows.numel(), _p(logits)), "pcy_llama_score")
+        if n:
+            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
+        return token_nll, n, (logits if logit_rows is not None else None)
 
     def decode(self, cache: KVCache, st: GenState, B):
         L.check(self.ctx.lib.pcy_llama_decode(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode")

@@ -410,13 +410,16 @@ class UnifiedProCyon:
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, inputs, return_mlm=False, retrieval=False, get_full_labels=False, aaseq_type='protein',
-                exclude_protein_structure=False, crop_off=False, output_attentions=False, full_logits=False):
+                exclude_protein_structure=False, crop_off=False, output_attentions=False, full_logits=False, compute_loss=False):
         """`forward` (model_unified.py:483-581), inference branches.  QA: `outputs.logits` reads like the reference's [B, T, V] tensor
         (:548-554) -- index it at the answer positions (`logits[torch.arange(B), pos]`, data/inference_utils.py:582-604) and the rows that
         were computed come back; any other access materialises every position once (_LazyLogits).  `outputs.answer_logits` [B, 1, V] and
         out["answer_positions"] are the engine's own handle on the answer rows.  Retrieval: contrastive_out["positive"]["text"] [B, D].
         full_logits=True (not in the reference's signature): outputs.logits is a plain [B, T_real, V] tensor from the start (the reference pads
-        every row to max_text_len and materialises [B, 2048, V]; the trailing all-pad columns are not computed here)."""
+        every row to max_text_len and materialises [B, 2048, V]; the trailing all-pad columns are not computed here).
+        `outputs.loss` (non-retrieval, bf16): the reference's causal-LM loss over `full_labels` (trainIT.py reads it for the validation loss and
+        perplexity), with `outputs.token_nll` / `outputs.n_tokens` -- computed on first access, or in this pass with compute_loss=True
+        (LlamaPostTokenization.forward); None for retrieval and on the fp32 path."""
         if return_mlm:
             raise NotImplementedError("return_mlm is a training path (model_unified.py:505-509)")
         self._require_bf16_or_fp32("forward")
@@ -444,7 +447,9 @@ class UnifiedProCyon:
             raise NotImplementedError("Invalid option {} for ret_token_access".format(self.config.ret_token_access))
         sum_all = retrieval and self.config.ret_token_access == 'all'
         ret_rows = ret_idx[:, :real].reshape(-1).nonzero()[:, 0] if sum_all else None   # flat b*T + t, row-major like boolean indexing
-        outputs = self.text_encoder(input_embeds=emb, attn_masks=attn_masks[:, :real], full_labels=full_labels,
+        # (labels cropped to the columns that are run: the reference's trailing pad columns are all -100)
+        outputs = self.text_encoder(input_embeds=emb, attn_masks=attn_masks[:, :real], full_labels=None if full_labels is None else full_labels[:, :real],
+                                    compute_loss=compute_loss and not retrieval,
                                     logit_positions=None if full_logits else (answer_pos if not retrieval else torch.zeros(B, dtype=torch.long)),
                                     want_hidden=retrieval and not sum_all, hidden_sum_positions=ret_rows, lazy_hidden=True)
         if not retrieval and not full_logits:
@@ -476,6 +481,21 @@ class UnifiedProCyon:
                     raise NotImplementedError
             out['contrastive_out'] = c
         return out
+
+    @torch.no_grad()
+    def score_text(self, inputs, aaseq_type='protein', crop_off=True):
+        """Teacher-forced likelihood of the text behind [ANSWER] in every row of a QA / caption batch (the reference: `forward` +
+        `out['outputs'].loss`, `np.exp(loss)` as perplexity, trainIT.py:1213-1217): caption ranking and perplexity filtering.
+        -> {"token_nll" [B, T] fp32 (0 where nothing is labelled), "seq_nll" [B] = its row sums, "n_tokens" [B] labelled tokens per row,
+        "loss" = seq_nll.sum() / n_tokens.sum() (HF's batch mean), "perplexity" = exp(loss)}.  One prefill pass, no [B, T, V] logits."""
+        out = self.forward(inputs, aaseq_type=aaseq_type, crop_off=crop_off, get_full_labels=True, compute_loss=True)
+        o = out['outputs']
+        if o.loss is None:
+            raise NotImplementedError("score_text needs the bf16 engine (the fp32 path computes no loss)")
+        tn = o.token_nll
+        n_tok = (out['full_labels'][:, 1:tn.shape[1]] != -100).sum(1)
+        loss = o.loss
+        return {"token_nll": tn, "seq_nll": tn.sum(1), "n_tokens": n_tok, "loss": loss, "perplexity": torch.exp(loss)}
 
     # ------------------------------------------------------------------------------------------
     @staticmethod

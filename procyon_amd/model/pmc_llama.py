@@ -67,6 +67,40 @@ class _HiddenStates:
         return iter(self._full())
 
 
+class CausalLMOutput:
+    """What `LlamaPostTokenization.forward` returns: `.logits`, `.past_key_values`, `.hidden_states`, `.hidden_state_sum_rows`, `.loss` (HF's
+    CausalLMOutputWithPast as the reference reads it) plus `.token_nll` [B,T] fp32 and `.n_tokens` of the scoring pass behind `.loss`.
+    The three scoring attributes are None when there is nothing to score with (`scorer` None); otherwise they come from `scorer()` ->
+    (token_nll, n_tokens), run on first access and cached -- or at once, by `forward(compute_loss=True)`, which hands the result in.
+    loss = token_nll.sum(1).sum() / n_tokens: HF's mean over all labelled tokens of the batch, NaN when there are none."""
+
+    def __init__(self, logits, past_key_values=None, hidden_states=None, hidden_state_sum_rows=None, scorer=None, scored=None):
+        self.logits, self.past_key_values, self.hidden_states = logits, past_key_values, hidden_states
+        self.hidden_state_sum_rows = hidden_state_sum_rows
+        self._scorer, self._scored = scorer, scored
+
+    def _score(self):
+        if self._scored is None and self._scorer is not None:
+            self._scored = self._scorer()
+            self._scorer = None
+        return self._scored
+
+    @property
+    def token_nll(self):
+        sc = self._score()
+        return None if sc is None else sc[0]
+
+    @property
+    def n_tokens(self):
+        sc = self._score()
+        return None if sc is None else sc[1]
+
+    @property
+    def loss(self):
+        sc = self._score()
+        return None if sc is None else sc[0].sum(1).sum() / sc[1]
+
+
 class LlamaPostTokenization:
     """forward(input_embeds|input_ids, attn_masks, full_labels, past_key_values, use_cache, output_attentions)
     -> object with .logits, .past_key_values, .hidden_states, .loss   (pmc_llama.py:546-596).
@@ -81,7 +115,14 @@ class LlamaPostTokenization:
         [B,T,V] (1 GB per 2048-token row).  None = all rows.
       * `want_hidden=False` skips the final hidden state, `hidden_sum_positions` asks for the sum over all L+1 states at
         given rows only (ret_token_access='all' without the tuple), `output_hidden_states=True` materialises the tuple eagerly.
-      * full_labels / loss / output_attentions: training-side, not computed (loss=None).
+      * full_labels / loss: with `full_labels` [B,>=T] (HF's `labels`, -100 = ignored) `.loss` is HF's causal-LM loss (shifted, mean over
+        the labelled tokens of the batch, NaN when there are none), with `.token_nll` [B,T] fp32 (token_nll[b, t+1] = NLL of token t+1) and
+        `.n_tokens` beside it -- computed by `LlamaEngine.score` (lm_head x cross-entropy fused, no [B,T,V] logits).  `compute_loss=True`
+        scores in this call (one pass together with the logits when `lazy_hidden=True` and no hidden-state sum is asked for; the hidden
+        states then come from a second pass if they are read).  With the default `compute_loss=False` nothing extra runs here: `.loss` is
+        computed on first access by a second, deterministic scoring pass (same bits) and cached, so callers that never read it pay nothing.
+        Without `full_labels`, on the fp32 path (fp32 `input_embeds`) and on the cached decode `.loss` stays None.
+      * output_attentions: not computed.
       * max_new_tokens: KV capacity reserved beyond the prompt when use_cache=True.
     """
 
@@ -118,13 +159,13 @@ class LlamaPostTokenization:
 
     def forward(self, input_embeds=None, input_ids=None, attn_masks=None, full_labels=None, past_key_values=None,
                 use_cache=False, output_attentions=None, logit_positions=None, want_hidden=True, hidden_sum_positions=None,
-                output_hidden_states=False, lazy_hidden=False):
+                output_hidden_states=False, lazy_hidden=False, compute_loss=False):
         assert (input_embeds is not None) != (input_ids is not None), "Only one of input_embeds or input_ids can be provided"
         if isinstance(past_key_values, _PastF32):      # cached decode of an fp32 generation
             assert input_ids is not None and input_ids.shape[1] == 1, "cached decode takes input_ids [B,1]"
             cache, t = past_key_values.cache, past_key_values.t
             logits = self.engine_f32.decode(cache, input_ids.view(-1), t)
-            return SimpleNamespace(logits=logits.view(input_ids.shape[0], 1, -1), past_key_values=_PastF32(cache, t + 1), hidden_states=None, loss=None)
+            return CausalLMOutput(logits.view(input_ids.shape[0], 1, -1), _PastF32(cache, t + 1))
         if input_embeds is not None and input_embeds.dtype == torch.float32:
             return self._forward_f32(input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions)
         eng = self.engine
@@ -145,7 +186,16 @@ class LlamaPostTokenization:
                 _, hall = eng.prefill_all(embeds_dev, attn_masks, eng.new_cache(B, T), None)
                 return [hall[i] for i in range(L1)]
 
-            if output_hidden_states or not lazy_hidden:
+            scorer = scored = None
+            if full_labels is not None:
+                labels = torch.as_tensor(full_labels)[:, :T]      # columns beyond T are not run (the reference's trailing pads: all -100)
+                scorer = lambda: eng.score(embeds_dev, attn_masks, labels)[:2]
+            if scorer is not None and compute_loss and lazy_hidden and not output_hidden_states and hidden_sum_positions is None:
+                # loss and logits from ONE pass; the final hidden state is not written by it (read: a second pass)
+                token_nll, n_tok, logits = eng.score(embeds_dev, attn_masks, labels, cache=cache, logit_rows=rows)
+                scored, scorer = (token_nll, n_tok), None
+                hs = _HiddenStates(L1, None, materialise)
+            elif output_hidden_states or not lazy_hidden:
                 logits, hall = eng.prefill_all(embeds_dev, attn_masks, cache, rows)
                 hs = tuple(hall[i] for i in range(L1))
                 if hidden_sum_positions is not None:
@@ -161,7 +211,10 @@ class LlamaPostTokenization:
                 hs = _HiddenStates(L1, hidden, materialise)
             logits = logits.view(B, -1, self.cfg.vocab)
             past = _Past(cache, T) if use_cache else None
-            return SimpleNamespace(logits=logits, past_key_values=past, hidden_states=hs, hidden_state_sum_rows=hsum, loss=None)
+            out = CausalLMOutput(logits, past, hs, hsum, scorer=scorer, scored=scored)
+            if compute_loss:
+                out._score()
+            return out
         # cached decode: one new token per row, no mask, position = cache length (quirks Q1/Q2)
         assert input_ids is not None and input_ids.shape[1] == 1, "cached decode takes input_ids [B,1]"
         cache, t = past_key_values.cache, past_key_values.t
@@ -174,8 +227,7 @@ class LlamaPostTokenization:
         st.pos.fill_(t)
         st.next_tok.copy_(input_ids.view(-1).to(torch.int32))
         eng.decode_graph(cache, st, B)
-        return SimpleNamespace(logits=st.logits.clone().view(B, 1, -1), past_key_values=_Past(cache, t + 1),
-                               hidden_states=None, loss=None)
+        return CausalLMOutput(st.logits.clone().view(B, 1, -1), _Past(cache, t + 1))
 
     def _forward_f32(self, input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions):
         """fp32 embeddings in -> the fp32 prefill (the callers that never call `.bfloat16()`); use_cache=True keeps the K / V rows in an fp32
@@ -193,7 +245,6 @@ class LlamaPostTokenization:
             logits, hidden = eng.prefill(input_embeds, attn_masks, rows, want_hidden=True, cache=cache)
         hs = _HiddenStates(self.cfg.n_layers + 1, hidden, lambda: (_ for _ in ()).throw(
             RuntimeError("the fp32 path keeps the final hidden state only (hidden_states[-1])")))
-        return SimpleNamespace(logits=logits.view(B, -1, self.cfg.vocab), past_key_values=_PastF32(cache, T) if use_cache else None,
-                               hidden_states=hs, hidden_state_sum_rows=hsum, loss=None)
+        return CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _PastF32(cache, T) if use_cache else None, hs, hsum)
 
     __call__ = forward
