@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define PCY_ABI_VERSION 12
+#define PCY_ABI_VERSION 13
 
 typedef struct pcy_ctx pcy_ctx;
 
@@ -43,7 +43,8 @@ int pcy_abi_version(void);
  * 7: one row, all layers in one launch, grouped-query geometry; 10: the same, multi-head geometry; 11: one row, a launch per layer;
  * 12: small-batch step (2..8 rows); 13: mid-batch step (9..32 rows, PCY_MB_MAX); 14: launch per stage, streaming GEMVs;
  * 15: launch per stage, MFMA GEMVs; 16: a step served from a shared-prefix cache (pcy_kv_cache.prefix_k), counted in addition to 14 / 15.
- * 17: calls of the fused lm_head x cross-entropy operator (pcy_lm_head_xent, also inside pcy_llama_score).
+ * 17: calls of the fused lm_head x cross-entropy operator (pcy_lm_head_xent, also inside pcy_llama_score / pcy_llama_extend).
+ * 18: calls of pcy_llama_extend (S more tokens per row against a filled cache).
  * A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
  * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
@@ -260,6 +261,29 @@ int pcy_llama_prefill_all(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, 
 int pcy_llama_score(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep, const int32_t* pos,
                     const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* score_rows, const int32_t* targets, int n_score,
                     float* nll_out, const int32_t* logit_rows, int n_logit_rows, void* logits_out);
+/* S new tokens per row against a filled cache.  qkv [B*S, ld] un-roped projections (row b*S+s = token s of row b).  Ropes q and k at
+ * position t_past + s (every row: quirk Q2), writes K/V of token s to LOGICAL slot t_past + s of row b in layer `layer` of the cache,
+ * then O[b*S+s] = attention of that query over logical slots [0, t_past + s] (causal), HF eager rounding points.
+ * kv: plain cache (t_past + S <= Tmax) or shared-prefix cache (t_past >= prefix_T, t_past + S <= prefix_T + Tmax; slots < prefix_T are
+ * read from prefix row b / rows_per_prefix and never written).  keep: optional [B, capacity] bytes in logical slots (row stride = the
+ * logical capacity, as pcy_gen_state.keep), non-zero = kept; it applies to old AND new key slots; bytes at and above t_past + S are
+ * not read; NULL = every slot kept.  A query with no kept key gets the reference's uniform softmax over all t_past + S slots.
+ * head_dim 64 or 128, any H / Hkv.  The same logical contents in a shared-prefix cache and in a plain cache give the same bits, and a
+ * row's bits do not depend on the other rows of the call. */
+int pcy_attn_extend(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past,
+                    const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh);
+/* S more tokens per row through all layers against a filled cache (HF: forward(inputs_embeds [B,S], past_key_values)).  embeds [B,S,d];
+ * t_past = tokens every row already holds; keep as pcy_attn_extend.  K/V of logical slots [t_past, t_past+S) are written.
+ * logit_rows / logits_out / hidden_out as pcy_llama_prefill, rows counted b*S + s.  score_rows / targets / nll_out as pcy_llama_score
+ * (n_score = 0: no scoring).  layers_fp8 != NULL is an argument error in this version.  The layer loop is the prefill's (same projections,
+ * norms and tails); the attention is pcy_attn_extend's, so no transposed copy of V is made and pcy_llama_extend_ws_bytes depends on
+ * B, S and the row counts only, never on t_past or the cache's size.  Argument errors (nothing is launched, the cache stays as it was):
+ * t_past + S beyond the logical capacity or max_pos, a shared cache with t_past < prefix_T, B beyond the cache's rows or beyond
+ * prefix_B * rows_per_prefix, S < 1, fp8 layers, a head_dim other than 64 / 128. */
+int pcy_llama_extend(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
+                     const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
+                     const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out);
+size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc*, int B, int S, int n_logit_rows, int n_score);   /* host arithmetic only */
 typedef struct {
   int32_t* pos;              /* device scalar: cache length == rotary position of the next token (Q2) */
   int32_t* step;             /* device scalar: index of the next generated token */

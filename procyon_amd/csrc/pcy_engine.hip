@@ -1260,31 +1260,61 @@ static int esm_encode_enqueue(pcy_ctx* c, const pcy_esm_desc* m, const int32_t* 
 namespace {
 // pcy_llama_score: token rows to score behind the prefill (nullptr: a plain prefill)
 struct ScoreReq { const int32_t* rows; const int32_t* targets; int n; float* nll; };
+// pcy_llama_extend: the T tokens of every row FOLLOW t_past tokens the cache already holds (nullptr: a prefill from slot 0).  The layer loop
+// is the prefill's; what differs is the rotary position (t_past + s, made on the device), where K / V go (logical slots t_past ..) and the
+// attention (pcy_attn_ext.hip reads the keys from the cache: no transposed V workspace on this path).
+struct ExtendReq { int t_past; };
+// workspace of llama_prefill_impl; vt_elems = elements of the transposed-V copy (0 on the extension path, which also holds its positions)
+size_t llama_prefill_ws_need(const pcy_llama_desc* m, int M, size_t vt_elems, int n_logit_rows, int n_sum_rows, int n_score, bool ext) {
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, qkvw = (H + 2 * Hkv) * dh;
+  const size_t score_need = n_score > 0 ? align_up((size_t)n_score * d * 2, 256) + align_up(pcy_xent_ws_bytes(n_score, m->vocab), 256) : 0;
+  return score_need + align_up((size_t)M * d * 2, 256) * 2 + align_up((size_t)M * qkvw * 2, 256) + align_up((size_t)M * H * dh * 2, 256) +
+         align_up((size_t)M * F * 2, 256) + align_up(vt_elems * 2, 256) +
+         align_up((size_t)(n_logit_rows + 1) * d * 2, 256) + align_up((size_t)(n_sum_rows + 1) * d * 6, 256) +
+         (M <= 1024 ? align_up((size_t)8 * M * qkvw * 4, 256) : 0) + 4096 +
+         (m->layers_fp8 ? align_up((size_t)M * (F > H * dh ? F : H * dh), 256) + align_up((size_t)M * 4, 256) : 0) +
+         (ext ? align_up((size_t)M * 4, 256) : 0);
+}
 int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
                        const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
                        int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* sum_rows, int n_sum_rows,
-                       void* hidden_sum_out, void* hidden_all_out, const ScoreReq* score = nullptr) {
+                       void* hidden_sum_out, void* hidden_all_out, const ScoreReq* score = nullptr, const ExtendReq* ext = nullptr) {
   PCY_STICKY(c);
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
   if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "pcy_llama_prefill: d, ffn, H*dh, Hkv*dh must be multiples of 64");
   if (F % 16) return fail(1, "pcy_llama_prefill: ffn %% 16");
+  const int t_past = ext ? ext->t_past : 0;
+  if (ext) {
+    if (dh != 64 && dh != 128) return fail(1, "pcy_llama_extend: head_dim %d unsupported (64/128)", dh);
+    if (H % Hkv) return fail(1, "pcy_llama_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
+    if (m->layers_fp8) return fail(1, "pcy_llama_extend: fp8 projections are not supported on the extension path");
+    if (B < 1 || T < 1 || t_past < 0) return fail(1, "pcy_llama_extend: B=%d S=%d t_past=%d", B, T, t_past);
+    if (!kv->k || !kv->v) return fail(1, "pcy_llama_extend: cache without k / v");
+    if (B > kv->B) return fail(1, "pcy_llama_extend: B=%d exceeds cache rows %d", B, kv->B);
+    if (kv_shared(kv)) {
+      if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
+        return fail(1, "pcy_llama_extend: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0");
+      if (t_past < kv->prefix_T) return fail(1, "pcy_llama_extend: t_past=%d lies inside the shared prefix of %d slots, which is never written", t_past, kv->prefix_T);
+      if ((B - 1) / kv->rows_per_prefix >= kv->prefix_B)
+        return fail(1, "pcy_llama_extend: %d rows of %d per prefix need more than the %d prefix rows of the cache", B, kv->rows_per_prefix, kv->prefix_B);
+    }
+    if ((long)t_past + T > kv_cap(kv)) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed the cache capacity %d", t_past, T, kv_cap(kv));
+    if ((long)t_past + T > m->max_pos) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed rope table %d", t_past, T, m->max_pos);
+  } else {
   if (kv_shared(kv)) return fail(1, "pcy_llama_prefill: a cache with a shared prefix cannot be prefilled (prefill the prefix cache itself)");
   if (B > kv->B || T > kv->Tmax) return fail(1, "pcy_llama_prefill: B=%d T=%d exceed cache (%d,%d)", B, T, kv->B, kv->Tmax);
   if (T > m->max_pos) return fail(1, "pcy_llama_prefill: T=%d exceeds rope table %d", T, m->max_pos);
+  }
   const int M = B * T, qkvw = (H + 2 * Hkv) * dh, Tp = (T + 31) / 32 * 32;
   // Row stride of the transposed V ([Hkv*dh][vt_total]): a power-of-two stride (one 512-token prompt: 1 KB) sends the 128 rows of a
   // key block's V tile to the same few L2 channels; pad it to an odd multiple of 64 bytes
   int vt_total = B * Tp;
   if ((vt_total / 32) % 2 == 0) vt_total += 32;
+  if (ext) vt_total = 0;   // (the extension attention reads V from the cache)
   const int n_score = score ? score->n : 0;
   if (n_score < 0 || (n_score > 0 && (!score->rows || !score->targets || !score->nll))) return fail(1, "pcy_llama_score: score_rows / targets / nll_out missing");
-  const size_t score_need = n_score > 0 ? align_up((size_t)n_score * d * 2, 256) + align_up(pcy_xent_ws_bytes(n_score, m->vocab), 256) : 0;
-  const size_t need = score_need + align_up((size_t)M * d * 2, 256) * 2 + align_up((size_t)M * qkvw * 2, 256) + align_up((size_t)M * H * dh * 2, 256) +
-                      align_up((size_t)M * F * 2, 256) + align_up((size_t)Hkv * dh * vt_total * 2, 256) +
-                      align_up((size_t)(n_logit_rows + 1) * d * 2, 256) + align_up((size_t)(n_sum_rows + 1) * d * 6, 256) +
-                      (M <= 1024 ? align_up((size_t)8 * M * qkvw * 4, 256) : 0) + 4096 +
-                      (m->layers_fp8 ? align_up((size_t)M * (F > H * dh ? F : H * dh), 256) + align_up((size_t)M * 4, 256) : 0);
+  const size_t need = llama_prefill_ws_need(m, M, (size_t)Hkv * dh * vt_total, n_logit_rows, n_sum_rows, n_score, ext != nullptr);
   if (n_sum_rows > 0 && (!sum_rows || !hidden_sum_out)) return fail(1, "pcy_llama_prefill: sum_rows / hidden_sum_out missing");
   if (m->layers_fp8 && (d % 128 || F % 128 || (H * dh) % 128)) return fail(1, "pcy_llama_prefill: the fp8 path needs d, ffn, H*dh %% 128 == 0");
   if (int r = c->reserve(need)) return r;
@@ -1306,6 +1336,15 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   float* sa8 = m->layers_fp8 ? cv.take<float>((size_t)M) : nullptr;
   bf16_t* score_x = n_score > 0 ? cv.take<bf16_t>((size_t)n_score * d) : nullptr;
   char* score_ws = n_score > 0 ? cv.take<char>(pcy_xent_ws_bytes(n_score, m->vocab)) : nullptr;
+  if (ext) {   // rotary positions t_past + s of the new tokens (every row: quirk Q2)
+    int32_t* pos_ext = cv.take<int32_t>((size_t)M);
+    pcy_launch_ext_pos(s, pos_ext, B, T, t_past);
+    pos = pos_ext;
+    ++g_pcy_dispatch[PCY_DISPATCH_EXTEND];
+  }
+  const bool shared = ext && kv_shared(kv);
+  const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;   // first written slot inside the rows' own panels
+  const size_t prefix_layer_stride = shared ? (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh : 0;
   // ln != nullptr: A is the raw hidden state, RMSNorm(A) * ln is what gets quantised (one fused pass; PCY_DISABLE=fp8_fused_norm = two launches)
   auto linear8 = [&](const bf16_t* A, int K, const void* W8, const float* sw, const bf16_t* resid, bf16_t* Cout, int ldc, int N, int epi,
                      const bf16_t* ln = nullptr) {
@@ -1338,6 +1377,23 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
       xn_ready = 0;
       linear(s, xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, qkv, qkvw, M, qkvw, d, EPI_STORE, sk_ws, sk_bytes);
     }
+    if (ext) {
+      // rope (q, k) in place, K / V of token s to slot own_slot0 + s of the row's panel (the panel pointer carries the offset, the row
+      // stride stays Tmax * dh), then the S queries of every row against the cache
+      bf16_t* kl = (bf16_t*)kv->k + l * layer_stride;
+      bf16_t* vl = (bf16_t*)kv->v + l * layer_stride;
+      pcy_launch_rope(s, qkv, qkvw, 0, H + Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, M, 0, 0.f);
+      pcy_launch_kv_scatter(s, qkv, qkvw, H * dh, (H + Hkv) * dh, Hkv, dh, kl + (size_t)own_slot0 * dh, vl + (size_t)own_slot0 * dh, B, T, kv->Tmax);
+      PcyExtAttnArgs e{};
+      e.q = qkv; e.ldq = qkvw; e.k_own = kl; e.v_own = vl; e.Town = kv->Tmax;
+      if (shared) {
+        e.k_pre = (const bf16_t*)kv->prefix_k + l * prefix_layer_stride; e.v_pre = (const bf16_t*)kv->prefix_v + l * prefix_layer_stride;
+        e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
+      }
+      e.o = ao; e.ldo = H * dh; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = T; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
+      e.scale = 1.0f / sqrtf((float)dh);
+      pcy_launch_attn_extend(s, e);
+    } else {
     if (pcy_off("prefill_post_qkv") ||   // (the three launches: the test compares both)
         !pcy_launch_prefill_post_qkv(s, qkv, qkvw, H, Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
                                      (bf16_t*)kv->k + l * layer_stride, (bf16_t*)kv->v + l * layer_stride, B, T, kv->Tmax, cu, vt_cu, vt, vt_total)) {
@@ -1351,6 +1407,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
     t.o = ao; t.ldo = H * dh; t.cu = cu; t.vt_cu = vt_cu; t.keep = keep; t.nseq = B; t.max_len = T; t.H = H; t.Hkv = Hkv; t.dh = dh;
     t.causal = 1; t.scale = 1.0f / sqrtf((float)dh);
     pcy_launch_attn(s, t);
+    }
     if (L8) linear8(ao, H * dh, L8->wo, L8->so, x, x, d, d, EPI_RESID);
     else linear(s, ao, H * dh, (const bf16_t*)L.wo, nullptr, x, d, x, d, M, d, H * dh, EPI_RESID, sk_ws, sk_bytes,
                 (const bf16_t*)L.ln2, xn, &xn_ready, m->rms_eps, m->rms_cast);   // (M <= 1024: the K-split finish also writes RMSNorm(x) * ln2)
@@ -1418,7 +1475,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
     xa.nll = score->nll; xa.ws = score_ws;
     pcy_launch_lm_head_xent(s, xa);
   }
-  return check_launch("pcy_llama_prefill");
+  return check_launch(ext ? "pcy_llama_extend" : "pcy_llama_prefill");
 }
 
 PcyBeamState beam_state_args(const pcy_beam_state* st) {
@@ -1498,6 +1555,60 @@ int pcy_llama_score(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
   const ScoreReq sr{score_rows, targets, n_score, nll_out};
   return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, nullptr, nullptr, 0,
                             nullptr, nullptr, &sr);
+}
+
+int pcy_llama_extend(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
+                     const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
+                     const int32_t* targets, int n_score, float* nll_out) {
+  const ScoreReq sr{score_rows, targets, n_score, nll_out};
+  const ExtendReq er{t_past};
+  return llama_prefill_impl(c, m, kv, embeds, keep, nullptr, nullptr, nullptr, B, S, logit_rows, n_logit_rows, logits_out, hidden_out, nullptr, 0,
+                            nullptr, nullptr, n_score > 0 ? &sr : nullptr, &er);
+}
+size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_logit_rows, int n_score) {
+  if (!m || B < 1 || S < 1) return 0;
+  return llama_prefill_ws_need(m, B * S, 0, n_logit_rows > 0 ? n_logit_rows : 0, 0, n_score > 0 ? n_score : 0, true);
+}
+
+int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
+                    const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
+  PCY_STICKY(c);
+  if (dh != 64 && dh != 128) return fail(1, "pcy_attn_extend: head_dim %d unsupported (64/128)", dh);
+  if (Hkv < 1 || H % Hkv) return fail(1, "pcy_attn_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
+  if (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0 || layer < 0) return fail(1, "pcy_attn_extend: B=%d S=%d t_past=%d layer=%d", B, S, t_past, layer);
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "pcy_attn_extend: ld=%d (rows of qkv must be 16-byte aligned)", ld);
+  const bool shared = kv_shared(kv);
+  if (shared) {
+    if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
+      return fail(1, "pcy_attn_extend: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0");
+    if (t_past < kv->prefix_T) return fail(1, "pcy_attn_extend: t_past=%d lies inside the shared prefix of %d slots", t_past, kv->prefix_T);
+    if ((B - 1) / kv->rows_per_prefix >= kv->prefix_B)
+      return fail(1, "pcy_attn_extend: %d rows of %d per prefix need more than the %d prefix rows of the cache", B, kv->rows_per_prefix, kv->prefix_B);
+  }
+  if (B > kv->B) return fail(1, "pcy_attn_extend: B=%d exceeds cache rows %d", B, kv->B);
+  if ((long)t_past + S > kv_cap(kv)) return fail(1, "pcy_attn_extend: t_past=%d + S=%d exceed the cache capacity %d", t_past, S, kv_cap(kv));
+  const int M = B * S;
+  if (int r = c->reserve(align_up((size_t)M * 4, 256) + 256)) return r;
+  int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
+  hipStream_t s = c->stream;
+  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
+  const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;
+  bf16_t* kl = (bf16_t*)kv->k + layer * layer_stride;
+  bf16_t* vl = (bf16_t*)kv->v + layer * layer_stride;
+  pcy_launch_ext_pos(s, pos, B, S, t_past);
+  pcy_launch_rope(s, (bf16_t*)qkv, ld, 0, H + Hkv, dh, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, M, 0, 0.f);
+  pcy_launch_kv_scatter(s, (const bf16_t*)qkv, ld, H * dh, (H + Hkv) * dh, Hkv, dh, kl + (size_t)own_slot0 * dh, vl + (size_t)own_slot0 * dh, B, S, kv->Tmax);
+  PcyExtAttnArgs e{};
+  e.q = (const bf16_t*)qkv; e.ldq = ld; e.k_own = kl; e.v_own = vl; e.Town = kv->Tmax;
+  if (shared) {
+    const size_t pls = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
+    e.k_pre = (const bf16_t*)kv->prefix_k + layer * pls; e.v_pre = (const bf16_t*)kv->prefix_v + layer * pls;
+    e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
+  }
+  e.o = (bf16_t*)o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
+  e.scale = 1.0f / sqrtf((float)dh);
+  pcy_launch_attn_extend(s, e);
+  return check_launch("pcy_attn_extend");
 }
 
 int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,

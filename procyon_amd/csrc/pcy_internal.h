@@ -137,7 +137,8 @@ enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BI
        PCY_DISPATCH_DEC_LOOP_MFMA = 15,    // launch-per-stage loop, skinny-MFMA GEMVs (`batched`)
        PCY_DISPATCH_SHARED_PREFIX = 16,   // a step served from a shared-prefix cache (in addition to the loop's own count)
        PCY_DISPATCH_XENT = 17,            // one pcy_launch_lm_head_xent call (pcy_xent.hip)
-       PCY_DISPATCH_N = 18 };
+       PCY_DISPATCH_EXTEND = 18,          // one pcy_llama_extend call
+       PCY_DISPATCH_N = 19 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
 
 // lm_head x cross-entropy without logits in memory (pcy_xent.hip): nll[m] = logsumexp_n(bf16(x[m] . W[n])) - bf16(x[m] . W[targets[m]]).
@@ -238,6 +239,19 @@ struct PcyDecAttnArgs {
   const bf16_t* prefix_k; const bf16_t* prefix_v; int Tp; int rows_per_prefix;
 };
 void pcy_launch_attn_decode(hipStream_t s, const PcyDecAttnArgs& a);
+// Extension attention (pcy_attn_ext.hip): S new query rows per row against the cache, K / V of the new slots already appended.
+struct PcyExtAttnArgs {
+  const bf16_t* q; int ldq;                    // roped queries, token-major [B*S, ldq], head h at column h*dh, row b*S + s
+  const bf16_t* k_own; const bf16_t* v_own;    // THIS layer's panels [rows, Hkv, Town, dh]: logical slot j >= Tp at j - Tp
+  const bf16_t* k_pre; const bf16_t* v_pre;    // shared prefix of THIS layer [prefix_B, Hkv, Tp, dh] or nullptr (plain cache: Tp, rows_per_prefix not read)
+  int Town, Tp, rows_per_prefix;
+  bf16_t* o; int ldo;                          // [B*S, H*dh]
+  const uint8_t* keep; int ld_keep;            // optional [B, ld_keep] key mask in logical slots, non-zero = kept
+  int B, S, H, Hkv, dh, t_past;                // query s of a row sits at logical slot t_past + s and attends slots [0, t_past + s]
+  float scale;
+};
+bool pcy_launch_attn_extend(hipStream_t s, const PcyExtAttnArgs& a);   // false = head_dim not covered (64 / 128), nothing launched
+void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past);   // pos[b*S + s] = t_past + s
 struct PcyGemvArgs;
 // decode attention + o projection (EPI_RESID GEMV over the attention output) in one launch; false = shape not covered,
 // nothing launched.  epoch: device word that differs between consecutive calls on the same `flags` (max_flags words).

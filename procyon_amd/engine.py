@@ -174,6 +174,21 @@ class Context:
                                          _p(sin_t), _p(keep), B, H, Hkv, dh, Tmax), "pcy_attn_decode")
         return o
 
+    def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None):
+        """pcy_attn_extend: qkv [B*S, (H+2Hkv)*dh] un-roped projections of S new tokens per row (row b*S+s; B rows, default the cache's);
+        `cache` a KVCache (plain or shared-prefix) that holds t_past tokens per row.  Ropes q / k in place at t_past + s, appends K / V at
+        logical slots t_past .. of layer `layer`, -> o [B*S, H*dh].  keep: [B, cache.capacity] uint8 in logical slots or None."""
+        _chk_bf16(qkv)
+        B = cache.B if B is None else int(B)
+        S = qkv.shape[0] // B
+        assert S * B == qkv.shape[0], (qkv.shape, B)
+        if keep is not None:
+            assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, cache.capacity), (keep.shape, keep.dtype)
+        o = torch.empty(B * S, H * dh, dtype=BF16, device=qkv.device)
+        L.check(self.lib.pcy_attn_extend(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), H * dh, int(t_past), _p(cos_t),
+                                         _p(sin_t), _p(keep), B, S, H, Hkv, dh), "pcy_attn_extend")
+        return o
+
     def retrieval_scores(self, query, targets):
         """cosine similarities [Q,N] (bf16) as `ProcyonRetrievalEval.get_predictions` forms them (procyon.py:400-406)."""
         _chk_bf16(query, targets)
@@ -603,6 +618,11 @@ class LlamaEngine:
         share the prompts' K / V and own [L, B*beam, Hkv, max_new, dh] suffix slots.  Row r belongs to prompt r // beam."""
         return KVCache(self.cfg, prefix_cache.B * int(beam), int(max_new), self.device, prefix=prefix_cache, rows_per_prefix=int(beam))
 
+    def new_shared_cache(self, prefix_cache: KVCache, rows_per_prefix, suffix_slots):
+        """A cache of prefix_cache.B * rows_per_prefix rows that share the K / V of the prompts prefilled into `prefix_cache` (Tmax == the prompt
+        length) and own `suffix_slots` slots each: what `extend` and the beam search run on.  Row r belongs to prompt r // rows_per_prefix."""
+        return self.new_beam_cache(prefix_cache, rows_per_prefix, suffix_slots)
+
     def embed_tokens(self, ids, soft=None, soft_map=None):
         """ids [B,T] int -> [B,T,d]; soft-token splice of `_prepare_input_embeddings` if soft_map given."""
         B, T = ids.shape
@@ -686,6 +706,54 @@ class LlamaEngine:
         if n:
             token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
         return token_nll, n, (logits if logit_rows is not None else None)
+
+    def extend(self, cache: KVCache, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False):
+        """S more tokens per row against a cache that holds t_past tokens per row (pcy_llama_extend; HF's forward(inputs_embeds [B,S],
+        past_key_values)).  embeds [B,S,d] bf16; cache plain or shared-prefix (`new_shared_cache`); keep [B, >= t_past + S] (0 = masked key,
+        old and new slots alike) or None; logit_rows "all" / "last" / flat rows b*S+s / None; labels [B,S] in HF's convention (-100 = not
+        scored): token_nll[b, s+1] = -log p(token s+1 | everything up to s, the cached prefix included), 0 elsewhere.
+        -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens).  K / V of slots [t_past, t_past+S) are written."""
+        B, S, d = embeds.shape
+        dev = self.device
+        embeds = embeds.contiguous()
+        _chk_bf16(embeds)
+        t_past = int(t_past)
+        keep_d = None
+        if keep is not None:
+            kp = (torch.as_tensor(keep) != 0)
+            if kp.dim() != 2 or kp.shape[0] != B or kp.shape[1] < min(t_past + S, cache.capacity):
+                raise ValueError(f"keep {tuple(kp.shape)}: expected [{B}, >= {t_past + S}]")
+            if not bool(kp[:, :t_past + S].all()):
+                keep_d = torch.zeros(B, cache.capacity, dtype=torch.uint8, device=dev)   # (row stride = the logical capacity)
+                n = min(kp.shape[1], cache.capacity)
+                keep_d[:, :n] = kp[:, :n].to(dev, torch.uint8)
+        if isinstance(logit_rows, str) and logit_rows == "all":
+            rows = torch.arange(B * S, dtype=torch.int32, device=dev)
+        elif isinstance(logit_rows, str) and logit_rows == "last":
+            rows = (torch.arange(B, dtype=torch.int32, device=dev) + 1) * S - 1
+        elif logit_rows is None:
+            rows = torch.zeros(0, dtype=torch.int32, device=dev)
+        else:
+            rows = logit_rows.to(dev, torch.int32).contiguous()
+        logits = torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
+        hidden = torch.empty(B, S, d, dtype=BF16, device=dev) if want_hidden else None
+        n, srows, tg, bt_d, nll, token_nll = 0, None, None, None, None, None
+        if labels is not None:
+            rows_c, tg_c, bt = score_plan(labels, S, self.cfg.vocab)
+            n = int(rows_c.numel())
+            token_nll = torch.zeros(B, S, dtype=torch.float32, device=dev)
+            if n:
+                srows, tg, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev)
+                nll = torch.empty(n, dtype=torch.float32, device=dev)
+        L.check(self.ctx.lib.pcy_llama_extend(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
+                                              _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
+        if n:
+            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
+        return (logits if logit_rows is not None else None), hidden, token_nll, n
+
+    def extend_ws_bytes(self, B, S, n_logit_rows=0, n_score=0):
+        """workspace of an `extend` call: host arithmetic, a function of the row counts only (never of the past length)"""
+        return int(self.ctx.lib.pcy_llama_extend_ws_bytes(C.byref(self.desc), int(B), int(S), int(n_logit_rows), int(n_score)))
 
     def decode(self, cache: KVCache, st: GenState, B):
         L.check(self.ctx.lib.pcy_llama_decode(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode")

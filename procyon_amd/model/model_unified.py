@@ -71,6 +71,84 @@ def multi_replace_tokens(a, b, replace_token, eval=False):
     return result
 
 
+def qa_full_labels(input_ids, pad_id, special_ids, answer_idx, use_llama_tokenizer=False, train_qa_full_lm=False):
+    """The labels `forward` scores a QA / caption batch against (model_unified.py:520-546): the ids with -100 on the pads, on the soft-token
+    slots (`special_ids`), on the last column (Llama tokenizer) and -- unless train_qa_full_lm -- on everything up to and including the last
+    [ANSWER] of the row."""
+    full_labels = input_ids.clone()
+    all_masks = full_labels == pad_id
+    for i in special_ids:
+        all_masks |= full_labels == i
+    if use_llama_tokenizer:
+        all_masks[:, -1] = True
+    if not train_qa_full_lm:
+        all_masks |= mask_before(full_labels, answer_idx, before_last_answer=True)
+    return torch.where(all_masks, -100, full_labels)
+
+
+def candidate_plan(tokenize, label_rule, instructions, candidates, answer_idx, pad_id):
+    """Host side of `UnifiedProCyon.score_candidates`: P prompts (instructions ending in [ANSWER]) x N candidate texts each, cut into the part
+    all candidates of a prompt share and the part that differs.  Pure: no device, no model.
+      tokenize(texts)  -> (ids [R, T], mask [R, T]) right-padded rows, eos included (`_prepare_text_inputs_and_tokenize(texts, [[]] * R, crop_off=True)`)
+      label_rule(ids)  -> labels [R, T], the rule `forward` applies to `full_labels` (`qa_full_labels`)
+    Row p*N + n is `instructions[p] + " " + candidates[p][n]`, tokenised exactly as `score_text` would, and cut IN FRONT of its last [ANSWER]:
+    the prefix (identical for the N rows of a prompt -- ValueError otherwise) and the suffix [ANSWER] + candidate + eos, which holds every
+    scored token.  -> dict:
+      prefix_ids / prefix_mask [P, Tp]   the prefixes LEFT-padded to the longest (as `generate` pads its prompts), mask 0 on the pads
+      suffix_ids / suffix_mask [P*N, S]  the suffixes RIGHT-padded to the longest
+      suffix_labels [P*N, S]             the labels of the suffix tokens, -100 on [ANSWER] and on the pads (HF's convention: `extend` shifts)
+      n_tokens [P, N]                    scored tokens per row = what `forward`'s rule gives for the concatenated row
+      cut [P*N], P, N, Tp, S
+    ValueError: candidate lists of unequal length (ragged lists are out of scope), no candidates, a row without [ANSWER], candidates of a
+    prompt whose prefixes differ, or labels in front of the cut (train_qa_full_lm: those rows lie in the prefix and cannot be scored here)."""
+    P = len(instructions)
+    if len(candidates) != P or P == 0:
+        raise ValueError(f"{len(candidates)} candidate lists for {P} prompts")
+    N = len(candidates[0])
+    if N == 0 or any(len(c) != N for c in candidates):
+        raise ValueError(f"every prompt needs the same number of candidates, got {[len(c) for c in candidates]}")
+    texts = [instructions[p] + " " + candidates[p][n] for p in range(P) for n in range(N)]
+    ids, mask = tokenize(texts)
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    for r in range(P * N):      # (before the label rule, which has no answer for such a row)
+        if not bool(((ids[r] == answer_idx) & mask[r]).any()):
+            raise ValueError(f"row {r}: no [ANSWER] token in {texts[r]!r}")
+    labels = torch.as_tensor(label_rule(ids)).long().cpu()
+    prefixes, suffixes, suf_labels, cuts = [], [], [], []
+    for r in range(P * N):
+        n_real = int(mask[r].sum())
+        assert bool(mask[r, :n_real].all()), "rows must be right-padded"
+        cut = int((ids[r, :n_real] == answer_idx).nonzero().max())
+        if bool((labels[r, :cut + 1] != -100).any()):
+            raise ValueError(f"row {r}: labelled tokens in front of the last [ANSWER]; they lie in the shared prefix and cannot be scored by the extension")
+        if r % N == 0:
+            prefixes.append(ids[r, :cut])
+        elif not torch.equal(prefixes[-1], ids[r, :cut]):
+            raise ValueError(f"prompt {r // N}: candidate {r % N} changes the tokens in front of [ANSWER]; the candidates of a prompt must share its prefix")
+        cuts.append(cut)
+        suffixes.append(ids[r, cut:n_real])
+        suf_labels.append(labels[r, cut:n_real])
+    Tp, S = max(int(t.numel()) for t in prefixes), max(int(t.numel()) for t in suffixes)
+    if Tp == 0:
+        raise ValueError("[ANSWER] is the first token of a row: nothing to prefill")
+    prefix_ids = torch.full((P, Tp), int(pad_id), dtype=torch.long)
+    prefix_mask = torch.zeros(P, Tp, dtype=torch.long)
+    for p, t in enumerate(prefixes):
+        if t.numel():
+            prefix_ids[p, Tp - t.numel():] = t
+            prefix_mask[p, Tp - t.numel():] = 1
+    suffix_ids = torch.full((P * N, S), int(pad_id), dtype=torch.long)
+    suffix_mask = torch.zeros(P * N, S, dtype=torch.long)
+    suffix_labels = torch.full((P * N, S), -100, dtype=torch.long)
+    for r, (t, lb) in enumerate(zip(suffixes, suf_labels)):
+        suffix_ids[r, :t.numel()] = t
+        suffix_mask[r, :t.numel()] = 1
+        suffix_labels[r, :t.numel()] = lb
+    n_tokens = (suffix_labels[:, 1:] != -100).sum(1).view(P, N)
+    return dict(prefix_ids=prefix_ids, prefix_mask=prefix_mask, suffix_ids=suffix_ids, suffix_mask=suffix_mask, suffix_labels=suffix_labels,
+                n_tokens=n_tokens, cut=torch.tensor(cuts), P=P, N=N, Tp=Tp, S=S)
+
+
 def special_token_ids(tokenizer, text_encoder_fname):
     """The token ids `UnifiedProCyon.__init__` / `_init_tokenizer` keep (model_unified.py:1100-1133, 342-347), read from a
     tokenizer on which the eight ProCyon tokens are already registered (`procyon_amd.checkpoint.hf_tokenizer` does that in the
@@ -283,12 +361,16 @@ class UnifiedProCyon:
         z, _ = self.protein_seq_encoder(seq, aggregate=True)
         return z
 
-    def _preprocessing(self, inputs, aaseq_type='protein', exclude_protein_structure=False, crop_off=False,
-                       no_pad=False, retrieval=False, left_pad=False):
-        """`_preprocessing` (model_unified.py:352-481)."""
-        aaseq_token_embeddings = aaseq_ret_embeddings = None
+    def _full_labels(self, input_ids):
+        """the labels `forward` scores against (`qa_full_labels` with this model's token ids)"""
+        return qa_full_labels(input_ids, self.tokenizer.pad_token_id, (self.prot_replacement_idx, self.prot_retrieval_idx, self.drug_idx, self.struct_idx),
+                              self.answer_idx, self.use_llama_tokenizer, self.train_qa_full_lm)
+
+    def _soft_tokens(self, inputs, aaseq_type):
+        """encoder + projector part of `_preprocessing`: (sequence embeddings | None, protein soft tokens | None, drug soft tokens | None)"""
+        aaseq_token_embeddings = None
         if inputs["data"]["seq"] is not None:
-            aaseq_token_embeddings = aaseq_ret_embeddings = self._encode_aaseq(inputs["data"]["seq"], aaseq_type)
+            aaseq_token_embeddings = self._encode_aaseq(inputs["data"]["seq"], aaseq_type)
         if inputs["input"]["seq"] is not None:
             full_index = list(chain.from_iterable(inputs["input"]["seq"]))
             pz_inputs = aaseq_token_embeddings[torch.tensor(full_index, dtype=torch.long, device=self.device)]
@@ -302,6 +384,13 @@ class UnifiedProCyon:
             drug_soft_tokens = self.token_projectors["drug"](drug_z)
         else:
             drug_soft_tokens = None
+        return aaseq_token_embeddings, protein_soft_tokens, drug_soft_tokens
+
+    def _preprocessing(self, inputs, aaseq_type='protein', exclude_protein_structure=False, crop_off=False,
+                       no_pad=False, retrieval=False, left_pad=False):
+        """`_preprocessing` (model_unified.py:352-481)."""
+        aaseq_token_embeddings, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
+        aaseq_ret_embeddings = aaseq_token_embeddings
         text_inputs = [[inputs["data"]["text"][i] for i in inp_list] for inp_list in inputs["input"]["text"]]
         instruction_list = inputs['instructions']
         protein_struct_tokens = []
@@ -433,15 +522,7 @@ class UnifiedProCyon:
         emb = input_embeds[:, :real].contiguous()
         answer_pos = None
         if not retrieval:
-            pad_id = self.tokenizer.pad_token_id
-            full_labels = input_ids.clone()
-            all_masks = (full_labels == pad_id) | (full_labels == self.prot_replacement_idx) | \
-                (full_labels == self.prot_retrieval_idx) | (full_labels == self.drug_idx) | (full_labels == self.struct_idx)
-            if self.use_llama_tokenizer:
-                all_masks[:, -1] = True
-            if not self.train_qa_full_lm:
-                all_masks |= mask_before(full_labels, self.answer_idx, before_last_answer=True)
-            full_labels = torch.where(all_masks, -100, full_labels)
+            full_labels = self._full_labels(input_ids)
             answer_pos = torch.tensor([int((input_ids[i] == self.answer_idx).nonzero()[:, 0].max()) for i in range(B)])
         if retrieval and self.config.ret_token_access not in ('last', 'all'):
             raise NotImplementedError("Invalid option {} for ret_token_access".format(self.config.ret_token_access))
@@ -496,6 +577,44 @@ class UnifiedProCyon:
         n_tok = (out['full_labels'][:, 1:tn.shape[1]] != -100).sum(1)
         loss = o.loss
         return {"token_nll": tn, "seq_nll": tn.sum(1), "n_tokens": n_tok, "loss": loss, "perplexity": torch.exp(loss)}
+
+    @torch.no_grad()
+    def score_candidates(self, inputs, candidates, aaseq_type='protein'):
+        """Rank N candidate texts per prompt by teacher-forced likelihood WITHOUT running the prompt N times.  `inputs`: a caption / QA batch as
+        `generate` takes it, every instruction ending in [ANSWER]; `candidates`: one list of N strings per prompt (the same N for all,
+        ValueError otherwise).  Row (p, n) is scored as `score_text` scores `instructions[p] + " " + candidates[p][n]` -- same tokens, same
+        labels -- but the prompts are encoded and prefilled ONCE (P rows, left-padded as `generate` pads them) and the P*N suffixes
+        [ANSWER] + candidate + eos run as one `LlamaEngine.extend` call on a cache whose rows share the prompts' K / V (`candidate_plan`).
+        -> {"token_nll" [P,N,S] fp32 over the suffix tokens (0 where nothing is labelled), "seq_nll" [P,N], "n_tokens" [P,N], "mean_nll" [P,N] =
+        seq_nll / n_tokens, "order" [P,N] = stable argsort of mean_nll, best first, "plan" = the `candidate_plan`, "cache" = the shared cache}."""
+        self._require_bf16_or_fp32("score_candidates")
+        if self._f32:
+            raise NotImplementedError("score_candidates needs the bf16 engine (the fp32 family has no cache extension)")
+        if self.config.use_protein_struct and inputs["input"]["seq"]:
+            raise NotImplementedError("score_candidates: structure tokens are dropped at random per call (struct_dropout_prob); score such batches with score_text")
+        if any(len(t) for t in inputs["input"]["text"]):
+            raise NotImplementedError("score_candidates: [EXT] text slots are not supported; write the text into the instruction")
+        instructions = list(inputs["instructions"])
+        tokenize = lambda texts: self._prepare_text_inputs_and_tokenize(texts, [[] for _ in texts], crop_off=True)
+        plan = candidate_plan(tokenize, self._full_labels, instructions, candidates, self.answer_idx, self.tokenizer.pad_token_id)
+        P, N, Tp, S = plan["P"], plan["N"], plan["Tp"], plan["S"]
+        soft_ids = (self.prot_replacement_idx, self.struct_idx, self.drug_idx)
+        if any(bool((plan["suffix_ids"] == i).any()) for i in soft_ids):
+            raise ValueError("score_candidates: a candidate holds a soft-token slot")
+        _, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
+        prefix_emb, _ = self._prepare_input_embeddings(plan["prefix_ids"], protein_soft_tokens=protein_soft_tokens, drug_soft_tokens=drug_soft_tokens)
+        eng = self.text_encoder.engine
+        prefix_cache = eng.new_cache(P, Tp)
+        eng.prefill(prefix_emb, plan["prefix_mask"], prefix_cache, logit_rows=None)
+        cache = eng.new_shared_cache(prefix_cache, N, S)
+        keep = torch.cat([plan["prefix_mask"].repeat_interleave(N, 0), plan["suffix_mask"]], 1)
+        _, _, token_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), Tp, keep=keep, labels=plan["suffix_labels"])
+        token_nll = token_nll.view(P, N, S)
+        seq_nll = token_nll.sum(2)
+        n_tokens = plan["n_tokens"].to(seq_nll.device)
+        mean_nll = seq_nll / n_tokens
+        return {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll,
+                "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
 
     # ------------------------------------------------------------------------------------------
     @staticmethod

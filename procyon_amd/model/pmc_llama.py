@@ -121,7 +121,14 @@ class LlamaPostTokenization:
         scores in this call (one pass together with the logits when `lazy_hidden=True` and no hidden-state sum is asked for; the hidden
         states then come from a second pass if they are read).  With the default `compute_loss=False` nothing extra runs here: `.loss` is
         computed on first access by a second, deterministic scoring pass (same bits) and cached, so callers that never read it pay nothing.
-        Without `full_labels`, on the fp32 path (fp32 `input_embeds`) and on the cached decode `.loss` stays None.
+        Without `full_labels`, on the fp32 path (fp32 `input_embeds`) and on the one-token cached decode `.loss` stays None.
+      * past_key_values with MORE than one new token (HF's `forward(input_ids [B,S], past_key_values=...)`): `input_ids` [B,S] with S > 1, or
+        bf16 `input_embeds` [B,S,d] at any S, extend the filled cache by S tokens per row in one pass (`LlamaEngine.extend`): positions
+        t .. t+S-1, causal among the new tokens, every cached key attended.  `attn_masks` None or [B, t+S] (cached AND new keys; 0 = masked),
+        `full_labels` [B,S] label the NEW tokens (token_nll[b, s+1] = NLL of new token s+1 given everything before it, the cache included),
+        `logit_positions` [B] index the new tokens.  Returns `.logits` [B,S,V] (or [B,1,V]), `.past_key_values` of t+S tokens,
+        `hidden_states[-1]` when `want_hidden`, `.loss / .token_nll / .n_tokens` as above (in the same pass with `compute_loss=True`).
+        `input_ids` [B,1] stays the decode step, bit for bit.  The fp32 family has no extension: an fp32 past takes `input_ids` [B,1] only.
       * output_attentions: not computed.
       * max_new_tokens: KV capacity reserved beyond the prompt when use_cache=True.
     """
@@ -215,8 +222,9 @@ class LlamaPostTokenization:
             if compute_loss:
                 out._score()
             return out
+        if input_embeds is not None or input_ids.shape[1] != 1:
+            return self._forward_extend(input_embeds, input_ids, attn_masks, full_labels, past_key_values, logit_positions, want_hidden, compute_loss)
         # cached decode: one new token per row, no mask, position = cache length (quirks Q1/Q2)
-        assert input_ids is not None and input_ids.shape[1] == 1, "cached decode takes input_ids [B,1]"
         cache, t = past_key_values.cache, past_key_values.t
         B = input_ids.shape[0]
         if t + 1 > cache.Tmax:
@@ -228,6 +236,36 @@ class LlamaPostTokenization:
         st.next_tok.copy_(input_ids.view(-1).to(torch.int32))
         eng.decode_graph(cache, st, B)
         return CausalLMOutput(st.logits.clone().view(B, 1, -1), _Past(cache, t + 1))
+
+    def _forward_extend(self, input_embeds, input_ids, attn_masks, full_labels, past_key_values, logit_positions, want_hidden, compute_loss):
+        """S new tokens per row against the filled cache of `past_key_values` (see the class docstring): one `LlamaEngine.extend` pass"""
+        eng = self.engine
+        cache, t = past_key_values.cache, past_key_values.t
+        if input_embeds is None:
+            input_embeds = eng.embed_tokens(input_ids)
+        B, S, _ = input_embeds.shape
+        if t + S > cache.capacity:
+            raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
+        embeds_dev = input_embeds.to(eng.device)
+        if attn_masks is not None:
+            attn_masks = torch.as_tensor(attn_masks)
+            assert tuple(attn_masks.shape) == (B, t + S), f"attn_masks {tuple(attn_masks.shape)}: the cached and the new keys, [{B}, {t + S}]"
+        rows = "all" if logit_positions is None else (torch.arange(B) * S + logit_positions.cpu().long()).to(torch.int32)
+        labels = None if full_labels is None else torch.as_tensor(full_labels)[:, :S]
+        L1 = self.cfg.n_layers + 1
+
+        def no_tuple():
+            raise RuntimeError("the cached multi-token forward keeps the final hidden state only (hidden_states[-1])")
+
+        if labels is not None and not compute_loss:
+            # `.loss` on first access: the new tokens' K / V are in the cache by then, so the scoring pass rewrites the same slots with the same bits
+            logits, hidden, _, _ = eng.extend(cache, embeds_dev, t, keep=attn_masks, logit_rows=rows, want_hidden=want_hidden)
+            scorer, scored = (lambda: tuple(eng.extend(cache, embeds_dev, t, keep=attn_masks, labels=labels)[2:])), None
+        else:
+            logits, hidden, token_nll, n_tok = eng.extend(cache, embeds_dev, t, keep=attn_masks, logit_rows=rows, labels=labels, want_hidden=want_hidden)
+            scorer, scored = None, (None if labels is None else (token_nll, n_tok))
+        hs = _HiddenStates(L1, hidden, no_tuple) if want_hidden else None
+        return CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _Past(cache, t + S), hs, None, scorer=scorer, scored=scored)
 
     def _forward_f32(self, input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions):
         """fp32 embeddings in -> the fp32 prefill (the callers that never call `.bfloat16()`); use_cache=True keeps the K / V rows in an fp32
