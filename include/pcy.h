@@ -129,7 +129,8 @@ int pcy_retrieval_topk_f32(pcy_ctx*, const float* query, int Q, const void* targ
  * at the answer row, then the yes / no columns or the argmax).  logits [rows, V] bf16 (is_f32 = 0: fp32 statistics, ONE rounding of
  * exp(x - max) / sum, torch.softmax on a bf16 tensor) or fp32 (is_f32 = 1).  Optional outputs (NULL = not wanted): probs_out [rows, V] in
  * the logits' dtype; yes_no_out [rows, 2] fp32 = the stored probabilities of yes_id / no_id; argmax_out [rows] int32 = argmax of the stored
- * probabilities, lowest index on ties. */
+ * probabilities, lowest index on ties.  -inf logits are allowed and mean "never chosen" (stored probability exactly 0); a row must hold
+ * at least one finite logit; NaN logits are outside the contract. */
 int pcy_qa_probs(pcy_ctx*, const void* logits, int is_f32, int rows, int V, int yes_id, int no_id, void* probs_out, float* yes_no_out,
                  int32_t* argmax_out);
 
@@ -313,7 +314,9 @@ int pcy_llama_decode_layers(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*
  * do their own selection between steps (sampling, diverse beam search).  next_tok and *pos are read from device memory. */
 int pcy_llama_decode_graph(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
 /* argmax of state->logits (lowest index on ties) -> next_tok / tokens_out[step], logprob, ++pos? no: ++step only
- * when advance_pos == 0 (used on the prefill logits), ++pos and ++step otherwise */
+ * when advance_pos == 0 (used on the prefill logits), ++pos and ++step otherwise.  logprob += bf16 log_softmax(logits)[token]: fp32
+ * statistics, one rounding.  -inf logits are allowed and mean "never chosen" (banned tokens, also whole runs of them); a row must hold
+ * at least one finite logit; NaN logits are outside the contract. */
 int pcy_greedy_pick(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int advance_pos);
 /* n_steps x (decode + pick) with no host synchronisation; use_graph != 0 replays a captured hipGraph */
 int pcy_llama_greedy(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int n_steps,
@@ -324,7 +327,9 @@ int pcy_llama_greedy(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const
  *   token = first index whose cumulative masked probability exceeds uniforms[step * B + b] * total (inverse CDF with the CALLER's
  *   uniform variates in [0,1): torch's multinomial stream is not reproducible, the probability vector and the draw for a given u
  *   are); logprob += bf16 log_softmax(unscaled logits)[token]; then next_tok / tokens_out / ++step (/ ++pos) like pcy_greedy_pick.
- * probs_out: optional [B, vocab] bf16 record of the pre-sampling probability vector.  uniforms: device fp32 [max_steps * B]. */
+ * probs_out: optional [B, vocab] bf16 record of the pre-sampling probability vector.  uniforms: device fp32 [max_steps * B].
+ * -inf logits are allowed and mean "never chosen" (probability exactly 0); a row must hold at least one finite logit; NaN logits are
+ * outside the contract. */
 int pcy_sample_pick(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int advance_pos,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out);
 /* n_steps x (decode + sample) with no host synchronisation */
@@ -335,7 +340,10 @@ int pcy_llama_sample(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const
  * token among the picks of the earlier groups at this step);  at step 0 only the first beam of a group is expanded.  Updates
  * the token histories, the running scores, `src` (parent slot of every slot: feed it to pcy_kv_reorder), `next_tok`, ++*step,
  * ++*pos (from step 1 on) and raises *done once every row holds `eos_id`; a launch with *done set changes nothing.
- * logits [B*beam, vocab] bf16.  All pointers are device memory; state layout in the struct below (BB = B * beam). */
+ * logits [B*beam, vocab] bf16.  All pointers are device memory; state layout in the struct below (BB = B * beam).
+ * Equal candidate scores go to the lowest flat index row * vocab + token.  -inf logits are allowed and mean "never chosen" as long as a
+ * group has group_size finite candidates left; a row must hold at least one finite logit; NaN logits are outside the contract (a
+ * selection that finds no candidate then commits the group's first row and token 0: wrong, but inside the state arrays). */
 typedef struct {
   int32_t* out; int32_t max_len;   /* [2][BB][max_len] token histories; buffer (*step & 1) is current; zero-initialised */
   float* cur; float* cur_new;      /* [BB] running scores (zero-initialised) + scratch */

@@ -444,7 +444,8 @@ __global__ __launch_bounds__(PICK_NT) void pick_stage1_kernel(const bf16_t* __re
   float se = 0.f;
   for (int i = lo + threadIdx.x; i < hi; i += PICK_NT) se += expf(bf2f(lg[i]) - best);
   se = block_sum<PICK_NT>(se, red);
-  if (threadIdx.x == 0) part[b * PICK_NB + c] = PickPartial{best, bi, (lo < hi) ? se : 0.f, 0};
+  // an empty chunk and a chunk of -inf logits (banned tokens) alike: (max = -inf, sum = 0), not exp(-inf + inf) = NaN
+  if (threadIdx.x == 0) part[b * PICK_NB + c] = PickPartial{best, bi, best > -INFINITY ? se : 0.f, 0};
 }
 
 // one workgroup for all rows (wave w takes rows w, w + 4, ...), so that the step / position counters can be advanced by the
@@ -519,7 +520,8 @@ __global__ __launch_bounds__(PICK_NT) void sample_stage1_kernel(const bf16_t* __
   }
   sr = block_sum<PICK_NT>(sr, red);
   ss = block_sum<PICK_NT>(ss, red);
-  if (threadIdx.x == 0) part[b * PICK_NB + c] = make_float4(mr, lo < hi ? sr : 0.f, ms, lo < hi ? ss : 0.f);
+  // empty chunk or only -inf logits: (max = -inf, sum = 0) for both statistics (exp(-inf + inf) would be NaN)
+  if (threadIdx.x == 0) part[b * PICK_NB + c] = make_float4(mr, mr > -INFINITY ? sr : 0.f, ms, ms > -INFINITY ? ss : 0.f);
 }
 
 // block-wide exclusive prefix sums of one value per thread (SMP_NT threads, thread order); *total = the sum
@@ -1050,7 +1052,8 @@ __global__ __launch_bounds__(256) void beam_rowstats_kernel(const bf16_t* __rest
     }
   }
   se = block_sum<256>(se, red);
-  if (threadIdx.x == 0) part[(size_t)row * BEAM_NCH + c] = make_float2(m, lo < hi ? se : 0.f);
+  // empty slice or only -inf logits: (max = -inf, sum = 0), not exp(-inf + inf) = NaN
+  if (threadIdx.x == 0) part[(size_t)row * BEAM_NCH + c] = make_float2(m, m > -INFINITY ? se : 0.f);
 }
 
 // Per (row, slice): the `n` best candidates of the slice in the order (log-probability descending, token ascending), as
@@ -1184,8 +1187,11 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(const bf16_t* __restric
       __syncthreads();
       const BeamPick pk = pick_s;
       prev_s = pk.s; prev_c = pk.c;
-      // commit slot gs + j: parent row gs + pk.c / V (an OLD row: the old buffers are never written in this launch)
-      const int parent = base + gs + pk.c / V, tok = pk.c % V, slot = base + gs + j;
+      // no eligible candidate (NaN scores, fewer than g candidates: outside the contract) leaves the sentinel: commit the group's first
+      // row and token 0 instead of indexing the state with it
+      const int pc = pk.c == 0x7fffffff ? 0 : pk.c;
+      // commit slot gs + j: parent row gs + pc / V (an OLD row: the old buffers are never written in this launch)
+      const int parent = base + gs + pc / V, tok = pc % V, slot = base + gs + j;
       for (int q = tid; q < i; q += 1024) out_new[(size_t)slot * st.max_len + q] = out_old[(size_t)parent * st.max_len + q];
       if (tid == 0) {
         out_new[(size_t)slot * st.max_len + i] = tok;

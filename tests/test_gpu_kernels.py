@@ -539,11 +539,7 @@ def test_beam_step_kernel_matches_reference_bookkeeping(ctx, monkeypatch, B, bea
     import torch.nn.functional as Fn
     from oracle import llama_ref as LR
     from procyon_amd.engine import BeamState, LlamaEngine
-
-    def lsm_rounded_once(x, dim=-1):
-        xd = x.double()
-        m = xd.max(dim, keepdim=True).values
-        return ((xd - m) - torch.log(torch.exp(xd - m).sum(dim, keepdim=True))).float().to(x.dtype)
+    from select_oracle import lsm_rounded_once
     monkeypatch.setattr(LR.F, "log_softmax", lsm_rounded_once)
     BB, M = B * beam, 13
     # Exact ties among the best candidates are natural here (bf16 log-probabilities + fp32 running scores) and torch.topk leaves
@@ -637,6 +633,7 @@ def test_sample_step_kernel_vs_oracle(V, mode):
     from oracle import llama_ref as LR
     from procyon_amd.engine import GenState, LlamaConfig, LlamaEngine
     from procyon_amd import synth
+    from select_oracle import assert_rounded_from, log_softmax64, logprob_preload, logprob_slack
     kw = dict(vocab=V, d=64, n_layers=1, n_heads=2, n_kv_heads=1, ffn=128)
     eng = LlamaEngine(synth.llama_state_dict(**kw), LlamaConfig(**kw, max_pos=64))
     B, steps = 3, 5
@@ -648,10 +645,12 @@ def test_sample_step_kernel_vs_oracle(V, mode):
     ud = u.cuda()
     nuc = float(mode[7:]) if mode.startswith("nucleus") else None
     temp = float(mode[4:]) if mode.startswith("temp") else 1.0
-    lp_ref = torch.zeros(B)
     for s_ in range(steps):
         logits = (torch.randn(B, V, generator=g) * (1.0 + s_)).to(BF)
         st.logits.copy_(logits)
+        before = logprob_preload(logits)                              # -8.0: the pick must ADD to what the accumulator holds
+        assert bool((before == -8.0).all())
+        st.logprob.copy_(before)
         probs = torch.empty(B, V, dtype=BF, device="cuda")
         eng.sample_pick(cache, st, B, False, ud, temp, nuc, probs)
         p_ref = LR.sampling_probs(logits, temperature=temp, nucleus_prob=nuc)
@@ -680,7 +679,8 @@ def test_sample_step_kernel_vs_oracle(V, mode):
                 near = min(abs(float(cdf[b, tok[b]]) - target), abs(float(cdf[b, t_ref[b]]) - target))
                 assert near < 1e-5 * float(cdf[b, -1]), (s_, b, int(tok[b]), int(t_ref[b]))
             assert p[b, tok[b]] > 0
-        lp_ref += torch.log_softmax(logits, -1)[torch.arange(B), tok].float()
+        # this step's gain of logprob (after - before, exact in fp32: select_oracle.logprob_preload) is the float64 log-softmax of the
+        # unscaled logits at the token, rounded to bf16 ONCE (torch's CPU bf16 log_softmax rounds log(sum) first: see the beam test)
+        assert_rounded_from(st.logprob.cpu() - before, log_softmax64(logits)[torch.arange(B), tok], logprob_slack(logits, tok), f"logprob gain of step {s_}")
         assert torch.equal(st.tokens_out[:, s_].cpu().long(), tok) and int(st.step) == s_ + 1
-    assert torch.allclose(st.logprob.cpu(), lp_ref, atol=0.15)    # CPU bf16 log_softmax rounds log(sum) separately (see the beam test)
     assert int(eng.ctx.lib.pcy_ctx_sync(eng.ctx.h)) == 0
