@@ -45,6 +45,7 @@ int pcy_abi_version(void);
  * 15: launch per stage, MFMA GEMVs; 16: a step served from a shared-prefix cache (pcy_kv_cache.prefix_k), counted in addition to 14 / 15.
  * 17: calls of the fused lm_head x cross-entropy operator (pcy_lm_head_xent, also inside pcy_llama_score / pcy_llama_extend).
  * 18: calls of pcy_llama_extend (S more tokens per row against a filled cache).
+ * 19: calls of pcy_llama_extend_packed (each also counts as kind 18).
  * A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
  * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
@@ -273,6 +274,12 @@ int pcy_llama_score(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const 
  * row's bits do not depend on the other rows of the call. */
 int pcy_attn_extend(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past,
                     const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh);
+/* pcy_attn_extend with another work split: the 64 query slots of a workgroup are packed over the rows of one prompt (rows b with the same
+ * b / rows_per_prefix; a plain cache: one row) and the H / Hkv query heads of one kv head, so that the whole 32-key blocks of the shared prefix
+ * are staged once per 64 packed queries instead of once per (row, head).  Same arguments, same argument errors, and the same bits in `o` and in
+ * the cache as pcy_attn_extend for every input (tests/test_gpu_extend_packed.py). */
+int pcy_attn_extend_packed(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past,
+                           const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh);
 /* S more tokens per row through all layers against a filled cache (HF: forward(inputs_embeds [B,S], past_key_values)).  embeds [B,S,d];
  * t_past = tokens every row already holds; keep as pcy_attn_extend.  K/V of logical slots [t_past, t_past+S) are written.
  * logit_rows / logits_out / hidden_out as pcy_llama_prefill, rows counted b*S + s.  score_rows / targets / nll_out as pcy_llama_score
@@ -285,6 +292,10 @@ int pcy_llama_extend(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const
                      const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
                      const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out);
 size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc*, int B, int S, int n_logit_rows, int n_score);   /* host arithmetic only */
+/* pcy_llama_extend with the attention of pcy_attn_extend_packed in every layer: same arguments, errors, workspace and bits. */
+int pcy_llama_extend_packed(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep, int B, int S,
+                            int t_past, const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
+                            const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out);
 typedef struct {
   int32_t* pos;              /* device scalar: cache length == rotary position of the next token (Q2) */
   int32_t* step;             /* device scalar: index of the next generated token */

@@ -14,7 +14,8 @@ ABI_VERSION = 13
 # pcy_debug_dispatch_count kinds
 (DISPATCH_GEMM_128, DISPATCH_GEMM_64, DISPATCH_GEMM_BIG, DISPATCH_GEMM_BIG_PERSIST, DISPATCH_GEMM_SPLITK, DISPATCH_GEMM_FP8, DISPATCH_ATTN_FAST,
  DISPATCH_DEC_STEP_GQA, DISPATCH_GEMM_MID, DISPATCH_ESM_GRAPH, DISPATCH_DEC_STEP_MHA, DISPATCH_DEC_LAYER, DISPATCH_DEC_STEP_NB, DISPATCH_DEC_STEP_MB,
- DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA, DISPATCH_SHARED_PREFIX, DISPATCH_XENT, DISPATCH_EXTEND) = range(19)
+ DISPATCH_DEC_LOOP_STREAM, DISPATCH_DEC_LOOP_MFMA, DISPATCH_SHARED_PREFIX, DISPATCH_XENT, DISPATCH_EXTEND,
+ DISPATCH_EXTEND_PACKED) = range(20)
 # which way a decode step was served (one count per step enqueued outside a graph replay; pcy_internal.h PCY_DISPATCH_DEC_*)
 DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STEP_MHA, layer=DISPATCH_DEC_LAYER, step_nb=DISPATCH_DEC_STEP_NB,
                        step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
@@ -92,6 +93,7 @@ SIGNATURES = {
     "pcy_attention": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, C.c_float]),
     "pcy_attn_decode": (ci, [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "pcy_attn_extend_packed": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_pool": (ci, [vp, vp, ci, vp, vp, ci, ci, vp]),
     "pcy_retrieval_scores": (ci, [vp, vp, ci, vp, ci, ci, vp]),
     "pcy_comm_unique_id": (ci, [vp]),
@@ -121,6 +123,7 @@ SIGNATURES = {
     "pcy_llama_prefill": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, vp]),
     "pcy_llama_prefill_all": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp]),
     "pcy_llama_extend": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp]),
+    "pcy_llama_extend_packed": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp]),
     "pcy_llama_extend_ws_bytes": (C.c_size_t, [C.POINTER(LlamaDesc), ci, ci, ci, ci]),
     "pcy_llama_decode": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_debug_mc_trace": (ci, [vp, ci]),

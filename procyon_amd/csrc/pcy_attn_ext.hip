@@ -229,6 +229,243 @@ __global__ __launch_bounds__(256) void attn_ext_kernel(PcyExtAttnArgs a) {
   }
 }
 
+// attn_ext_packed_kernel<DH>: the same arithmetic with the 64 query slots of a workgroup PACKED over the rows of one prompt and the G query
+// heads of one kv head.  Workgroup (tile, kv head g, prompt p); packed query index ((r * G + hg) * S + s), r over the rows of prompt p
+// that the call holds (a plain cache: every row is its own prompt, Tp = 0, one row -- GQA packing only); a wave owns 16 packed slots.
+//   shared phase: key blocks [0, 32 * (Tp / 32)) come from the prompt's prefix panel, are staged ONCE per tile and scored for all 64
+//                 packed queries;
+//   own phase:    for every row rho with a query in the tile (a workgroup-uniform loop) the blocks from 32 * (Tp / 32) to t_past + S,
+//                 staged with the logical-slot addressing above (the block that straddles Tp reads both panels).  Lanes whose query
+//                 belongs to another row take no part: no update of (m, l), P = 0 exactly; a wave without a query of rho skips the
+//                 block's arithmetic (wave-uniform) but stages and synchronises with the others.
+// Every row is walked to nk = t_past + S: the keys beyond a query's own position score -2^126 and contribute exactly 0, and a query
+// without any allowed key gets the uniform softmax over all nk keys in the first walk (attn_ext_kernel's second attempt).
+// Bits: a query meets the same 32-key blocks in the same order as in attn_ext_kernel; an MFMA output element depends on its own row
+// and column only; a foreign block adds P = 0 times finite V; blocks beyond attn_ext_kernel's causal range add exp2(-2^126 - m) = 0.
+// So the output equals attn_ext_kernel's bit for bit, and a query's bits depend on its own row of the batch only.
+template <int DH>
+__global__ __launch_bounds__(256) void attn_ext_packed_kernel(PcyExtAttnArgs a) {
+  constexpr int KB = DH / 32, NT = DH / 16;
+  constexpr int KCH = DH / 8;
+  constexpr int NLD = (32 * KCH) / 256;
+  constexpr int KTILE = 32 * DH * 2;
+  constexpr int VSTR = DH * 2 + 32;
+  constexpr int VTILE = 32 * VSTR;
+  __shared__ __attribute__((aligned(16))) char smem[2 * (KTILE + VTILE)];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int g = blockIdx.y, p = blockIdx.z;
+  const int S = a.S, t_past = a.t_past;
+  const int nk = t_past + S;
+  const int G = a.H / a.Hkv, GS = G * S;
+  const int Tp = a.k_pre ? a.Tp : 0;
+  const int rpp = a.k_pre ? a.rows_per_prefix : 1;
+  const int row0 = p * rpp;                    // (< B by the grid)
+  const int rows = (a.B - row0) < rpp ? (a.B - row0) : rpp;   // the last prompt may be short of rows
+  const int total = rows * GS;                 // packed queries of this (prompt, kv head)
+  const int i0 = blockIdx.x * 64;
+  if (i0 >= total) return;                     // workgroup-uniform (the grid is sized for a full prompt)
+  const int iw0 = i0 + wave * 16;
+  const bool active = iw0 < total;             // wave-uniform
+  constexpr float LOG2E = 1.4426950408889634f;
+  constexpr float MASKZ = -0x1p126f;
+  // this lane's query (slots beyond the last packed query repeat it: finite statistics, never stored)
+  int idx = iw0 + fr;
+  idx = idx < total ? idx : total - 1;
+  const int qrow_r = idx / GS;
+  const int qh = (idx - qrow_r * GS) / S, qs = idx - qrow_r * GS - qh * S;
+  const int qb = row0 + qrow_r;
+  const int qpos = t_past + qs;                // logical slot of the query = its last allowed key
+  const uint8_t* keep = a.keep ? a.keep + (size_t)qb * a.ld_keep : nullptr;   // per lane: the query's own row
+  // rows with a query in the tile / in this wave
+  const int last_i = (i0 + 63) < total ? (i0 + 63) : total - 1;
+  const int r_lo = i0 / GS, r_hi = last_i / GS;
+  const int wlast_i = (iw0 + 15) < total ? (iw0 + 15) : total - 1;
+  const int wr_lo = (iw0 < total ? iw0 : total - 1) / GS, wr_hi = wlast_i / GS;
+  const int Tps = Tp & ~31;                    // keys of the shared phase
+
+  const size_t panel = (size_t)a.Town * DH;
+  const bf16_t* k_own0 = a.k_own + ((size_t)row0 * a.Hkv + g) * panel;   // row r of the prompt: + r * Hkv * panel
+  const bf16_t* v_own0 = a.v_own + ((size_t)row0 * a.Hkv + g) * panel;
+  const size_t row_step = (size_t)a.Hkv * panel;
+  const size_t pre_off = a.k_pre ? ((size_t)p * a.Hkv + g) * Tp * DH : 0;
+  const bf16_t* k_pre = a.k_pre ? a.k_pre + pre_off : nullptr;
+  const bf16_t* v_pre = a.k_pre ? a.v_pre + pre_off : nullptr;
+
+  bf16x8 qf[KB];
+  {
+    const bf16_t* qp = a.q + (size_t)(qb * S + qs) * a.ldq + (g * G + qh) * DH + fq * 8;
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) qf[kb] = *reinterpret_cast<const bf16x8*>(qp + kb * 32);
+  }
+  auto kswz = [](int row) __attribute__((always_inline)) { return DH == 64 ? (row & 7) : (row & 15); };
+  struct Regs { uint4 v[NLD]; };
+  // rows of key block kb0 as row `rho` of the prompt sees them (slots beyond the range are clamped to the last key, never skipped)
+  auto fetch = [&](const bf16_t* own0, const bf16_t* pre, int rho, int kb0) __attribute__((always_inline)) {
+    Regs rr;
+    const bf16_t* own = own0 + (size_t)(rho < 0 ? r_lo : rho) * row_step;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int c = tid + i * 256, key = c / KCH, ch = c % KCH;
+      int j = kb0 + key;
+      j = j < nk ? j : nk - 1;
+      const bf16_t* row = j < Tp ? pre + (size_t)j * DH : own + (size_t)(j - Tp) * DH;
+      rr.v[i] = *reinterpret_cast<const uint4*>(row + ch * 8);
+    }
+    return rr;
+  };
+  auto put_k = [&](char* buf, const Regs& rr) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int c = tid + i * 256, key = c / KCH, ch = c % KCH;
+      *reinterpret_cast<uint4*>(buf + (key * KCH + (ch ^ kswz(key))) * 16) = rr.v[i];
+    }
+  };
+  auto put_v = [&](char* buf, const Regs& rr) __attribute__((always_inline)) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int c = tid + i * 256, key = c / KCH, ch = c % KCH;
+      *reinterpret_cast<uint4*>(buf + key * VSTR + ch * 16) = rr.v[i];
+    }
+  };
+  const int krow_a = (fr >> 2) * 8 + (fr & 3);
+  auto kfrag = [&](const char* buf, int tile, int kb) __attribute__((always_inline)) {
+    const int row = krow_a + tile * 4;
+    return *reinterpret_cast<const bf16x8*>(buf + (row * KCH + ((kb * 4 + fq) ^ kswz(row))) * 16);
+  };
+  const int vlane = (fq * 8 + (fr >> 2)) * VSTR + (fr & 3) * 8;
+  auto vfrag = [&](const char* buf, int n) __attribute__((always_inline)) {
+    typedef __attribute__((address_space(3))) ext_s16x4* tr_ptr_t;
+    const char* pp = buf + vlane + n * 32;
+    const ext_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr_t)(pp));
+    const ext_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((tr_ptr_t)(pp + 4 * VSTR));
+    return __builtin_bit_cast(bf16x8, (ext_s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+  };
+  auto scores = [&](const char* kbuf, int kb0, float (&s)[8]) __attribute__((always_inline)) {
+    f32x4 sa = {0.f, 0.f, 0.f, 0.f}, sb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < KB; ++kb) {
+      sa = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag(kbuf, 0, kb), qf[kb], sa, 0, 0, 0);
+      sb = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag(kbuf, 1, kb), qf[kb], sb, 0, 0, 0);
+    }
+    const bool interior = !a.keep && (kb0 + 31 <= t_past);   // every key allowed for every query; workgroup-uniform
+    if (interior) {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        float v = rbf(r < 4 ? sa[r & 3] : sb[r & 3]);
+        v = rbf(v * a.scale);
+        s[r] = v * LOG2E;
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 8; ++r) {
+        const int j = kb0 + fq * 8 + r;
+        float v = rbf(r < 4 ? sa[r & 3] : sb[r & 3]);
+        v = rbf(v * a.scale);
+        bool allowed = j <= qpos;
+        if (keep && j < nk) allowed = allowed && (keep[j] != 0);
+        s[r] = j < nk ? (allowed ? v * LOG2E : MASKZ) : -INFINITY;
+      }
+    }
+  };
+  // the walk: (rho, kb0) = (-1, 0), (-1, 32) .. (-1, Tps - 32), then for rho = r_lo .. r_hi: (rho, Tps), (rho, Tps + 32) .. below nk
+  const int rho_first = Tps > 0 ? -1 : r_lo;
+  struct Step { int rho, kb0; };
+  auto advance = [=](Step c) __attribute__((always_inline)) {
+    const int kb1 = c.kb0 + 32;
+    Step n;
+    if (c.rho < 0) { n.rho = kb1 >= Tps ? r_lo : -1; n.kb0 = kb1; }          // (kb1 == Tps at the change)
+    else if (kb1 >= nk) { n.rho = c.rho + 1; n.kb0 = Tps; }
+    else { n.rho = c.rho; n.kb0 = kb1; }
+    return n;
+  };
+  // wave-uniform: does this wave hold a query that meets the block of row rho
+  auto takes_part = [&](int rho) __attribute__((always_inline)) { return active && (rho < 0 || (rho >= wr_lo && rho <= wr_hi)); };
+
+  char* kb_base = smem;
+  char* vb_base = smem + 2 * KTILE;
+  float m = -INFINITY, l = 0.f;
+  {
+    int rho = rho_first, kb0 = 0;
+    Regs ka = fetch(k_own0, k_pre, rho, kb0);
+    put_k(kb_base, ka);
+    __syncthreads();
+    int cur = 0;
+    while (rho <= r_hi) {
+      const Step nx = advance(Step{rho, kb0});
+      const int nrho = nx.rho, nkb0 = nx.kb0;
+      const bool more = nrho <= r_hi;           // uniform
+      if (more) ka = fetch(k_own0, k_pre, nrho, nkb0);
+      if (takes_part(rho)) {
+        const bool mine = rho < 0 || qrow_r == rho;   // the same for the 4 lanes of a query
+        float s[8];
+        scores(kb_base + cur * KTILE, kb0, s);
+        float bm = s[0];
+#pragma unroll
+        for (int r = 1; r < 8; ++r) bm = fmaxf(bm, s[r]);
+        bm = fmaxf(bm, __shfl_xor(bm, 16, 64));
+        bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+        const float mn = fmaxf(m, bm);         // finite: every block holds a key below nk (so never -inf - -inf below)
+        float bs = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) bs += __builtin_amdgcn_exp2f(s[r] - mn);
+        bs += __shfl_xor(bs, 16, 64);
+        bs += __shfl_xor(bs, 32, 64);
+        const float nl = l * __builtin_amdgcn_exp2f(m - mn) + bs;
+        l = mine ? nl : l;
+        m = mine ? mn : m;
+      }
+      if (more) put_k(kb_base + (cur ^ 1) * KTILE, ka);
+      __syncthreads();
+      rho = nrho; kb0 = nkb0; cur ^= 1;
+    }
+  }
+
+  const float rl = 1.0f / l;
+  f32x4 oacc[NT];
+#pragma unroll
+  for (int n = 0; n < NT; ++n) oacc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  {
+    int rho = rho_first, kb0 = 0;
+    Regs ka = fetch(k_own0, k_pre, rho, kb0), va = fetch(v_own0, v_pre, rho, kb0);
+    __syncthreads();
+    put_k(kb_base, ka); put_v(vb_base, va);
+    __syncthreads();
+    int cur = 0;
+    while (rho <= r_hi) {
+      const Step nx = advance(Step{rho, kb0});
+      const int nrho = nx.rho, nkb0 = nx.kb0;
+      const bool more = nrho <= r_hi;
+      if (more) { ka = fetch(k_own0, k_pre, nrho, nkb0); va = fetch(v_own0, v_pre, nrho, nkb0); }
+      if (takes_part(rho)) {                   // wave-uniform: all 64 lanes take the transposed reads together
+        const bool mine = rho < 0 || qrow_r == rho;
+        float s[8];
+        scores(kb_base + cur * KTILE, kb0, s);
+        bf16x8 pf;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) pf[r] = mine ? (short)f2bf(__builtin_amdgcn_exp2f(s[r] - m) * rl) : (short)0;   // (m is finite)
+        const char* vbuf = vb_base + cur * VTILE;
+#pragma unroll
+        for (int n = 0; n < NT; ++n) oacc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pf, vfrag(vbuf, n), oacc[n], 0, 0, 0);
+      }
+      if (more) { put_k(kb_base + (cur ^ 1) * KTILE, ka); put_v(vb_base + (cur ^ 1) * VTILE, va); }
+      __syncthreads();
+      rho = nrho; kb0 = nkb0; cur ^= 1;
+    }
+  }
+  if (!active) return;
+  // O[packed query iw0 + fq*4 + r][d = n*16 + fr]
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int qi = iw0 + fq * 4 + r;
+    if (qi >= total) continue;
+    const int orow = qi / GS, oh = (qi - orow * GS) / S, os = qi - orow * GS - oh * S;
+    bf16_t* op = a.o + (size_t)((row0 + orow) * S + os) * a.ldo + (g * G + oh) * DH + fr;
+#pragma unroll
+    for (int n = 0; n < NT; ++n) op[n * 16] = f2bf(oacc[n][r]);
+  }
+}
+
 }  // namespace
 
 void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past) {
@@ -241,6 +478,18 @@ bool pcy_launch_attn_extend(hipStream_t s, const PcyExtAttnArgs& a) {
   const dim3 grid((a.S + 63) / 64, a.H, a.B);
   if (a.dh == 64) hipLaunchKernelGGL(attn_ext_kernel<64>, grid, dim3(256), 0, s, a);
   else if (a.dh == 128) hipLaunchKernelGGL(attn_ext_kernel<128>, grid, dim3(256), 0, s, a);
+  else return false;
+  return true;
+}
+
+bool pcy_launch_attn_extend_packed(hipStream_t s, const PcyExtAttnArgs& a) {
+  if (a.B <= 0 || a.S <= 0) return true;
+  const int rpp = a.k_pre ? a.rows_per_prefix : 1;
+  const int rows = a.B < rpp ? a.B : rpp;
+  const long total = (long)rows * (a.H / a.Hkv) * a.S;
+  const dim3 grid((unsigned)((total + 63) / 64), a.Hkv, (a.B + rpp - 1) / rpp);
+  if (a.dh == 64) hipLaunchKernelGGL(attn_ext_packed_kernel<64>, grid, dim3(256), 0, s, a);
+  else if (a.dh == 128) hipLaunchKernelGGL(attn_ext_packed_kernel<128>, grid, dim3(256), 0, s, a);
   else return false;
   return true;
 }

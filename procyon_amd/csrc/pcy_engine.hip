@@ -1263,7 +1263,7 @@ struct ScoreReq { const int32_t* rows; const int32_t* targets; int n; float* nll
 // pcy_llama_extend: the T tokens of every row FOLLOW t_past tokens the cache already holds (nullptr: a prefill from slot 0).  The layer loop
 // is the prefill's; what differs is the rotary position (t_past + s, made on the device), where K / V go (logical slots t_past ..) and the
 // attention (pcy_attn_ext.hip reads the keys from the cache: no transposed V workspace on this path).
-struct ExtendReq { int t_past; };
+struct ExtendReq { int t_past; bool packed; };   // packed: the attention launch is pcy_launch_attn_extend_packed
 // workspace of llama_prefill_impl; vt_elems = elements of the transposed-V copy (0 on the extension path, which also holds its positions)
 size_t llama_prefill_ws_need(const pcy_llama_desc* m, int M, size_t vt_elems, int n_logit_rows, int n_sum_rows, int n_score, bool ext) {
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, qkvw = (H + 2 * Hkv) * dh;
@@ -1341,6 +1341,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
     pcy_launch_ext_pos(s, pos_ext, B, T, t_past);
     pos = pos_ext;
     ++g_pcy_dispatch[PCY_DISPATCH_EXTEND];
+    if (ext->packed) ++g_pcy_dispatch[PCY_DISPATCH_EXTEND_PACKED];
   }
   const bool shared = ext && kv_shared(kv);
   const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;   // first written slot inside the rows' own panels
@@ -1392,7 +1393,8 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
       }
       e.o = ao; e.ldo = H * dh; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = T; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
       e.scale = 1.0f / sqrtf((float)dh);
-      pcy_launch_attn_extend(s, e);
+      if (ext->packed) pcy_launch_attn_extend_packed(s, e);
+      else pcy_launch_attn_extend(s, e);
     } else {
     if (pcy_off("prefill_post_qkv") ||   // (the three launches: the test compares both)
         !pcy_launch_prefill_post_qkv(s, qkv, qkvw, H, Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
@@ -1557,21 +1559,39 @@ int pcy_llama_score(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
                             nullptr, nullptr, &sr);
 }
 
+}  // extern "C"
+namespace {
+int llama_extend_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
+                       const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
+                       const int32_t* targets, int n_score, float* nll_out, bool packed) {
+  const ScoreReq sr{score_rows, targets, n_score, nll_out};
+  const ExtendReq er{t_past, packed};
+  return llama_prefill_impl(c, m, kv, embeds, keep, nullptr, nullptr, nullptr, B, S, logit_rows, n_logit_rows, logits_out, hidden_out, nullptr, 0,
+                            nullptr, nullptr, n_score > 0 ? &sr : nullptr, &er);
+}
+}  // namespace
+extern "C" {
 int pcy_llama_extend(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
                      const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
                      const int32_t* targets, int n_score, float* nll_out) {
-  const ScoreReq sr{score_rows, targets, n_score, nll_out};
-  const ExtendReq er{t_past};
-  return llama_prefill_impl(c, m, kv, embeds, keep, nullptr, nullptr, nullptr, B, S, logit_rows, n_logit_rows, logits_out, hidden_out, nullptr, 0,
-                            nullptr, nullptr, n_score > 0 ? &sr : nullptr, &er);
+  return llama_extend_entry(c, m, kv, embeds, keep, B, S, t_past, logit_rows, n_logit_rows, logits_out, hidden_out, score_rows, targets, n_score,
+                            nll_out, false);
+}
+int pcy_llama_extend_packed(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S,
+                            int t_past, const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
+                            const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
+  return llama_extend_entry(c, m, kv, embeds, keep, B, S, t_past, logit_rows, n_logit_rows, logits_out, hidden_out, score_rows, targets, n_score,
+                            nll_out, true);
 }
 size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_logit_rows, int n_score) {
   if (!m || B < 1 || S < 1) return 0;
   return llama_prefill_ws_need(m, B * S, 0, n_logit_rows > 0 ? n_logit_rows : 0, 0, n_score > 0 ? n_score : 0, true);
 }
 
-int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
-                    const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
+}  // extern "C"
+namespace {
+int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
+                      const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
   PCY_STICKY(c);
   if (dh != 64 && dh != 128) return fail(1, "pcy_attn_extend: head_dim %d unsupported (64/128)", dh);
   if (Hkv < 1 || H % Hkv) return fail(1, "pcy_attn_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
@@ -1607,8 +1627,19 @@ int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int l
   }
   e.o = (bf16_t*)o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
   e.scale = 1.0f / sqrtf((float)dh);
-  pcy_launch_attn_extend(s, e);
+  if (packed) pcy_launch_attn_extend_packed(s, e);
+  else pcy_launch_attn_extend(s, e);
   return check_launch("pcy_attn_extend");
+}
+}  // namespace
+extern "C" {
+int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
+                    const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
+  return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, false);
+}
+int pcy_attn_extend_packed(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
+                           const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
+  return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, true);
 }
 
 int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,

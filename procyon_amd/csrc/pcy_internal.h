@@ -138,7 +138,8 @@ enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BI
        PCY_DISPATCH_SHARED_PREFIX = 16,   // a step served from a shared-prefix cache (in addition to the loop's own count)
        PCY_DISPATCH_XENT = 17,            // one pcy_launch_lm_head_xent call (pcy_xent.hip)
        PCY_DISPATCH_EXTEND = 18,          // one pcy_llama_extend call
-       PCY_DISPATCH_N = 19 };
+       PCY_DISPATCH_EXTEND_PACKED = 19,   // one pcy_llama_extend_packed call (in addition to PCY_DISPATCH_EXTEND)
+       PCY_DISPATCH_N = 20 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
 
 // lm_head x cross-entropy without logits in memory (pcy_xent.hip): nll[m] = logsumexp_n(bf16(x[m] . W[n])) - bf16(x[m] . W[targets[m]]).
@@ -251,6 +252,9 @@ struct PcyExtAttnArgs {
   float scale;
 };
 bool pcy_launch_attn_extend(hipStream_t s, const PcyExtAttnArgs& a);   // false = head_dim not covered (64 / 128), nothing launched
+// the same operator, same bits, with the query slots of a workgroup packed over the rows of a prompt and the query heads of a kv head
+// (attn_ext_packed_kernel): the shared prefix is staged once per 64 packed queries
+bool pcy_launch_attn_extend_packed(hipStream_t s, const PcyExtAttnArgs& a);
 void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past);   // pos[b*S + s] = t_past + s
 struct PcyGemvArgs;
 // decode attention + o projection (EPI_RESID GEMV over the attention output) in one launch; false = shape not covered,

@@ -174,10 +174,11 @@ class Context:
                                          _p(sin_t), _p(keep), B, H, Hkv, dh, Tmax), "pcy_attn_decode")
         return o
 
-    def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None):
+    def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, packed=False):
         """pcy_attn_extend: qkv [B*S, (H+2Hkv)*dh] un-roped projections of S new tokens per row (row b*S+s; B rows, default the cache's);
         `cache` a KVCache (plain or shared-prefix) that holds t_past tokens per row.  Ropes q / k in place at t_past + s, appends K / V at
-        logical slots t_past .. of layer `layer`, -> o [B*S, H*dh].  keep: [B, cache.capacity] uint8 in logical slots or None."""
+        logical slots t_past .. of layer `layer`, -> o [B*S, H*dh].  keep: [B, cache.capacity] uint8 in logical slots or None.
+        packed: pcy_attn_extend_packed -- the queries of a prompt's rows and of a kv head's query heads share workgroups (same bits)."""
         _chk_bf16(qkv)
         B = cache.B if B is None else int(B)
         S = qkv.shape[0] // B
@@ -185,8 +186,9 @@ class Context:
         if keep is not None:
             assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, cache.capacity), (keep.shape, keep.dtype)
         o = torch.empty(B * S, H * dh, dtype=BF16, device=qkv.device)
-        L.check(self.lib.pcy_attn_extend(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), H * dh, int(t_past), _p(cos_t),
-                                         _p(sin_t), _p(keep), B, S, H, Hkv, dh), "pcy_attn_extend")
+        fn = self.lib.pcy_attn_extend_packed if packed else self.lib.pcy_attn_extend
+        L.check(fn(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), H * dh, int(t_past), _p(cos_t), _p(sin_t), _p(keep),
+                   B, S, H, Hkv, dh), "pcy_attn_extend")
         return o
 
     def retrieval_scores(self, query, targets):
@@ -707,12 +709,14 @@ class LlamaEngine:
             token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
         return token_nll, n, (logits if logit_rows is not None else None)
 
-    def extend(self, cache: KVCache, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False):
+    def extend(self, cache: KVCache, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False, packed=False):
         """S more tokens per row against a cache that holds t_past tokens per row (pcy_llama_extend; HF's forward(inputs_embeds [B,S],
         past_key_values)).  embeds [B,S,d] bf16; cache plain or shared-prefix (`new_shared_cache`); keep [B, >= t_past + S] (0 = masked key,
         old and new slots alike) or None; logit_rows "all" / "last" / flat rows b*S+s / None; labels [B,S] in HF's convention (-100 = not
         scored): token_nll[b, s+1] = -log p(token s+1 | everything up to s, the cached prefix included), 0 elsewhere.
-        -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens).  K / V of slots [t_past, t_past+S) are written."""
+        -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens).  K / V of slots [t_past, t_past+S) are written.
+        packed: pcy_llama_extend_packed -- the attention packs the queries of a prompt's rows into shared workgroups (same bits; it pays when
+        many rows per prefix carry few new tokens each)."""
         B, S, d = embeds.shape
         dev = self.device
         embeds = embeds.contiguous()
@@ -745,8 +749,9 @@ class LlamaEngine:
             if n:
                 srows, tg, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev)
                 nll = torch.empty(n, dtype=torch.float32, device=dev)
-        L.check(self.ctx.lib.pcy_llama_extend(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
-                                              _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
+        fn = self.ctx.lib.pcy_llama_extend_packed if packed else self.ctx.lib.pcy_llama_extend
+        L.check(fn(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
+                   _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
         if n:
             token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
         return (logits if logit_rows is not None else None), hidden, token_nll, n

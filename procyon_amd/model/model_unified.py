@@ -149,6 +149,62 @@ def candidate_plan(tokenize, label_rule, instructions, candidates, answer_idx, p
                 n_tokens=n_tokens, cut=torch.tensor(cuts), P=P, N=N, Tp=Tp, S=S)
 
 
+def shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id):
+    """Host side of `UnifiedProCyon.forward(share_prefix=True)`: where a QA batch can be cut into the part every row shares and the part
+    that differs.  Pure: no device, no model.
+      ids / mask [B, T]   the right-padded rows `forward` tokenises (mask 0 on the pads)
+      slot_sources[i]     in row order, what feeds each soft-token slot of row i (a token of `soft_slot_ids`): any comparable value per
+                          slot, e.g. ("seq", inputs["input"]["seq"][i][k]) -- two slots hold the same embedding iff their sources are equal
+    Tp is the largest t such that columns [0, t) are real and identical in every row, the soft slots inside them have equal sources, and
+    t <= min_i(position of the last [ANSWER] of row i): every answer row lies in the suffix, S >= 1.  -> dict:
+      Tp, S, B
+      suffix_ids / suffix_mask [B, S]   tokens [Tp, answer_pos_i] of every row (the answer token included, what follows it is not needed
+                                        for the answer logits), right-padded with pad_id / 0
+      answer_pos [B]                    position of the last [ANSWER] in the full row
+      answer_rows [B] int32             flat row b * S + answer_pos_b - Tp of the [B, S] suffix batch
+    ValueError: a row without [ANSWER], rows that are not right-padded, slot_sources that do not match the slots of a row."""
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    if ids.dim() != 2 or ids.shape != mask.shape or ids.shape[0] == 0:
+        raise ValueError(f"ids {tuple(ids.shape)} / mask {tuple(mask.shape)}: expected two equal [B, T] arrays, B >= 1")
+    B, T = ids.shape
+    if len(slot_sources) != B:
+        raise ValueError(f"{len(slot_sources)} slot source lists for {B} rows")
+    is_slot = torch.zeros_like(mask)
+    for i in soft_slot_ids:
+        is_slot |= ids == int(i)
+    n_real = mask.sum(1)
+    if not bool((mask == (torch.arange(T)[None] < n_real[:, None])).all()):
+        bad = int((mask != (torch.arange(T)[None] < n_real[:, None])).any(1).nonzero()[0])
+        raise ValueError(f"row {bad} is not right-padded")
+    is_ans = (ids == int(answer_idx)) & mask
+    if not bool(is_ans.any(1).all()):
+        raise ValueError(f"row {int((~is_ans.any(1)).nonzero()[0])}: no [ANSWER] token")
+    answer_pos = (T - 1 - is_ans.flip(1).int().argmax(1)).tolist()          # the LAST [ANSWER] among the real tokens
+    n_slots = (is_slot & mask).sum(1).tolist()
+    for r in range(B):
+        if n_slots[r] != len(slot_sources[r]):
+            raise ValueError(f"row {r}: {n_slots[r]} soft-token slots, {len(slot_sources[r])} sources")
+    # columns in front of the first one that differs between the rows (or is a pad somewhere), at most the earliest answer position ...
+    same = ((ids == ids[0:1]) & mask).all(0)
+    Tp = min(min(answer_pos), T if bool(same.all()) else int((~same).int().argmax()))
+    # ... and in front of the first soft slot whose sources differ (the columns up to there are identical: slot k sits at the same column)
+    cols = is_slot[0, :Tp].nonzero()[:, 0].tolist()
+    for k, c in enumerate(cols):
+        if any(slot_sources[r][k] != slot_sources[0][k] for r in range(1, B)):
+            Tp = c
+            break
+    S = max(answer_pos) - Tp + 1
+    suffix_ids = torch.full((B, S), int(pad_id), dtype=torch.long)
+    suffix_mask = torch.zeros(B, S, dtype=torch.long)
+    for r in range(B):
+        n = answer_pos[r] - Tp + 1
+        suffix_ids[r, :n] = ids[r, Tp:answer_pos[r] + 1]
+        suffix_mask[r, :n] = 1
+    ap = torch.tensor(answer_pos, dtype=torch.long)
+    return dict(Tp=Tp, S=S, B=B, suffix_ids=suffix_ids, suffix_mask=suffix_mask, answer_pos=ap,
+                answer_rows=(torch.arange(B) * S + ap - Tp).to(torch.int32))
+
+
 def special_token_ids(tokenizer, text_encoder_fname):
     """The token ids `UnifiedProCyon.__init__` / `_init_tokenizer` keep (model_unified.py:1100-1133, 342-347), read from a
     tokenizer on which the eight ProCyon tokens are already registered (`procyon_amd.checkpoint.hf_tokenizer` does that in the
@@ -499,7 +555,8 @@ class UnifiedProCyon:
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, inputs, return_mlm=False, retrieval=False, get_full_labels=False, aaseq_type='protein',
-                exclude_protein_structure=False, crop_off=False, output_attentions=False, full_logits=False, compute_loss=False):
+                exclude_protein_structure=False, crop_off=False, output_attentions=False, full_logits=False, compute_loss=False,
+                share_prefix=False, packed=True):
         """`forward` (model_unified.py:483-581), inference branches.  QA: `outputs.logits` reads like the reference's [B, T, V] tensor
         (:548-554) -- index it at the answer positions (`logits[torch.arange(B), pos]`, data/inference_utils.py:582-604) and the rows that
         were computed come back; any other access materialises every position once (_LazyLogits).  `outputs.answer_logits` [B, 1, V] and
@@ -508,10 +565,29 @@ class UnifiedProCyon:
         every row to max_text_len and materialises [B, 2048, V]; the trailing all-pad columns are not computed here).
         `outputs.loss` (non-retrieval, bf16): the reference's causal-LM loss over `full_labels` (trainIT.py reads it for the validation loss and
         perplexity), with `outputs.token_nll` / `outputs.n_tokens` -- computed on first access, or in this pass with compute_loss=True
-        (LlamaPostTokenization.forward); None for retrieval and on the fp32 path."""
+        (LlamaPostTokenization.forward); None for retrieval and on the fp32 path.
+        share_prefix=True (QA, bf16; not in the reference's signature): the columns every row of the batch shares -- in-context examples, the
+        receptor -- are prefilled ONCE and the rows' differing ends run as one `LlamaEngine.extend` call on a cache whose rows share that
+        prefix (`shared_prefix_plan`; `packed`: with the packed extension attention, read only here).  Same dictionary, plus
+        out["prefix_plan"]; the answer logits differ from the ordinary path's by kernel rounding only; `outputs.logits` / `.loss` /
+        `.hidden_states` beyond the answer rows come from the ordinary full pass on first access.  A batch that shares nothing (Tp = 0) takes
+        the ordinary path.  Not with retrieval, compute_loss or full_logits (ValueError); not on the fp32 family, with structure tokens
+        (dropped at random per call) or with fp8 weights (NotImplementedError)."""
         if return_mlm:
             raise NotImplementedError("return_mlm is a training path (model_unified.py:505-509)")
         self._require_bf16_or_fp32("forward")
+        if share_prefix:
+            if retrieval:
+                raise ValueError("forward(share_prefix=True): retrieval batches read the [PROT] rows of every prompt; there is no shared-prefix path for them")
+            if compute_loss or full_logits:
+                raise ValueError("forward(share_prefix=True) computes the answer rows only: compute_loss / full_logits need the ordinary pass")
+            if self._f32:
+                raise NotImplementedError("forward(share_prefix=True) needs the bf16 engine (the fp32 family has no cache extension)")
+            if self.config.use_protein_struct and inputs["input"]["seq"]:
+                raise NotImplementedError("forward(share_prefix=True): structure tokens are dropped at random per call (struct_dropout_prob), so rows "
+                                          "that read alike need not share a prefix")
+            if bool(self.text_encoder.engine.desc.layers_fp8):
+                raise NotImplementedError("forward(share_prefix=True): the cache extension has no fp8 projections (set_fp8(False) first)")
         input_embeds, input_ids, attn_masks, ret_idx, tok_emb, ret_emb = self._preprocessing(
             inputs, aaseq_type=aaseq_type, crop_off=crop_off, retrieval=retrieval, exclude_protein_structure=False)
         full_labels = None
@@ -526,6 +602,10 @@ class UnifiedProCyon:
             answer_pos = torch.tensor([int((input_ids[i] == self.answer_idx).nonzero()[:, 0].max()) for i in range(B)])
         if retrieval and self.config.ret_token_access not in ('last', 'all'):
             raise NotImplementedError("Invalid option {} for ret_token_access".format(self.config.ret_token_access))
+        if share_prefix:
+            out = self._forward_shared_prefix(inputs, emb, input_ids, attn_masks[:, :real], full_labels, answer_pos, real, get_full_labels, packed)
+            if out is not None:
+                return out
         sum_all = retrieval and self.config.ret_token_access == 'all'
         ret_rows = ret_idx[:, :real].reshape(-1).nonzero()[:, 0] if sum_all else None   # flat b*T + t, row-major like boolean indexing
         # (labels cropped to the columns that are run: the reference's trailing pad columns are all -100)
@@ -563,6 +643,50 @@ class UnifiedProCyon:
             out['contrastive_out'] = c
         return out
 
+    def _slot_sources(self, inputs, input_ids):
+        """per row, in row order, what feeds each soft-token slot (`shared_prefix_plan`): ("seq" | "drug", index into inputs["data"])"""
+        seq, drug = inputs["input"].get("seq"), inputs["input"].get("drug")
+        out = [[] for _ in range(input_ids.shape[0])]
+        # (row, column, kind) of every slot, row-major: the slots of a row in row order
+        slots = sorted([(i, t, 0) for i, t in (input_ids == self.prot_replacement_idx).nonzero().tolist()] +
+                       [(i, t, 1) for i, t in (input_ids == self.drug_idx).nonzero().tolist()])
+        k = [[0, 0] for _ in out]
+        for i, _, kind in slots:
+            out[i].append(("drug" if kind else "seq", int((drug if kind else seq)[i][k[i][kind]])))
+            k[i][kind] += 1
+        return out
+
+    def _forward_shared_prefix(self, inputs, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels, packed):
+        """the share_prefix=True branch of `forward` behind `_preprocessing` (emb [B, real, d], am [B, real]); None = nothing is shared"""
+        from .pmc_llama import CausalLMOutput, _HiddenStates
+        plan = shared_prefix_plan(input_ids[:, :real], am, self._slot_sources(inputs, input_ids[:, :real]), self.answer_idx,
+                                  (self.prot_replacement_idx, self.drug_idx), self.tokenizer.pad_token_id)
+        Tp, S, B = plan["Tp"], plan["S"], plan["B"]
+        if Tp == 0:
+            return None
+        enc = self.text_encoder
+        eng = enc.engine
+        prefix_cache = eng.new_cache(1, Tp)
+        eng.prefill(emb[0:1, :Tp].contiguous(), None, prefix_cache, logit_rows=None)
+        cache = eng.new_shared_cache(prefix_cache, B, S)
+        # (columns behind a row's [ANSWER] inside [Tp, Tp + S): masked as keys, and no answer row attends them anyway)
+        # suffixes of one length (the screening batches): no mask at all, the kernel takes its unmasked block path
+        keep = None if bool(plan["suffix_mask"].all()) else torch.cat([torch.ones(B, Tp, dtype=torch.long), plan["suffix_mask"]], 1)
+        logits, _, _, _ = eng.extend(cache, emb[:, Tp:Tp + S].contiguous(), Tp, keep=keep, logit_rows=plan["answer_rows"], packed=bool(packed))
+        L1, labels = eng.cfg.n_layers + 1, full_labels[:, :real]
+
+        def materialise():
+            _, hall = eng.prefill_all(emb, am, eng.new_cache(B, real), None)
+            return [hall[i] for i in range(L1)]
+
+        outputs = CausalLMOutput(logits.view(B, 1, -1), None, _HiddenStates(L1, None, materialise), None,
+                                 scorer=lambda: eng.score(emb, am, labels)[:2])
+        outputs.answer_logits = outputs.logits
+        outputs.logits = _LazyLogits(outputs.answer_logits[:, 0], answer_pos, real,
+                                     lambda: enc(input_embeds=emb, attn_masks=am, logit_positions=None, want_hidden=False, lazy_hidden=True).logits)
+        return {'outputs': outputs, 'text_toks': input_ids, 'full_labels': full_labels if get_full_labels else None,
+                'contrastive_out': None, 'contrastive_loss': None, 'answer_positions': answer_pos, 'prefix_plan': plan}
+
     @torch.no_grad()
     def score_text(self, inputs, aaseq_type='protein', crop_off=True):
         """Teacher-forced likelihood of the text behind [ANSWER] in every row of a QA / caption batch (the reference: `forward` +
@@ -579,14 +703,15 @@ class UnifiedProCyon:
         return {"token_nll": tn, "seq_nll": tn.sum(1), "n_tokens": n_tok, "loss": loss, "perplexity": torch.exp(loss)}
 
     @torch.no_grad()
-    def score_candidates(self, inputs, candidates, aaseq_type='protein'):
+    def score_candidates(self, inputs, candidates, aaseq_type='protein', packed=False):
         """Rank N candidate texts per prompt by teacher-forced likelihood WITHOUT running the prompt N times.  `inputs`: a caption / QA batch as
         `generate` takes it, every instruction ending in [ANSWER]; `candidates`: one list of N strings per prompt (the same N for all,
         ValueError otherwise).  Row (p, n) is scored as `score_text` scores `instructions[p] + " " + candidates[p][n]` -- same tokens, same
         labels -- but the prompts are encoded and prefilled ONCE (P rows, left-padded as `generate` pads them) and the P*N suffixes
         [ANSWER] + candidate + eos run as one `LlamaEngine.extend` call on a cache whose rows share the prompts' K / V (`candidate_plan`).
         -> {"token_nll" [P,N,S] fp32 over the suffix tokens (0 where nothing is labelled), "seq_nll" [P,N], "n_tokens" [P,N], "mean_nll" [P,N] =
-        seq_nll / n_tokens, "order" [P,N] = stable argsort of mean_nll, best first, "plan" = the `candidate_plan`, "cache" = the shared cache}."""
+        seq_nll / n_tokens, "order" [P,N] = stable argsort of mean_nll, best first, "plan" = the `candidate_plan`, "cache" = the shared cache}.
+        packed: the extension runs the packed attention (`LlamaEngine.extend(packed=True)`): same bits."""
         self._require_bf16_or_fp32("score_candidates")
         if self._f32:
             raise NotImplementedError("score_candidates needs the bf16 engine (the fp32 family has no cache extension)")
@@ -608,7 +733,8 @@ class UnifiedProCyon:
         eng.prefill(prefix_emb, plan["prefix_mask"], prefix_cache, logit_rows=None)
         cache = eng.new_shared_cache(prefix_cache, N, S)
         keep = torch.cat([plan["prefix_mask"].repeat_interleave(N, 0), plan["suffix_mask"]], 1)
-        _, _, token_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), Tp, keep=keep, labels=plan["suffix_labels"])
+        _, _, token_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), Tp, keep=keep, labels=plan["suffix_labels"],
+                                        packed=bool(packed))
         token_nll = token_nll.view(P, N, S)
         seq_nll = token_nll.sum(2)
         n_tokens = plan["n_tokens"].to(seq_nll.device)
