@@ -151,10 +151,10 @@ struct pcy_ctx {
 namespace {
 
 struct Carver {
-  char* p; size_t off = 0;
+  char* p; size_t off = 0;   // base == nullptr: a sizing run, `off` is all that counts
   explicit Carver(char* base) : p(base) {}
   template <typename T> T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(p + off);
+    T* r = p ? reinterpret_cast<T*>(p + off) : nullptr;
     off = align_up(off + n * sizeof(T), 256);
     return r;
   }
@@ -419,13 +419,19 @@ DecodePlan plan_decode(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_c
   p.tag_word = try_layer ? c->ao_sync + 1 : nb_step ? c->nb_sync + B : nullptr;
   return p;
 }
-// A cache with a shared prefix must be well formed and must take the batched loop: anything else is the caller's error, not a fallback.
-int check_decode_cache(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw, const char* what) {
+// A cache with a shared prefix must be well formed and hold a prefix row for each of the call's B rows (decode and extension entries alike)
+int check_shared_cache(const pcy_kv_cache* kv, int B, const char* what) {
   if (!kv_shared(kv)) return 0;
   if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
     return fail(1, "%s: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0", what);
   if (B < 1 || (B - 1) / kv->rows_per_prefix >= kv->prefix_B)
     return fail(1, "%s: %d rows of %d per prefix need more than the %d prefix rows of the cache", what, B, kv->rows_per_prefix, kv->prefix_B);
+  return 0;
+}
+// ... and must take the batched loop: anything else is the caller's error, not a fallback.
+int check_decode_cache(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw, const char* what) {
+  if (!kv_shared(kv)) return 0;
+  if (int r = check_shared_cache(kv, B, what)) return r;
   if (plan_decode(c, m, kv, B, sw).path == DEC_LOOP_MFMA) return 0;
   if (B < pcy_mfma_min_batch())
     return fail(1, "%s: a shared-prefix cache is served by the batched decode loop only (>= %d rows), not %d row%s", what, pcy_mfma_min_batch(), B, B == 1 ? "" : "s");
@@ -1258,226 +1264,268 @@ static int esm_encode_enqueue(pcy_ctx* c, const pcy_esm_desc* m, const int32_t* 
 
 }  // extern "C"
 namespace {
-// pcy_llama_score: token rows to score behind the prefill (nullptr: a plain prefill)
+// The prefill family -- pcy_llama_prefill / _prefill_all / _score / _extend / _extend_packed -- is ONE request (PrefillReq) to ONE layer loop
+// (llama_prefill_impl); every entry point fills the fields it has.  ScoreReq: token rows to score behind the layers (n == 0: none)
 struct ScoreReq { const int32_t* rows; const int32_t* targets; int n; float* nll; };
-// pcy_llama_extend: the T tokens of every row FOLLOW t_past tokens the cache already holds (nullptr: a prefill from slot 0).  The layer loop
+// pcy_llama_extend: the T tokens of every row FOLLOW t_past tokens the cache already holds (on == false: a prefill from slot 0).  The layer loop
 // is the prefill's; what differs is the rotary position (t_past + s, made on the device), where K / V go (logical slots t_past ..) and the
 // attention (pcy_attn_ext.hip reads the keys from the cache: no transposed V workspace on this path).
-struct ExtendReq { int t_past; bool packed; };   // packed: the attention launch is pcy_launch_attn_extend_packed
-// workspace of llama_prefill_impl; vt_elems = elements of the transposed-V copy (0 on the extension path, which also holds its positions)
-size_t llama_prefill_ws_need(const pcy_llama_desc* m, int M, size_t vt_elems, int n_logit_rows, int n_sum_rows, int n_score, bool ext) {
-  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, qkvw = (H + 2 * Hkv) * dh;
-  const size_t score_need = n_score > 0 ? align_up((size_t)n_score * d * 2, 256) + align_up(pcy_xent_ws_bytes(n_score, m->vocab), 256) : 0;
-  return score_need + align_up((size_t)M * d * 2, 256) * 2 + align_up((size_t)M * qkvw * 2, 256) + align_up((size_t)M * H * dh * 2, 256) +
-         align_up((size_t)M * F * 2, 256) + align_up(vt_elems * 2, 256) +
-         align_up((size_t)(n_logit_rows + 1) * d * 2, 256) + align_up((size_t)(n_sum_rows + 1) * d * 6, 256) +
-         (M <= 1024 ? align_up((size_t)8 * M * qkvw * 4, 256) : 0) + 4096 +
-         (m->layers_fp8 ? align_up((size_t)M * (F > H * dh ? F : H * dh), 256) + align_up((size_t)M * 4, 256) : 0) +
-         (ext ? align_up((size_t)M * 4, 256) : 0);
+struct ExtendReq { bool on; int t_past; bool packed; };   // packed: the attention launch is pcy_launch_attn_extend_packed
+struct PrefillReq {
+  const void* embeds; const uint8_t* keep; int B, T;
+  const int32_t *pos, *cu, *vt_cu;                                    // a prefill's (an extension makes its positions itself)
+  const int32_t* logit_rows; int n_logit_rows; void* logits_out;
+  const int32_t* sum_rows; int n_sum_rows; void* hidden_sum_out;      // ret_token_access='all'
+  void *hidden_out, *hidden_all_out;                                  // final-normed [M][d]; [L+1][M][d] (pcy_llama_prefill_all)
+  ScoreReq score; ExtendReq ext;
+};
+// The carve of the prefill workspace, in ONE place; bytes = its end + slack, what a call reserves (sized by a carve of a null base).  vt_elems: the transposed V
+struct PrefillWs {
+  bf16_t *x, *xn, *qkv, *ao, *act, *vt, *lastx;
+  float* sk_ws; size_t sk_bytes;      // split-K partials for the projections that under-fill the chip
+  float* hsum; bf16_t* hsum_tmp;      // ret_token_access='all': fp32 sum of the L+1 hidden states
+  unsigned char* a8; float* sa8;      // fp8 weight path: per-token e4m3 codes and scales of a projection's input
+  bf16_t* score_x; char* score_ws; int32_t* pos_ext; size_t bytes;   // (pos_ext: rotary positions t_past + s of an extension's tokens)
+};
+PrefillWs carve_prefill_ws(char* base, const pcy_llama_desc* m, int M, size_t vt_elems, int n_logit_rows, int n_sum_rows, int n_score, bool fp8, bool ext) {
+  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn, qkvw = (H + 2 * m->n_kv_heads) * dh;
+  Carver cv(base);
+  PrefillWs w{};
+  w.x = cv.take<bf16_t>((size_t)M * d); w.xn = cv.take<bf16_t>((size_t)M * d);
+  w.qkv = cv.take<bf16_t>((size_t)M * qkvw);
+  w.ao = cv.take<bf16_t>((size_t)M * H * dh);
+  w.act = cv.take<bf16_t>((size_t)M * F);
+  w.vt = cv.take<bf16_t>(vt_elems);
+  w.lastx = cv.take<bf16_t>((size_t)(n_logit_rows + 1) * d);
+  w.sk_bytes = M <= 1024 ? (size_t)8 * M * qkvw * 4 : 0;
+  w.sk_ws = w.sk_bytes ? cv.take<float>(w.sk_bytes / 4) : nullptr;
+  w.hsum = cv.take<float>((size_t)(n_sum_rows + 1) * d);
+  w.hsum_tmp = cv.take<bf16_t>((size_t)(n_sum_rows + 1) * d);
+  if (fp8) { w.a8 = cv.take<unsigned char>((size_t)M * (F > H * dh ? F : H * dh)); w.sa8 = cv.take<float>((size_t)M); }
+  if (n_score > 0) { w.score_x = cv.take<bf16_t>((size_t)n_score * d); w.score_ws = cv.take<char>(pcy_xent_ws_bytes(n_score, m->vocab)); }
+  if (ext) w.pos_ext = cv.take<int32_t>((size_t)M);
+  w.bytes = cv.off + 4096;
+  return w;
 }
-int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
-                       const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
-                       int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* sum_rows, int n_sum_rows,
-                       void* hidden_sum_out, void* hidden_all_out, const ScoreReq* score = nullptr, const ExtendReq* ext = nullptr) {
-  PCY_STICKY(c);
-  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+// An extension of S tokens behind t_past: the rows exist, a shared prefix is well formed and is never written, the new slots fit
+int check_extend_span(const pcy_kv_cache* kv, int B, int S, int t_past, const char* what) {
+  if (B > kv->B) return fail(1, "%s: B=%d exceeds cache rows %d", what, B, kv->B);
+  if (int r = check_shared_cache(kv, B, what)) return r;
+  if (kv_shared(kv) && t_past < kv->prefix_T)
+    return fail(1, "%s: t_past=%d lies inside the shared prefix of %d slots, which is never written", what, t_past, kv->prefix_T);
+  if ((long)t_past + S > kv_cap(kv)) return fail(1, "%s: t_past=%d + S=%d exceed the cache capacity %d", what, t_past, S, kv_cap(kv));
+  return 0;
+}
+int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r) {
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
   if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "pcy_llama_prefill: d, ffn, H*dh, Hkv*dh must be multiples of 64");
-  if (F % 16) return fail(1, "pcy_llama_prefill: ffn %% 16");
-  const int t_past = ext ? ext->t_past : 0;
-  if (ext) {
+  if (r.ext.on) {
+    const int t_past = r.ext.t_past;
     if (dh != 64 && dh != 128) return fail(1, "pcy_llama_extend: head_dim %d unsupported (64/128)", dh);
     if (H % Hkv) return fail(1, "pcy_llama_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
     if (m->layers_fp8) return fail(1, "pcy_llama_extend: fp8 projections are not supported on the extension path");
     if (B < 1 || T < 1 || t_past < 0) return fail(1, "pcy_llama_extend: B=%d S=%d t_past=%d", B, T, t_past);
     if (!kv->k || !kv->v) return fail(1, "pcy_llama_extend: cache without k / v");
-    if (B > kv->B) return fail(1, "pcy_llama_extend: B=%d exceeds cache rows %d", B, kv->B);
-    if (kv_shared(kv)) {
-      if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
-        return fail(1, "pcy_llama_extend: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0");
-      if (t_past < kv->prefix_T) return fail(1, "pcy_llama_extend: t_past=%d lies inside the shared prefix of %d slots, which is never written", t_past, kv->prefix_T);
-      if ((B - 1) / kv->rows_per_prefix >= kv->prefix_B)
-        return fail(1, "pcy_llama_extend: %d rows of %d per prefix need more than the %d prefix rows of the cache", B, kv->rows_per_prefix, kv->prefix_B);
-    }
-    if ((long)t_past + T > kv_cap(kv)) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed the cache capacity %d", t_past, T, kv_cap(kv));
+    if (int e = check_extend_span(kv, B, T, t_past, "pcy_llama_extend")) return e;
     if ((long)t_past + T > m->max_pos) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed rope table %d", t_past, T, m->max_pos);
   } else {
-  if (kv_shared(kv)) return fail(1, "pcy_llama_prefill: a cache with a shared prefix cannot be prefilled (prefill the prefix cache itself)");
-  if (B > kv->B || T > kv->Tmax) return fail(1, "pcy_llama_prefill: B=%d T=%d exceed cache (%d,%d)", B, T, kv->B, kv->Tmax);
-  if (T > m->max_pos) return fail(1, "pcy_llama_prefill: T=%d exceeds rope table %d", T, m->max_pos);
+    if (kv_shared(kv)) return fail(1, "pcy_llama_prefill: a cache with a shared prefix cannot be prefilled (prefill the prefix cache itself)");
+    if (B > kv->B || T > kv->Tmax) return fail(1, "pcy_llama_prefill: B=%d T=%d exceed cache (%d,%d)", B, T, kv->B, kv->Tmax);
+    if (T > m->max_pos) return fail(1, "pcy_llama_prefill: T=%d exceeds rope table %d", T, m->max_pos);
   }
-  const int M = B * T, qkvw = (H + 2 * Hkv) * dh, Tp = (T + 31) / 32 * 32;
-  // Row stride of the transposed V ([Hkv*dh][vt_total]): a power-of-two stride (one 512-token prompt: 1 KB) sends the 128 rows of a
-  // key block's V tile to the same few L2 channels; pad it to an odd multiple of 64 bytes
-  int vt_total = B * Tp;
-  if ((vt_total / 32) % 2 == 0) vt_total += 32;
-  if (ext) vt_total = 0;   // (the extension attention reads V from the cache)
-  const int n_score = score ? score->n : 0;
-  if (n_score < 0 || (n_score > 0 && (!score->rows || !score->targets || !score->nll))) return fail(1, "pcy_llama_score: score_rows / targets / nll_out missing");
-  const size_t need = llama_prefill_ws_need(m, M, (size_t)Hkv * dh * vt_total, n_logit_rows, n_sum_rows, n_score, ext != nullptr);
-  if (n_sum_rows > 0 && (!sum_rows || !hidden_sum_out)) return fail(1, "pcy_llama_prefill: sum_rows / hidden_sum_out missing");
+  if (r.score.n < 0 || (r.score.n > 0 && (!r.score.rows || !r.score.targets || !r.score.nll))) return fail(1, "pcy_llama_score: score_rows / targets / nll_out missing");
+  if (r.n_sum_rows > 0 && (!r.sum_rows || !r.hidden_sum_out)) return fail(1, "pcy_llama_prefill: sum_rows / hidden_sum_out missing");
   if (m->layers_fp8 && (d % 128 || F % 128 || (H * dh) % 128)) return fail(1, "pcy_llama_prefill: the fp8 path needs d, ffn, H*dh %% 128 == 0");
-  if (int r = c->reserve(need)) return r;
-  Carver cv(c->ws);
-  bf16_t* x = cv.take<bf16_t>((size_t)M * d);
-  bf16_t* xn = cv.take<bf16_t>((size_t)M * d);
-  bf16_t* qkv = cv.take<bf16_t>((size_t)M * qkvw);
-  bf16_t* ao = cv.take<bf16_t>((size_t)M * H * dh);
-  bf16_t* act = cv.take<bf16_t>((size_t)M * F);
-  bf16_t* vt = cv.take<bf16_t>((size_t)Hkv * dh * vt_total);
-  bf16_t* lastx = cv.take<bf16_t>((size_t)(n_logit_rows + 1) * d);
-  const size_t sk_bytes = M <= 1024 ? (size_t)8 * M * qkvw * 4 : 0;   // split-K partials for the projections that under-fill the chip
-  float* sk_ws = sk_bytes ? cv.take<float>(sk_bytes / 4) : nullptr;
-  float* hsum = cv.take<float>((size_t)(n_sum_rows + 1) * d);      // ret_token_access='all': fp32 sum of the L+1 hidden states
-  bf16_t* hsum_tmp = cv.take<bf16_t>((size_t)(n_sum_rows + 1) * d);
-  hipStream_t s = c->stream;
-  // fp8 weight path: every projection = per-token e4m3 quantisation of its bf16 input + the fp8 MFMA GEMM
-  unsigned char* a8 = m->layers_fp8 ? cv.take<unsigned char>((size_t)M * (F > H * dh ? F : H * dh)) : nullptr;
-  float* sa8 = m->layers_fp8 ? cv.take<float>((size_t)M) : nullptr;
-  bf16_t* score_x = n_score > 0 ? cv.take<bf16_t>((size_t)n_score * d) : nullptr;
-  char* score_ws = n_score > 0 ? cv.take<char>(pcy_xent_ws_bytes(n_score, m->vocab)) : nullptr;
-  if (ext) {   // rotary positions t_past + s of the new tokens (every row: quirk Q2)
-    int32_t* pos_ext = cv.take<int32_t>((size_t)M);
-    pcy_launch_ext_pos(s, pos_ext, B, T, t_past);
-    pos = pos_ext;
-    ++g_pcy_dispatch[PCY_DISPATCH_EXTEND];
-    if (ext->packed) ++g_pcy_dispatch[PCY_DISPATCH_EXTEND_PACKED];
-  }
-  const bool shared = ext && kv_shared(kv);
+  return 0;
+}
+// The extension attention stage of a layer (pcy_attn_extend, pcy_llama_extend): rope (q, k) in place at `pos`, K / V of token s to slot own_slot0 + s of
+// the row's own panel (the panel pointer carries the offset, the row stride stays Tmax * dh), then the S queries of every row against the cache
+void enqueue_extend_attention(hipStream_t s, bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, int t_past, const int32_t* pos,
+                              const bf16_t* cos_t, const bf16_t* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
+  const bool shared = kv_shared(kv);
   const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;   // first written slot inside the rows' own panels
-  const size_t prefix_layer_stride = shared ? (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh : 0;
-  // ln != nullptr: A is the raw hidden state, RMSNorm(A) * ln is what gets quantised (one fused pass; PCY_DISABLE=fp8_fused_norm = two launches)
-  auto linear8 = [&](const bf16_t* A, int K, const void* W8, const float* sw, const bf16_t* resid, bf16_t* Cout, int ldc, int N, int epi,
-                     const bf16_t* ln = nullptr) {
-    if (ln && !pcy_off("fp8_fused_norm") && pcy_launch_rmsnorm_quant_fp8(s, A, ln, M, K, m->rms_eps, m->rms_cast, a8, sa8)) {
-    } else {
-      if (ln) { pcy_launch_rmsnorm(s, A, ln, xn, M, K, m->rms_eps, m->rms_cast); A = xn; }
-      pcy_launch_quant_rows_fp8(s, A, K, M, K, a8, sa8);
-    }
-    PcyGemmArgs g{};
-    g.A = (const bf16_t*)a8; g.W = (const bf16_t*)W8; g.C = Cout; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = ldc;
-    g.ldr = ldc; g.epi = epi; g.fp8 = 1; g.sa = sa8; g.sw = sw;
-    pcy_launch_gemm(s, g);
-  };
-  HIP_TRY(hipMemcpyAsync(x, embeds, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
-  // hidden_all_out [L+1][M][d]: HF's `hidden_states` tuple -- the embeddings, the output of layers 0..L-2, and the FINAL-NORMED
-  // output of layer L-1 (pmc_llama.py:575,584 always asks for it; only materialised here when the caller does)
-  bf16_t* hall = (bf16_t*)hidden_all_out;
-  if (hall) HIP_TRY(hipMemcpyAsync(hall, embeds, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
-  // hidden_states = (embeddings, output of layers 0..L-2, final-normed output of layer L-1)  [HF LlamaModel.forward]
-  pcy_launch_acc_rows(s, x, d, sum_rows, hsum, n_sum_rows, d, 1);
   const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
-  int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
-  for (int l = 0; l < m->n_layers; ++l) {
-    const pcy_llama_layer& L = m->layers[l];
-    const pcy_llama_layer_fp8* L8 = m->layers_fp8 ? &m->layers_fp8[l] : nullptr;
-    if (L8) {
-      linear8(x, d, L8->wqkv, L8->sqkv, nullptr, qkv, qkvw, qkvw, EPI_STORE, (const bf16_t*)L.ln1);
-    } else {
-      if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln1, xn, M, d, m->rms_eps, m->rms_cast);
-      xn_ready = 0;
-      linear(s, xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, qkv, qkvw, M, qkvw, d, EPI_STORE, sk_ws, sk_bytes);
-    }
-    if (ext) {
-      // rope (q, k) in place, K / V of token s to slot own_slot0 + s of the row's panel (the panel pointer carries the offset, the row
-      // stride stays Tmax * dh), then the S queries of every row against the cache
-      bf16_t* kl = (bf16_t*)kv->k + l * layer_stride;
-      bf16_t* vl = (bf16_t*)kv->v + l * layer_stride;
-      pcy_launch_rope(s, qkv, qkvw, 0, H + Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, M, 0, 0.f);
-      pcy_launch_kv_scatter(s, qkv, qkvw, H * dh, (H + Hkv) * dh, Hkv, dh, kl + (size_t)own_slot0 * dh, vl + (size_t)own_slot0 * dh, B, T, kv->Tmax);
-      PcyExtAttnArgs e{};
-      e.q = qkv; e.ldq = qkvw; e.k_own = kl; e.v_own = vl; e.Town = kv->Tmax;
-      if (shared) {
-        e.k_pre = (const bf16_t*)kv->prefix_k + l * prefix_layer_stride; e.v_pre = (const bf16_t*)kv->prefix_v + l * prefix_layer_stride;
-        e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
-      }
-      e.o = ao; e.ldo = H * dh; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = T; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
-      e.scale = 1.0f / sqrtf((float)dh);
-      if (ext->packed) pcy_launch_attn_extend_packed(s, e);
-      else pcy_launch_attn_extend(s, e);
-    } else {
-    if (pcy_off("prefill_post_qkv") ||   // (the three launches: the test compares both)
-        !pcy_launch_prefill_post_qkv(s, qkv, qkvw, H, Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
-                                     (bf16_t*)kv->k + l * layer_stride, (bf16_t*)kv->v + l * layer_stride, B, T, kv->Tmax, cu, vt_cu, vt, vt_total)) {
-      pcy_launch_rope(s, qkv, qkvw, 0, H + Hkv, dh, pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, M, 0, 0.f);
-      pcy_launch_kv_scatter(s, qkv, qkvw, H * dh, (H + Hkv) * dh, Hkv, dh, (bf16_t*)kv->k + l * layer_stride,
-                            (bf16_t*)kv->v + l * layer_stride, B, T, kv->Tmax);
-      pcy_launch_transpose_v(s, qkv, qkvw, (H + Hkv) * dh, Hkv, dh, cu, vt_cu, B, T, vt, vt_total);
-    }
-    PcyAttnArgs t{};
-    t.q = qkv; t.ldq = qkvw; t.qcol0 = 0; t.k = qkv; t.ldk = qkvw; t.kcol0 = H * dh; t.vt = vt; t.vt_total = vt_total;
-    t.o = ao; t.ldo = H * dh; t.cu = cu; t.vt_cu = vt_cu; t.keep = keep; t.nseq = B; t.max_len = T; t.H = H; t.Hkv = Hkv; t.dh = dh;
-    t.causal = 1; t.scale = 1.0f / sqrtf((float)dh);
-    pcy_launch_attn(s, t);
-    }
-    if (L8) linear8(ao, H * dh, L8->wo, L8->so, x, x, d, d, EPI_RESID);
-    else linear(s, ao, H * dh, (const bf16_t*)L.wo, nullptr, x, d, x, d, M, d, H * dh, EPI_RESID, sk_ws, sk_bytes,
-                (const bf16_t*)L.ln2, xn, &xn_ready, m->rms_eps, m->rms_cast);   // (M <= 1024: the K-split finish also writes RMSNorm(x) * ln2)
-    if (!L8 && !xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln2, xn, M, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    if (L8) {
-      linear8(x, d, L8->wgu, L8->sgu, nullptr, act, F, 2 * F, EPI_SWIGLU, (const bf16_t*)L.ln2);
-      linear8(act, F, L8->wdown, L8->sdown, x, x, d, d, EPI_RESID);
-      if (l + 1 < m->n_layers) pcy_launch_acc_rows(s, x, d, sum_rows, hsum, n_sum_rows, d, 0);
-      if (hall && l + 1 < m->n_layers) HIP_TRY(hipMemcpyAsync(hall + (size_t)(l + 1) * M * d, x, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
-      continue;
-    }
-    if (M <= 8) {
-      PcyGemvArgs u{};
-      u.W = (const bf16_t*)L.wgu; u.x = xn; u.y = act; u.N = F; u.K = d; u.B = M; u.ldx = d; u.ldy = F; u.epi = EPI_SWIGLU;
-      pcy_launch_gemv(s, u);
-    } else {
-      linear(s, xn, d, (const bf16_t*)L.wgu, nullptr, nullptr, 0, act, F, M, 2 * F, d, EPI_SWIGLU);
-    }
-    if (l + 1 < m->n_layers && !m->layers_fp8)   // ... and the next layer's input norm
-      linear(s, act, F, (const bf16_t*)L.wdown, nullptr, x, d, x, d, M, d, F, EPI_RESID, sk_ws, sk_bytes,
-             (const bf16_t*)m->layers[l + 1].ln1, xn, &xn_ready, m->rms_eps, m->rms_cast);
-    else linear(s, act, F, (const bf16_t*)L.wdown, nullptr, x, d, x, d, M, d, F, EPI_RESID, sk_ws, sk_bytes);
-    if (l + 1 < m->n_layers) pcy_launch_acc_rows(s, x, d, sum_rows, hsum, n_sum_rows, d, 0);
-    if (hall && l + 1 < m->n_layers) HIP_TRY(hipMemcpyAsync(hall + (size_t)(l + 1) * M * d, x, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
+  bf16_t *kl = (bf16_t*)kv->k + layer * layer_stride, *vl = (bf16_t*)kv->v + layer * layer_stride;
+  pcy_launch_rope(s, qkv, ld, 0, H + Hkv, dh, pos, cos_t, sin_t, B * S, 0, 0.f);
+  pcy_launch_kv_scatter(s, qkv, ld, H * dh, (H + Hkv) * dh, Hkv, dh, kl + (size_t)own_slot0 * dh, vl + (size_t)own_slot0 * dh, B, S, kv->Tmax);
+  PcyExtAttnArgs e{};
+  e.q = qkv; e.ldq = ld; e.k_own = kl; e.v_own = vl; e.Town = kv->Tmax; e.scale = 1.0f / sqrtf((float)dh);
+  if (shared) {
+    const size_t prefix_layer_stride = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
+    e.k_pre = (const bf16_t*)kv->prefix_k + layer * prefix_layer_stride; e.v_pre = (const bf16_t*)kv->prefix_v + layer * prefix_layer_stride;
+    e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
   }
-  if (hall) pcy_launch_rmsnorm(s, x, (const bf16_t*)m->final_norm, hall + (size_t)m->n_layers * M * d, M, d, m->rms_eps, m->rms_cast);
-  if (hidden_out) pcy_launch_rmsnorm(s, x, (const bf16_t*)m->final_norm, (bf16_t*)hidden_out, M, d, m->rms_eps, m->rms_cast);
-  if (n_sum_rows > 0) {
-    pcy_launch_copy_rows(s, x, d, hsum_tmp, d, sum_rows, n_sum_rows, d);
-    pcy_launch_rmsnorm(s, hsum_tmp, (const bf16_t*)m->final_norm, hsum_tmp, n_sum_rows, d, m->rms_eps, m->rms_cast);
-    pcy_launch_acc_rows(s, hsum_tmp, d, nullptr, hsum, n_sum_rows, d, 0);
-    pcy_launch_acc_finish(s, hsum, (bf16_t*)hidden_sum_out, (size_t)n_sum_rows * d);
+  e.o = o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
+  if (packed) pcy_launch_attn_extend_packed(s, e);
+  else pcy_launch_attn_extend(s, e);
+}
+// The prefill's own attention stage: rope, K / V into the cache from slot 0, the transposed V copy, causal attention over the rows' own tokens
+void enqueue_prefill_attention(hipStream_t s, const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r, const PrefillWs& w, int l, int vt_total) {
+  const int H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, qkvw = (H + 2 * Hkv) * dh, B = r.B, T = r.T;
+  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
+  bf16_t *kl = (bf16_t*)kv->k + l * layer_stride, *vl = (bf16_t*)kv->v + l * layer_stride;
+  const bf16_t *cos_t = (const bf16_t*)m->rope_cos, *sin_t = (const bf16_t*)m->rope_sin;
+  if (pcy_off("prefill_post_qkv") ||   // (the three launches: the test compares both)
+      !pcy_launch_prefill_post_qkv(s, w.qkv, qkvw, H, Hkv, dh, r.pos, cos_t, sin_t, kl, vl, B, T, kv->Tmax, r.cu, r.vt_cu, w.vt, vt_total)) {
+    pcy_launch_rope(s, w.qkv, qkvw, 0, H + Hkv, dh, r.pos, cos_t, sin_t, B * T, 0, 0.f);
+    pcy_launch_kv_scatter(s, w.qkv, qkvw, H * dh, (H + Hkv) * dh, Hkv, dh, kl, vl, B, T, kv->Tmax);
+    pcy_launch_transpose_v(s, w.qkv, qkvw, (H + Hkv) * dh, Hkv, dh, r.cu, r.vt_cu, B, T, w.vt, vt_total);
   }
-  if (hall && n_logit_rows > 64 && logits_out) {
+  PcyAttnArgs t{};
+  t.q = w.qkv; t.ldq = qkvw; t.qcol0 = 0; t.k = w.qkv; t.ldk = qkvw; t.kcol0 = H * dh; t.vt = w.vt; t.vt_total = vt_total;
+  t.o = w.ao; t.ldo = H * dh; t.cu = r.cu; t.vt_cu = r.vt_cu; t.keep = r.keep; t.nseq = B; t.max_len = T; t.H = H; t.Hkv = Hkv; t.dh = dh;
+  t.causal = 1; t.scale = 1.0f / sqrtf((float)dh);
+  pcy_launch_attn(s, t);
+}
+// ---- what follows the layers: x = the un-normed output of the last layer
+void enqueue_logit_rows(hipStream_t s, const pcy_llama_desc* m, const PrefillReq& r, const bf16_t* x, bf16_t* lastx) {
+  const int d = m->d, n = r.n_logit_rows;
+  if (n <= 0 || !r.logits_out) return;
+  pcy_launch_copy_rows(s, x, d, lastx, d, r.logit_rows, n, d);
+  if (r.hidden_all_out && n > 64) {
     // pcy_llama_prefill_all with many rows (the reference's full [B,T,V] logits): final norm of those rows, then lm_head as an MFMA
     // GEMM -- the GEMV would stream the 1 GB matrix once per 32 rows.  ONLY on this entry point: the GEMM accumulates in another
     // order than the fused-norm GEMV, and a row's logits from pcy_llama_prefill must not depend on how many rows were asked for
     // (QA / pair scoring with 64 or 65 rows: same bits per row; tests/test_gpu_round4.py).
-    pcy_launch_copy_rows(s, x, d, lastx, d, logit_rows, n_logit_rows, d);
-    pcy_launch_rmsnorm(s, lastx, (const bf16_t*)m->final_norm, lastx, n_logit_rows, d, m->rms_eps, m->rms_cast);
-    linear(s, lastx, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)logits_out, m->vocab, n_logit_rows, m->vocab, d, EPI_STORE);
-  } else if (n_logit_rows > 0 && logits_out) {
-    // final norm of the selected rows, then lm_head on the MFMA GEMV (32 rows per pass over the matrix) for EVERY row count, one row
-    // included: the same arithmetic per row whatever the number of rows asked for (the fused-norm streaming GEMV it replaces ran 4 rows
-    // per pass: QA / pair scoring with more than 64 rows streamed the 1 GB matrix rows / 4 times -- advisor finding, round 4)
-    pcy_launch_copy_rows(s, x, d, lastx, d, logit_rows, n_logit_rows, d);
-    PcyGemvArgs h{};
-    h.W = (const bf16_t*)m->lm_head; h.x = lastx; h.y = (bf16_t*)logits_out; h.N = m->vocab; h.K = d; h.B = n_logit_rows; h.ldx = d; h.ldy = m->vocab;
-    h.epi = EPI_STORE;
-    if (d % 512 == 0) {
-      pcy_launch_rmsnorm(s, lastx, (const bf16_t*)m->final_norm, lastx, n_logit_rows, d, m->rms_eps, m->rms_cast);
-      h.force_mfma = 1;
-    } else {   // (toy geometries: the streaming kernel with the norm fused)
-      h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps; h.rms_cast = m->rms_cast;
+    pcy_launch_rmsnorm(s, lastx, (const bf16_t*)m->final_norm, lastx, n, d, m->rms_eps, m->rms_cast);
+    linear(s, lastx, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)r.logits_out, m->vocab, n, m->vocab, d, EPI_STORE);
+    return;
+  }
+  // final norm of the selected rows, then lm_head on the MFMA GEMV (32 rows per pass over the matrix) for EVERY row count, one row
+  // included: the same arithmetic per row whatever the number of rows asked for (the fused-norm streaming GEMV it replaces ran 4 rows
+  // per pass: QA / pair scoring with more than 64 rows streamed the 1 GB matrix rows / 4 times -- advisor finding, round 4)
+  PcyGemvArgs h{};
+  h.W = (const bf16_t*)m->lm_head; h.x = lastx; h.y = (bf16_t*)r.logits_out; h.N = m->vocab; h.K = d; h.B = n; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
+  if (d % 512 == 0) {
+    pcy_launch_rmsnorm(s, lastx, (const bf16_t*)m->final_norm, lastx, n, d, m->rms_eps, m->rms_cast);
+    h.force_mfma = 1;
+  } else {   // (toy geometries: the streaming kernel with the norm fused)
+    h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps; h.rms_cast = m->rms_cast;
+  }
+  pcy_launch_gemv(s, h);
+}
+// the last of the L+1 hidden states of the sum rows (the final-normed one) onto the fp32 sums, then the one rounding
+void enqueue_sum_rows(hipStream_t s, const pcy_llama_desc* m, const PrefillReq& r, const bf16_t* x, const PrefillWs& w) {
+  const int d = m->d, n = r.n_sum_rows;
+  if (n <= 0) return;
+  pcy_launch_copy_rows(s, x, d, w.hsum_tmp, d, r.sum_rows, n, d);
+  pcy_launch_rmsnorm(s, w.hsum_tmp, (const bf16_t*)m->final_norm, w.hsum_tmp, n, d, m->rms_eps, m->rms_cast);
+  pcy_launch_acc_rows(s, w.hsum_tmp, d, nullptr, w.hsum, n, d, 0);
+  pcy_launch_acc_finish(s, w.hsum, (bf16_t*)r.hidden_sum_out, (size_t)n * d);
+}
+// teacher-forced scoring: final norm of the scored rows, then lm_head x cross-entropy with the logits kept in registers
+void enqueue_scored_rows(hipStream_t s, const pcy_llama_desc* m, const ScoreReq& sc, const bf16_t* x, const PrefillWs& w) {
+  const int d = m->d;
+  if (sc.n <= 0) return;
+  pcy_launch_copy_rows(s, x, d, w.score_x, d, sc.rows, sc.n, d);
+  pcy_launch_rmsnorm(s, w.score_x, (const bf16_t*)m->final_norm, w.score_x, sc.n, d, m->rms_eps, m->rms_cast);
+  PcyXentArgs xa{};
+  xa.x = w.score_x; xa.ldx = d; xa.W = (const bf16_t*)m->lm_head; xa.targets = sc.targets; xa.M = sc.n; xa.V = m->vocab; xa.d = d;
+  xa.nll = sc.nll; xa.ws = w.score_ws;
+  pcy_launch_lm_head_xent(s, xa);
+}
+int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r) {
+  PCY_STICKY(c);
+  if (int e = check_prefill_req(m, kv, r)) return e;
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
+  const int M = B * T, qkvw = (H + 2 * Hkv) * dh, Tp = (T + 31) / 32 * 32, n_sum_rows = r.n_sum_rows;
+  const bool ext = r.ext.on;
+  // Row stride of the transposed V ([Hkv*dh][vt_total]): a power-of-two stride (one 512-token prompt: 1 KB) sends the 128 rows of a
+  // key block's V tile to the same few L2 channels; pad it to an odd multiple of 64 bytes
+  int vt_total = ext ? 0 : B * Tp;   // (the extension attention reads V from the cache)
+  if (!ext && (vt_total / 32) % 2 == 0) vt_total += 32;
+  const size_t need = carve_prefill_ws(nullptr, m, M, (size_t)Hkv * dh * vt_total, r.n_logit_rows, n_sum_rows, r.score.n, m->layers_fp8 != nullptr, ext).bytes;
+  if (int e = c->reserve(need)) return e;
+  const PrefillWs w = carve_prefill_ws(c->ws, m, M, (size_t)Hkv * dh * vt_total, r.n_logit_rows, n_sum_rows, r.score.n, m->layers_fp8 != nullptr, ext);
+  bf16_t *x = w.x, *xn = w.xn, *hall = (bf16_t*)r.hidden_all_out;
+  hipStream_t s = c->stream;
+  if (ext) {   // rotary positions t_past + s of the new tokens (every row: quirk Q2)
+    pcy_launch_ext_pos(s, w.pos_ext, B, T, r.ext.t_past);
+    ++g_pcy_dispatch[PCY_DISPATCH_EXTEND];
+    if (r.ext.packed) ++g_pcy_dispatch[PCY_DISPATCH_EXTEND_PACKED];
+  }
+  // fp8 weight path: every projection = per-token e4m3 quantisation of its bf16 input + the fp8 MFMA GEMM
+  // ln != nullptr: A is the raw hidden state, RMSNorm(A) * ln is what gets quantised (one fused pass; PCY_DISABLE=fp8_fused_norm = two launches)
+  auto linear8 = [&](const bf16_t* A, int K, const void* W8, const float* sw, const bf16_t* resid, bf16_t* Cout, int ldc, int N, int epi,
+                     const bf16_t* ln = nullptr) {
+    if (ln && !pcy_off("fp8_fused_norm") && pcy_launch_rmsnorm_quant_fp8(s, A, ln, M, K, m->rms_eps, m->rms_cast, w.a8, w.sa8)) {
+    } else {
+      if (ln) { pcy_launch_rmsnorm(s, A, ln, xn, M, K, m->rms_eps, m->rms_cast); A = xn; }
+      pcy_launch_quant_rows_fp8(s, A, K, M, K, w.a8, w.sa8);
     }
-    pcy_launch_gemv(s, h);
+    PcyGemmArgs g{};
+    g.A = (const bf16_t*)w.a8; g.W = (const bf16_t*)W8; g.C = Cout; g.resid = resid; g.M = M; g.N = N; g.K = K; g.lda = K; g.ldc = ldc;
+    g.ldr = ldc; g.epi = epi; g.fp8 = 1; g.sa = w.sa8; g.sw = sw;
+    pcy_launch_gemm(s, g);
+  };
+  HIP_TRY(hipMemcpyAsync(x, r.embeds, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
+  // hidden_all_out [L+1][M][d]: HF's `hidden_states` tuple -- the embeddings, the output of layers 0..L-2, and the FINAL-NORMED
+  // output of layer L-1 (pmc_llama.py:575,584 always asks for it; only materialised here when the caller does)
+  if (hall) HIP_TRY(hipMemcpyAsync(hall, r.embeds, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
+  pcy_launch_acc_rows(s, x, d, r.sum_rows, w.hsum, n_sum_rows, d, 1);
+  int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer& L = m->layers[l];
+    const pcy_llama_layer_fp8* L8 = m->layers_fp8 ? &m->layers_fp8[l] : nullptr;
+    const bool last = l + 1 == m->n_layers;
+    if (L8) linear8(x, d, L8->wqkv, L8->sqkv, nullptr, w.qkv, qkvw, qkvw, EPI_STORE, (const bf16_t*)L.ln1);
+    else {
+      if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln1, xn, M, d, m->rms_eps, m->rms_cast);
+      xn_ready = 0;
+      linear(s, xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, w.qkv, qkvw, M, qkvw, d, EPI_STORE, w.sk_ws, w.sk_bytes);
+    }
+    if (ext) enqueue_extend_attention(s, w.qkv, qkvw, kv, l, w.ao, H * dh, r.ext.t_past, w.pos_ext, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
+                                      r.keep, B, T, H, Hkv, dh, r.ext.packed);
+    else enqueue_prefill_attention(s, m, kv, r, w, l, vt_total);
+    if (L8) {
+      linear8(w.ao, H * dh, L8->wo, L8->so, x, x, d, d, EPI_RESID);
+      linear8(x, d, L8->wgu, L8->sgu, nullptr, w.act, F, 2 * F, EPI_SWIGLU, (const bf16_t*)L.ln2);
+      linear8(w.act, F, L8->wdown, L8->sdown, x, x, d, d, EPI_RESID);
+    } else {
+      linear(s, w.ao, H * dh, (const bf16_t*)L.wo, nullptr, x, d, x, d, M, d, H * dh, EPI_RESID, w.sk_ws, w.sk_bytes,
+             (const bf16_t*)L.ln2, xn, &xn_ready, m->rms_eps, m->rms_cast);   // (M <= 1024: the K-split finish also writes RMSNorm(x) * ln2)
+      if (!xn_ready) pcy_launch_rmsnorm(s, x, (const bf16_t*)L.ln2, xn, M, d, m->rms_eps, m->rms_cast);
+      xn_ready = 0;
+      if (M <= 8) {
+        PcyGemvArgs u{};
+        u.W = (const bf16_t*)L.wgu; u.x = xn; u.y = w.act; u.N = F; u.K = d; u.B = M; u.ldx = d; u.ldy = F; u.epi = EPI_SWIGLU;
+        pcy_launch_gemv(s, u);
+      } else {
+        linear(s, xn, d, (const bf16_t*)L.wgu, nullptr, nullptr, 0, w.act, F, M, 2 * F, d, EPI_SWIGLU);
+      }
+      if (!last)   // ... and the next layer's input norm
+        linear(s, w.act, F, (const bf16_t*)L.wdown, nullptr, x, d, x, d, M, d, F, EPI_RESID, w.sk_ws, w.sk_bytes,
+               (const bf16_t*)m->layers[l + 1].ln1, xn, &xn_ready, m->rms_eps, m->rms_cast);
+      else linear(s, w.act, F, (const bf16_t*)L.wdown, nullptr, x, d, x, d, M, d, F, EPI_RESID, w.sk_ws, w.sk_bytes);
+    }
+    // hidden_states = (embeddings, output of layers 0..L-2, final-normed output of layer L-1)  [HF LlamaModel.forward]
+    if (!last) {
+      pcy_launch_acc_rows(s, x, d, r.sum_rows, w.hsum, n_sum_rows, d, 0);
+      if (hall) HIP_TRY(hipMemcpyAsync(hall + (size_t)(l + 1) * M * d, x, (size_t)M * d * 2, hipMemcpyDeviceToDevice, s));
+    }
   }
-  if (n_score > 0) {
-    // teacher-forced scoring: final norm of the scored rows, then lm_head x cross-entropy with the logits kept in registers
-    pcy_launch_copy_rows(s, x, d, score_x, d, score->rows, n_score, d);
-    pcy_launch_rmsnorm(s, score_x, (const bf16_t*)m->final_norm, score_x, n_score, d, m->rms_eps, m->rms_cast);
-    PcyXentArgs xa{};
-    xa.x = score_x; xa.ldx = d; xa.W = (const bf16_t*)m->lm_head; xa.targets = score->targets; xa.M = n_score; xa.V = m->vocab; xa.d = d;
-    xa.nll = score->nll; xa.ws = score_ws;
-    pcy_launch_lm_head_xent(s, xa);
-  }
+  if (hall) pcy_launch_rmsnorm(s, x, (const bf16_t*)m->final_norm, hall + (size_t)m->n_layers * M * d, M, d, m->rms_eps, m->rms_cast);
+  if (r.hidden_out) pcy_launch_rmsnorm(s, x, (const bf16_t*)m->final_norm, (bf16_t*)r.hidden_out, M, d, m->rms_eps, m->rms_cast);
+  enqueue_sum_rows(s, m, r, x, w);
+  enqueue_logit_rows(s, m, r, x, w.lastx);
+  enqueue_scored_rows(s, m, r.score, x, w);
   return check_launch(ext ? "pcy_llama_extend" : "pcy_llama_prefill");
+}
+int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
+                      const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
+  PCY_STICKY(c);
+  if (dh != 64 && dh != 128) return fail(1, "pcy_attn_extend: head_dim %d unsupported (64/128)", dh);
+  if (Hkv < 1 || H % Hkv) return fail(1, "pcy_attn_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
+  if (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0 || layer < 0) return fail(1, "pcy_attn_extend: B=%d S=%d t_past=%d layer=%d", B, S, t_past, layer);
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "pcy_attn_extend: ld=%d (rows of qkv must be 16-byte aligned)", ld);
+  if (int r = check_extend_span(kv, B, S, t_past, "pcy_attn_extend")) return r;
+  if (int r = c->reserve(align_up((size_t)B * S * 4, 256) + 256)) return r;
+  int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
+  pcy_launch_ext_pos(c->stream, pos, B, S, t_past);
+  enqueue_extend_attention(c->stream, (bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, t_past, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
+                           B, S, H, Hkv, dh, packed);
+  return check_launch("pcy_attn_extend");
 }
 
 PcyBeamState beam_state_args(const pcy_beam_state* st) {
@@ -1548,91 +1596,50 @@ int pcy_llama_prefill(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* k
                       const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
                       int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* sum_rows, int n_sum_rows,
                       void* hidden_sum_out) {
-  return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, hidden_out, sum_rows,
-                            n_sum_rows, hidden_sum_out, nullptr);
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.pos = pos; r.cu = cu; r.vt_cu = vt_cu; r.B = B; r.T = T; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows;
+  r.logits_out = logits_out; r.hidden_out = hidden_out; r.sum_rows = sum_rows; r.n_sum_rows = n_sum_rows; r.hidden_sum_out = hidden_sum_out;
+  return llama_prefill_impl(c, m, kv, r);
+}
+int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
+                          const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
+                          int n_logit_rows, void* logits_out, void* hidden_all_out) {
+  if (!hidden_all_out) return fail(1, "pcy_llama_prefill_all: hidden_all_out is NULL");
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.pos = pos; r.cu = cu; r.vt_cu = vt_cu; r.B = B; r.T = T;
+  r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out; r.hidden_all_out = hidden_all_out;
+  return llama_prefill_impl(c, m, kv, r);
 }
 int pcy_llama_score(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, const int32_t* pos,
                     const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* score_rows, const int32_t* targets, int n_score,
                     float* nll_out, const int32_t* logit_rows, int n_logit_rows, void* logits_out) {
-  const ScoreReq sr{score_rows, targets, n_score, nll_out};
-  return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, nullptr, nullptr, 0,
-                            nullptr, nullptr, &sr);
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.pos = pos; r.cu = cu; r.vt_cu = vt_cu; r.B = B; r.T = T; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows;
+  r.logits_out = logits_out; r.score = ScoreReq{score_rows, targets, n_score, nll_out};
+  return llama_prefill_impl(c, m, kv, r);
 }
-
-}  // extern "C"
-namespace {
-int llama_extend_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
-                       const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
-                       const int32_t* targets, int n_score, float* nll_out, bool packed) {
-  const ScoreReq sr{score_rows, targets, n_score, nll_out};
-  const ExtendReq er{t_past, packed};
-  return llama_prefill_impl(c, m, kv, embeds, keep, nullptr, nullptr, nullptr, B, S, logit_rows, n_logit_rows, logits_out, hidden_out, nullptr, 0,
-                            nullptr, nullptr, n_score > 0 ? &sr : nullptr, &er);
-}
-}  // namespace
-extern "C" {
 int pcy_llama_extend(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
                      const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
                      const int32_t* targets, int n_score, float* nll_out) {
-  return llama_extend_entry(c, m, kv, embeds, keep, B, S, t_past, logit_rows, n_logit_rows, logits_out, hidden_out, score_rows, targets, n_score,
-                            nll_out, false);
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
+  r.hidden_out = hidden_out; r.ext = ExtendReq{true, t_past, false};
+  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
+  return llama_prefill_impl(c, m, kv, r);
 }
 int pcy_llama_extend_packed(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S,
                             int t_past, const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
                             const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
-  return llama_extend_entry(c, m, kv, embeds, keep, B, S, t_past, logit_rows, n_logit_rows, logits_out, hidden_out, score_rows, targets, n_score,
-                            nll_out, true);
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
+  r.hidden_out = hidden_out; r.ext = ExtendReq{true, t_past, true};
+  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
+  return llama_prefill_impl(c, m, kv, r);
 }
 size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_logit_rows, int n_score) {
   if (!m || B < 1 || S < 1) return 0;
-  return llama_prefill_ws_need(m, B * S, 0, n_logit_rows > 0 ? n_logit_rows : 0, 0, n_score > 0 ? n_score : 0, true);
+  return carve_prefill_ws(nullptr, m, B * S, 0, n_logit_rows > 0 ? n_logit_rows : 0, 0, n_score > 0 ? n_score : 0, false, true).bytes;   // (no transposed V, no fp8, no sum rows)
 }
-
-}  // extern "C"
-namespace {
-int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
-                      const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
-  PCY_STICKY(c);
-  if (dh != 64 && dh != 128) return fail(1, "pcy_attn_extend: head_dim %d unsupported (64/128)", dh);
-  if (Hkv < 1 || H % Hkv) return fail(1, "pcy_attn_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
-  if (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0 || layer < 0) return fail(1, "pcy_attn_extend: B=%d S=%d t_past=%d layer=%d", B, S, t_past, layer);
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "pcy_attn_extend: ld=%d (rows of qkv must be 16-byte aligned)", ld);
-  const bool shared = kv_shared(kv);
-  if (shared) {
-    if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->rows_per_prefix <= 0 || kv->Tmax <= 0)
-      return fail(1, "pcy_attn_extend: shared-prefix cache needs prefix_k, prefix_v, prefix_T, prefix_B, rows_per_prefix and a suffix capacity > 0");
-    if (t_past < kv->prefix_T) return fail(1, "pcy_attn_extend: t_past=%d lies inside the shared prefix of %d slots", t_past, kv->prefix_T);
-    if ((B - 1) / kv->rows_per_prefix >= kv->prefix_B)
-      return fail(1, "pcy_attn_extend: %d rows of %d per prefix need more than the %d prefix rows of the cache", B, kv->rows_per_prefix, kv->prefix_B);
-  }
-  if (B > kv->B) return fail(1, "pcy_attn_extend: B=%d exceeds cache rows %d", B, kv->B);
-  if ((long)t_past + S > kv_cap(kv)) return fail(1, "pcy_attn_extend: t_past=%d + S=%d exceed the cache capacity %d", t_past, S, kv_cap(kv));
-  const int M = B * S;
-  if (int r = c->reserve(align_up((size_t)M * 4, 256) + 256)) return r;
-  int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
-  hipStream_t s = c->stream;
-  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
-  const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;
-  bf16_t* kl = (bf16_t*)kv->k + layer * layer_stride;
-  bf16_t* vl = (bf16_t*)kv->v + layer * layer_stride;
-  pcy_launch_ext_pos(s, pos, B, S, t_past);
-  pcy_launch_rope(s, (bf16_t*)qkv, ld, 0, H + Hkv, dh, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, M, 0, 0.f);
-  pcy_launch_kv_scatter(s, (const bf16_t*)qkv, ld, H * dh, (H + Hkv) * dh, Hkv, dh, kl + (size_t)own_slot0 * dh, vl + (size_t)own_slot0 * dh, B, S, kv->Tmax);
-  PcyExtAttnArgs e{};
-  e.q = (const bf16_t*)qkv; e.ldq = ld; e.k_own = kl; e.v_own = vl; e.Town = kv->Tmax;
-  if (shared) {
-    const size_t pls = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
-    e.k_pre = (const bf16_t*)kv->prefix_k + layer * pls; e.v_pre = (const bf16_t*)kv->prefix_v + layer * pls;
-    e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
-  }
-  e.o = (bf16_t*)o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
-  e.scale = 1.0f / sqrtf((float)dh);
-  if (packed) pcy_launch_attn_extend_packed(s, e);
-  else pcy_launch_attn_extend(s, e);
-  return check_launch("pcy_attn_extend");
-}
-}  // namespace
-extern "C" {
 int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
                     const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
   return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, false);
@@ -1640,14 +1647,6 @@ int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int l
 int pcy_attn_extend_packed(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
                            const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
   return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, true);
-}
-
-int pcy_llama_prefill_all(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep,
-                          const int32_t* pos, const int32_t* cu, const int32_t* vt_cu, int B, int T, const int32_t* logit_rows,
-                          int n_logit_rows, void* logits_out, void* hidden_all_out) {
-  if (!hidden_all_out) return fail(1, "pcy_llama_prefill_all: hidden_all_out is NULL");
-  return llama_prefill_impl(c, m, kv, embeds, keep, pos, cu, vt_cu, B, T, logit_rows, n_logit_rows, logits_out, nullptr, nullptr, 0,
-                            nullptr, hidden_all_out);
 }
 
 int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {

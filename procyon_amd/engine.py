@@ -615,15 +615,13 @@ class LlamaEngine:
     def new_cache(self, B, Tmax):
         return KVCache(self.cfg, B, Tmax, self.device)
 
-    def new_beam_cache(self, prefix_cache: KVCache, beam, max_new):
-        """The cache of a beam search over the prompts prefilled into `prefix_cache` (B rows, Tmax == the prompt length): B * beam rows that
-        share the prompts' K / V and own [L, B*beam, Hkv, max_new, dh] suffix slots.  Row r belongs to prompt r // beam."""
-        return KVCache(self.cfg, prefix_cache.B * int(beam), int(max_new), self.device, prefix=prefix_cache, rows_per_prefix=int(beam))
-
     def new_shared_cache(self, prefix_cache: KVCache, rows_per_prefix, suffix_slots):
         """A cache of prefix_cache.B * rows_per_prefix rows that share the K / V of the prompts prefilled into `prefix_cache` (Tmax == the prompt
         length) and own `suffix_slots` slots each: what `extend` and the beam search run on.  Row r belongs to prompt r // rows_per_prefix."""
-        return self.new_beam_cache(prefix_cache, rows_per_prefix, suffix_slots)
+        n = int(rows_per_prefix)
+        return KVCache(self.cfg, prefix_cache.B * n, int(suffix_slots), self.device, prefix=prefix_cache, rows_per_prefix=n)
+
+    new_beam_cache = new_shared_cache   # (prefix_cache, beam, max_new): the same call in the beam search's words
 
     def embed_tokens(self, ids, soft=None, soft_map=None):
         """ids [B,T] int -> [B,T,d]; soft-token splice of `_prepare_input_embeddings` if soft_map given."""
@@ -631,6 +629,31 @@ class LlamaEngine:
         i32 = ids.to(self.device, torch.int32).contiguous().view(-1)
         sm = None if soft_map is None else soft_map.to(self.device, torch.int32).contiguous().view(-1)
         return self.ctx.embed_splice(self.embed, i32, soft, sm).view(B, T, self.cfg.d)
+
+    def _logit_rows(self, spec, B, T, allow_all):
+        """the flat token rows b*T+t (int32, on the device) a call returns logits for"""
+        dev = self.device
+        if isinstance(spec, str):
+            if spec == "last":
+                return (torch.arange(B, dtype=torch.int32, device=dev) + 1) * T - 1
+            if spec == "all" and allow_all:
+                return torch.arange(B * T, dtype=torch.int32, device=dev)
+            raise ValueError(f"logit_rows={spec!r}: expected " + ('"all", ' if allow_all else "") + '"last", None or a tensor of flat rows b*T+t')
+        if spec is None:
+            return torch.zeros(0, dtype=torch.int32, device=dev)
+        return spec.to(dev, torch.int32).contiguous()
+
+    def _score_upload(self, labels, B, T):
+        """score_plan of `labels` on the device -> (n, score rows, targets, (b, t) pairs, nll [n] to fill: all None when n == 0; token_nll [B,T] = 0)"""
+        rows_c, tg_c, bt = score_plan(labels, T, self.cfg.vocab)
+        n, dev = int(rows_c.numel()), self.device
+        up = (*_h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev), torch.empty(n, dtype=torch.float32, device=dev)) if n else (None,) * 4
+        return (n, *up, torch.zeros(B, T, dtype=torch.float32, device=dev))
+
+    @staticmethod
+    def _scatter_nll(token_nll, bt_d, nll):
+        if nll is not None:   # row (b, t) scores the token at t + 1
+            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
 
     def _prefill_args(self, embeds, attn_mask, logit_rows, all_rows=False):
         """What both prefill entry points hand the library -> (embeds contiguous, keep mask uint8 [B,T] | None when nothing is masked, positions,
@@ -645,14 +668,7 @@ class LlamaEngine:
         pos = torch.arange(T, dtype=torch.int32, device=dev).repeat(B)
         cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * T
         vt_cu = torch.arange(B + 1, dtype=torch.int32, device=dev) * ((T + 31) // 32 * 32)
-        if all_rows and isinstance(logit_rows, str) and logit_rows == "all":
-            rows = torch.arange(B * T, dtype=torch.int32, device=dev)
-        elif isinstance(logit_rows, str) and logit_rows == "last":
-            rows = (torch.arange(B, dtype=torch.int32, device=dev) + 1) * T - 1
-        elif logit_rows is None:
-            rows = torch.zeros(0, dtype=torch.int32, device=dev)
-        else:
-            rows = logit_rows.to(dev, torch.int32).contiguous()
+        rows = self._logit_rows(logit_rows, B, T, all_rows)
         return embeds, keep, pos, cu, vt_cu, rows, torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
 
     def prefill(self, embeds, attn_mask, cache: KVCache, logit_rows="last", want_hidden=False, sum_rows=None):
@@ -693,20 +709,14 @@ class LlamaEngine:
         tokens; logits [n,V] for `logit_rows` (flat rows b*T+t or "last"; the bits of `prefill`) or None.  The [rows, V] logits of the scored
         rows are never materialised.  K/V go to `cache` (a scratch one when None).  Nothing is launched when there is nothing to do."""
         B, T, _ = embeds.shape
-        dev = self.device
-        rows_c, tg_c, bt = score_plan(full_labels, T, self.cfg.vocab)
-        n = int(rows_c.numel())
-        token_nll = torch.zeros(B, T, dtype=torch.float32, device=dev)
+        n, srows, tg, bt_d, nll, token_nll = self._score_upload(full_labels, B, T)
         if n == 0 and logit_rows is None:
             return token_nll, 0, None
         cache = self.new_cache(B, T) if cache is None else cache
         embeds, keep, pos, cu, vt_cu, rows, logits = self._prefill_args(embeds, attn_mask, logit_rows)
-        srows, tg, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev) if n else (None, None, None)
-        nll = torch.empty(n, dtype=torch.float32, device=dev)
         L.check(self.ctx.lib.pcy_llama_score(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep), _p(pos), _p(cu), _p(vt_cu),
                                              B, T, _p(srows), _p(tg), n, _p(nll), _p(rows), rows.numel(), _p(logits)), "pcy_llama_score")
-        if n:
-            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
+        self._scatter_nll(token_nll, bt_d, nll)
         return token_nll, n, (logits if logit_rows is not None else None)
 
     def extend(self, cache: KVCache, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False, packed=False):
@@ -731,29 +741,14 @@ class LlamaEngine:
                 keep_d = torch.zeros(B, cache.capacity, dtype=torch.uint8, device=dev)   # (row stride = the logical capacity)
                 n = min(kp.shape[1], cache.capacity)
                 keep_d[:, :n] = kp[:, :n].to(dev, torch.uint8)
-        if isinstance(logit_rows, str) and logit_rows == "all":
-            rows = torch.arange(B * S, dtype=torch.int32, device=dev)
-        elif isinstance(logit_rows, str) and logit_rows == "last":
-            rows = (torch.arange(B, dtype=torch.int32, device=dev) + 1) * S - 1
-        elif logit_rows is None:
-            rows = torch.zeros(0, dtype=torch.int32, device=dev)
-        else:
-            rows = logit_rows.to(dev, torch.int32).contiguous()
+        rows = self._logit_rows(logit_rows, B, S, True)
         logits = torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
         hidden = torch.empty(B, S, d, dtype=BF16, device=dev) if want_hidden else None
-        n, srows, tg, bt_d, nll, token_nll = 0, None, None, None, None, None
-        if labels is not None:
-            rows_c, tg_c, bt = score_plan(labels, S, self.cfg.vocab)
-            n = int(rows_c.numel())
-            token_nll = torch.zeros(B, S, dtype=torch.float32, device=dev)
-            if n:
-                srows, tg, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], dev)
-                nll = torch.empty(n, dtype=torch.float32, device=dev)
+        n, srows, tg, bt_d, nll, token_nll = self._score_upload(labels, B, S) if labels is not None else (0,) + (None,) * 5
         fn = self.ctx.lib.pcy_llama_extend_packed if packed else self.ctx.lib.pcy_llama_extend
         L.check(fn(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
                    _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
-        if n:
-            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll
+        self._scatter_nll(token_nll, bt_d, nll)
         return (logits if logit_rows is not None else None), hidden, token_nll, n
 
     def extend_ws_bytes(self, B, S, n_logit_rows=0, n_score=0):

@@ -45,6 +45,18 @@ def test_workspace_depends_on_the_row_counts_only():
     assert ws(_desc(), 0, 32, 0, 0) == 0 and ws(_desc(), 2, 0, 0, 0) == 0
 
 
+def test_workspace_bytes_stay_within_the_slack_of_the_formula_they_replace():
+    """The reported bytes are where the engine's own carve of the workspace ends (+ its 4096 bytes of slack); the values below are what the
+    closed formula that carve replaced reported for the same calls.  The two may differ by alignment padding only, which the slack covers."""
+    from procyon_amd import _lib
+    lib = _lib.load()
+    formula = {(2, 32, 64, 62): 18095872, (4, 32, 64, 62): 34873344, (2, 32, 128, 62): 18620160, (2, 32, 64, 0): 17338624,
+               (1, 64, 64, 64): 18120192, (16, 4, 64, 64): 18120192}
+    for args, was in formula.items():
+        now = int(lib.pcy_llama_extend_ws_bytes(C.byref(_desc()), *args))
+        assert abs(now - was) <= 4096, (args, now, was)
+
+
 @pytest.mark.parametrize("B,S", [(1, 64), (2, 32), (16, 4)])
 def test_workspace_is_below_one_copy_of_the_prefix(B, S):
     """B*S = 64 rows, logits and scores for all of them: the workspace stays below what ONE per-row copy of a 512-slot prefix (K and V,
