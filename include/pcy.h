@@ -45,10 +45,13 @@ int pcy_abi_version(void);
  * 15: launch per stage, MFMA GEMVs; 16: a step served from a shared-prefix cache (pcy_kv_cache.prefix_k), counted in addition to 14 / 15.
  * 17: calls of the fused lm_head x cross-entropy operator (pcy_lm_head_xent, also inside pcy_llama_score / pcy_llama_extend).
  * 18: calls of pcy_llama_extend (S more tokens per row against a filled cache).
- * 19: calls of pcy_llama_extend_packed (each also counts as kind 18).
+ * 19: calls of pcy_llama_extend_packed (each also counts as kind 18).  A pcy_llama_extend_grouped call counts as kind 18, as kind 19 when
+ * packed, and in pcy_debug_extend_grouped_count() below.
  * A fused step may decline at launch time (LDS size for the cache length, co-residency) and the step
  * then runs launch by launch with the same bits.  Parity tests use the counters to assert that they reach the kernel they claim to test. */
 unsigned long long pcy_debug_dispatch_count(int kind);
+/* calls of pcy_llama_extend_grouped (each also counts as kind 18, and as kind 19 when packed) */
+unsigned long long pcy_debug_extend_grouped_count(void);
 const char* pcy_last_error(void);
 /* stream: a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream) or NULL for the default stream */
 int pcy_ctx_create(int device_id, void* stream, pcy_ctx** out);
@@ -296,6 +299,35 @@ size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc*, int B, int S, int n_logi
 int pcy_llama_extend_packed(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const void* embeds, const uint8_t* keep, int B, int S,
                             int t_past, const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
                             const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out);
+/* Grouped extension: the B rows of the call are n_groups contiguous groups.  Group g holds rows[g] rows (in order) that read prefix row g of the
+ * cache, whose first len[g] <= prefix_T slots are real and start at position 0; slots at and above len[g] of that prefix row are never addressed.
+ * A row's own panel starts right behind its group's prefix: logical slot j < len[g] is prefix[g][j] (panel stride prefix_T), slot j >= len[g] is
+ * k[b][j - len[g]].  t_own >= 0 tokens already sit in every row's own panel; query s of a row of group g sits at logical slot (= rotary position)
+ * len[g] + t_own + s and attends logical slots [0, len[g] + t_own + s]; K / V of the new tokens go to own slots [t_own, t_own + S) of every row.
+ * keep: optional [B, prefix_T + Tmax] bytes in logical slots (so a row's bytes are packed against ITS len[g]); bytes at and above
+ * len[g] + t_own + S are not read; a query without a kept key gets the uniform softmax over the row's len[g] + t_own + S keys.
+ * The cache: prefix_k, prefix_v, prefix_B >= n_groups, prefix_T, a suffix capacity Tmax and rows_per_prefix == 0 (every other entry refuses such a
+ * cache).  rows / len are HOST arrays (the argument checks read them); d_row0 [n_groups + 1] (prefix sums of rows), d_len [n_groups] and
+ * d_row_grp [B] (row -> group) are DEVICE copies that the caller keeps equal to them and alive until the stream has run the call.
+ * Bits: every row gets what it gets ALONE from pcy_attn_extend on a one-row plain cache with the same logical contents and
+ * t_past = len[g] + t_own; packed != 0 (the work split of pcy_attn_extend_packed, a workgroup per (tile, kv head, group)) gives the same bits.
+ * Argument errors (nothing is launched, the caches stay as they were): sum(rows) != B, B beyond the cache's rows, a rows[g] < 1, a len[g] outside
+ * [1, prefix_T], t_own + S > Tmax, max(len) + t_own + S > max_pos (pcy_llama_extend_grouped), n_groups > prefix_B, a plain cache or one with
+ * rows_per_prefix != 0, S < 1, fp8 layers, a head_dim other than 64 / 128. */
+typedef struct {
+  int32_t n_groups, t_own;
+  const int32_t* rows;       /* HOST [n_groups], >= 1 */
+  const int32_t* len;        /* HOST [n_groups], 1 <= len[g] <= prefix_T */
+  const int32_t* d_row0;     /* DEVICE [n_groups + 1] */
+  const int32_t* d_len;      /* DEVICE [n_groups] */
+  const int32_t* d_row_grp;  /* DEVICE [B] */
+} pcy_prefix_groups;
+int pcy_attn_extend_grouped(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, const pcy_prefix_groups* groups, int layer, void* o, int ldo,
+                            const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, int packed);
+/* pcy_llama_extend on groups: logit_rows .. nll_out and the workspace (pcy_llama_extend_ws_bytes) exactly as there */
+int pcy_llama_extend_grouped(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_prefix_groups* groups, const void* embeds,
+                             const uint8_t* keep, int B, int S, int packed, const int32_t* logit_rows, int n_logit_rows, void* logits_out,
+                             void* hidden_out, const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out);
 typedef struct {
   int32_t* pos;              /* device scalar: cache length == rotary position of the next token (Q2) */
   int32_t* step;             /* device scalar: index of the next generated token */

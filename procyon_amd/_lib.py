@@ -60,6 +60,11 @@ class KvCache(C.Structure):
                 ("rows_per_prefix", i32)]
 
 
+class PrefixGroups(C.Structure):
+    # (pcy_prefix_groups: rows / len are HOST arrays, the d_* tables live on the device)
+    _fields_ = [("n_groups", i32), ("t_own", i32), ("rows", C.POINTER(i32)), ("len", C.POINTER(i32)), ("d_row0", vp), ("d_len", vp), ("d_row_grp", vp)]
+
+
 class GenState(C.Structure):
     _fields_ = [("pos", vp), ("step", vp), ("next_tok", vp), ("tokens_out", vp), ("logprob", vp), ("logits", vp),
                 ("logits_all", vp), ("keep", vp), ("max_steps", i32), ("logits_all_ld", i32)]
@@ -94,6 +99,7 @@ SIGNATURES = {
     "pcy_attn_decode": (ci, [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend_packed": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
+    "pcy_attn_extend_grouped": (ci, [vp, vp, ci, C.POINTER(KvCache), C.POINTER(PrefixGroups), ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci]),
     "pcy_pool": (ci, [vp, vp, ci, vp, vp, ci, ci, vp]),
     "pcy_retrieval_scores": (ci, [vp, vp, ci, vp, ci, ci, vp]),
     "pcy_comm_unique_id": (ci, [vp]),
@@ -124,6 +130,9 @@ SIGNATURES = {
     "pcy_llama_prefill_all": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, vp, vp, vp, ci, ci, vp, ci, vp, vp]),
     "pcy_llama_extend": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp]),
     "pcy_llama_extend_packed": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp, ci, vp]),
+    "pcy_llama_extend_grouped": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(PrefixGroups), vp, vp, ci, ci, ci, vp, ci, vp, vp, vp, vp,
+                                      ci, vp]),
+    "pcy_debug_extend_grouped_count": (C.c_ulonglong, []),
     "pcy_llama_extend_ws_bytes": (C.c_size_t, [C.POINTER(LlamaDesc), ci, ci, ci, ci]),
     "pcy_llama_decode": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_debug_mc_trace": (ci, [vp, ci]),

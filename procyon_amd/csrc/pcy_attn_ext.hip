@@ -22,6 +22,9 @@
 // A query row whose allowed-key set is empty (a pad query) gets the reference's uniform softmax over ALL t_past + S keys, future
 // ones included: the workgroup then repeats pass 1 over the full range, as attn_lds_kernel does.
 // A row's bits depend on nothing but its own row of the batch: B rows at once = each row alone.
+// Both kernels have a GROUPED mode (PcyExtAttnArgs::g_*): the prefix row, the split point between the two panels and the
+// past length come from per-group device tables instead of (rows_per_prefix, Tp, t_past).  The walk over logical slots is the same, so a
+// row of a grouped call has the bits of that row alone on a plain cache.
 #include "pcy_internal.h"
 
 namespace {
@@ -33,8 +36,16 @@ __global__ void ext_pos_kernel(int32_t* __restrict__ pos, int n, int S, int t_pa
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) pos[i] = t_past + i % S;
 }
+__global__ void ext_pos_grouped_kernel(int32_t* __restrict__ pos, int n, int S, int t_own, const int32_t* __restrict__ g_len,
+                                       const int32_t* __restrict__ g_row_grp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) pos[i] = g_len[g_row_grp[i / S]] + t_own + i % S;
+}
 
-template <int DH>
+// GROUPED (pcy_attn_extend_grouped): row b belongs to group grp = g_row_grp[b]; the split point between the prefix panel (of prefix row grp,
+// panel stride a.Tp) and the row's own panel is g_len[grp], and the row's past length is g_len[grp] + a.t_past.  Nothing else changes: the
+// walk over logical slots, the blocks and the arithmetic are those of a one-row plain cache with the same logical contents.
+template <int DH, bool GROUPED>
 __global__ __launch_bounds__(256) void attn_ext_kernel(PcyExtAttnArgs a) {
   constexpr int KB = DH / 32, NT = DH / 16;
   constexpr int KCH = DH / 8;                  // 16-B chunks per K / V row
@@ -46,7 +57,9 @@ __global__ __launch_bounds__(256) void attn_ext_kernel(PcyExtAttnArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int h = blockIdx.y, b = blockIdx.z;
-  const int S = a.S, t_past = a.t_past;
+  int grp = 0, glen = 0;                       // (GROUPED only; workgroup-uniform)
+  if constexpr (GROUPED) { grp = a.g_row_grp[b]; glen = a.g_len[grp]; }
+  const int S = a.S, t_past = GROUPED ? glen + a.t_past : a.t_past;
   const int nk = t_past + S;                   // keys of the row after the append
   const int bq0 = blockIdx.x * 64;             // (< S by the grid)
   const int qr0 = bq0 + wave * 16;
@@ -58,9 +71,10 @@ __global__ __launch_bounds__(256) void attn_ext_kernel(PcyExtAttnArgs a) {
   const uint8_t* keep = a.keep ? a.keep + (size_t)b * a.ld_keep : nullptr;
 
   // logical slot -> row address: the prompt's prefix panel below Tp, the row's own panel above
-  const int Tp = a.k_pre ? a.Tp : 0;
+  const int Tp = GROUPED ? glen : (a.k_pre ? a.Tp : 0);
   const size_t own_off = ((size_t)b * a.Hkv + kvh) * a.Town * DH;
-  const size_t pre_off = a.k_pre ? ((size_t)(b / a.rows_per_prefix) * a.Hkv + kvh) * Tp * DH : 0;
+  const size_t pre_off = GROUPED ? ((size_t)grp * a.Hkv + kvh) * a.Tp * DH
+                                 : (a.k_pre ? ((size_t)(b / a.rows_per_prefix) * a.Hkv + kvh) * Tp * DH : 0);
   const bf16_t* k_own = a.k_own + own_off;
   const bf16_t* v_own = a.v_own + own_off;
   const bf16_t* k_pre = a.k_pre ? a.k_pre + pre_off : nullptr;
@@ -243,7 +257,9 @@ __global__ __launch_bounds__(256) void attn_ext_kernel(PcyExtAttnArgs a) {
 // Bits: a query meets the same 32-key blocks in the same order as in attn_ext_kernel; an MFMA output element depends on its own row
 // and column only; a foreign block adds P = 0 times finite V; blocks beyond attn_ext_kernel's causal range add exp2(-2^126 - m) = 0.
 // So the output equals attn_ext_kernel's bit for bit, and a query's bits depend on its own row of the batch only.
-template <int DH>
+// GROUPED: the workgroup's "prompt" p is group p of the table -- row0 / rows from g_row0, the split point Tp = g_len[p] (panel stride a.Tp),
+// t_past = g_len[p] + a.t_past.  The grid is sized for the largest group; everything below is written in terms of (row0, rows, Tp, t_past).
+template <int DH, bool GROUPED>
 __global__ __launch_bounds__(256) void attn_ext_packed_kernel(PcyExtAttnArgs a) {
   constexpr int KB = DH / 32, NT = DH / 16;
   constexpr int KCH = DH / 8;
@@ -255,16 +271,18 @@ __global__ __launch_bounds__(256) void attn_ext_packed_kernel(PcyExtAttnArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fq = lane >> 4;
   const int g = blockIdx.y, p = blockIdx.z;
-  const int S = a.S, t_past = a.t_past;
+  int g_r0 = 0, g_rows = 0, glen = 0;          // (GROUPED only; workgroup-uniform)
+  if constexpr (GROUPED) { g_r0 = a.g_row0[p]; g_rows = a.g_row0[p + 1] - g_r0; glen = a.g_len[p]; }
+  const int S = a.S, t_past = GROUPED ? glen + a.t_past : a.t_past;
   const int nk = t_past + S;
   const int G = a.H / a.Hkv, GS = G * S;
-  const int Tp = a.k_pre ? a.Tp : 0;
+  const int Tp = GROUPED ? glen : (a.k_pre ? a.Tp : 0);
   const int rpp = a.k_pre ? a.rows_per_prefix : 1;
-  const int row0 = p * rpp;                    // (< B by the grid)
-  const int rows = (a.B - row0) < rpp ? (a.B - row0) : rpp;   // the last prompt may be short of rows
+  const int row0 = GROUPED ? g_r0 : p * rpp;   // (< B by the grid)
+  const int rows = GROUPED ? g_rows : ((a.B - row0) < rpp ? (a.B - row0) : rpp);   // the last prompt may be short of rows
   const int total = rows * GS;                 // packed queries of this (prompt, kv head)
   const int i0 = blockIdx.x * 64;
-  if (i0 >= total) return;                     // workgroup-uniform (the grid is sized for a full prompt)
+  if (i0 >= total) return;                     // workgroup-uniform (the grid is sized for a full prompt / the largest group)
   const int iw0 = i0 + wave * 16;
   const bool active = iw0 < total;             // wave-uniform
   constexpr float LOG2E = 1.4426950408889634f;
@@ -288,7 +306,7 @@ __global__ __launch_bounds__(256) void attn_ext_packed_kernel(PcyExtAttnArgs a) 
   const bf16_t* k_own0 = a.k_own + ((size_t)row0 * a.Hkv + g) * panel;   // row r of the prompt: + r * Hkv * panel
   const bf16_t* v_own0 = a.v_own + ((size_t)row0 * a.Hkv + g) * panel;
   const size_t row_step = (size_t)a.Hkv * panel;
-  const size_t pre_off = a.k_pre ? ((size_t)p * a.Hkv + g) * Tp * DH : 0;
+  const size_t pre_off = a.k_pre ? ((size_t)p * a.Hkv + g) * (GROUPED ? a.Tp : Tp) * DH : 0;
   const bf16_t* k_pre = a.k_pre ? a.k_pre + pre_off : nullptr;
   const bf16_t* v_pre = a.k_pre ? a.v_pre + pre_off : nullptr;
 
@@ -472,24 +490,40 @@ void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past) {
   const int n = B * S;
   if (n > 0) hipLaunchKernelGGL(ext_pos_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pos, n, S, t_past);
 }
+void pcy_launch_ext_pos_grouped(hipStream_t s, int32_t* pos, int B, int S, int t_own, const int32_t* g_len, const int32_t* g_row_grp) {
+  const int n = B * S;
+  if (n > 0) hipLaunchKernelGGL(ext_pos_grouped_kernel, dim3((n + 255) / 256), dim3(256), 0, s, pos, n, S, t_own, g_len, g_row_grp);
+}
 
 bool pcy_launch_attn_extend(hipStream_t s, const PcyExtAttnArgs& a) {
   if (a.B <= 0 || a.S <= 0) return true;
   const dim3 grid((a.S + 63) / 64, a.H, a.B);
-  if (a.dh == 64) hipLaunchKernelGGL(attn_ext_kernel<64>, grid, dim3(256), 0, s, a);
-  else if (a.dh == 128) hipLaunchKernelGGL(attn_ext_kernel<128>, grid, dim3(256), 0, s, a);
-  else return false;
+  if (a.dh != 64 && a.dh != 128) return false;
+  if (a.g_row_grp) {   // grouped mode: the tables say which prefix row and which split point a row has
+    if (a.dh == 64) hipLaunchKernelGGL((attn_ext_kernel<64, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_ext_kernel<128, true>), grid, dim3(256), 0, s, a);
+  } else {
+    if (a.dh == 64) hipLaunchKernelGGL((attn_ext_kernel<64, false>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_ext_kernel<128, false>), grid, dim3(256), 0, s, a);
+  }
   return true;
 }
 
 bool pcy_launch_attn_extend_packed(hipStream_t s, const PcyExtAttnArgs& a) {
   if (a.B <= 0 || a.S <= 0) return true;
+  if (a.dh != 64 && a.dh != 128) return false;
+  if (a.g_row0) {      // grouped mode: one grid layer per group, sized for the largest one (a smaller group's spare tiles return at once)
+    const long total = (long)a.g_max_rows * (a.H / a.Hkv) * a.S;
+    const dim3 grid((unsigned)((total + 63) / 64), a.Hkv, a.n_groups);
+    if (a.dh == 64) hipLaunchKernelGGL((attn_ext_packed_kernel<64, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((attn_ext_packed_kernel<128, true>), grid, dim3(256), 0, s, a);
+    return true;
+  }
   const int rpp = a.k_pre ? a.rows_per_prefix : 1;
   const int rows = a.B < rpp ? a.B : rpp;
   const long total = (long)rows * (a.H / a.Hkv) * a.S;
   const dim3 grid((unsigned)((total + 63) / 64), a.Hkv, (a.B + rpp - 1) / rpp);
-  if (a.dh == 64) hipLaunchKernelGGL(attn_ext_packed_kernel<64>, grid, dim3(256), 0, s, a);
-  else if (a.dh == 128) hipLaunchKernelGGL(attn_ext_packed_kernel<128>, grid, dim3(256), 0, s, a);
-  else return false;
+  if (a.dh == 64) hipLaunchKernelGGL((attn_ext_packed_kernel<64, false>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_ext_packed_kernel<128, false>), grid, dim3(256), 0, s, a);
   return true;
 }

@@ -34,6 +34,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // and the score rows count in -- is prefix_T + Tmax.  A plain cache has all-zero prefix fields: kv_cap == Tmax.
 inline bool kv_shared(const pcy_kv_cache* kv) { return kv->prefix_k != nullptr || kv->prefix_v != nullptr || kv->prefix_T != 0; }
 inline int kv_cap(const pcy_kv_cache* kv) { return kv->Tmax + (kv_shared(kv) ? kv->prefix_T : 0); }
+// calls of pcy_llama_extend_grouped (pcy_debug_extend_grouped_count).  A word of its own, not a kind of pcy_debug_dispatch_count: the kinds
+// [0, PCY_DISPATCH_N) and the ABI number are pinned by the suite, and a new entry point is an addition that old callers never see.
+unsigned long long g_pcy_extend_grouped = 0;
 
 }  // namespace
 
@@ -1270,7 +1273,8 @@ struct ScoreReq { const int32_t* rows; const int32_t* targets; int n; float* nll
 // pcy_llama_extend: the T tokens of every row FOLLOW t_past tokens the cache already holds (on == false: a prefill from slot 0).  The layer loop
 // is the prefill's; what differs is the rotary position (t_past + s, made on the device), where K / V go (logical slots t_past ..) and the
 // attention (pcy_attn_ext.hip reads the keys from the cache: no transposed V workspace on this path).
-struct ExtendReq { bool on; int t_past; bool packed; };   // packed: the attention launch is pcy_launch_attn_extend_packed
+// grp (pcy_llama_extend_grouped): the rows are groups with a prefix length each; t_past then counts the tokens in the rows' OWN panels (t_own)
+struct ExtendReq { bool on; int t_past; bool packed; const pcy_prefix_groups* grp; };   // packed: the attention launch is pcy_launch_attn_extend_packed
 struct PrefillReq {
   const void* embeds; const uint8_t* keep; int B, T;
   const int32_t *pos, *cu, *vt_cu;                                    // a prefill's (an extension makes its positions itself)
@@ -1316,6 +1320,30 @@ int check_extend_span(const pcy_kv_cache* kv, int B, int S, int t_past, const ch
   if ((long)t_past + S > kv_cap(kv)) return fail(1, "%s: t_past=%d + S=%d exceed the cache capacity %d", what, t_past, S, kv_cap(kv));
   return 0;
 }
+// A grouped extension (include/pcy.h, pcy_prefix_groups), checked on the HOST arrays: the cache carries a prefix and no uniform rows_per_prefix,
+// the groups cover the call's rows exactly, every prefix length is real, the new slots fit.  max_rows / max_len: the largest group / prefix length
+int check_prefix_groups(const pcy_kv_cache* kv, const pcy_prefix_groups* gr, int B, int S, const char* what, int* max_rows, int* max_len) {
+  if (!gr || !gr->rows || !gr->len || !gr->d_row0 || !gr->d_len || !gr->d_row_grp) return fail(1, "%s: group tables missing", what);
+  if (gr->n_groups < 1 || gr->t_own < 0 || B < 1 || S < 1) return fail(1, "%s: n_groups=%d t_own=%d B=%d S=%d", what, gr->n_groups, gr->t_own, B, S);
+  if (!kv || !kv->k || !kv->v) return fail(1, "%s: cache without k / v", what);
+  if (!kv->prefix_k || !kv->prefix_v || kv->prefix_T <= 0 || kv->prefix_B <= 0 || kv->Tmax <= 0 || kv->rows_per_prefix != 0)
+    return fail(1, "%s: a grouped extension needs a cache with prefix_k, prefix_v, prefix_T, prefix_B, a suffix capacity > 0 and rows_per_prefix == 0", what);
+  if (gr->n_groups > kv->prefix_B) return fail(1, "%s: %d groups need more than the %d prefix rows of the cache", what, gr->n_groups, kv->prefix_B);
+  long sum = 0;
+  int mr = 0, ml = 0;
+  for (int g = 0; g < gr->n_groups; ++g) {
+    if (gr->rows[g] < 1) return fail(1, "%s: group %d has rows=%d (>= 1 expected)", what, g, gr->rows[g]);
+    if (gr->len[g] < 1 || gr->len[g] > kv->prefix_T) return fail(1, "%s: group %d has len=%d outside [1, prefix_T=%d]", what, g, gr->len[g], kv->prefix_T);
+    sum += gr->rows[g];
+    mr = gr->rows[g] > mr ? gr->rows[g] : mr;
+    ml = gr->len[g] > ml ? gr->len[g] : ml;
+  }
+  if (sum != B) return fail(1, "%s: the groups hold %ld rows, the call B=%d", what, sum, B);
+  if (B > kv->B) return fail(1, "%s: B=%d exceeds cache rows %d", what, B, kv->B);
+  if ((long)gr->t_own + S > kv->Tmax) return fail(1, "%s: t_own=%d + S=%d exceed the suffix capacity %d", what, gr->t_own, S, kv->Tmax);
+  *max_rows = mr; *max_len = ml;
+  return 0;
+}
 int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r) {
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
@@ -1326,9 +1354,16 @@ int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const Pre
     if (H % Hkv) return fail(1, "pcy_llama_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
     if (m->layers_fp8) return fail(1, "pcy_llama_extend: fp8 projections are not supported on the extension path");
     if (B < 1 || T < 1 || t_past < 0) return fail(1, "pcy_llama_extend: B=%d S=%d t_past=%d", B, T, t_past);
-    if (!kv->k || !kv->v) return fail(1, "pcy_llama_extend: cache without k / v");
-    if (int e = check_extend_span(kv, B, T, t_past, "pcy_llama_extend")) return e;
-    if ((long)t_past + T > m->max_pos) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed rope table %d", t_past, T, m->max_pos);
+    if (r.ext.grp) {
+      int max_rows = 0, max_len = 0;
+      if (int e = check_prefix_groups(kv, r.ext.grp, B, T, "pcy_llama_extend_grouped", &max_rows, &max_len)) return e;
+      if ((long)max_len + t_past + T > m->max_pos)
+        return fail(1, "pcy_llama_extend_grouped: len=%d + t_own=%d + S=%d exceed rope table %d", max_len, t_past, T, m->max_pos);
+    } else {
+      if (!kv->k || !kv->v) return fail(1, "pcy_llama_extend: cache without k / v");
+      if (int e = check_extend_span(kv, B, T, t_past, "pcy_llama_extend")) return e;
+      if ((long)t_past + T > m->max_pos) return fail(1, "pcy_llama_extend: t_past=%d + S=%d exceed rope table %d", t_past, T, m->max_pos);
+    }
   } else {
     if (kv_shared(kv)) return fail(1, "pcy_llama_prefill: a cache with a shared prefix cannot be prefilled (prefill the prefix cache itself)");
     if (B > kv->B || T > kv->Tmax) return fail(1, "pcy_llama_prefill: B=%d T=%d exceed cache (%d,%d)", B, T, kv->B, kv->Tmax);
@@ -1342,9 +1377,11 @@ int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const Pre
 // The extension attention stage of a layer (pcy_attn_extend, pcy_llama_extend): rope (q, k) in place at `pos`, K / V of token s to slot own_slot0 + s of
 // the row's own panel (the panel pointer carries the offset, the row stride stays Tmax * dh), then the S queries of every row against the cache
 void enqueue_extend_attention(hipStream_t s, bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, int t_past, const int32_t* pos,
-                              const bf16_t* cos_t, const bf16_t* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
+                              const bf16_t* cos_t, const bf16_t* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed,
+                              const pcy_prefix_groups* grp = nullptr) {
   const bool shared = kv_shared(kv);
-  const int own_slot0 = shared ? t_past - kv->prefix_T : t_past;   // first written slot inside the rows' own panels
+  // first written slot inside the rows' own panels (grouped: t_past IS the count of own tokens, the same for every row)
+  const int own_slot0 = grp ? t_past : shared ? t_past - kv->prefix_T : t_past;
   const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
   bf16_t *kl = (bf16_t*)kv->k + layer * layer_stride, *vl = (bf16_t*)kv->v + layer * layer_stride;
   pcy_launch_rope(s, qkv, ld, 0, H + Hkv, dh, pos, cos_t, sin_t, B * S, 0, 0.f);
@@ -1357,6 +1394,10 @@ void enqueue_extend_attention(hipStream_t s, bf16_t* qkv, int ld, const pcy_kv_c
     e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
   }
   e.o = o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
+  if (grp) {
+    e.g_row0 = grp->d_row0; e.g_len = grp->d_len; e.g_row_grp = grp->d_row_grp; e.n_groups = grp->n_groups;
+    for (int g = 0; g < grp->n_groups; ++g) e.g_max_rows = grp->rows[g] > e.g_max_rows ? grp->rows[g] : e.g_max_rows;
+  }
   if (packed) pcy_launch_attn_extend_packed(s, e);
   else pcy_launch_attn_extend(s, e);
 }
@@ -1441,9 +1482,11 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   bf16_t *x = w.x, *xn = w.xn, *hall = (bf16_t*)r.hidden_all_out;
   hipStream_t s = c->stream;
   if (ext) {   // rotary positions t_past + s of the new tokens (every row: quirk Q2)
-    pcy_launch_ext_pos(s, w.pos_ext, B, T, r.ext.t_past);
+    if (r.ext.grp) pcy_launch_ext_pos_grouped(s, w.pos_ext, B, T, r.ext.t_past, r.ext.grp->d_len, r.ext.grp->d_row_grp);
+    else pcy_launch_ext_pos(s, w.pos_ext, B, T, r.ext.t_past);
     ++g_pcy_dispatch[PCY_DISPATCH_EXTEND];
     if (r.ext.packed) ++g_pcy_dispatch[PCY_DISPATCH_EXTEND_PACKED];
+    if (r.ext.grp) ++g_pcy_extend_grouped;
   }
   // fp8 weight path: every projection = per-token e4m3 quantisation of its bf16 input + the fp8 MFMA GEMM
   // ln != nullptr: A is the raw hidden state, RMSNorm(A) * ln is what gets quantised (one fused pass; PCY_DISABLE=fp8_fused_norm = two launches)
@@ -1476,7 +1519,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
       linear(s, xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, w.qkv, qkvw, M, qkvw, d, EPI_STORE, w.sk_ws, w.sk_bytes);
     }
     if (ext) enqueue_extend_attention(s, w.qkv, qkvw, kv, l, w.ao, H * dh, r.ext.t_past, w.pos_ext, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
-                                      r.keep, B, T, H, Hkv, dh, r.ext.packed);
+                                      r.keep, B, T, H, Hkv, dh, r.ext.packed, r.ext.grp);
     else enqueue_prefill_attention(s, m, kv, r, w, l, vt_total);
     if (L8) {
       linear8(w.ao, H * dh, L8->wo, L8->so, x, x, d, d, EPI_RESID);
@@ -1635,6 +1678,34 @@ int pcy_llama_extend_packed(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_ca
   r.hidden_out = hidden_out; r.ext = ExtendReq{true, t_past, true};
   if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
   return llama_prefill_impl(c, m, kv, r);
+}
+int pcy_llama_extend_grouped(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_prefix_groups* groups, const void* embeds,
+                             const uint8_t* keep, int B, int S, int packed, const int32_t* logit_rows, int n_logit_rows, void* logits_out,
+                             void* hidden_out, const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
+  if (!groups) return fail(1, "pcy_llama_extend_grouped: group tables missing");
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
+  r.hidden_out = hidden_out; r.ext = ExtendReq{true, groups->t_own, packed != 0, groups};
+  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
+  return llama_prefill_impl(c, m, kv, r);
+}
+unsigned long long pcy_debug_extend_grouped_count(void) { return g_pcy_extend_grouped; }
+int pcy_attn_extend_grouped(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, const pcy_prefix_groups* groups, int layer, void* o, int ldo,
+                            const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, int packed) {
+  PCY_STICKY(c);
+  const char* what = "pcy_attn_extend_grouped";
+  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv) return fail(1, "%s: H=%d is no multiple of Hkv=%d", what, H, Hkv);
+  if (layer < 0) return fail(1, "%s: layer=%d", what, layer);
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "%s: ld=%d (rows of qkv must be 16-byte aligned)", what, ld);
+  int max_rows = 0, max_len = 0;
+  if (int r = check_prefix_groups(kv, groups, B, S, what, &max_rows, &max_len)) return r;
+  if (int r = c->reserve(align_up((size_t)B * S * 4, 256) + 256)) return r;
+  int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
+  pcy_launch_ext_pos_grouped(c->stream, pos, B, S, groups->t_own, groups->d_len, groups->d_row_grp);
+  enqueue_extend_attention(c->stream, (bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, groups->t_own, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
+                           B, S, H, Hkv, dh, packed != 0, groups);
+  return check_launch(what);
 }
 size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_logit_rows, int n_score) {
   if (!m || B < 1 || S < 1) return 0;

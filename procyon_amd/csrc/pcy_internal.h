@@ -250,12 +250,22 @@ struct PcyExtAttnArgs {
   const uint8_t* keep; int ld_keep;            // optional [B, ld_keep] key mask in logical slots, non-zero = kept
   int B, S, H, Hkv, dh, t_past;                // query s of a row sits at logical slot t_past + s and attends slots [0, t_past + s]
   float scale;
+  // Grouped mode (pcy_attn_extend_grouped; all nullptr / 0 = the uniform description above, exactly).  The rows of the call are n_groups
+  // contiguous groups: group g = rows [g_row0[g], g_row0[g + 1]) reads prefix row g, whose first g_len[g] <= Tp slots are real; the row's own
+  // panel follows right behind them.  Logical slot j < g_len[g] is prefix[g][j] (panel stride Tp), slot j >= g_len[g] is own[b][j - g_len[g]];
+  // `t_past` then counts the tokens already in the OWN panel (t_own): the row's past length is g_len[g] + t_past.  rows_per_prefix is not read.
+  const int32_t* g_row0;                       // DEVICE [n_groups + 1]
+  const int32_t* g_len;                        // DEVICE [n_groups]
+  const int32_t* g_row_grp;                    // DEVICE [B] row -> group
+  int n_groups, g_max_rows;                    // g_max_rows: the largest group (sizes the packed grid)
 };
 bool pcy_launch_attn_extend(hipStream_t s, const PcyExtAttnArgs& a);   // false = head_dim not covered (64 / 128), nothing launched
 // the same operator, same bits, with the query slots of a workgroup packed over the rows of a prompt and the query heads of a kv head
 // (attn_ext_packed_kernel): the shared prefix is staged once per 64 packed queries
 bool pcy_launch_attn_extend_packed(hipStream_t s, const PcyExtAttnArgs& a);
 void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past);   // pos[b*S + s] = t_past + s
+// grouped sibling: pos[b*S + s] = g_len[g_row_grp[b]] + t_own + s
+void pcy_launch_ext_pos_grouped(hipStream_t s, int32_t* pos, int B, int S, int t_own, const int32_t* g_len, const int32_t* g_row_grp);
 struct PcyGemvArgs;
 // decode attention + o projection (EPI_RESID GEMV over the attention output) in one launch; false = shape not covered,
 // nothing launched.  epoch: device word that differs between consecutive calls on the same `flags` (max_flags words).

@@ -174,11 +174,13 @@ class Context:
                                          _p(sin_t), _p(keep), B, H, Hkv, dh, Tmax), "pcy_attn_decode")
         return o
 
-    def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, packed=False):
+    def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, packed=False, groups=None):
         """pcy_attn_extend: qkv [B*S, (H+2Hkv)*dh] un-roped projections of S new tokens per row (row b*S+s; B rows, default the cache's);
         `cache` a KVCache (plain or shared-prefix) that holds t_past tokens per row.  Ropes q / k in place at t_past + s, appends K / V at
         logical slots t_past .. of layer `layer`, -> o [B*S, H*dh].  keep: [B, cache.capacity] uint8 in logical slots or None.
-        packed: pcy_attn_extend_packed -- the queries of a prompt's rows and of a kv head's query heads share workgroups (same bits)."""
+        packed: pcy_attn_extend_packed -- the queries of a prompt's rows and of a kv head's query heads share workgroups (same bits).
+        groups: a grouped cache (`new_grouped_cache`) whose tables describe the rows -- pcy_attn_extend_grouped on `cache`; t_past then counts the
+        tokens already in the rows' OWN panels (t_own)."""
         _chk_bf16(qkv)
         B = cache.B if B is None else int(B)
         S = qkv.shape[0] // B
@@ -186,6 +188,11 @@ class Context:
         if keep is not None:
             assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, cache.capacity), (keep.shape, keep.dtype)
         o = torch.empty(B * S, H * dh, dtype=BF16, device=qkv.device)
+        if groups is not None:
+            ga = groups.groups_arg(t_past)
+            L.check(self.lib.pcy_attn_extend_grouped(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), C.byref(ga), int(layer), _p(o), H * dh, _p(cos_t),
+                                                     _p(sin_t), _p(keep), B, S, H, Hkv, dh, int(bool(packed))), "pcy_attn_extend_grouped")
+            return o
         fn = self.lib.pcy_attn_extend_packed if packed else self.lib.pcy_attn_extend
         L.check(fn(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), H * dh, int(t_past), _p(cos_t), _p(sin_t), _p(keep),
                    B, S, H, Hkv, dh), "pcy_attn_extend")
@@ -443,9 +450,61 @@ class KVCache:
         """logical key slots per row: what the position counter and the keep mask count in"""
         return self.prefix_T + self.Tmax
 
+    @classmethod
+    def grouped(cls, cfg, device, prefix: "KVCache", group_rows, group_len, suffix_slots):
+        """A cache whose rows are GROUPS over the rows of `prefix` (LlamaEngine.new_grouped_cache; include/pcy.h, pcy_prefix_groups): group g
+        = group_rows[g] contiguous rows that read the first group_len[g] slots of prefix row g, their own panels right behind.  Holds the host
+        lists and the device tables of the call argument; `c.rows_per_prefix` is 0, which every entry but the grouped ones refuses."""
+        rows, lens = [int(r) for r in group_rows], [int(n) for n in group_len]
+        if prefix is None or prefix.prefix is not None:
+            raise ValueError("grouped cache: the prefix must be a plain cache")
+        if not rows or len(rows) != len(lens):
+            raise ValueError(f"grouped cache: {len(rows)} group_rows for {len(lens)} group_len (at least one group each)")
+        if len(rows) > prefix.B:
+            raise ValueError(f"grouped cache: {len(rows)} groups on a prefix cache of {prefix.B} rows")
+        if min(rows) < 1:
+            raise ValueError(f"grouped cache: group_rows {rows}: every group holds at least one row")
+        if min(lens) < 1 or max(lens) > prefix.Tmax:
+            raise ValueError(f"grouped cache: group_len {lens} outside [1, {prefix.Tmax}]")
+        if int(suffix_slots) < 1:
+            raise ValueError(f"grouped cache: suffix_slots={suffix_slots}")
+        self = cls.__new__(cls)
+        B = sum(rows)
+        self.k = torch.zeros(cfg.n_layers, B, cfg.n_kv_heads, int(suffix_slots), cfg.head_dim, dtype=BF16, device=device)
+        self.v = torch.zeros_like(self.k)
+        self.B, self.Tmax, self.prefix, self.rows_per_prefix = B, int(suffix_slots), prefix, 0
+        self.group_rows, self.group_len = rows, lens
+        self.c = L.KvCache(self.k.data_ptr(), self.v.data_ptr(), B, self.Tmax, prefix.k.data_ptr(), prefix.v.data_ptr(), prefix.B, prefix.Tmax, 0)
+        row0 = [0]
+        for r in rows:
+            row0.append(row0[-1] + r)
+        self.row_group = [g for g, r in enumerate(rows) for _ in range(r)]
+        i32 = lambda x: torch.tensor(x, dtype=torch.int32)
+        self.d_row0, self.d_len, self.d_row_grp = _h2d_many([i32(row0), i32(lens), i32(self.row_group)], torch.device(device))
+        self._h_rows, self._h_len = (C.c_int32 * len(rows))(*rows), (C.c_int32 * len(lens))(*lens)
+        return self
+
+    def groups_arg(self, t_own):
+        """the pcy_prefix_groups of a call with t_own tokens already in the rows' own panels (the tables live as long as the cache)"""
+        return L.PrefixGroups(len(self.group_rows), int(t_own), self._h_rows, self._h_len, self.d_row0.data_ptr(), self.d_len.data_ptr(),
+                              self.d_row_grp.data_ptr())
+
+    @property
+    def is_grouped(self):
+        return getattr(self, "group_rows", None) is not None
+
+    def row_len(self):
+        """[B] prefix length of every row of a grouped cache"""
+        return torch.tensor([self.group_len[g] for g in self.row_group])
+
     def layer(self, l, t):
         if self.prefix is None:
             return self.k[l, :, :, :t], self.v[l, :, :, :t]
+        if self.is_grouped:
+            # (tests / debugging only) per row: its group's real prefix slots, then t of its own -> lists of [Hkv, len + t, dh]
+            ks = [torch.cat([self.prefix.k[l, g, :, :self.group_len[g]], self.k[l, b, :, :t]], 1) for b, g in enumerate(self.row_group)]
+            vs = [torch.cat([self.prefix.v[l, g, :, :self.group_len[g]], self.v[l, b, :, :t]], 1) for b, g in enumerate(self.row_group)]
+            return ks, vs
         # (tests / debugging only: the logical [B, Hkv, t, dh] rows materialised, prefix rows repeated + suffix)
         Tp = self.prefix_T
         rows = torch.arange(self.B, device=self.k.device) // self.rows_per_prefix
@@ -623,6 +682,12 @@ class LlamaEngine:
 
     new_beam_cache = new_shared_cache   # (prefix_cache, beam, max_new): the same call in the beam search's words
 
+    def new_grouped_cache(self, prefix_cache: KVCache, group_rows, group_len, suffix_slots):
+        """A cache of sum(group_rows) rows in groups: group g = group_rows[g] contiguous rows that share the first group_len[g] slots of row g of
+        `prefix_cache` (RIGHT-padded prompts: the real tokens start at position 0) and own `suffix_slots` slots each, right behind their prefix.
+        What `extend(cache, embeds, own_past=...)` runs on; ValueError for tables the library would refuse."""
+        return KVCache.grouped(self.cfg, self.device, prefix_cache, group_rows, group_len, suffix_slots)
+
     def embed_tokens(self, ids, soft=None, soft_map=None):
         """ids [B,T] int -> [B,T,d]; soft-token splice of `_prepare_input_embeddings` if soft_map given."""
         B, T = ids.shape
@@ -719,25 +784,44 @@ class LlamaEngine:
         self._scatter_nll(token_nll, bt_d, nll)
         return token_nll, n, (logits if logit_rows is not None else None)
 
-    def extend(self, cache: KVCache, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False, packed=False):
+    def extend(self, cache: KVCache, embeds, t_past=None, keep=None, logit_rows=None, labels=None, want_hidden=False, packed=False, own_past=None):
         """S more tokens per row against a cache that holds t_past tokens per row (pcy_llama_extend; HF's forward(inputs_embeds [B,S],
         past_key_values)).  embeds [B,S,d] bf16; cache plain or shared-prefix (`new_shared_cache`); keep [B, >= t_past + S] (0 = masked key,
         old and new slots alike) or None; logit_rows "all" / "last" / flat rows b*S+s / None; labels [B,S] in HF's convention (-100 = not
         scored): token_nll[b, s+1] = -log p(token s+1 | everything up to s, the cached prefix included), 0 elsewhere.
         -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens).  K / V of slots [t_past, t_past+S) are written.
         packed: pcy_llama_extend_packed -- the attention packs the queries of a prompt's rows into shared workgroups (same bits; it pays when
-        many rows per prefix carry few new tokens each)."""
+        many rows per prefix carry few new tokens each).
+        A grouped cache (`new_grouped_cache`) takes `own_past` (default 0) instead of t_past: the tokens already in the rows' own panels; row b
+        of group g then holds group_len[g] + own_past tokens, and keep [B, >= max over the rows of that + S] is in the row's own logical slots
+        (pcy_llama_extend_grouped)."""
         B, S, d = embeds.shape
         dev = self.device
         embeds = embeds.contiguous()
         _chk_bf16(embeds)
+        grouped = cache.is_grouped
+        if grouped:
+            if t_past is not None:
+                raise ValueError("extend: a grouped cache takes own_past (the tokens in the rows' own panels), not t_past")
+            own_past = 0 if own_past is None else int(own_past)
+            if B != cache.B:
+                raise ValueError(f"extend: {B} rows on a grouped cache of {cache.B}")
+            row_end = cache.row_len() + own_past + S                             # [B] keys of every row after the append
+            t_past = int(row_end.max()) - S
+        else:
+            if own_past is not None:
+                raise ValueError("extend: own_past belongs to a grouped cache (new_grouped_cache); this cache takes t_past")
+            if t_past is None:
+                raise ValueError("extend: t_past missing")
+            row_end = None
         t_past = int(t_past)
         keep_d = None
         if keep is not None:
             kp = (torch.as_tensor(keep) != 0)
             if kp.dim() != 2 or kp.shape[0] != B or kp.shape[1] < min(t_past + S, cache.capacity):
                 raise ValueError(f"keep {tuple(kp.shape)}: expected [{B}, >= {t_past + S}]")
-            if not bool(kp[:, :t_past + S].all()):
+            live = kp[:, :t_past + S] if row_end is None else (kp[:, :t_past + S] | (torch.arange(t_past + S)[None] >= row_end[:, None]))
+            if not bool(live.all()):
                 keep_d = torch.zeros(B, cache.capacity, dtype=torch.uint8, device=dev)   # (row stride = the logical capacity)
                 n = min(kp.shape[1], cache.capacity)
                 keep_d[:, :n] = kp[:, :n].to(dev, torch.uint8)
@@ -745,9 +829,15 @@ class LlamaEngine:
         logits = torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
         hidden = torch.empty(B, S, d, dtype=BF16, device=dev) if want_hidden else None
         n, srows, tg, bt_d, nll, token_nll = self._score_upload(labels, B, S) if labels is not None else (0,) + (None,) * 5
-        fn = self.ctx.lib.pcy_llama_extend_packed if packed else self.ctx.lib.pcy_llama_extend
-        L.check(fn(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
-                   _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
+        if grouped:
+            ga = cache.groups_arg(own_past)
+            L.check(self.ctx.lib.pcy_llama_extend_grouped(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(ga), _p(embeds), _p(keep_d), B, S,
+                                                          int(bool(packed)), _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n,
+                                                          _p(nll)), "pcy_llama_extend_grouped")
+        else:
+            fn = self.ctx.lib.pcy_llama_extend_packed if packed else self.ctx.lib.pcy_llama_extend
+            L.check(fn(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
+                       _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
         self._scatter_nll(token_nll, bt_d, nll)
         return (logits if logit_rows is not None else None), hidden, token_nll, n
 

@@ -205,6 +205,132 @@ def shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_i
                 answer_rows=(torch.arange(B) * S + ap - Tp).to(torch.int32))
 
 
+def shared_prefix_groups(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id):
+    """Host side of `UnifiedProCyon.forward(share_prefix="groups")`: a QA batch that mixes several shared prefixes (receptors), cut into
+    GROUPS of rows with a prefix each.  Pure: no device, no model.  Arguments as `shared_prefix_plan`.
+      key     of a row: its real tokens in front of its last soft-token slot in front of its last [ANSWER] (in front of the [ANSWER] if no
+              slot lies there), soft slots compared by their source
+      groups  rows with equal keys, numbered in order of first appearance
+      cut     within a group exactly what `shared_prefix_plan` returns for the group's rows: a one-group batch reproduces that plan
+    -> dict:
+      order [B] / inverse [B]          rows sorted by group (stable): sorted row i is caller row order[i]; inverse[order[i]] == i
+      group_rows / group_len [n]       rows per group; the group's Tp (0 = the group shares nothing: there is no grouped call for such a batch)
+      prefix_rows [n]                  the first caller row of every group: its columns [0, group_len[g]) are the group's prefix
+      prefix_T, S, B, n_groups         max(group_len); the longest suffix over all groups
+      suffix_ids / suffix_mask [B, S]  in SORTED order: tokens [group_len[g], answer_pos] of every row, right-padded with pad_id / 0
+      answer_pos [B]                   caller order, position in the full row
+      answer_rows [B] int32            flat row i * S + answer_pos - group_len[g] of the sorted [B, S] suffix batch
+    ValueError: as `shared_prefix_plan`."""
+    shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id)       # (the argument errors, stated once)
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    B, T = ids.shape
+    is_slot = torch.zeros_like(mask)
+    for i in soft_slot_ids:
+        is_slot |= ids == int(i)
+    is_slot &= mask
+    is_ans = (ids == int(answer_idx)) & mask
+    answer_pos = (T - 1 - is_ans.flip(1).int().argmax(1)).tolist()
+    id_rows, slot_rows = ids.tolist(), is_slot.tolist()
+    groups, members = {}, []
+    for r in range(B):
+        slot_cols = [c for c, f in enumerate(slot_rows[r]) if f]
+        front = [c for c in slot_cols if c < answer_pos[r]]
+        end = front[-1] if front else answer_pos[r]
+        row = id_rows[r][:end]
+        for c, src in zip(slot_cols, slot_sources[r]):            # a slot is what feeds it, not its token
+            if c < end:
+                row[c] = ("slot", src)
+        key = tuple(row)
+        if key not in groups:
+            groups[key] = len(members)
+            members.append([])
+        members[groups[key]].append(r)
+    order = [r for rows in members for r in rows]
+    inverse = [0] * B
+    for i, r in enumerate(order):
+        inverse[r] = i
+    plans = [shared_prefix_plan(ids[rows], mask[rows], [slot_sources[r] for r in rows], answer_idx, soft_slot_ids, pad_id) for rows in members]
+    group_len = [p["Tp"] for p in plans]
+    S = max(p["S"] for p in plans)
+    suffix_ids = torch.full((B, S), int(pad_id), dtype=torch.long)
+    suffix_mask = torch.zeros(B, S, dtype=torch.long)
+    i = 0
+    for p in plans:
+        suffix_ids[i:i + p["B"], :p["S"]] = p["suffix_ids"]
+        suffix_mask[i:i + p["B"], :p["S"]] = p["suffix_mask"]
+        i += p["B"]
+    ap = torch.tensor(answer_pos, dtype=torch.long)
+    row_len = torch.tensor([n for n, rows in zip(group_len, members) for _ in rows], dtype=torch.long)
+    return dict(order=torch.tensor(order), inverse=torch.tensor(inverse), group_rows=[len(rows) for rows in members], group_len=group_len,
+                prefix_rows=[rows[0] for rows in members], prefix_T=max(group_len), S=S, B=B, n_groups=len(members), suffix_ids=suffix_ids,
+                suffix_mask=suffix_mask, answer_pos=ap, answer_rows=(torch.arange(B) * S + ap[order] - row_len).to(torch.int32))
+
+
+def candidate_plan_groups(tokenize, label_rule, instructions, candidates, answer_idx, pad_id):
+    """`candidate_plan` for RAGGED candidate lists (`score_candidates(ragged=True)`): P prompts with len(candidates[p]) >= 1 texts each.  The
+    rows are cut as there (in front of the last [ANSWER]; same ValueErrors but the one on unequal lists), prompt after prompt; what differs:
+      prefix_ids / prefix_mask [P, Tp]   the prefixes RIGHT-padded: every prompt starts at position 0, where `score_text` has it
+      group_rows / group_len [P]         candidates per prompt; real tokens of every prefix -- the tables of `LlamaEngine.new_grouped_cache`
+      suffix_ids / suffix_mask / suffix_labels [R, S], cut [R]   R = sum(group_rows) rows
+      n_candidates [P], row_of [P, Nmax] the row of candidate (p, n), -1 in the padding; n_tokens [P, Nmax], 0 in the padding
+      P, Nmax, R, Tp, S"""
+    P = len(instructions)
+    if len(candidates) != P or P == 0:
+        raise ValueError(f"{len(candidates)} candidate lists for {P} prompts")
+    if any(len(c) < 1 for c in candidates):
+        raise ValueError(f"every prompt needs at least one candidate, got {[len(c) for c in candidates]}")
+    owner = [(p, n) for p in range(P) for n in range(len(candidates[p]))]
+    texts = [instructions[p] + " " + candidates[p][n] for p, n in owner]
+    ids, mask = tokenize(texts)
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    R = len(owner)
+    for r in range(R):
+        if not bool(((ids[r] == answer_idx) & mask[r]).any()):
+            raise ValueError(f"row {r}: no [ANSWER] token in {texts[r]!r}")
+    labels = torch.as_tensor(label_rule(ids)).long().cpu()
+    prefixes, suffixes, suf_labels, cuts = [], [], [], []
+    for r, (p, n) in enumerate(owner):
+        n_real = int(mask[r].sum())
+        assert bool(mask[r, :n_real].all()), "rows must be right-padded"
+        cut = int((ids[r, :n_real] == answer_idx).nonzero().max())
+        if bool((labels[r, :cut + 1] != -100).any()):
+            raise ValueError(f"row {r}: labelled tokens in front of the last [ANSWER]; they lie in the shared prefix and cannot be scored by the extension")
+        if n == 0:
+            prefixes.append(ids[r, :cut])
+        elif not torch.equal(prefixes[-1], ids[r, :cut]):
+            raise ValueError(f"prompt {p}: candidate {n} changes the tokens in front of [ANSWER]; the candidates of a prompt must share its prefix")
+        cuts.append(cut)
+        suffixes.append(ids[r, cut:n_real])
+        suf_labels.append(labels[r, cut:n_real])
+    group_len = [int(t.numel()) for t in prefixes]
+    if min(group_len) == 0:
+        raise ValueError("[ANSWER] is the first token of a row: nothing to prefill")
+    Tp, S = max(group_len), max(int(t.numel()) for t in suffixes)
+    prefix_ids = torch.full((P, Tp), int(pad_id), dtype=torch.long)
+    prefix_mask = torch.zeros(P, Tp, dtype=torch.long)
+    for p, t in enumerate(prefixes):
+        prefix_ids[p, :t.numel()] = t
+        prefix_mask[p, :t.numel()] = 1
+    suffix_ids = torch.full((R, S), int(pad_id), dtype=torch.long)
+    suffix_mask = torch.zeros(R, S, dtype=torch.long)
+    suffix_labels = torch.full((R, S), -100, dtype=torch.long)
+    for r, (t, lb) in enumerate(zip(suffixes, suf_labels)):
+        suffix_ids[r, :t.numel()] = t
+        suffix_mask[r, :t.numel()] = 1
+        suffix_labels[r, :t.numel()] = lb
+    n_cand = [len(c) for c in candidates]
+    Nmax = max(n_cand)
+    row_of = torch.full((P, Nmax), -1, dtype=torch.long)
+    n_tokens = torch.zeros(P, Nmax, dtype=torch.long)
+    per_row = (suffix_labels[:, 1:] != -100).sum(1)
+    for r, (p, n) in enumerate(owner):
+        row_of[p, n] = r
+        n_tokens[p, n] = per_row[r]
+    return dict(prefix_ids=prefix_ids, prefix_mask=prefix_mask, group_rows=n_cand, group_len=group_len, suffix_ids=suffix_ids,
+                suffix_mask=suffix_mask, suffix_labels=suffix_labels, n_candidates=torch.tensor(n_cand), row_of=row_of, n_tokens=n_tokens,
+                cut=torch.tensor(cuts), P=P, Nmax=Nmax, R=R, Tp=Tp, S=S)
+
+
 def special_token_ids(tokenizer, text_encoder_fname):
     """The token ids `UnifiedProCyon.__init__` / `_init_tokenizer` keep (model_unified.py:1100-1133, 342-347), read from a
     tokenizer on which the eight ProCyon tokens are already registered (`procyon_amd.checkpoint.hf_tokenizer` does that in the
@@ -572,7 +698,13 @@ class UnifiedProCyon:
         out["prefix_plan"]; the answer logits differ from the ordinary path's by kernel rounding only; `outputs.logits` / `.loss` /
         `.hidden_states` beyond the answer rows come from the ordinary full pass on first access.  A batch that shares nothing (Tp = 0) takes
         the ordinary path.  Not with retrieval, compute_loss or full_logits (ValueError); not on the fp32 family, with structure tokens
-        (dropped at random per call) or with fp8 weights (NotImplementedError)."""
+        (dropped at random per call) or with fp8 weights (NotImplementedError).
+        share_prefix="groups": the batch may mix SEVERAL shared prefixes (receptors).  `shared_prefix_groups` sorts the rows into groups with a
+        prefix each; ONE prefill runs the n_groups prefixes (right-padded to the longest, under the mask) and ONE grouped `extend` runs every
+        row's end behind its own group's prefix, at the positions the ordinary pass gives it.  The answer logits come back in the caller's row
+        order; out["prefix_plan"] is the groups plan.  Same refusals; a batch with a group that shares nothing takes the ordinary path."""
+        if share_prefix not in (False, True, "groups"):
+            raise ValueError(f"forward: share_prefix={share_prefix!r} (False, True or \"groups\")")
         if return_mlm:
             raise NotImplementedError("return_mlm is a training path (model_unified.py:505-509)")
         self._require_bf16_or_fp32("forward")
@@ -603,7 +735,8 @@ class UnifiedProCyon:
         if retrieval and self.config.ret_token_access not in ('last', 'all'):
             raise NotImplementedError("Invalid option {} for ret_token_access".format(self.config.ret_token_access))
         if share_prefix:
-            out = self._forward_shared_prefix(inputs, emb, input_ids, attn_masks[:, :real], full_labels, answer_pos, real, get_full_labels, packed)
+            branch = self._forward_prefix_groups if share_prefix == "groups" else self._forward_shared_prefix
+            out = branch(inputs, emb, input_ids, attn_masks[:, :real], full_labels, answer_pos, real, get_full_labels, packed)
             if out is not None:
                 return out
         sum_all = retrieval and self.config.ret_token_access == 'all'
@@ -658,7 +791,6 @@ class UnifiedProCyon:
 
     def _forward_shared_prefix(self, inputs, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels, packed):
         """the share_prefix=True branch of `forward` behind `_preprocessing` (emb [B, real, d], am [B, real]); None = nothing is shared"""
-        from .pmc_llama import CausalLMOutput, _HiddenStates
         plan = shared_prefix_plan(input_ids[:, :real], am, self._slot_sources(inputs, input_ids[:, :real]), self.answer_idx,
                                   (self.prot_replacement_idx, self.drug_idx), self.tokenizer.pad_token_id)
         Tp, S, B = plan["Tp"], plan["S"], plan["B"]
@@ -673,6 +805,41 @@ class UnifiedProCyon:
         # suffixes of one length (the screening batches): no mask at all, the kernel takes its unmasked block path
         keep = None if bool(plan["suffix_mask"].all()) else torch.cat([torch.ones(B, Tp, dtype=torch.long), plan["suffix_mask"]], 1)
         logits, _, _, _ = eng.extend(cache, emb[:, Tp:Tp + S].contiguous(), Tp, keep=keep, logit_rows=plan["answer_rows"], packed=bool(packed))
+        return self._answer_rows_output(logits, plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels)
+
+    def _forward_prefix_groups(self, inputs, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels, packed):
+        """the share_prefix="groups" branch of `forward`; None = some group shares nothing (the ordinary path serves the batch)"""
+        plan = shared_prefix_groups(input_ids[:, :real], am, self._slot_sources(inputs, input_ids[:, :real]), self.answer_idx,
+                                    (self.prot_replacement_idx, self.drug_idx), self.tokenizer.pad_token_id)
+        if min(plan["group_len"]) == 0:
+            return None
+        Tp, S, B, n = plan["prefix_T"], plan["S"], plan["B"], plan["n_groups"]
+        eng = self.text_encoder.engine
+        glen = torch.tensor(plan["group_len"])
+        prefix_cache = eng.new_cache(n, Tp)
+        # the groups' prefixes RIGHT-padded to the longest: the real tokens start at position 0 (the columns behind a shorter prefix hold its
+        # first row's own tokens, masked as keys; their K / V slots are never addressed by the extension)
+        eng.prefill(emb[plan["prefix_rows"], :Tp].contiguous(), (torch.arange(Tp)[None] < glen[:, None]).long(), prefix_cache, logit_rows=None)
+        cache = eng.new_grouped_cache(prefix_cache, plan["group_rows"], plan["group_len"], S)
+        row_len = cache.row_len()                                                   # [B] in sorted order
+        order = plan["order"].to(emb.device)
+        cols = (row_len[:, None] + torch.arange(S)[None]).clamp(max=real - 1).to(emb.device)   # (clamped columns lie behind the row's [ANSWER]: masked)
+        suffix_emb = emb[order[:, None], cols].contiguous()
+        keep = None
+        if not bool(plan["suffix_mask"].all()):                                     # keep in the row's OWN logical slots: its prefix, then its suffix
+            keep = torch.zeros(B, Tp + S, dtype=torch.long)
+            for i in range(B):
+                keep[i, :int(row_len[i])] = 1
+                keep[i, int(row_len[i]):int(row_len[i]) + S] = plan["suffix_mask"][i]
+        logits, _, _, _ = eng.extend(cache, suffix_emb, keep=keep, logit_rows=plan["answer_rows"], packed=bool(packed))
+        return self._answer_rows_output(logits[plan["inverse"].to(logits.device)], plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels)
+
+    def _answer_rows_output(self, logits, plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels):
+        """what both shared-prefix branches return: the answer logits [B, V] (caller order) with the lazy rest of the ordinary pass"""
+        from .pmc_llama import CausalLMOutput, _HiddenStates
+        enc = self.text_encoder
+        eng = enc.engine
+        B = input_ids.shape[0]
         L1, labels = eng.cfg.n_layers + 1, full_labels[:, :real]
 
         def materialise():
@@ -703,7 +870,7 @@ class UnifiedProCyon:
         return {"token_nll": tn, "seq_nll": tn.sum(1), "n_tokens": n_tok, "loss": loss, "perplexity": torch.exp(loss)}
 
     @torch.no_grad()
-    def score_candidates(self, inputs, candidates, aaseq_type='protein', packed=False):
+    def score_candidates(self, inputs, candidates, aaseq_type='protein', packed=False, ragged=False):
         """Rank N candidate texts per prompt by teacher-forced likelihood WITHOUT running the prompt N times.  `inputs`: a caption / QA batch as
         `generate` takes it, every instruction ending in [ANSWER]; `candidates`: one list of N strings per prompt (the same N for all,
         ValueError otherwise).  Row (p, n) is scored as `score_text` scores `instructions[p] + " " + candidates[p][n]` -- same tokens, same
@@ -711,7 +878,11 @@ class UnifiedProCyon:
         [ANSWER] + candidate + eos run as one `LlamaEngine.extend` call on a cache whose rows share the prompts' K / V (`candidate_plan`).
         -> {"token_nll" [P,N,S] fp32 over the suffix tokens (0 where nothing is labelled), "seq_nll" [P,N], "n_tokens" [P,N], "mean_nll" [P,N] =
         seq_nll / n_tokens, "order" [P,N] = stable argsort of mean_nll, best first, "plan" = the `candidate_plan`, "cache" = the shared cache}.
-        packed: the extension runs the packed attention (`LlamaEngine.extend(packed=True)`): same bits."""
+        packed: the extension runs the packed attention (`LlamaEngine.extend(packed=True)`): same bits.
+        ragged=True: lists of any lengths >= 1 (`candidate_plan_groups`).  The prompts are RIGHT-padded -- every prompt sits at the positions
+        `score_text` gives it and no pad column runs in front of it -- and the suffixes run as one grouped `extend`.  The results are padded to
+        Nmax = the longest list: "n_candidates" [P]; in the padding token_nll = 0, n_tokens = 0, seq_nll = mean_nll = +inf, so that "order"
+        (stable argsort) puts it last."""
         self._require_bf16_or_fp32("score_candidates")
         if self._f32:
             raise NotImplementedError("score_candidates needs the bf16 engine (the fp32 family has no cache extension)")
@@ -721,6 +892,8 @@ class UnifiedProCyon:
             raise NotImplementedError("score_candidates: [EXT] text slots are not supported; write the text into the instruction")
         instructions = list(inputs["instructions"])
         tokenize = lambda texts: self._prepare_text_inputs_and_tokenize(texts, [[] for _ in texts], crop_off=True)
+        if ragged:
+            return self._score_candidates_ragged(inputs, candidates, aaseq_type, packed, tokenize)
         plan = candidate_plan(tokenize, self._full_labels, instructions, candidates, self.answer_idx, self.tokenizer.pad_token_id)
         P, N, Tp, S = plan["P"], plan["N"], plan["Tp"], plan["S"]
         soft_ids = (self.prot_replacement_idx, self.struct_idx, self.drug_idx)
@@ -740,6 +913,34 @@ class UnifiedProCyon:
         n_tokens = plan["n_tokens"].to(seq_nll.device)
         mean_nll = seq_nll / n_tokens
         return {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll,
+                "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
+
+    def _score_candidates_ragged(self, inputs, candidates, aaseq_type, packed, tokenize):
+        plan = candidate_plan_groups(tokenize, self._full_labels, list(inputs["instructions"]), candidates, self.answer_idx, self.tokenizer.pad_token_id)
+        P, Nmax, R, Tp, S = plan["P"], plan["Nmax"], plan["R"], plan["Tp"], plan["S"]
+        if any(bool((plan["suffix_ids"] == i).any()) for i in (self.prot_replacement_idx, self.struct_idx, self.drug_idx)):
+            raise ValueError("score_candidates: a candidate holds a soft-token slot")
+        _, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
+        prefix_emb, _ = self._prepare_input_embeddings(plan["prefix_ids"], protein_soft_tokens=protein_soft_tokens, drug_soft_tokens=drug_soft_tokens)
+        eng = self.text_encoder.engine
+        prefix_cache = eng.new_cache(P, Tp)
+        eng.prefill(prefix_emb, plan["prefix_mask"], prefix_cache, logit_rows=None)
+        cache = eng.new_grouped_cache(prefix_cache, plan["group_rows"], plan["group_len"], S)
+        row_len = cache.row_len()
+        keep = torch.zeros(R, Tp + S, dtype=torch.long)                              # in every row's own logical slots
+        for r in range(R):
+            keep[r, :int(row_len[r])] = 1
+            keep[r, int(row_len[r]):int(row_len[r]) + S] = plan["suffix_mask"][r]
+        _, _, row_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), keep=keep, labels=plan["suffix_labels"], packed=bool(packed))
+        row_of = plan["row_of"].to(row_nll.device)
+        real = row_of >= 0
+        token_nll = torch.zeros(P, Nmax, S, dtype=row_nll.dtype, device=row_nll.device)
+        token_nll[real] = row_nll[row_of[real]]
+        inf = torch.full((P, Nmax), float("inf"), dtype=row_nll.dtype, device=row_nll.device)
+        seq_nll = torch.where(real, token_nll.sum(2), inf)
+        n_tokens = plan["n_tokens"].to(row_nll.device)
+        mean_nll = torch.where(real, seq_nll / n_tokens, inf)
+        return {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll, "n_candidates": plan["n_candidates"],
                 "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
 
     # ------------------------------------------------------------------------------------------

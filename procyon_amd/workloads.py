@@ -194,12 +194,13 @@ def config5_inputs(pairs=256, chunk=64, seed=7):
 def score_pairs(model, pairs=256, chunk=64, first=0, count=None, share_prefix=False):
     """-> (P(yes), P(no)) [count, 2] fp32 and a 1/61 sample of every answer-row logit vector, for pairs [first, first + count) of the
     `pairs`-pair workload (default: all of them), `chunk` prompts per forward call.  share_prefix: the rows of a chunk differ in their last
-    protein slot only; `forward(share_prefix=True)` prefills what they share once per chunk"""
+    protein slot only; `forward(share_prefix=True)` prefills what they share once per chunk.  The value is passed through: "groups" serves
+    chunks that mix several receptors (one prefill of the groups' prefixes, one grouped extension)"""
     make, _ = config5_inputs(pairs, chunk)
     count = pairs if count is None else count
     ys, ls = [], []
     for lo in range(first, first + count, chunk):
-        kw = dict(share_prefix=True) if share_prefix else {}
+        kw = dict(share_prefix=share_prefix) if share_prefix else {}
         lg = model.forward(make(lo, min(chunk, first + count - lo)), retrieval=False, **kw)["outputs"].answer_logits[:, 0]
         # the reference's read-out (data/inference_utils.py:582-604): softmax over the vocabulary in the model dtype, then the yes / no columns
         from .engine import Context

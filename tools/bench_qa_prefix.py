@@ -18,8 +18,17 @@ between the sides.  Then the attention operator alone (pcy_attn_extend / pcy_att
 rope, K / V append and the attention launch -- the first three are the same launches on both sides), us per call at S in {3, 32} and
 rows_per_prefix in {16, 64}, 64 rows, interleaved the same way.
 
+`--groups G` measures something else and nothing of the above: the chunk of `--rows` rows spread over G receptors, rows / G each
+(the receptor slots of group g read another protein; the rows of a group still differ in the peptide of the last slot; every call carries
+only the proteins its own rows read), end to end:
+  A  model.forward(inputs, share_prefix="groups")                 ONE prefill of the G prefixes + ONE grouped extension
+  P  G calls of model.forward(inputs of one receptor, share_prefix=True)   (the parent's way for this batch: chunk by receptor)
+  F  model.forward(inputs)                                        (the ordinary pass, for scale)
+interleaved APF / FPA; prints ms per batch of every side (median) and the per-round ratio A / P as min . median . max.
+
   python tools/bench_qa_prefix.py
-  python tools/bench_qa_prefix.py --pairs 1 --layers 4"""
+  python tools/bench_qa_prefix.py --pairs 1 --layers 4
+  python tools/bench_qa_prefix.py --groups 4"""
 import argparse
 import os
 import statistics
@@ -43,6 +52,7 @@ ap.add_argument("--pairs", type=int, default=5)
 ap.add_argument("--block-ms", type=float, default=300.0)
 ap.add_argument("--layers", type=int, default=0, help="decoder layers (0 = the geometry's 32)")
 ap.add_argument("--attn-reps", type=int, default=200)
+ap.add_argument("--groups", type=int, default=0, help="G > 0: the rows spread over G receptors, forward(share_prefix=\"groups\") against G calls of share_prefix=True")
 args = ap.parse_args()
 
 g = dict(GEOMETRIES["full"]["llama"])
@@ -85,6 +95,51 @@ def ratio_line(ms, num, den):
 
 # ---- end to end: UnifiedProCyon.forward on a chunk of the pair workload
 make, _ = workloads.config5_inputs(256, B)
+
+if args.groups:
+    G = args.groups
+    per = B // G
+    assert per * G == B, f"--rows {B} is no multiple of --groups {G}"
+    receptors = [0] + [3 + 200 + j for j in range(1, G)]        # group 0 keeps the 805-residue receptor, the others read another protein
+
+
+    def part(lo, hi):
+        inp = make(0)
+        seq = [[receptors[i // per], 1, receptors[i // per], 2, receptors[i // per], 3 + i] for i in range(lo, hi)]
+        used = sorted({j for row in seq for j in row})           # every call carries (and encodes) only the proteins its rows read
+        new = {j: n for n, j in enumerate(used)}
+        inp["data"]["seq"] = inp["data"]["seq"][used].clone()
+        inp["data"]["seq_idx"] = torch.arange(len(used))
+        seq = [[new[j] for j in row] for row in seq]
+        inp["input"] = {"seq": seq, "text": [[] for _ in seq], "drug": None}
+        inp["instructions"] = inp["instructions"][lo:hi]
+        return inp
+
+
+    def side_p():
+        return torch.cat([model.forward(part(j * per, (j + 1) * per), retrieval=False, share_prefix=True)["outputs"].answer_logits[:, 0] for j in range(G)])
+
+
+    e2e = {"A": lambda: model.forward(part(0, B), retrieval=False, share_prefix="groups")["outputs"].answer_logits[:, 0],
+           "P": side_p,
+           "F": lambda: model.forward(part(0, B), retrieval=False)["outputs"].answer_logits[:, 0]}
+    plan = model.forward(part(0, B), retrieval=False, share_prefix="groups")["prefix_plan"]
+    one = model.forward(part(0, per), retrieval=False, share_prefix=True)["prefix_plan"]
+    reps, outs = {}, {}
+    for k, fn in e2e.items():
+        outs[k] = fn().float()
+        ctx.sync()
+        t0 = time.perf_counter(); fn(); ctx.sync()
+        reps[k] = max(1, int(args.block_ms / max((time.perf_counter() - t0) * 1e3, 1e-3)))
+    ms = interleaved(e2e, args.pairs, reps, "ms", 1.0, f"groups={G}", wall=True)
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    print(f"SUMMARY groups={G} rows={B} ({per} per receptor) group_len={plan['group_len']} S={plan['S']} (one receptor alone: Tp={one['Tp']} S={one['S']}) "
+          f"layers={eng.cfg.n_layers}: A {med['A']:.3f} P {med['P']:.3f} F {med['F']:.3f} ms/batch wall (median of {args.pairs}); {ratio_line(ms, 'A', 'P')}; "
+          f"{ratio_line(ms, 'A', 'F')}; token rows A = P {sum(plan['group_len']) + B * plan['S']} F {B * args.t}; "
+          f"max |logits_A - logits_P| {float((outs['A'] - outs['P']).abs().max()):.3e} A and P bit-equal: {bool(torch.equal(outs['A'], outs['P']))}; "
+          f"max |logits_A - logits_F| {float((outs['A'] - outs['F']).abs().max()):.3e} (max |logit| {float(outs['F'].abs().max()):.3e})", flush=True)
+    sys.exit(0)
+
 e2e = {"A": lambda: model.forward(make(0), retrieval=False),
        "B": lambda: model.forward(make(0), retrieval=False, share_prefix=True, packed=False),
        "C": lambda: model.forward(make(0), retrieval=False, share_prefix=True)}
