@@ -361,6 +361,46 @@ int pcy_llama_decode_graph(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*,
  * statistics, one rounding.  -inf logits are allowed and mean "never chosen" (banned tokens, also whole runs of them); a row must hold
  * at least one finite logit; NaN logits are outside the contract. */
 int pcy_greedy_pick(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int advance_pos);
+/* ---- greedy decoding with lookahead: several drafted tokens checked per pass over the weights ----
+ * One prompt.  A pass is pcy_llama_extend with S = W rows at t_past = *pos: row 0 is the last committed token, rows 1..W-1 are drafts of
+ * the tokens behind it.  Between two passes, on the device: pcy_look_verify (pick every row, count the leading drafts that were right, commit)
+ * and pcy_look_draft (draft again, gather the W embedding rows).  A pass ALWAYS has W rows, also when fewer tokens remain: the projections'
+ * tile and K-split choices depend on the row count, so only a fixed count keeps a token's bits independent of the drafts.
+ * The state below works beside an ordinary one-row pcy_gen_state, of which pos, step, next_tok, tokens_out, logprob, logits_all and max_steps
+ * are used; every pointer is device memory.
+ *   hist     [cap] the prompt's token ids followed by every committed token; a negative entry is a slot that is no text token (soft-token
+ *            slots, anything the caller wants kept out of the lookup): it never matches and ends a draft
+ *   n_hist   device scalar, 1 <= *n_hist <= cap (appends beyond cap are dropped)
+ *   window   [W] row 0 = the last committed token (the caller sets it once, before the first draft), rows 1..W-1 = the drafts
+ *   forced   optional [max_steps] (NULL: none): forced[i] >= 0 replaces the draft of output token i -- how tests and measurements dictate
+ *            the acceptance
+ *   counters [2 + W] zero-initialised: [0] passes, [1] committed tokens, [2 + k] passes that committed k drafts (k + 1 tokens)
+ *   last     [4] of the latest pcy_look_verify: leading drafts that were right, tokens committed, *step and *pos before the commit
+ * Draft rule: with h = hist[0, n), for g = ngram_max down to ngram_min take the LARGEST i with i + g < n, h[i..i+g) == h[n-g..n) and every
+ * compared entry >= 0; draft j = h[i+g+j], j = 0, 1, ... until the history ends, an entry is negative or W-1 drafts are filled; every draft
+ * not filled that way (all of them when no g matches) is h[n-1].  (procyon_amd.engine.lookup_draft restates it on the host.) */
+typedef struct {
+  int32_t* hist;
+  int32_t* n_hist;
+  int32_t* window;
+  const int32_t* forced;
+  int32_t* counters;
+  int32_t* last;
+  int32_t cap, W;            /* 2 <= W <= 32 */
+  int32_t ngram_max, ngram_min;   /* 1 <= ngram_min <= ngram_max <= 16 */
+} pcy_look_state;
+/* window[1..W) by the rule above, then embeds_out [W, d] bf16 = embed[window[r]] (bit copies of the table's rows).  d % 8 == 0. */
+int pcy_look_draft(pcy_ctx*, const pcy_llama_desc*, const pcy_look_state*, const pcy_gen_state*, void* embeds_out);
+/* logits [W, vocab] bf16 of the pass.  Per row the argmax and bf16 log_softmax(logits)[argmax] with the selection rule and the bits of
+ * pcy_greedy_pick (lowest index on ties, -inf = never chosen, fp32 statistics, one rounding; the same device code).  a = the number of leading
+ * drafts j with window[j+1] == argmax(row j); n = min(a + 1, max_steps - *step) tokens are committed: the argmaxes of rows 0..n-1 go to
+ * tokens_out[*step..] and hist, their log-probabilities are added to logprob[0] in row order, rows 0..n-1 of the logits to rows *step.. of
+ * logits_all (when kept; pinned host memory works), next_tok[0] = window[0] = the last of them, *pos += n, *step += n.  Deterministic.
+ * The K / V of rejected rows stay in slots [*pos, ...) behind the new *pos; the next W-row pass rewrites them before any query reads them. */
+int pcy_look_verify(pcy_ctx*, const pcy_llama_desc*, const pcy_look_state*, const pcy_gen_state*, const void* logits);
+/* calls since the library was loaded -- 0: pcy_look_draft, 1: pcy_look_verify (= passes); anything else reads 0.  Words of their own, as
+ * pcy_debug_extend_grouped_count: the kinds of pcy_debug_dispatch_count are pinned. */
+unsigned long long pcy_debug_look_count(int which);
 /* n_steps x (decode + pick) with no host synchronisation; use_graph != 0 replays a captured hipGraph */
 int pcy_llama_greedy(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int n_steps,
                      int use_graph);

@@ -70,6 +70,12 @@ class GenState(C.Structure):
                 ("logits_all", vp), ("keep", vp), ("max_steps", i32), ("logits_all_ld", i32)]
 
 
+class LookState(C.Structure):
+    # (pcy_look_state: the device-side state of greedy decoding with lookahead, beside a one-row GenState)
+    _fields_ = [("hist", vp), ("n_hist", vp), ("window", vp), ("forced", vp), ("counters", vp), ("last", vp), ("cap", i32), ("W", i32),
+                ("ngram_max", i32), ("ngram_min", i32)]
+
+
 class BeamState(C.Structure):
     _fields_ = [("out", vp), ("max_len", i32), ("cur", vp), ("cur_new", vp), ("next_tok", vp), ("src", vp), ("anc", vp),
                 ("has_eos", vp), ("blk_eos", vp), ("ticket", vp), ("pos", vp), ("step", vp), ("done", vp), ("eos_id", i32)]
@@ -139,6 +145,9 @@ SIGNATURES = {
     "pcy_llama_decode_layers": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
     "pcy_llama_decode_graph": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_greedy_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
+    "pcy_look_draft": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
+    "pcy_look_verify": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
+    "pcy_debug_look_count": (C.c_ulonglong, [ci]),
     "pcy_llama_greedy": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci]),
     "pcy_sample_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp, vp]),
     "pcy_llama_sample": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp]),

@@ -2,6 +2,7 @@
 // KV scatter, V transpose, protein pooler, greedy pick.  All 16-byte vectorised along the feature
 // dimension, fp32 math, bf16 rounding exactly where the reference's torch ops round.
 #include "pcy_internal.h"
+#include "pcy_pick.h"
 
 namespace {
 
@@ -411,9 +412,7 @@ __global__ __launch_bounds__(NT) void pool_finish_kernel(const float* __restrict
 // two stages so the 128k-entry vocabulary is scanned by 64 workgroups instead of one:
 //   stage 1: block c of row b scans a contiguous chunk -> (max, lowest argmax, sum exp(x - local max))
 //   stage 2: one wave per row merges the 64 partials, picks the token, adds bf16 log_softmax(logits)[tok]
-constexpr int PICK_NT = 256;
-constexpr int PICK_NB = 64;
-struct PickPartial { float mx; int idx; float se; int pad; };
+// (PICK_NT, PICK_NB, PickPartial and the row merge of stage 2: pcy_pick.h, shared with the lookahead verify kernel)
 
 __global__ __launch_bounds__(PICK_NT) void pick_stage1_kernel(const bf16_t* __restrict__ logits, int V, PickPartial* __restrict__ part) {
   __shared__ float redv[PICK_NT / 64];
@@ -457,20 +456,11 @@ __global__ __launch_bounds__(256) void pick_stage2_kernel(const bf16_t* __restri
   const int l = threadIdx.x & 63;
   const int step = *step_dev;
   for (int b = threadIdx.x >> 6; b < B; b += 4) {
-    const PickPartial pp = part[b * PICK_NB + l];
-    float best = pp.mx;
-    int bi = pp.idx;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    float se = pp.se * expf(pp.mx - best);   // empty chunks: mx = -inf -> exp(-inf) = 0
-    se = wave_sum(se);
+    float best, se;
+    int bi;
+    pick_merge_row(part[b * PICK_NB + l], best, bi, se);
     if (l == 0) {
-      // log_softmax in model dtype: bf16( x - max - log(sum exp(x - max)) ), x[tok] == max
-      const float lsm = rbf((bf2f(logits[(size_t)b * V + bi]) - best) - logf(se));
+      const float lsm = pick_logprob(logits + (size_t)b * V, bi, best, se);
       logprob[b] += lsm;
       next_tok[b] = bi;
       tokens_out[(size_t)b * max_steps + step] = bi;
@@ -1450,6 +1440,9 @@ void pcy_launch_pool(hipStream_t s, const bf16_t* h, int d, const int32_t* seg, 
   int* wcnt = reinterpret_cast<int*>(wsum + (size_t)nprot * POOL_CH * d);
   hipLaunchKernelGGL(pool_partial_kernel, dim3(nprot, (d + 511) / 512, POOL_CH), dim3(NT), 0, s, h, d, seg, rng, mode, wsum, wcnt);
   hipLaunchKernelGGL(pool_finish_kernel, dim3(nprot, (d + NT - 1) / NT), dim3(NT), 0, s, wsum, wcnt, d, mode, out);
+}
+void pcy_launch_pick_stage1(hipStream_t s, const bf16_t* logits, int rows, int V, void* partials) {
+  if (rows > 0) hipLaunchKernelGGL(pick_stage1_kernel, dim3(PICK_NB, rows), dim3(PICK_NT), 0, s, logits, V, reinterpret_cast<PickPartial*>(partials));
 }
 void pcy_launch_greedy_pick(hipStream_t s, const bf16_t* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out,
                             int max_steps, float* logprob, int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials) {

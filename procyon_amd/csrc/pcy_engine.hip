@@ -37,6 +37,8 @@ inline int kv_cap(const pcy_kv_cache* kv) { return kv->Tmax + (kv_shared(kv) ? k
 // calls of pcy_llama_extend_grouped (pcy_debug_extend_grouped_count).  A word of its own, not a kind of pcy_debug_dispatch_count: the kinds
 // [0, PCY_DISPATCH_N) and the ABI number are pinned by the suite, and a new entry point is an addition that old callers never see.
 unsigned long long g_pcy_extend_grouped = 0;
+// calls of pcy_look_draft / pcy_look_verify (pcy_debug_look_count): words of their own for the same reason
+unsigned long long g_pcy_look[2] = {0, 0};
 
 }  // namespace
 
@@ -1748,6 +1750,40 @@ int pcy_greedy_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
   enqueue_pick(c, m, st, B, advance_pos, kv_cap(kv));
   return check_launch("pcy_greedy_pick");
 }
+
+// ---- greedy decoding with lookahead (kernels: pcy_lookahead.hip) ----
+static int look_args(const char* what, const pcy_look_state* ls, const pcy_gen_state* st, PcyLookArgs* a) {
+  if (!ls || !st) return fail(1, "%s: state missing", what);
+  if (ls->W < 2 || ls->W > 32) return fail(1, "%s: W=%d outside [2, 32]", what, ls->W);
+  if (ls->ngram_min < 1 || ls->ngram_max < ls->ngram_min || ls->ngram_max > 16)
+    return fail(1, "%s: n-gram range [%d, %d] (1 <= min <= max <= 16)", what, ls->ngram_min, ls->ngram_max);
+  if (ls->cap < 1 || !ls->hist || !ls->n_hist || !ls->window || !ls->counters || !ls->last) return fail(1, "%s: history / window / counters missing", what);
+  if (!st->pos || !st->step || !st->next_tok || !st->tokens_out || !st->logprob || st->max_steps < 1) return fail(1, "%s: generation state incomplete", what);
+  *a = PcyLookArgs{ls->hist, ls->n_hist, ls->window, ls->forced, ls->counters, ls->last, ls->cap, ls->W, ls->ngram_max, ls->ngram_min,
+                   st->pos, st->step, st->next_tok, st->tokens_out, st->logprob, st->max_steps};
+  return 0;
+}
+int pcy_look_draft(pcy_ctx* c, const pcy_llama_desc* m, const pcy_look_state* ls, const pcy_gen_state* st, void* embeds_out) {
+  PCY_STICKY(c);
+  PcyLookArgs a;
+  if (int r = look_args("pcy_look_draft", ls, st, &a)) return r;
+  if (!embeds_out) return fail(1, "pcy_look_draft: embeds_out is NULL");
+  if (m->d % 8) return fail(1, "pcy_look_draft: d %% 8 != 0");
+  pcy_launch_look_draft(c->stream, a, (const bf16_t*)m->embed, m->vocab, m->d, (bf16_t*)embeds_out);
+  ++g_pcy_look[0];
+  return check_launch("pcy_look_draft");
+}
+int pcy_look_verify(pcy_ctx* c, const pcy_llama_desc* m, const pcy_look_state* ls, const pcy_gen_state* st, const void* logits) {
+  PCY_STICKY(c);
+  PcyLookArgs a;
+  if (int r = look_args("pcy_look_verify", ls, st, &a)) return r;
+  if (!logits) return fail(1, "pcy_look_verify: logits is NULL");
+  if (int r = c->reserve(pcy_look_verify_ws_bytes(a.W))) return r;
+  pcy_launch_look_verify(c->stream, a, (const bf16_t*)logits, m->vocab, (bf16_t*)st->logits_all, st->logits_all_ld, c->ws);
+  ++g_pcy_look[1];
+  return check_launch("pcy_look_verify");
+}
+unsigned long long pcy_debug_look_count(int which) { return (which == 0 || which == 1) ? g_pcy_look[which] : 0; }
 
 
 int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps,

@@ -363,6 +363,18 @@ void pcy_launch_pool(hipStream_t s, const bf16_t* h, int d, const int32_t* seg, 
 void pcy_launch_greedy_pick(hipStream_t s, const bf16_t* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out,
                             int max_steps, float* logprob, int32_t* pos_dev, int32_t* step_dev, int advance_pos,
                             void* partials /* B*64*16 bytes of scratch */);
+// stage 1 of the pick alone: the 64 chunk partials of every row of logits [rows, V] -> partials (rows * 64 * 16 bytes)
+void pcy_launch_pick_stage1(hipStream_t s, const bf16_t* logits, int rows, int V, void* partials);
+// Greedy decoding with lookahead (pcy_lookahead.hip; pcy.h, pcy_look_state + the scalars of the pcy_gen_state it works beside): device pointers
+struct PcyLookArgs {
+  int32_t* hist; int32_t* n_hist; int32_t* window; const int32_t* forced; int32_t* counters; int32_t* last;
+  int cap, W, gmax, gmin;
+  int32_t* pos; int32_t* step; int32_t* next_tok; int32_t* tokens_out; float* logprob; int max_steps;
+};
+size_t pcy_look_verify_ws_bytes(int W);
+void pcy_launch_look_draft(hipStream_t s, const PcyLookArgs& a, const bf16_t* embed, int V, int d, bf16_t* embeds_out /* [W, d] */);
+void pcy_launch_look_verify(hipStream_t s, const PcyLookArgs& a, const bf16_t* logits /* [W, V] */, int V, bf16_t* logits_all, int logits_all_ld,
+                            void* partials /* pcy_look_verify_ws_bytes(W) */);
 // sampling / nucleus selection of one step (model_unified.py:896-906): token ~ multinomial(probs) by inverse CDF with the caller's
 // uniform variate uniforms[step * B + b]; nucleus_p <= 0: plain temperature sampling.  hist: [B][65536] uint32, zero on entry / exit;
 // partials: B * 64 * 16 bytes; probs_out: optional [B,V] record of the pre-sampling probability vector

@@ -596,6 +596,76 @@ class BeamState:
         return self.out[steps & 1, :, :steps].long(), steps
 
 
+def lookup_draft(hist, window, ngram_max, ngram_min):
+    """The draft rule of greedy decoding with lookahead (include/pcy.h, pcy_look_state; the device twin is pcy_look_draft) in plain Python:
+    hist = the prompt's token ids followed by every committed token (negative = no text token) -> the window - 1 drafts.  For g = ngram_max
+    down to ngram_min: the LARGEST i with i + g < n and hist[i:i+g] == hist[n-g:n], every compared entry >= 0; the drafts are what followed,
+    hist[i+g], hist[i+g+1], ... until the history ends or an entry is negative; whatever is not filled that way is the filler hist[n-1]."""
+    h = [int(t) for t in hist]
+    n, W = len(h), int(window)
+    if n < 1 or W < 2:
+        raise ValueError(f"lookup_draft: a history of {n} tokens, window {W}")
+    drafts = []
+    for g in range(int(ngram_max), int(ngram_min) - 1, -1):
+        if g < 1 or g >= n or min(h[n - g:]) < 0:
+            continue
+        hit = next((i for i in range(n - g - 1, -1, -1) if h[i:i + g] == h[n - g:]), None)
+        if hit is not None:
+            for t in h[hit + g:hit + g + W - 1]:
+                if t < 0:
+                    break
+                drafts.append(t)
+            break
+    return drafts + [h[n - 1]] * (W - 1 - len(drafts))
+
+
+def lookahead_passes(tokens, prompt_ids, window, ngram=(3, 1), forced=None):
+    """How many passes `LlamaEngine.generate_lookahead` takes for a KNOWN greedy token sequence `tokens` (token 0 comes from the prefill):
+    -> (passes, accepted histogram [window]: passes that committed k drafts).  Each pass drafts by `lookup_draft` over prompt_ids + the tokens
+    committed so far (forced[i] >= 0 replaces the draft of output token i), accepts the leading drafts that equal the sequence and commits one
+    token more, clamped at the end of the sequence."""
+    toks, W = [int(t) for t in tokens], int(window)
+    hist = [int(t) for t in prompt_ids] + toks[:1]
+    step, passes, accepted = 1, 0, [0] * W
+    while step < len(toks):
+        drafts = lookup_draft(hist, W, ngram[0], ngram[1])
+        if forced is not None:
+            drafts = [int(forced[step + j]) if step + j < len(forced) and int(forced[step + j]) >= 0 else t for j, t in enumerate(drafts)]
+        a = 0
+        while a < W - 1 and step + a < len(toks) and drafts[a] == toks[step + a]:
+            a += 1
+        n = min(a + 1, len(toks) - step)
+        hist += toks[step:step + n]
+        step += n
+        passes += 1
+        accepted[n - 1] += 1
+    return passes, accepted
+
+
+class LookState:
+    """Device-side state of greedy decoding with lookahead for one prompt (include/pcy.h, pcy_look_state), beside a one-row GenState."""
+
+    def __init__(self, hist_ids, max_new, window, ngram, device, forced=None):
+        T = int(hist_ids.numel())
+        self.W, self.cap = int(window), T + int(max_new)
+        self.hist = torch.full((self.cap,), -1, dtype=torch.int32, device=device)
+        self.hist[:T] = hist_ids.to(device, torch.int32).view(-1)
+        self.n_hist = torch.full((1,), T, dtype=torch.int32, device=device)
+        self.window = torch.zeros(self.W, dtype=torch.int32, device=device)
+        self.counters = torch.zeros(2 + self.W, dtype=torch.int32, device=device)
+        self.last = torch.zeros(4, dtype=torch.int32, device=device)
+        self.forced = None if forced is None else forced.to(device, torch.int32).contiguous()
+        self.c = L.LookState(self.hist.data_ptr(), self.n_hist.data_ptr(), self.window.data_ptr(),
+                             0 if self.forced is None else self.forced.data_ptr(), self.counters.data_ptr(), self.last.data_ptr(),
+                             self.cap, self.W, int(ngram[0]), int(ngram[1]))
+
+    def stats(self):
+        """-> dict(passes, tokens (committed by passes: the prefill's token 0 is not one), accepted [W] (passes that committed k drafts),
+        tokens_per_pass)"""
+        c = self.counters.cpu().tolist()
+        return dict(passes=c[0], tokens=c[1], accepted=c[2:], tokens_per_pass=(c[1] / c[0] if c[0] else 0.0))
+
+
 def score_plan(full_labels, T_real, vocab):
     """Which token rows a teacher-forced scoring pass scores, and against what -- HF's shift (`logits[:, :-1]` against `labels[:, 1:]`,
     ignore_index -100), on the host, no device involved.  full_labels [B, T] (-100 = not scored); the engine runs T_real columns, so row
@@ -934,6 +1004,81 @@ class LlamaEngine:
         self.ctx.sync()
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
         return st.tokens_out.long(), st.logprob, la, (st, cache)
+
+    def look_draft(self, look: "LookState", st: GenState, embeds_out):
+        """window[1..W) by prompt lookup + the W embedding rows of the window -> embeds_out [W, d] (pcy_look_draft)"""
+        L.check(self.ctx.lib.pcy_look_draft(self.ctx.h, C.byref(self.desc), C.byref(look.c), C.byref(st.c), _p(embeds_out)), "pcy_look_draft")
+
+    def look_verify(self, look: "LookState", st: GenState, logits):
+        """pick the W rows of a pass, accept the leading drafts that were right, commit (pcy_look_verify); logits [W, V] bf16"""
+        _chk_bf16(logits)
+        L.check(self.ctx.lib.pcy_look_verify(self.ctx.h, C.byref(self.desc), C.byref(look.c), C.byref(st.c), _p(logits)), "pcy_look_verify")
+
+    def generate_lookahead(self, embeds, input_ids, max_len, window, ngram=(3, 1), forced=None, keep_logits=False):
+        """Greedy generation of ONE prompt with `window - 1` drafted tokens checked per pass over the weights: prefill, token 0
+        from its logits as in `generate_greedy`, then passes of draft (prompt lookup over `input_ids` + the text so far, pcy_look_draft) ->
+        `extend` of exactly `window` rows at the cache length -> verify + commit (pcy_look_verify) until max_len tokens are committed; no EOS
+        stop.  embeds [1,T,d] bf16 of an unpadded prompt; input_ids [T] its token ids, negative where a slot holds no text token (soft
+        tokens: never matched, never drafted); ngram = (longest, shortest) n-gram looked up; forced: optional [max_len] ints, forced[i] >= 0
+        replaces the draft of output token i (tests, measurements).  Returns what `generate_greedy` returns: (tokens [1,max_len] int64,
+        logprob [1] fp32, logits [1,max_len,V] bf16 | None, (state, cache, look state)).
+        At a fixed window the tokens, the log-prob, the logits record and the K / V of every committed slot do not depend on the drafts; they
+        are NOT promised bit-equal to `generate_greedy` (a window-row pass and a one-row decode step are different arithmetic)."""
+        if embeds.dim() != 3 or embeds.shape[0] != 1:
+            raise ValueError(f"generate_lookahead: one prompt at a time, embeds {tuple(embeds.shape)}")
+        if embeds.dtype != BF16:
+            raise ValueError(f"generate_lookahead needs the bf16 engine, embeds are {embeds.dtype}")
+        if bool(self.desc.layers_fp8):
+            raise ValueError("generate_lookahead: the cache extension has no fp8 projections (set_fp8(False) first)")
+        T, W, max_len = int(embeds.shape[1]), int(window), int(max_len)
+        if not 2 <= W <= 32:
+            raise ValueError(f"generate_lookahead: window={window} outside [2, 32]")
+        ids = torch.as_tensor(input_ids).view(-1)
+        if ids.numel() != T:
+            raise ValueError(f"generate_lookahead: {ids.numel()} input_ids for {T} prompt slots (one unpadded prompt)")
+        if max_len < 1 or T + max_len + W - 1 > self.cfg.max_pos:
+            raise ValueError(f"generate_lookahead: T + max_len + window - 1 = {T + max_len + W - 1} exceeds max_pos {self.cfg.max_pos}" if max_len >= 1
+                             else f"generate_lookahead: max_len={max_len}")
+        g_hi, g_lo = int(ngram[0]), int(ngram[1])
+        if not 1 <= g_lo <= g_hi <= 16:
+            raise ValueError(f"generate_lookahead: ngram={ngram}: (longest, shortest) with 1 <= shortest <= longest <= 16")
+        fz = None
+        if forced is not None:
+            fz = torch.as_tensor(forced).view(-1).to(torch.int32)
+            if fz.numel() != max_len or int(fz.max()) >= self.cfg.vocab:
+                raise ValueError(f"generate_lookahead: forced holds {fz.numel()} entries for max_len {max_len}, largest {int(fz.max())} (vocab {self.cfg.vocab})")
+        dev, V, d = self.device, self.cfg.vocab, self.cfg.d
+        # a pass ALWAYS has W rows, also when fewer tokens remain (the projections' tile / K-split choices depend on the row count): the last
+        # pass may write up to W - 1 slots beyond the last committed token, hence the spare slots
+        cache = self.new_cache(1, T + max_len + W - 1)
+        st = GenState(1, V, max_len, dev, keep_logits)
+        logits0, _ = self.prefill(embeds, None, cache, "last")
+        st.logits.copy_(logits0)
+        st.pos.fill_(T)
+        self.pick(cache, st, 1, advance_pos=False)
+        look = LookState(ids, max_len, W, (g_hi, g_lo), dev, fz)
+        look.hist[T:T + 1] = st.next_tok
+        look.n_hist.fill_(T + 1)
+        look.window[0:1] = st.next_tok
+        emb = torch.empty(1, W, d, dtype=BF16, device=dev)
+        rows = torch.arange(W, dtype=torch.int32, device=dev)
+        logits = torch.empty(W, V, dtype=BF16, device=dev)
+        pos, step = T, 1
+        while step < max_len:
+            self.look_draft(look, st, emb)
+            # rows of rejected drafts left K / V in slots [pos, pos + W - 1 - accepted) of the previous pass's range: this pass starts at pos,
+            # has W rows and so rewrites every one of them before any of its queries reads it (a query at slot p reads [0, p] only)
+            L.check(self.ctx.lib.pcy_llama_extend(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(emb), None, 1, W, pos, _p(rows), W, _p(logits),
+                                                  None, None, None, 0, None), "pcy_llama_extend")
+            self.look_verify(look, st, logits)
+            # the one host read of a pass: `extend` takes t_past from the host (DESIGN.md 4.9 names the follow-up)
+            _, n, step0, pos0 = look.last.tolist()
+            if n < 1:
+                raise L.PcyError(f"generate_lookahead: a pass committed nothing at step {step0}")
+            pos, step = pos0 + n, step0 + n
+        self.ctx.sync()       # the record may live in host memory (as in generate_greedy)
+        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        return st.tokens_out.long(), st.logprob, la, (st, cache, look)
 
     def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new):
         """`_generate_beam_search` (model_unified.py:702-842): diverse beam search of B prompts x beam_size beams, at most max_len tokens, on
