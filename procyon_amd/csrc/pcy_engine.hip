@@ -1285,6 +1285,15 @@ struct PrefillReq {
   void *hidden_out, *hidden_all_out;                                  // final-normed [M][d]; [L+1][M][d] (pcy_llama_prefill_all)
   ScoreReq score; ExtendReq ext;
 };
+// the request of pcy_llama_extend / _packed / _grouped: what the three entries share, `ext` is what tells them apart
+PrefillReq extend_req(const void* embeds, const uint8_t* keep, int B, int S, ExtendReq ext, const int32_t* logit_rows, int n_logit_rows, void* logits_out,
+                      void* hidden_out, const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
+  PrefillReq r{};
+  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
+  r.hidden_out = hidden_out; r.ext = ext;
+  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
+  return r;
+}
 // The carve of the prefill workspace, in ONE place; bytes = its end + slack, what a call reserves (sized by a carve of a null base).  vt_elems: the transposed V
 struct PrefillWs {
   bf16_t *x, *xn, *qkv, *ao, *act, *vt, *lastx;
@@ -1346,7 +1355,7 @@ int check_prefix_groups(const pcy_kv_cache* kv, const pcy_prefix_groups* gr, int
   *max_rows = mr; *max_len = ml;
   return 0;
 }
-int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r) {
+int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r, int* g_max_rows) {   // g_max_rows: of a grouped extension
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
   if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "pcy_llama_prefill: d, ffn, H*dh, Hkv*dh must be multiples of 64");
@@ -1357,8 +1366,8 @@ int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const Pre
     if (m->layers_fp8) return fail(1, "pcy_llama_extend: fp8 projections are not supported on the extension path");
     if (B < 1 || T < 1 || t_past < 0) return fail(1, "pcy_llama_extend: B=%d S=%d t_past=%d", B, T, t_past);
     if (r.ext.grp) {
-      int max_rows = 0, max_len = 0;
-      if (int e = check_prefix_groups(kv, r.ext.grp, B, T, "pcy_llama_extend_grouped", &max_rows, &max_len)) return e;
+      int max_len = 0;
+      if (int e = check_prefix_groups(kv, r.ext.grp, B, T, "pcy_llama_extend_grouped", g_max_rows, &max_len)) return e;
       if ((long)max_len + t_past + T > m->max_pos)
         return fail(1, "pcy_llama_extend_grouped: len=%d + t_own=%d + S=%d exceed rope table %d", max_len, t_past, T, m->max_pos);
     } else {
@@ -1380,7 +1389,7 @@ int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const Pre
 // the row's own panel (the panel pointer carries the offset, the row stride stays Tmax * dh), then the S queries of every row against the cache
 void enqueue_extend_attention(hipStream_t s, bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, int t_past, const int32_t* pos,
                               const bf16_t* cos_t, const bf16_t* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed,
-                              const pcy_prefix_groups* grp = nullptr) {
+                              const pcy_prefix_groups* grp, int g_max_rows) {   // (g_max_rows: the largest group, from check_prefix_groups)
   const bool shared = kv_shared(kv);
   // first written slot inside the rows' own panels (grouped: t_past IS the count of own tokens, the same for every row)
   const int own_slot0 = grp ? t_past : shared ? t_past - kv->prefix_T : t_past;
@@ -1396,10 +1405,7 @@ void enqueue_extend_attention(hipStream_t s, bf16_t* qkv, int ld, const pcy_kv_c
     e.Tp = kv->prefix_T; e.rows_per_prefix = kv->rows_per_prefix;
   }
   e.o = o; e.ldo = ldo; e.keep = keep; e.ld_keep = kv_cap(kv); e.B = B; e.S = S; e.H = H; e.Hkv = Hkv; e.dh = dh; e.t_past = t_past;
-  if (grp) {
-    e.g_row0 = grp->d_row0; e.g_len = grp->d_len; e.g_row_grp = grp->d_row_grp; e.n_groups = grp->n_groups;
-    for (int g = 0; g < grp->n_groups; ++g) e.g_max_rows = grp->rows[g] > e.g_max_rows ? grp->rows[g] : e.g_max_rows;
-  }
+  if (grp) { e.g_row0 = grp->d_row0; e.g_len = grp->d_len; e.g_row_grp = grp->d_row_grp; e.n_groups = grp->n_groups; e.g_max_rows = g_max_rows; }
   if (packed) pcy_launch_attn_extend_packed(s, e);
   else pcy_launch_attn_extend(s, e);
 }
@@ -1470,7 +1476,8 @@ void enqueue_scored_rows(hipStream_t s, const pcy_llama_desc* m, const ScoreReq&
 }
 int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r) {
   PCY_STICKY(c);
-  if (int e = check_prefill_req(m, kv, r)) return e;
+  int g_max_rows = 0;
+  if (int e = check_prefill_req(m, kv, r, &g_max_rows)) return e;
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
   const int M = B * T, qkvw = (H + 2 * Hkv) * dh, Tp = (T + 31) / 32 * 32, n_sum_rows = r.n_sum_rows;
   const bool ext = r.ext.on;
@@ -1521,7 +1528,7 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
       linear(s, xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, w.qkv, qkvw, M, qkvw, d, EPI_STORE, w.sk_ws, w.sk_bytes);
     }
     if (ext) enqueue_extend_attention(s, w.qkv, qkvw, kv, l, w.ao, H * dh, r.ext.t_past, w.pos_ext, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
-                                      r.keep, B, T, H, Hkv, dh, r.ext.packed, r.ext.grp);
+                                      r.keep, B, T, H, Hkv, dh, r.ext.packed, r.ext.grp, g_max_rows);
     else enqueue_prefill_attention(s, m, kv, r, w, l, vt_total);
     if (L8) {
       linear8(w.ao, H * dh, L8->wo, L8->so, x, x, d, d, EPI_RESID);
@@ -1557,20 +1564,25 @@ int llama_prefill_impl(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* 
   enqueue_scored_rows(s, m, r.score, x, w);
   return check_launch(ext ? "pcy_llama_extend" : "pcy_llama_prefill");
 }
-int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
-                      const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
+// pcy_attn_extend / _packed (grp == nullptr) and pcy_attn_extend_grouped (t_past = the tokens in the rows' own panels)
+int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, const pcy_prefix_groups* grp, int layer, void* o, int ldo, int t_past,
+                      const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
   PCY_STICKY(c);
-  if (dh != 64 && dh != 128) return fail(1, "pcy_attn_extend: head_dim %d unsupported (64/128)", dh);
-  if (Hkv < 1 || H % Hkv) return fail(1, "pcy_attn_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
-  if (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0 || layer < 0) return fail(1, "pcy_attn_extend: B=%d S=%d t_past=%d layer=%d", B, S, t_past, layer);
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "pcy_attn_extend: ld=%d (rows of qkv must be 16-byte aligned)", ld);
-  if (int r = check_extend_span(kv, B, S, t_past, "pcy_attn_extend")) return r;
+  const char* what = grp ? "pcy_attn_extend_grouped" : "pcy_attn_extend";
+  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv) return fail(1, "%s: H=%d is no multiple of Hkv=%d", what, H, Hkv);
+  if (layer < 0 || (!grp && (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0)))   // (a grouped call: check_prefix_groups has words of its own)
+    return fail(1, "%s: B=%d S=%d t_past=%d layer=%d", what, B, S, t_past, layer);
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "%s: ld=%d (rows of qkv must be 16-byte aligned)", what, ld);
+  int g_max_rows = 0, g_max_len = 0;
+  if (int r = grp ? check_prefix_groups(kv, grp, B, S, what, &g_max_rows, &g_max_len) : check_extend_span(kv, B, S, t_past, what)) return r;
   if (int r = c->reserve(align_up((size_t)B * S * 4, 256) + 256)) return r;
   int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
-  pcy_launch_ext_pos(c->stream, pos, B, S, t_past);
+  if (grp) pcy_launch_ext_pos_grouped(c->stream, pos, B, S, t_past, grp->d_len, grp->d_row_grp);
+  else pcy_launch_ext_pos(c->stream, pos, B, S, t_past);
   enqueue_extend_attention(c->stream, (bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, t_past, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
-                           B, S, H, Hkv, dh, packed);
-  return check_launch("pcy_attn_extend");
+                           B, S, H, Hkv, dh, packed, grp, g_max_rows);
+  return check_launch(what);
 }
 
 PcyBeamState beam_state_args(const pcy_beam_state* st) {
@@ -1666,48 +1678,27 @@ int pcy_llama_score(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
 int pcy_llama_extend(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S, int t_past,
                      const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out, const int32_t* score_rows,
                      const int32_t* targets, int n_score, float* nll_out) {
-  PrefillReq r{};
-  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
-  r.hidden_out = hidden_out; r.ext = ExtendReq{true, t_past, false};
-  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
-  return llama_prefill_impl(c, m, kv, r);
+  return llama_prefill_impl(c, m, kv, extend_req(embeds, keep, B, S, ExtendReq{true, t_past, false}, logit_rows, n_logit_rows, logits_out, hidden_out,
+                                                 score_rows, targets, n_score, nll_out));
 }
 int pcy_llama_extend_packed(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const void* embeds, const uint8_t* keep, int B, int S,
                             int t_past, const int32_t* logit_rows, int n_logit_rows, void* logits_out, void* hidden_out,
                             const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
-  PrefillReq r{};
-  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
-  r.hidden_out = hidden_out; r.ext = ExtendReq{true, t_past, true};
-  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
-  return llama_prefill_impl(c, m, kv, r);
+  return llama_prefill_impl(c, m, kv, extend_req(embeds, keep, B, S, ExtendReq{true, t_past, true}, logit_rows, n_logit_rows, logits_out, hidden_out,
+                                                 score_rows, targets, n_score, nll_out));
 }
 int pcy_llama_extend_grouped(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_prefix_groups* groups, const void* embeds,
                              const uint8_t* keep, int B, int S, int packed, const int32_t* logit_rows, int n_logit_rows, void* logits_out,
                              void* hidden_out, const int32_t* score_rows, const int32_t* targets, int n_score, float* nll_out) {
   if (!groups) return fail(1, "pcy_llama_extend_grouped: group tables missing");
-  PrefillReq r{};
-  r.embeds = embeds; r.keep = keep; r.B = B; r.T = S; r.logit_rows = logit_rows; r.n_logit_rows = n_logit_rows; r.logits_out = logits_out;
-  r.hidden_out = hidden_out; r.ext = ExtendReq{true, groups->t_own, packed != 0, groups};
-  if (n_score > 0) r.score = ScoreReq{score_rows, targets, n_score, nll_out};
-  return llama_prefill_impl(c, m, kv, r);
+  return llama_prefill_impl(c, m, kv, extend_req(embeds, keep, B, S, ExtendReq{true, groups->t_own, packed != 0, groups}, logit_rows, n_logit_rows,
+                                                 logits_out, hidden_out, score_rows, targets, n_score, nll_out));
 }
 unsigned long long pcy_debug_extend_grouped_count(void) { return g_pcy_extend_grouped; }
 int pcy_attn_extend_grouped(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, const pcy_prefix_groups* groups, int layer, void* o, int ldo,
                             const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, int packed) {
-  PCY_STICKY(c);
-  const char* what = "pcy_attn_extend_grouped";
-  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
-  if (Hkv < 1 || H % Hkv) return fail(1, "%s: H=%d is no multiple of Hkv=%d", what, H, Hkv);
-  if (layer < 0) return fail(1, "%s: layer=%d", what, layer);
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh) return fail(1, "%s: ld=%d (rows of qkv must be 16-byte aligned)", what, ld);
-  int max_rows = 0, max_len = 0;
-  if (int r = check_prefix_groups(kv, groups, B, S, what, &max_rows, &max_len)) return r;
-  if (int r = c->reserve(align_up((size_t)B * S * 4, 256) + 256)) return r;
-  int32_t* pos = reinterpret_cast<int32_t*>(c->ws);
-  pcy_launch_ext_pos_grouped(c->stream, pos, B, S, groups->t_own, groups->d_len, groups->d_row_grp);
-  enqueue_extend_attention(c->stream, (bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, groups->t_own, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
-                           B, S, H, Hkv, dh, packed != 0, groups);
-  return check_launch(what);
+  if (!groups) return fail(1, "pcy_attn_extend_grouped: group tables missing");
+  return attn_extend_entry(c, qkv, ld, kv, groups, layer, o, ldo, groups->t_own, cos_t, sin_t, keep, B, S, H, Hkv, dh, packed != 0);
 }
 size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_logit_rows, int n_score) {
   if (!m || B < 1 || S < 1) return 0;
@@ -1715,11 +1706,11 @@ size_t pcy_llama_extend_ws_bytes(const pcy_llama_desc* m, int B, int S, int n_lo
 }
 int pcy_attn_extend(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
                     const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
-  return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, false);
+  return attn_extend_entry(c, qkv, ld, kv, nullptr, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, false);
 }
 int pcy_attn_extend_packed(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, int t_past, const void* cos_t,
                            const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh) {
-  return attn_extend_entry(c, qkv, ld, kv, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, true);
+  return attn_extend_entry(c, qkv, ld, kv, nullptr, layer, o, ldo, t_past, cos_t, sin_t, keep, B, S, H, Hkv, dh, true);
 }
 
 int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {

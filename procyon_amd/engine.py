@@ -514,6 +514,23 @@ class KVCache:
         return torch.cat([pk, self.k[l, :, :, :t - Tp]], 2), torch.cat([pv, self.v[l, :, :, :t - Tp]], 2)
 
 
+def uniform_keep(prefix_mask, suffix_mask, Tp):
+    """keep [R, Tp + S] int64 of an extension on a `new_shared_cache`: the prefixes' mask [P, Tp] (None: ones), every row of it repeated for
+    the R // P rows behind that prefix, then the rows' own suffix_mask [R, S]"""
+    R = suffix_mask.shape[0]
+    head = torch.ones(R, Tp, dtype=torch.long) if prefix_mask is None else prefix_mask.repeat_interleave(R // prefix_mask.shape[0], 0)
+    return torch.cat([head, suffix_mask], 1)
+
+
+def grouped_keep(row_len, Tp, suffix_mask):
+    """keep [R, Tp + S] int64 of an extension on a `new_grouped_cache`, in every row's OWN logical slots: ones on its row_len[r] prefix slots,
+    its suffix_mask [R, S] right behind them, zeros from there on"""
+    S = suffix_mask.shape[1]
+    col = torch.arange(Tp + S)[None] - row_len[:, None]                      # the column counted from the row's first own slot
+    own = suffix_mask.long().gather(1, col.clamp(0, S - 1)) * ((col >= 0) & (col < S))
+    return own + (col < 0)
+
+
 # The beams of a prompt share ONE copy of its K / V (KVCache with a prefix) when the plan below says so.  A pure function of the call's shape
 # and the PCY_DISABLE names: the rule lives here and nowhere else.
 #   beam > 1                     -- one row per prompt has nothing to share
@@ -855,16 +872,16 @@ class LlamaEngine:
         return token_nll, n, (logits if logit_rows is not None else None)
 
     def extend(self, cache: KVCache, embeds, t_past=None, keep=None, logit_rows=None, labels=None, want_hidden=False, packed=False, own_past=None):
-        """S more tokens per row against a cache that holds t_past tokens per row (pcy_llama_extend; HF's forward(inputs_embeds [B,S],
+        """S more tokens per row against a cache that holds t_past tokens per row (the library's extension, `_extend_call`; HF's forward(inputs_embeds [B,S],
         past_key_values)).  embeds [B,S,d] bf16; cache plain or shared-prefix (`new_shared_cache`); keep [B, >= t_past + S] (0 = masked key,
         old and new slots alike) or None; logit_rows "all" / "last" / flat rows b*S+s / None; labels [B,S] in HF's convention (-100 = not
         scored): token_nll[b, s+1] = -log p(token s+1 | everything up to s, the cached prefix included), 0 elsewhere.
         -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens).  K / V of slots [t_past, t_past+S) are written.
-        packed: pcy_llama_extend_packed -- the attention packs the queries of a prompt's rows into shared workgroups (same bits; it pays when
+        packed: the packed entry -- the attention packs the queries of a prompt's rows into shared workgroups (same bits; it pays when
         many rows per prefix carry few new tokens each).
         A grouped cache (`new_grouped_cache`) takes `own_past` (default 0) instead of t_past: the tokens already in the rows' own panels; row b
         of group g then holds group_len[g] + own_past tokens, and keep [B, >= max over the rows of that + S] is in the row's own logical slots
-        (pcy_llama_extend_grouped)."""
+        (the grouped entry)."""
         B, S, d = embeds.shape
         dev = self.device
         embeds = embeds.contiguous()
@@ -899,17 +916,42 @@ class LlamaEngine:
         logits = torch.empty(rows.numel(), self.cfg.vocab, dtype=BF16, device=dev)
         hidden = torch.empty(B, S, d, dtype=BF16, device=dev) if want_hidden else None
         n, srows, tg, bt_d, nll, token_nll = self._score_upload(labels, B, S) if labels is not None else (0,) + (None,) * 5
-        if grouped:
-            ga = cache.groups_arg(own_past)
-            L.check(self.ctx.lib.pcy_llama_extend_grouped(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(ga), _p(embeds), _p(keep_d), B, S,
-                                                          int(bool(packed)), _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n,
-                                                          _p(nll)), "pcy_llama_extend_grouped")
-        else:
-            fn = self.ctx.lib.pcy_llama_extend_packed if packed else self.ctx.lib.pcy_llama_extend
-            L.check(fn(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(embeds), _p(keep_d), B, S, t_past,
-                       _p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll)), "pcy_llama_extend")
+        self._extend_call(cache, embeds, keep_d, own_past if grouped else t_past, packed, rows, logits, hidden, srows, tg, n, nll)
         self._scatter_nll(token_nll, bt_d, nll)
         return (logits if logit_rows is not None else None), hidden, token_nll, n
+
+    def _extend_call(self, cache, embeds, keep_d, t_past, packed, rows, logits, hidden=None, srows=None, tg=None, n=0, nll=None):
+        """The one call site of pcy_llama_extend / _packed / _grouped, on device tensors the caller has prepared (embeds [B,S,d], keep_d uint8
+        [B, cache.capacity] | None, rows int32, logits [rows, V], ...); t_past of a grouped cache counts the tokens in the rows' own panels."""
+        lib, (B, S, _) = self.ctx.lib, embeds.shape
+        head = (self.ctx.h, C.byref(self.desc), C.byref(cache.c))
+        tail = (_p(rows), rows.numel(), _p(logits), _p(hidden), _p(srows), _p(tg), n, _p(nll))
+        if cache.is_grouped:
+            ga = cache.groups_arg(t_past)
+            L.check(lib.pcy_llama_extend_grouped(*head, C.byref(ga), _p(embeds), _p(keep_d), B, S, int(bool(packed)), *tail), "pcy_llama_extend_grouped")
+        else:
+            fn = lib.pcy_llama_extend_packed if packed else lib.pcy_llama_extend
+            L.check(fn(*head, _p(embeds), _p(keep_d), B, S, int(t_past), *tail), "pcy_llama_extend")
+
+    def extend_behind(self, prefix_emb, prefix_mask, suffix_emb, suffix_mask, rows_per_prefix=None, groups=None, **what):
+        """Prefill P prefixes ONCE and run the rows behind them as ONE `extend`: prefix_emb [P,Tp,d]; suffix_emb [R,S,d], suffix_mask [R,S] (0 on
+        the right pads).  Either rows_per_prefix (R = P * rows_per_prefix rows on a `new_shared_cache`; prefix_mask [P,Tp] with the pads on the
+        LEFT, or None = no pads) or groups = (group_rows, group_len) (a `new_grouped_cache`; the prefixes RIGHT-padded to Tp, so group_len is
+        their mask).  what: logit_rows / labels / want_hidden / packed of `extend`.  -> (*what `extend` returns, the cache).
+        The key mask of the extension is None -- the kernels' unmasked block path -- whenever nothing is masked: no prefix pads and full suffixes."""
+        P, Tp, _ = prefix_emb.shape
+        S, full = suffix_emb.shape[1], bool(suffix_mask.all())
+        prefix_cache = self.new_cache(P, Tp)
+        if groups is not None:
+            prefix_mask = (torch.arange(Tp)[None] < torch.tensor(groups[1])[:, None]).long()
+        self.prefill(prefix_emb, prefix_mask, prefix_cache, logit_rows=None)
+        if groups is not None:
+            cache, t_past = self.new_grouped_cache(prefix_cache, *groups, S), None
+            keep = None if full else grouped_keep(cache.row_len(), Tp, suffix_mask)
+        else:
+            cache, t_past = self.new_shared_cache(prefix_cache, rows_per_prefix, S), Tp
+            keep = None if full and prefix_mask is None else uniform_keep(prefix_mask, suffix_mask, Tp)
+        return (*self.extend(cache, suffix_emb, t_past, keep=keep, **what), cache)
 
     def extend_ws_bytes(self, B, S, n_logit_rows=0, n_score=0):
         """workspace of an `extend` call: host arithmetic, a function of the row counts only (never of the past length)"""
@@ -1068,8 +1110,7 @@ class LlamaEngine:
             self.look_draft(look, st, emb)
             # rows of rejected drafts left K / V in slots [pos, pos + W - 1 - accepted) of the previous pass's range: this pass starts at pos,
             # has W rows and so rewrites every one of them before any of its queries reads it (a query at slot p reads [0, p] only)
-            L.check(self.ctx.lib.pcy_llama_extend(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(emb), None, 1, W, pos, _p(rows), W, _p(logits),
-                                                  None, None, None, 0, None), "pcy_llama_extend")
+            self._extend_call(cache, emb, None, pos, False, rows, logits)
             self.look_verify(look, st, logits)
             # the one host read of a pass: `extend` takes t_past from the host (DESIGN.md 4.9 names the follow-up)
             _, n, step0, pos0 = look.last.tolist()

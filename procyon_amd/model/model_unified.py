@@ -86,6 +86,59 @@ def qa_full_labels(input_ids, pad_id, special_ids, answer_idx, use_llama_tokeniz
     return torch.where(all_masks, -100, full_labels)
 
 
+def _pad_rows(rows, fill, left=False):
+    """a list of 1-D tensors -> [R, the longest] int64, `fill` in the padding: on the right, or on the left"""
+    width = max(int(t.numel()) for t in rows)
+    out = torch.full((len(rows), width), int(fill), dtype=torch.long)
+    for r, t in enumerate(rows):
+        lo = width - int(t.numel()) if left else 0
+        out[r, lo:lo + int(t.numel())] = t
+    return out
+
+
+def _pad_mask(rows, left=False):
+    """the mask that goes with `_pad_rows(rows, ..., left)`: 1 on the tokens, 0 on the padding"""
+    return _pad_rows([torch.ones_like(t) for t in rows], 0, left)
+
+
+def _cut_candidates(tokenize, label_rule, instructions, candidates, answer_idx, pad_id):
+    """What both candidate planners share (arguments as `candidate_plan`; lists of any lengths >= 1): the texts, their tokens and labels,
+    and every row cut IN FRONT of its last [ANSWER].  -> (owner, prefixes, suffix):
+      owner[r] = (p, n)   row r is candidate n of prompt p, prompt after prompt
+      prefixes[p]         the tokens in front of the cut, identical for the rows of a prompt
+      suffix              dict: suffix_ids / suffix_mask / suffix_labels [R, S], the rows behind the cut RIGHT-padded with pad_id / 0 / -100; cut [R]
+    Every ValueError of the planners' docstrings but the ones on the shape of the lists and on an empty prefix."""
+    P = len(instructions)
+    if len(candidates) != P or P == 0:
+        raise ValueError(f"{len(candidates)} candidate lists for {P} prompts")
+    if any(len(c) < 1 for c in candidates):
+        raise ValueError(f"every prompt needs at least one candidate, got {[len(c) for c in candidates]}")
+    owner = [(p, n) for p in range(P) for n in range(len(candidates[p]))]
+    texts = [instructions[p] + " " + candidates[p][n] for p, n in owner]
+    ids, mask = tokenize(texts)
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    for r in range(len(owner)):      # (before the label rule, which has no answer for such a row)
+        if not bool(((ids[r] == answer_idx) & mask[r]).any()):
+            raise ValueError(f"row {r}: no [ANSWER] token in {texts[r]!r}")
+    labels = torch.as_tensor(label_rule(ids)).long().cpu()
+    prefixes, suffixes, suf_labels, cuts = [], [], [], []
+    for r, (p, n) in enumerate(owner):
+        n_real = int(mask[r].sum())
+        assert bool(mask[r, :n_real].all()), "rows must be right-padded"
+        cut = int((ids[r, :n_real] == answer_idx).nonzero().max())
+        if bool((labels[r, :cut + 1] != -100).any()):
+            raise ValueError(f"row {r}: labelled tokens in front of the last [ANSWER]; they lie in the shared prefix and cannot be scored by the extension")
+        if n == 0:
+            prefixes.append(ids[r, :cut])
+        elif not torch.equal(prefixes[-1], ids[r, :cut]):
+            raise ValueError(f"prompt {p}: candidate {n} changes the tokens in front of [ANSWER]; the candidates of a prompt must share its prefix")
+        cuts.append(cut)
+        suffixes.append(ids[r, cut:n_real])
+        suf_labels.append(labels[r, cut:n_real])
+    return owner, prefixes, dict(suffix_ids=_pad_rows(suffixes, pad_id), suffix_mask=_pad_mask(suffixes),
+                                 suffix_labels=_pad_rows(suf_labels, -100), cut=torch.tensor(cuts))
+
+
 def candidate_plan(tokenize, label_rule, instructions, candidates, answer_idx, pad_id):
     """Host side of `UnifiedProCyon.score_candidates`: P prompts (instructions ending in [ANSWER]) x N candidate texts each, cut into the part
     all candidates of a prompt share and the part that differs.  Pure: no device, no model.
@@ -101,52 +154,52 @@ def candidate_plan(tokenize, label_rule, instructions, candidates, answer_idx, p
       cut [P*N], P, N, Tp, S
     ValueError: candidate lists of unequal length (ragged lists are out of scope), no candidates, a row without [ANSWER], candidates of a
     prompt whose prefixes differ, or labels in front of the cut (train_qa_full_lm: those rows lie in the prefix and cannot be scored here)."""
-    P = len(instructions)
-    if len(candidates) != P or P == 0:
-        raise ValueError(f"{len(candidates)} candidate lists for {P} prompts")
-    N = len(candidates[0])
-    if N == 0 or any(len(c) != N for c in candidates):
-        raise ValueError(f"every prompt needs the same number of candidates, got {[len(c) for c in candidates]}")
-    texts = [instructions[p] + " " + candidates[p][n] for p in range(P) for n in range(N)]
-    ids, mask = tokenize(texts)
-    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
-    for r in range(P * N):      # (before the label rule, which has no answer for such a row)
-        if not bool(((ids[r] == answer_idx) & mask[r]).any()):
-            raise ValueError(f"row {r}: no [ANSWER] token in {texts[r]!r}")
-    labels = torch.as_tensor(label_rule(ids)).long().cpu()
-    prefixes, suffixes, suf_labels, cuts = [], [], [], []
-    for r in range(P * N):
-        n_real = int(mask[r].sum())
-        assert bool(mask[r, :n_real].all()), "rows must be right-padded"
-        cut = int((ids[r, :n_real] == answer_idx).nonzero().max())
-        if bool((labels[r, :cut + 1] != -100).any()):
-            raise ValueError(f"row {r}: labelled tokens in front of the last [ANSWER]; they lie in the shared prefix and cannot be scored by the extension")
-        if r % N == 0:
-            prefixes.append(ids[r, :cut])
-        elif not torch.equal(prefixes[-1], ids[r, :cut]):
-            raise ValueError(f"prompt {r // N}: candidate {r % N} changes the tokens in front of [ANSWER]; the candidates of a prompt must share its prefix")
-        cuts.append(cut)
-        suffixes.append(ids[r, cut:n_real])
-        suf_labels.append(labels[r, cut:n_real])
-    Tp, S = max(int(t.numel()) for t in prefixes), max(int(t.numel()) for t in suffixes)
+    counts = [len(c) for c in candidates]
+    if len(counts) == len(instructions) > 0 and (counts[0] == 0 or len(set(counts)) > 1):     # (any other count of lists: the cutter's error)
+        raise ValueError(f"every prompt needs the same number of candidates, got {counts}")
+    _, prefixes, suffix = _cut_candidates(tokenize, label_rule, instructions, candidates, answer_idx, pad_id)
+    P, N, Tp = len(prefixes), counts[0], max(int(t.numel()) for t in prefixes)
     if Tp == 0:
         raise ValueError("[ANSWER] is the first token of a row: nothing to prefill")
-    prefix_ids = torch.full((P, Tp), int(pad_id), dtype=torch.long)
-    prefix_mask = torch.zeros(P, Tp, dtype=torch.long)
-    for p, t in enumerate(prefixes):
-        if t.numel():
-            prefix_ids[p, Tp - t.numel():] = t
-            prefix_mask[p, Tp - t.numel():] = 1
-    suffix_ids = torch.full((P * N, S), int(pad_id), dtype=torch.long)
-    suffix_mask = torch.zeros(P * N, S, dtype=torch.long)
-    suffix_labels = torch.full((P * N, S), -100, dtype=torch.long)
-    for r, (t, lb) in enumerate(zip(suffixes, suf_labels)):
-        suffix_ids[r, :t.numel()] = t
-        suffix_mask[r, :t.numel()] = 1
-        suffix_labels[r, :t.numel()] = lb
-    n_tokens = (suffix_labels[:, 1:] != -100).sum(1).view(P, N)
-    return dict(prefix_ids=prefix_ids, prefix_mask=prefix_mask, suffix_ids=suffix_ids, suffix_mask=suffix_mask, suffix_labels=suffix_labels,
-                n_tokens=n_tokens, cut=torch.tensor(cuts), P=P, N=N, Tp=Tp, S=S)
+    return dict(prefix_ids=_pad_rows(prefixes, pad_id, left=True), prefix_mask=_pad_mask(prefixes, left=True),
+                **suffix, n_tokens=(suffix["suffix_labels"][:, 1:] != -100).sum(1).view(P, N), P=P, N=N, Tp=Tp, S=suffix["suffix_ids"].shape[1])
+
+
+def _qa_batch_view(ids, mask, slot_sources, answer_idx, soft_slot_ids):
+    """The validated view of a QA batch that both shared-prefix planners cut (their arguments, their ValueErrors) -> (ids [B, T] int64,
+    mask [B, T] bool, is_slot [B, T] bool: the real soft-token slots, answer_pos: the column of every row's LAST [ANSWER] among its real tokens)"""
+    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
+    if ids.dim() != 2 or ids.shape != mask.shape or ids.shape[0] == 0:
+        raise ValueError(f"ids {tuple(ids.shape)} / mask {tuple(mask.shape)}: expected two equal [B, T] arrays, B >= 1")
+    B, T = ids.shape
+    if len(slot_sources) != B:
+        raise ValueError(f"{len(slot_sources)} slot source lists for {B} rows")
+    right_padded = torch.arange(T)[None] < mask.sum(1)[:, None]
+    if not bool((mask == right_padded).all()):
+        raise ValueError(f"row {int((mask != right_padded).any(1).nonzero()[0])} is not right-padded")
+    is_ans = (ids == int(answer_idx)) & mask
+    if not bool(is_ans.any(1).all()):
+        raise ValueError(f"row {int((~is_ans.any(1)).nonzero()[0])}: no [ANSWER] token")
+    is_slot = torch.zeros_like(mask)
+    for i in soft_slot_ids:
+        is_slot |= ids == int(i)
+    is_slot &= mask
+    for r, n in enumerate(is_slot.sum(1).tolist()):
+        if n != len(slot_sources[r]):
+            raise ValueError(f"row {r}: {n} soft-token slots, {len(slot_sources[r])} sources")
+    return ids, mask, is_slot, (T - 1 - is_ans.flip(1).int().argmax(1)).tolist()
+
+
+def _shared_cut(ids, mask, is_slot, slot_sources, answer_pos):
+    """Tp of `shared_prefix_plan` for the rows of a `_qa_batch_view` (or of a subset of them)"""
+    # columns in front of the first one that differs between the rows (or is a pad somewhere), at most the earliest answer position ...
+    same = ((ids == ids[0:1]) & mask).all(0)
+    Tp = min(min(answer_pos), ids.shape[1] if bool(same.all()) else int((~same).int().argmax()))
+    # ... and in front of the first soft slot whose sources differ (the columns up to there are identical: slot k sits at the same column)
+    for k, c in enumerate(is_slot[0, :Tp].nonzero()[:, 0].tolist()):
+        if any(src[k] != slot_sources[0][k] for src in slot_sources[1:]):
+            return c
+    return Tp
 
 
 def shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id):
@@ -163,46 +216,14 @@ def shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_i
       answer_pos [B]                    position of the last [ANSWER] in the full row
       answer_rows [B] int32             flat row b * S + answer_pos_b - Tp of the [B, S] suffix batch
     ValueError: a row without [ANSWER], rows that are not right-padded, slot_sources that do not match the slots of a row."""
-    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
-    if ids.dim() != 2 or ids.shape != mask.shape or ids.shape[0] == 0:
-        raise ValueError(f"ids {tuple(ids.shape)} / mask {tuple(mask.shape)}: expected two equal [B, T] arrays, B >= 1")
-    B, T = ids.shape
-    if len(slot_sources) != B:
-        raise ValueError(f"{len(slot_sources)} slot source lists for {B} rows")
-    is_slot = torch.zeros_like(mask)
-    for i in soft_slot_ids:
-        is_slot |= ids == int(i)
-    n_real = mask.sum(1)
-    if not bool((mask == (torch.arange(T)[None] < n_real[:, None])).all()):
-        bad = int((mask != (torch.arange(T)[None] < n_real[:, None])).any(1).nonzero()[0])
-        raise ValueError(f"row {bad} is not right-padded")
-    is_ans = (ids == int(answer_idx)) & mask
-    if not bool(is_ans.any(1).all()):
-        raise ValueError(f"row {int((~is_ans.any(1)).nonzero()[0])}: no [ANSWER] token")
-    answer_pos = (T - 1 - is_ans.flip(1).int().argmax(1)).tolist()          # the LAST [ANSWER] among the real tokens
-    n_slots = (is_slot & mask).sum(1).tolist()
-    for r in range(B):
-        if n_slots[r] != len(slot_sources[r]):
-            raise ValueError(f"row {r}: {n_slots[r]} soft-token slots, {len(slot_sources[r])} sources")
-    # columns in front of the first one that differs between the rows (or is a pad somewhere), at most the earliest answer position ...
-    same = ((ids == ids[0:1]) & mask).all(0)
-    Tp = min(min(answer_pos), T if bool(same.all()) else int((~same).int().argmax()))
-    # ... and in front of the first soft slot whose sources differ (the columns up to there are identical: slot k sits at the same column)
-    cols = is_slot[0, :Tp].nonzero()[:, 0].tolist()
-    for k, c in enumerate(cols):
-        if any(slot_sources[r][k] != slot_sources[0][k] for r in range(1, B)):
-            Tp = c
-            break
+    ids, mask, is_slot, answer_pos = _qa_batch_view(ids, mask, slot_sources, answer_idx, soft_slot_ids)
+    B = ids.shape[0]
+    Tp = _shared_cut(ids, mask, is_slot, slot_sources, answer_pos)
+    suffixes = [ids[r, Tp:answer_pos[r] + 1] for r in range(B)]
     S = max(answer_pos) - Tp + 1
-    suffix_ids = torch.full((B, S), int(pad_id), dtype=torch.long)
-    suffix_mask = torch.zeros(B, S, dtype=torch.long)
-    for r in range(B):
-        n = answer_pos[r] - Tp + 1
-        suffix_ids[r, :n] = ids[r, Tp:answer_pos[r] + 1]
-        suffix_mask[r, :n] = 1
     ap = torch.tensor(answer_pos, dtype=torch.long)
-    return dict(Tp=Tp, S=S, B=B, suffix_ids=suffix_ids, suffix_mask=suffix_mask, answer_pos=ap,
-                answer_rows=(torch.arange(B) * S + ap - Tp).to(torch.int32))
+    return dict(Tp=Tp, S=S, B=B, suffix_ids=_pad_rows(suffixes, pad_id), suffix_mask=_pad_mask(suffixes),
+                answer_pos=ap, answer_rows=(torch.arange(B) * S + ap - Tp).to(torch.int32))
 
 
 def shared_prefix_groups(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id):
@@ -221,15 +242,8 @@ def shared_prefix_groups(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad
       answer_pos [B]                   caller order, position in the full row
       answer_rows [B] int32            flat row i * S + answer_pos - group_len[g] of the sorted [B, S] suffix batch
     ValueError: as `shared_prefix_plan`."""
-    shared_prefix_plan(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad_id)       # (the argument errors, stated once)
-    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
-    B, T = ids.shape
-    is_slot = torch.zeros_like(mask)
-    for i in soft_slot_ids:
-        is_slot |= ids == int(i)
-    is_slot &= mask
-    is_ans = (ids == int(answer_idx)) & mask
-    answer_pos = (T - 1 - is_ans.flip(1).int().argmax(1)).tolist()
+    ids, mask, is_slot, answer_pos = _qa_batch_view(ids, mask, slot_sources, answer_idx, soft_slot_ids)
+    B = ids.shape[0]
     id_rows, slot_rows = ids.tolist(), is_slot.tolist()
     groups, members = {}, []
     for r in range(B):
@@ -249,21 +263,16 @@ def shared_prefix_groups(ids, mask, slot_sources, answer_idx, soft_slot_ids, pad
     inverse = [0] * B
     for i, r in enumerate(order):
         inverse[r] = i
-    plans = [shared_prefix_plan(ids[rows], mask[rows], [slot_sources[r] for r in rows], answer_idx, soft_slot_ids, pad_id) for rows in members]
-    group_len = [p["Tp"] for p in plans]
-    S = max(p["S"] for p in plans)
-    suffix_ids = torch.full((B, S), int(pad_id), dtype=torch.long)
-    suffix_mask = torch.zeros(B, S, dtype=torch.long)
-    i = 0
-    for p in plans:
-        suffix_ids[i:i + p["B"], :p["S"]] = p["suffix_ids"]
-        suffix_mask[i:i + p["B"], :p["S"]] = p["suffix_mask"]
-        i += p["B"]
+    group_len = [_shared_cut(ids[rows], mask[rows], is_slot[rows], [slot_sources[r] for r in rows], [answer_pos[r] for r in rows]) for rows in members]
+    row_len = [n for n, rows in zip(group_len, members) for _ in rows]                   # sorted order, as everything per row below
+    suffixes = [ids[r, n:answer_pos[r] + 1] for r, n in zip(order, row_len)]
+    suffix_ids = _pad_rows(suffixes, pad_id)
+    S = suffix_ids.shape[1]
     ap = torch.tensor(answer_pos, dtype=torch.long)
-    row_len = torch.tensor([n for n, rows in zip(group_len, members) for _ in rows], dtype=torch.long)
     return dict(order=torch.tensor(order), inverse=torch.tensor(inverse), group_rows=[len(rows) for rows in members], group_len=group_len,
                 prefix_rows=[rows[0] for rows in members], prefix_T=max(group_len), S=S, B=B, n_groups=len(members), suffix_ids=suffix_ids,
-                suffix_mask=suffix_mask, answer_pos=ap, answer_rows=(torch.arange(B) * S + ap[order] - row_len).to(torch.int32))
+                suffix_mask=_pad_mask(suffixes), answer_pos=ap,
+                answer_rows=(torch.arange(B) * S + ap[order] - torch.tensor(row_len)).to(torch.int32))
 
 
 def candidate_plan_groups(tokenize, label_rule, instructions, candidates, answer_idx, pad_id):
@@ -274,61 +283,20 @@ def candidate_plan_groups(tokenize, label_rule, instructions, candidates, answer
       suffix_ids / suffix_mask / suffix_labels [R, S], cut [R]   R = sum(group_rows) rows
       n_candidates [P], row_of [P, Nmax] the row of candidate (p, n), -1 in the padding; n_tokens [P, Nmax], 0 in the padding
       P, Nmax, R, Tp, S"""
-    P = len(instructions)
-    if len(candidates) != P or P == 0:
-        raise ValueError(f"{len(candidates)} candidate lists for {P} prompts")
-    if any(len(c) < 1 for c in candidates):
-        raise ValueError(f"every prompt needs at least one candidate, got {[len(c) for c in candidates]}")
-    owner = [(p, n) for p in range(P) for n in range(len(candidates[p]))]
-    texts = [instructions[p] + " " + candidates[p][n] for p, n in owner]
-    ids, mask = tokenize(texts)
-    ids, mask = torch.as_tensor(ids).long().cpu(), torch.as_tensor(mask).cpu() != 0
-    R = len(owner)
-    for r in range(R):
-        if not bool(((ids[r] == answer_idx) & mask[r]).any()):
-            raise ValueError(f"row {r}: no [ANSWER] token in {texts[r]!r}")
-    labels = torch.as_tensor(label_rule(ids)).long().cpu()
-    prefixes, suffixes, suf_labels, cuts = [], [], [], []
-    for r, (p, n) in enumerate(owner):
-        n_real = int(mask[r].sum())
-        assert bool(mask[r, :n_real].all()), "rows must be right-padded"
-        cut = int((ids[r, :n_real] == answer_idx).nonzero().max())
-        if bool((labels[r, :cut + 1] != -100).any()):
-            raise ValueError(f"row {r}: labelled tokens in front of the last [ANSWER]; they lie in the shared prefix and cannot be scored by the extension")
-        if n == 0:
-            prefixes.append(ids[r, :cut])
-        elif not torch.equal(prefixes[-1], ids[r, :cut]):
-            raise ValueError(f"prompt {p}: candidate {n} changes the tokens in front of [ANSWER]; the candidates of a prompt must share its prefix")
-        cuts.append(cut)
-        suffixes.append(ids[r, cut:n_real])
-        suf_labels.append(labels[r, cut:n_real])
+    owner, prefixes, suffix = _cut_candidates(tokenize, label_rule, instructions, candidates, answer_idx, pad_id)
     group_len = [int(t.numel()) for t in prefixes]
     if min(group_len) == 0:
         raise ValueError("[ANSWER] is the first token of a row: nothing to prefill")
-    Tp, S = max(group_len), max(int(t.numel()) for t in suffixes)
-    prefix_ids = torch.full((P, Tp), int(pad_id), dtype=torch.long)
-    prefix_mask = torch.zeros(P, Tp, dtype=torch.long)
-    for p, t in enumerate(prefixes):
-        prefix_ids[p, :t.numel()] = t
-        prefix_mask[p, :t.numel()] = 1
-    suffix_ids = torch.full((R, S), int(pad_id), dtype=torch.long)
-    suffix_mask = torch.zeros(R, S, dtype=torch.long)
-    suffix_labels = torch.full((R, S), -100, dtype=torch.long)
-    for r, (t, lb) in enumerate(zip(suffixes, suf_labels)):
-        suffix_ids[r, :t.numel()] = t
-        suffix_mask[r, :t.numel()] = 1
-        suffix_labels[r, :t.numel()] = lb
     n_cand = [len(c) for c in candidates]
-    Nmax = max(n_cand)
+    P, Nmax, R = len(prefixes), max(n_cand), len(owner)
+    at = tuple(torch.tensor(owner).T)                                            # (p, n) of every row
     row_of = torch.full((P, Nmax), -1, dtype=torch.long)
+    row_of[at] = torch.arange(R)
     n_tokens = torch.zeros(P, Nmax, dtype=torch.long)
-    per_row = (suffix_labels[:, 1:] != -100).sum(1)
-    for r, (p, n) in enumerate(owner):
-        row_of[p, n] = r
-        n_tokens[p, n] = per_row[r]
-    return dict(prefix_ids=prefix_ids, prefix_mask=prefix_mask, group_rows=n_cand, group_len=group_len, suffix_ids=suffix_ids,
-                suffix_mask=suffix_mask, suffix_labels=suffix_labels, n_candidates=torch.tensor(n_cand), row_of=row_of, n_tokens=n_tokens,
-                cut=torch.tensor(cuts), P=P, Nmax=Nmax, R=R, Tp=Tp, S=S)
+    n_tokens[at] = (suffix["suffix_labels"][:, 1:] != -100).sum(1)
+    return dict(prefix_ids=_pad_rows(prefixes, pad_id), prefix_mask=_pad_mask(prefixes), group_rows=n_cand,
+                group_len=group_len, **suffix, n_candidates=torch.tensor(n_cand), row_of=row_of, n_tokens=n_tokens, P=P, Nmax=Nmax, R=R,
+                Tp=max(group_len), S=suffix["suffix_ids"].shape[1])
 
 
 def special_token_ids(tokenizer, text_encoder_fname):
@@ -514,6 +482,16 @@ class UnifiedProCyon:
     def _require_bf16_or_fp32(self, what):
         if self.dtype not in (BF16, torch.float32):
             raise RuntimeError(f"UnifiedProCyon.{what}: the engine computes in bfloat16 or float32, not {self.dtype}")
+
+    def _require_cache_extension(self, what, inputs):
+        """what every path over `LlamaEngine.extend` refuses (`forward(share_prefix=...)`, `score_candidates`)"""
+        if self._f32:
+            raise NotImplementedError(f"{what} needs the bf16 engine (the fp32 family has no cache extension)")
+        if self.config.use_protein_struct and inputs["input"]["seq"]:
+            raise NotImplementedError(f"{what}: structure tokens are dropped at random per call (struct_dropout_prob), so rows that read alike need "
+                                      "not share a prefix; score such batches with the ordinary forward / score_text")
+        if bool(self.text_encoder.engine.desc.layers_fp8):
+            raise NotImplementedError(f"{what}: the cache extension has no fp8 projections (set_fp8(False) first)")
 
     def __call__(self, *a, **k):
         return self.forward(*a, **k)
@@ -713,13 +691,7 @@ class UnifiedProCyon:
                 raise ValueError("forward(share_prefix=True): retrieval batches read the [PROT] rows of every prompt; there is no shared-prefix path for them")
             if compute_loss or full_logits:
                 raise ValueError("forward(share_prefix=True) computes the answer rows only: compute_loss / full_logits need the ordinary pass")
-            if self._f32:
-                raise NotImplementedError("forward(share_prefix=True) needs the bf16 engine (the fp32 family has no cache extension)")
-            if self.config.use_protein_struct and inputs["input"]["seq"]:
-                raise NotImplementedError("forward(share_prefix=True): structure tokens are dropped at random per call (struct_dropout_prob), so rows "
-                                          "that read alike need not share a prefix")
-            if bool(self.text_encoder.engine.desc.layers_fp8):
-                raise NotImplementedError("forward(share_prefix=True): the cache extension has no fp8 projections (set_fp8(False) first)")
+            self._require_cache_extension("forward(share_prefix=True)", inputs)
         input_embeds, input_ids, attn_masks, ret_idx, tok_emb, ret_emb = self._preprocessing(
             inputs, aaseq_type=aaseq_type, crop_off=crop_off, retrieval=retrieval, exclude_protein_structure=False)
         full_labels = None
@@ -796,15 +768,10 @@ class UnifiedProCyon:
         Tp, S, B = plan["Tp"], plan["S"], plan["B"]
         if Tp == 0:
             return None
-        enc = self.text_encoder
-        eng = enc.engine
-        prefix_cache = eng.new_cache(1, Tp)
-        eng.prefill(emb[0:1, :Tp].contiguous(), None, prefix_cache, logit_rows=None)
-        cache = eng.new_shared_cache(prefix_cache, B, S)
-        # (columns behind a row's [ANSWER] inside [Tp, Tp + S): masked as keys, and no answer row attends them anyway)
-        # suffixes of one length (the screening batches): no mask at all, the kernel takes its unmasked block path
-        keep = None if bool(plan["suffix_mask"].all()) else torch.cat([torch.ones(B, Tp, dtype=torch.long), plan["suffix_mask"]], 1)
-        logits, _, _, _ = eng.extend(cache, emb[:, Tp:Tp + S].contiguous(), Tp, keep=keep, logit_rows=plan["answer_rows"], packed=bool(packed))
+        # ONE prefix row for the B rows, no prefix mask (columns behind a row's [ANSWER] inside [Tp, Tp + S): masked as keys, and no answer row
+        # attends them anyway); suffixes of one length (the screening batches): no mask at all, the kernel takes its unmasked block path
+        logits, *_ = self.text_encoder.engine.extend_behind(emb[0:1, :Tp].contiguous(), None, emb[:, Tp:Tp + S].contiguous(), plan["suffix_mask"],
+                                                            rows_per_prefix=B, logit_rows=plan["answer_rows"], packed=bool(packed))
         return self._answer_rows_output(logits, plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels)
 
     def _forward_prefix_groups(self, inputs, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels, packed):
@@ -813,25 +780,15 @@ class UnifiedProCyon:
                                     (self.prot_replacement_idx, self.drug_idx), self.tokenizer.pad_token_id)
         if min(plan["group_len"]) == 0:
             return None
-        Tp, S, B, n = plan["prefix_T"], plan["S"], plan["B"], plan["n_groups"]
-        eng = self.text_encoder.engine
-        glen = torch.tensor(plan["group_len"])
-        prefix_cache = eng.new_cache(n, Tp)
-        # the groups' prefixes RIGHT-padded to the longest: the real tokens start at position 0 (the columns behind a shorter prefix hold its
-        # first row's own tokens, masked as keys; their K / V slots are never addressed by the extension)
-        eng.prefill(emb[plan["prefix_rows"], :Tp].contiguous(), (torch.arange(Tp)[None] < glen[:, None]).long(), prefix_cache, logit_rows=None)
-        cache = eng.new_grouped_cache(prefix_cache, plan["group_rows"], plan["group_len"], S)
-        row_len = cache.row_len()                                                   # [B] in sorted order
+        Tp, S = plan["prefix_T"], plan["S"]
+        row_len = torch.tensor(plan["group_len"]).repeat_interleave(torch.tensor(plan["group_rows"]))   # [B] in sorted order
         order = plan["order"].to(emb.device)
         cols = (row_len[:, None] + torch.arange(S)[None]).clamp(max=real - 1).to(emb.device)   # (clamped columns lie behind the row's [ANSWER]: masked)
-        suffix_emb = emb[order[:, None], cols].contiguous()
-        keep = None
-        if not bool(plan["suffix_mask"].all()):                                     # keep in the row's OWN logical slots: its prefix, then its suffix
-            keep = torch.zeros(B, Tp + S, dtype=torch.long)
-            for i in range(B):
-                keep[i, :int(row_len[i])] = 1
-                keep[i, int(row_len[i]):int(row_len[i]) + S] = plan["suffix_mask"][i]
-        logits, _, _, _ = eng.extend(cache, suffix_emb, keep=keep, logit_rows=plan["answer_rows"], packed=bool(packed))
+        # the groups' prefixes RIGHT-padded to the longest: the real tokens start at position 0 (the columns behind a shorter prefix hold its
+        # first row's own tokens, masked as keys; their K / V slots are never addressed by the extension)
+        logits, *_ = self.text_encoder.engine.extend_behind(emb[plan["prefix_rows"], :Tp].contiguous(), None, emb[order[:, None], cols].contiguous(),
+                                                            plan["suffix_mask"], groups=(plan["group_rows"], plan["group_len"]),
+                                                            logit_rows=plan["answer_rows"], packed=bool(packed))
         return self._answer_rows_output(logits[plan["inverse"].to(logits.device)], plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels)
 
     def _answer_rows_output(self, logits, plan, emb, input_ids, am, full_labels, answer_pos, real, get_full_labels):
@@ -882,66 +839,39 @@ class UnifiedProCyon:
         ragged=True: lists of any lengths >= 1 (`candidate_plan_groups`).  The prompts are RIGHT-padded -- every prompt sits at the positions
         `score_text` gives it and no pad column runs in front of it -- and the suffixes run as one grouped `extend`.  The results are padded to
         Nmax = the longest list: "n_candidates" [P]; in the padding token_nll = 0, n_tokens = 0, seq_nll = mean_nll = +inf, so that "order"
-        (stable argsort) puts it last."""
+        (stable argsort) puts it last.
+        Not on the fp32 family, with structure tokens or with fp8 weights (NotImplementedError, the refusals of `forward(share_prefix=True)`)."""
         self._require_bf16_or_fp32("score_candidates")
-        if self._f32:
-            raise NotImplementedError("score_candidates needs the bf16 engine (the fp32 family has no cache extension)")
-        if self.config.use_protein_struct and inputs["input"]["seq"]:
-            raise NotImplementedError("score_candidates: structure tokens are dropped at random per call (struct_dropout_prob); score such batches with score_text")
+        self._require_cache_extension("score_candidates", inputs)
         if any(len(t) for t in inputs["input"]["text"]):
             raise NotImplementedError("score_candidates: [EXT] text slots are not supported; write the text into the instruction")
-        instructions = list(inputs["instructions"])
         tokenize = lambda texts: self._prepare_text_inputs_and_tokenize(texts, [[] for _ in texts], crop_off=True)
-        if ragged:
-            return self._score_candidates_ragged(inputs, candidates, aaseq_type, packed, tokenize)
-        plan = candidate_plan(tokenize, self._full_labels, instructions, candidates, self.answer_idx, self.tokenizer.pad_token_id)
-        P, N, Tp, S = plan["P"], plan["N"], plan["Tp"], plan["S"]
-        soft_ids = (self.prot_replacement_idx, self.struct_idx, self.drug_idx)
-        if any(bool((plan["suffix_ids"] == i).any()) for i in soft_ids):
-            raise ValueError("score_candidates: a candidate holds a soft-token slot")
-        _, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
-        prefix_emb, _ = self._prepare_input_embeddings(plan["prefix_ids"], protein_soft_tokens=protein_soft_tokens, drug_soft_tokens=drug_soft_tokens)
-        eng = self.text_encoder.engine
-        prefix_cache = eng.new_cache(P, Tp)
-        eng.prefill(prefix_emb, plan["prefix_mask"], prefix_cache, logit_rows=None)
-        cache = eng.new_shared_cache(prefix_cache, N, S)
-        keep = torch.cat([plan["prefix_mask"].repeat_interleave(N, 0), plan["suffix_mask"]], 1)
-        _, _, token_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), Tp, keep=keep, labels=plan["suffix_labels"],
-                                        packed=bool(packed))
-        token_nll = token_nll.view(P, N, S)
-        seq_nll = token_nll.sum(2)
-        n_tokens = plan["n_tokens"].to(seq_nll.device)
-        mean_nll = seq_nll / n_tokens
-        return {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll,
-                "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
-
-    def _score_candidates_ragged(self, inputs, candidates, aaseq_type, packed, tokenize):
-        plan = candidate_plan_groups(tokenize, self._full_labels, list(inputs["instructions"]), candidates, self.answer_idx, self.tokenizer.pad_token_id)
-        P, Nmax, R, Tp, S = plan["P"], plan["Nmax"], plan["R"], plan["Tp"], plan["S"]
+        plan = (candidate_plan_groups if ragged else candidate_plan)(tokenize, self._full_labels, list(inputs["instructions"]), candidates,
+                                                                     self.answer_idx, self.tokenizer.pad_token_id)
         if any(bool((plan["suffix_ids"] == i).any()) for i in (self.prot_replacement_idx, self.struct_idx, self.drug_idx)):
             raise ValueError("score_candidates: a candidate holds a soft-token slot")
         _, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
         prefix_emb, _ = self._prepare_input_embeddings(plan["prefix_ids"], protein_soft_tokens=protein_soft_tokens, drug_soft_tokens=drug_soft_tokens)
         eng = self.text_encoder.engine
-        prefix_cache = eng.new_cache(P, Tp)
-        eng.prefill(prefix_emb, plan["prefix_mask"], prefix_cache, logit_rows=None)
-        cache = eng.new_grouped_cache(prefix_cache, plan["group_rows"], plan["group_len"], S)
-        row_len = cache.row_len()
-        keep = torch.zeros(R, Tp + S, dtype=torch.long)                              # in every row's own logical slots
-        for r in range(R):
-            keep[r, :int(row_len[r])] = 1
-            keep[r, int(row_len[r]):int(row_len[r]) + S] = plan["suffix_mask"][r]
-        _, _, row_nll, _ = eng.extend(cache, eng.embed_tokens(plan["suffix_ids"]), keep=keep, labels=plan["suffix_labels"], packed=bool(packed))
-        row_of = plan["row_of"].to(row_nll.device)
-        real = row_of >= 0
-        token_nll = torch.zeros(P, Nmax, S, dtype=row_nll.dtype, device=row_nll.device)
-        token_nll[real] = row_nll[row_of[real]]
-        inf = torch.full((P, Nmax), float("inf"), dtype=row_nll.dtype, device=row_nll.device)
-        seq_nll = torch.where(real, token_nll.sum(2), inf)
+        rows = dict(groups=(plan["group_rows"], plan["group_len"])) if ragged else dict(rows_per_prefix=plan["N"])
+        _, _, row_nll, _, cache = eng.extend_behind(prefix_emb, plan["prefix_mask"], eng.embed_tokens(plan["suffix_ids"]), plan["suffix_mask"],
+                                                    labels=plan["suffix_labels"], packed=bool(packed), **rows)
         n_tokens = plan["n_tokens"].to(row_nll.device)
-        mean_nll = torch.where(real, seq_nll / n_tokens, inf)
-        return {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll, "n_candidates": plan["n_candidates"],
-                "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
+        if not ragged:
+            token_nll = row_nll.view(plan["P"], plan["N"], plan["S"])
+            seq_nll = token_nll.sum(2)
+            mean_nll = seq_nll / n_tokens
+        else:                                        # [P, Nmax] with the padding of the shorter lists sorted last
+            row_of = plan["row_of"].to(row_nll.device)
+            real = row_of >= 0
+            token_nll = torch.zeros(plan["P"], plan["Nmax"], plan["S"], dtype=row_nll.dtype, device=row_nll.device)
+            token_nll[real] = row_nll[row_of[real]]
+            inf = torch.full_like(n_tokens, float("inf"), dtype=row_nll.dtype)
+            seq_nll = torch.where(real, token_nll.sum(2), inf)
+            mean_nll = torch.where(real, seq_nll / n_tokens, inf)
+        out = {"token_nll": token_nll, "seq_nll": seq_nll, "n_tokens": n_tokens, "mean_nll": mean_nll,
+               "order": torch.argsort(mean_nll, dim=1, stable=True), "plan": plan, "cache": cache}
+        return dict(out, n_candidates=plan["n_candidates"]) if ragged else out
 
     # ------------------------------------------------------------------------------------------
     @staticmethod

@@ -597,6 +597,43 @@ def _split(instr):
     return head + "[ANSWER]", tail.strip()
 
 
+def test_every_shared_prefix_call_is_one_extension(env, prot):
+    """The one-call-per-batch property of every driver over `LlamaEngine.extend`: the extension counters advance by ONE per call -- the packed
+    one only when asked for, the grouped one only on the two grouped paths -- and `generate_lookahead` by one plain extension per pass.
+    (Expected values read off the drivers: each makes exactly one `extend` call, the lookahead loop one pcy_llama_extend per pass.)  A second,
+    identical call returns the same bits."""
+    m = env["model"]
+    eng = m.text_encoder.engine
+    lib = eng.ctx.lib
+    prompts = [_split(i)[0] for i in SC.INSTR]
+    two = [i for i in range(len(MIX_INSTR)) if i != 2]                                           # 2 receptors x 3 rows, tails of 0 / 1 / 2 words
+    qa = lambda instr, slots, **kw: m.forward(_inputs(prot, instr, slots), **kw)["outputs"].answer_logits
+    cand = lambda n, lists, **kw: m.score_candidates(SC.make_inputs(env, instr=prompts[:n], slots=SC.SLOTS[:n]), lists, **kw)["token_nll"]
+    #        name                         the call                                                                            grouped
+    calls = [("forward(share_prefix=True)", lambda pk: qa(ONE_INSTR[:4], ONE_SLOTS[:4], share_prefix=True, packed=pk), 0),     # 4 rows, one receptor
+             ("forward(share_prefix='groups')", lambda pk: qa([MIX_INSTR[i] for i in two], [MIX_SLOTS[i] for i in two], share_prefix="groups", packed=pk), 1),
+             ("score_candidates", lambda pk: cand(2, [["yes", "w3 w4", "no w5 w6"], ["alpha", "beta gamma", "w7"]], packed=pk), 0),
+             ("score_candidates(ragged)", lambda pk: cand(3, [["yes"], ["alpha", "w7 w8", "beta gamma delta"], ["q r", "w9"]], ragged=True, packed=pk), 1)]
+    for name, call, grouped in calls:
+        for packed in (False, True):
+            e0, p0, g0 = _counts(lib)
+            first = call(packed)
+            assert _counts(lib) == (e0 + 1, p0 + int(packed), g0 + grouped), f"{name}, packed={packed}"
+            assert torch.equal(call(packed), first), f"{name}, packed={packed}: a second call"
+    emb, ids, *_ = m._preprocessing(_inputs(prot, [MIX_INSTR[0]], [MIX_SLOTS[0]]), aaseq_type="protein", crop_off=True, no_pad=True, left_pad=True)
+    hist = ids[0].clone()
+    hist[hist == m.prot_replacement_idx] = -1
+    runs = []
+    for _ in range(2):
+        e0, p0, g0 = _counts(lib)
+        tok, lp, lg, (_, _, look) = eng.generate_lookahead(emb, hist, 6, 4, keep_logits=True)
+        passes = look.stats()["passes"]
+        assert 2 <= passes <= 5                                                                  # 5 tokens behind the prefill's, 1 to 4 per pass
+        assert _counts(lib) == (e0 + passes, p0, g0), "generate_lookahead: one plain extension per pass"
+        runs.append((tok.cpu(), lp.cpu(), lg.cpu().clone()))
+    assert all(torch.equal(a, b) for a, b in zip(*runs))
+
+
 def test_score_candidates_ragged_against_score_text(env, work):
     m = env["model"]
     lib = m.text_encoder.engine.ctx.lib
