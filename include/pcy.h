@@ -356,6 +356,27 @@ int pcy_llama_decode_layers(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*
 /* the same step as ONE replayed hipGraph (captured on first use per model / cache / state / batch): for host-driven loops that
  * do their own selection between steps (sampling, diverse beam search).  next_tok and *pos are read from device memory. */
 int pcy_llama_decode_graph(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* ---- the decode step for more than 32 rows: one pass over the weights whatever B ----
+ * Opt-in, beside pcy_llama_decode, whose step above 32 rows streams every weight matrix once per 32 rows.  Here every projection and lm_head
+ * is ONE MFMA GEMM over all B rows (the dispatcher of the prefill and of the cache extension); the attention is the default loop's launch.
+ * Contract -- pcy_llama_decode's: next_tok -> logits in state->logits, K / V of the new token appended at logical slot *pos of every row;
+ * does not pick, does not advance.  next_tok, *pos and keep are read from DEVICE memory: no host read, no synchronisation.  keep has the
+ * decode meaning (slot *pos always attended, bytes at and above *pos not read; NULL = quirk Q1).  Plain caches and shared-prefix caches
+ * (prefix_k / prefix_v, rows_per_prefix >= 1).  1 <= B <= the cache's rows, no other upper limit; meant for B >= 33.  One launch per stage
+ * on the context's stream, never captured; the workspace is the context's (sized by B, the geometry and the cache capacity).
+ * Argument errors (nothing launched, nothing written): a grouped cache (rows_per_prefix == 0 with a prefix), a model with fp8 layers,
+ * B outside [1, cache rows], a geometry the GEMMs / the attention do not cover (d, ffn, H*dh, Hkv*dh % 64; head_dim 32 / 64 / 128;
+ * H / Hkv in 1, 2, 4, 8).
+ * NOT promised: the bits of pcy_llama_decode.  The GEMMs add up in another order than the default step's GEMVs, and a row's bits may depend
+ * on B: tile shapes and K splits are chosen by the row count.  Tokens may therefore part from the default path's where two logits tie
+ * within bf16 noise.
+ * Promised: within ONE call a row's logits and appended K / V depend on that row's inputs alone -- not on the M tile it sits in nor on what
+ * its batch mates hold (equal rows give equal bits); the same call repeated gives the same bits; plain and shared-prefix caches of equal
+ * contents give equal bits; every row meets the oracle within the project's bar (tests/test_gpu_decode_gemm.py). */
+int pcy_llama_decode_gemm(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* steps enqueued by pcy_llama_decode_gemm since the library was loaded.  A word of its own, as pcy_debug_look_count: the kinds of
+ * pcy_debug_dispatch_count are pinned, and this step counts under none of the decode kinds. */
+unsigned long long pcy_debug_decode_gemm_count(void);
 /* argmax of state->logits (lowest index on ties) -> next_tok / tokens_out[step], logprob, ++pos? no: ++step only
  * when advance_pos == 0 (used on the prefill logits), ++pos and ++step otherwise.  logprob += bf16 log_softmax(logits)[token]: fp32
  * statistics, one rounding.  -inf logits are allowed and mean "never chosen" (banned tokens, also whole runs of them); a row must hold

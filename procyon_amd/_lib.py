@@ -144,6 +144,8 @@ SIGNATURES = {
     "pcy_debug_mc_trace": (ci, [vp, ci]),
     "pcy_llama_decode_layers": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
     "pcy_llama_decode_graph": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_llama_decode_gemm": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_debug_decode_gemm_count": (C.c_ulonglong, []),
     "pcy_greedy_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
     "pcy_look_draft": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
     "pcy_look_verify": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),

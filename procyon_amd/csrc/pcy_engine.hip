@@ -39,6 +39,8 @@ inline int kv_cap(const pcy_kv_cache* kv) { return kv->Tmax + (kv_shared(kv) ? k
 unsigned long long g_pcy_extend_grouped = 0;
 // calls of pcy_look_draft / pcy_look_verify (pcy_debug_look_count): words of their own for the same reason
 unsigned long long g_pcy_look[2] = {0, 0};
+// steps enqueued by pcy_llama_decode_gemm (pcy_debug_decode_gemm_count): a word of its own for the same reason
+unsigned long long g_pcy_decode_gemm = 0;
 
 }  // namespace
 
@@ -191,7 +193,7 @@ int check_launch(const char* what) {
 // (*fused = 1), see PcyGemmArgs
 void linear(hipStream_t s, const bf16_t* A, int lda, const bf16_t* W, const bf16_t* bias, const bf16_t* resid, int ldr,
             bf16_t* C, int ldc, int M, int N, int K, int epi, float* splitk_ws = nullptr, size_t splitk_ws_bytes = 0,
-            const bf16_t* next_w = nullptr, bf16_t* next_xn = nullptr, int* fused = nullptr, float rms_eps = 0.f, int rms_cast = 0) {
+            const bf16_t* next_w = nullptr, bf16_t* next_xn = nullptr, int* fused = nullptr, float rms_eps = 0.f, int rms_cast = 0, int splitk_fill = 0) {
   if (M <= 8 && epi != EPI_SWIGLU && (resid == nullptr || ldr == ldc)) {
     PcyGemvArgs g{};
     g.W = W; g.x = A; g.y = C; g.bias = bias; g.resid = resid; g.rms_w = nullptr;
@@ -203,7 +205,7 @@ void linear(hipStream_t s, const bf16_t* A, int lda, const bf16_t* W, const bf16
   a.A = A; a.W = W; a.C = C; a.bias = bias; a.resid = resid;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.epi = epi;
   a.splitk_ws = splitk_ws; a.splitk_ws_bytes = splitk_ws_bytes;
-  a.next_rms_w = next_w; a.next_xn = next_xn; a.fused_next = fused; a.rms_eps = rms_eps; a.rms_cast = rms_cast;
+  a.next_rms_w = next_w; a.next_xn = next_xn; a.fused_next = fused; a.rms_eps = rms_eps; a.rms_cast = rms_cast; a.splitk_fill = splitk_fill;
   pcy_launch_gemm(s, a);
 }
 
@@ -1804,6 +1806,55 @@ int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cac
   if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode_graph")) return r;
   return replay_decode_graph(c, m, kv, st, B, 1, 1, sw);
 }
+
+// ---- the decode step for more than 32 rows: every projection is ONE GEMM over all B rows ----
+// The default loop above cuts a projection into 32-row passes that each stream the whole matrix (pcy_launch_gemv); here the B rows are the M of
+// `linear`, the prefill's and the extension's dispatcher: MFMA tiles, the K-split finish and the RMSNorm fused into it, SwiGLU / residual
+// epilogues.  The attention is the loop's stand-alone launch (all rows, *pos and the keep mask from device memory, shared-prefix caches).
+// The workspace is the decode carve: the pick / sampling launches behind the step find their partials where they expect them.
+static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  hipStream_t s = c->stream;
+  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
+  const DecodeCx cx = decode_cx(c, m, kv, st, B);
+  const DecodePlan p{};   // (the stand-alone attention: no key split, its own column cut)
+  pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
+  int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer& L = m->layers[l];
+    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    linear(s, cx.xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, cx.qkv, cx.qkvw, B, cx.qkvw, d, EPI_STORE, cx.sk_ws, cx.sk_bytes);
+    pcy_launch_attn_decode(s, attn_args(cx, p, l));
+    linear(s, cx.ao, H * dh, (const bf16_t*)L.wo, nullptr, cx.x, d, cx.x, d, B, d, H * dh, EPI_RESID, cx.sk_ws, cx.sk_bytes,
+           (const bf16_t*)L.ln2, cx.xn, &xn_ready, m->rms_eps, m->rms_cast, 1);   // (1: K splits that fill the chip at one or two row tiles)
+    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, B, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    linear(s, cx.xn, d, (const bf16_t*)L.wgu, nullptr, nullptr, 0, cx.act, F, B, 2 * F, d, EPI_SWIGLU);
+    linear(s, cx.act, F, (const bf16_t*)L.wdown, nullptr, cx.x, d, cx.x, d, B, d, F, EPI_RESID, cx.sk_ws, cx.sk_bytes,
+           (const bf16_t*)(l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm), cx.xn, &xn_ready, m->rms_eps, m->rms_cast, 1);
+  }
+  if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, B, d, m->rms_eps, m->rms_cast);
+  linear(s, cx.xn, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)st->logits, m->vocab, B, m->vocab, d, EPI_STORE);
+  ++g_pcy_decode_gemm;
+}
+
+int pcy_llama_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  PCY_STICKY(c);
+  const char* what = "pcy_llama_decode_gemm";
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
+  if (kv_shared(kv) && kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
+  if (int r = check_shared_cache(kv, B, what)) return r;
+  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (32/64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "%s: d, ffn, H*dh, Hkv*dh must be multiples of 64", what);
+  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
+  enqueue_decode_gemm(c, m, kv, st, B);
+  return check_launch(what);
+}
+unsigned long long pcy_debug_decode_gemm_count(void) { return g_pcy_decode_gemm; }
 
 int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out) {

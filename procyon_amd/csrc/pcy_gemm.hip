@@ -1198,6 +1198,8 @@ void pcy_launch_gemm(hipStream_t s, const PcyGemmArgs& a0) {
     // (a 2-way split buys less than its finish launch costs: Llama-3-8B qkv at one 512-token prompt 41.3 + 6.4 us split vs 41.9 us as one
     // gemm_kernel_mid launch -- and the rule stays a function of (N, K) only)
     if (splits == 2) splits = 1;
+    if (a.splitk_fill)   // (the decode step's o / down projections at 160 rows: 256 workgroups of 4 splits -> 512 of 8)
+      while (splits < 8 && tiles * splits < 512 && a.K % (splits * 2 * 64) == 0 && a.K / (splits * 2) >= 512) splits *= 2;
     if (splits > 1 && (size_t)splits * a.M * a.N * 4 <= a.splitk_ws_bytes) {
       ++g_pcy_dispatch[PCY_DISPATCH_GEMM_SPLITK];
       hipLaunchKernelGGL(gemm_splitk_kernel, dim3(tiles * splits), dim3(GEMM_THREADS), 0, s, a, splits, a.K / splits);

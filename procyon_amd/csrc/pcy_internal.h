@@ -112,6 +112,10 @@ struct PcyGemmArgs {
   const bf16_t* next_rms_w; bf16_t* next_xn; int* fused_next; float rms_eps; int rms_cast;
   int gelu_select;      // set by the launcher (PCY_DISABLE=gelu_fast): the ESM-GELU kernel skips the fast table epilogue
   int mid_cfg;          // > 0: this configuration of gemm_kernel_mid (pcy_gemm_mid.h); 0: the launcher's own choice
+  // split-K path only: go on doubling the splits (up to 8) while THIS call's tiles x splits leave the 512 workgroup slots under-filled.
+  // The split count then depends on M: only for callers whose rows all come from one call (the GEMM decode step, M = 33..256: the d x d
+  // and ffn x d projections have one or two row tiles).  0 (everyone else): the count stays a function of (N, K) alone.
+  int splitk_fill;
 };
 struct pcy_ctx;
 hipStream_t pcy_ctx_stream(pcy_ctx* c);               // the context's stream (pcy_engine.hip owns the struct)

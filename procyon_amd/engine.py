@@ -553,6 +553,19 @@ def beam_cache_plan(B, beam, T, max_new, disabled_names=()):
                 slots_shared=B * T + rows * max_new, slots_plain=rows * (T + max_new))
 
 
+# The decode step for more than 32 rows (LlamaEngine.decode_gemm): from how many rows `decode_gemm="auto"` takes it.  The default
+# step streams the weights once per 32 rows, the new one once per step: DECODE_GEMM_MIN_ROWS is the smallest measured row count from which the
+# new step won every pair of tools/bench_decode_gemm.py on both geometries (profiles/decode_gemm_ab.log).  Never below 33.
+DECODE_GEMM_MIN_ROWS = 33
+
+
+def decode_gemm_plan(rows, shared=False, mha=False):
+    """-> bool: whether `decode_gemm="auto"` runs a decode step of `rows` rows on the one-pass GEMM step.  shared: the cache carries a shared
+    prefix; mha: the multi-head geometry class (Llama-2-7B / ProCyon-Split) instead of the grouped-query one (Llama-3-8B).  Pure: the one
+    place that decides what "auto" means.  The measurement gave the same threshold for both classes and both cache layouts."""
+    return int(rows) >= max(33, DECODE_GEMM_MIN_ROWS)
+
+
 def disabled_switches():
     """The names in PCY_DISABLE (procyon_amd/csrc/pcy_switch.h: comma separated, whole names), read now: the one reader on the Python side."""
     return frozenset(n.strip() for n in os.environ.get("PCY_DISABLE", "").split(",") if n.strip())
@@ -968,6 +981,21 @@ class LlamaEngine:
         """decode step as one replayed hipGraph (~190 launches otherwise): loops that select between steps on the device."""
         L.check(self.ctx.lib.pcy_llama_decode_graph(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_graph")
 
+    def decode_gemm(self, cache: KVCache, st: GenState, B):
+        """the decode step for more than 32 rows: every projection one GEMM over the B rows, one pass over the weights (pcy_llama_decode_gemm).
+        The contract of `decode`; not its bits."""
+        L.check(self.ctx.lib.pcy_llama_decode_gemm(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm")
+
+    def _use_decode_gemm(self, decode_gemm, rows, shared=False):
+        """What a driver's `decode_gemm=False | True | "auto"` means for `rows` decode rows."""
+        if decode_gemm is False or decode_gemm is None:
+            return False
+        if decode_gemm is True:
+            return True
+        if decode_gemm == "auto":
+            return decode_gemm_plan(rows, shared, self.cfg.n_kv_heads == self.cfg.n_heads)
+        raise ValueError(f"decode_gemm={decode_gemm!r}: False, True or 'auto'")
+
     def beam_step(self, logits, bs: "BeamState", group_size, diversity_penalty):
         """one step of the reference's diverse-beam bookkeeping on the device (pcy_beam_step); logits [BB, vocab] bf16."""
         _chk_bf16(logits)
@@ -1009,15 +1037,21 @@ class LlamaEngine:
         st.pos.fill_(T)
         return cache, st
 
-    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None):
+    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, decode_gemm=False):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) entirely on the device: prefill, then per step the
         decode launches + the sampling kernels (pcy_llama_sample); the uniform variates of all steps are drawn up front from
-        torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state)."""
+        torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state).
+        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + sample_pick per step."""
         B = embeds.shape[0]
+        gemm = self._use_decode_gemm(decode_gemm, B)
         u = torch.rand(max_len * B, device=self.device, dtype=torch.float32) if uniforms is None else uniforms.to(self.device, torch.float32).contiguous()
         cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits)
         self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
-        if max_len > 1:
+        if gemm:
+            for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
+                self.decode_gemm(cache, st, B)
+                self.sample_pick(cache, st, B, True, u, temperature, nucleus_prob)
+        elif max_len > 1:
             self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob)
         self.ctx.sync()       # the record may live in host memory; and a watchdog of the fused decode launches must fail THIS call
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
@@ -1028,18 +1062,24 @@ class LlamaEngine:
         src = src_rows.to(self.device, torch.int32).contiguous()
         L.check(self.ctx.lib.pcy_kv_reorder_range(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(src), src.numel(), int(t0), t), "pcy_kv_reorder")
 
-    def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, clean_decode_mask=False, use_graph=True):
+    def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, clean_decode_mask=False, use_graph=True, decode_gemm=False):
         """`_generate_sampling(greedy=True)` (model_unified.py:861-921): prefill, then max_len-1 cached decode
         steps with no mask and position = cache length (Q1/Q2); no EOS stop.  Everything stays on the device;
-        returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,max_len,V] bf16 | None, state)."""
+        returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,max_len,V] bf16 | None, state).
+        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + pick per step."""
         B, T, _ = embeds.shape
+        gemm = self._use_decode_gemm(decode_gemm, B)
         keep = None
         if clean_decode_mask and attn_mask is not None:
             keep = torch.ones(B, T + max_len, dtype=torch.uint8, device=self.device)
             keep[:, :T] = (attn_mask != 0).to(self.device, torch.uint8)
         cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, keep)
         self.pick(cache, st, B, advance_pos=False)
-        if max_len > 1:
+        if gemm:
+            for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
+                self.decode_gemm(cache, st, B)
+                self.pick(cache, st, B, advance_pos=True)
+        elif max_len > 1:
             self.greedy_steps(cache, st, B, max_len - 1, use_graph)
         # complete before anything is handed out: the logits record may live in host memory, and a watchdog that fired inside a
         # fused decode launch (workgroups not all resident) must fail THIS call, not a later one (pcy_ctx_sync reads the sticky word)
@@ -1121,14 +1161,16 @@ class LlamaEngine:
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
         return st.tokens_out.long(), st.logprob, la, (st, cache, look)
 
-    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new):
+    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new, decode_gemm=False):
         """`_generate_beam_search` (model_unified.py:702-842): diverse beam search of B prompts x beam_size beams, at most max_len tokens, on
         a cache with room for max_new (>= max_len) generated ones.  Returns (tokens [BB,max_len] int64 and scores [BB] on the host, logits
         [BB,steps,V] in pinned host memory), BB = B * beam_size, row r = beam r % beam_size of prompt r // beam_size.
         Nothing synchronises inside a step: the decode step is ONE replayed hipGraph reading the next tokens and the position from device
         memory, the reference's per-group bookkeeping ONE launch (pcy_beam_step), the KV reorder two.  The logits record is kept per SLOT and
         step and re-indexed once at the end along the parent chain (the reference re-indexes the whole history in every group of every step,
-        :827-829).  The EOS stop (:833) is decided on the device; the host looks at the flag every 8 steps."""
+        :827-829).  The EOS stop (:833) is decided on the device; the host looks at the flag every 8 steps.
+        decode_gemm (False | True | "auto"): the four-call body with the one-pass GEMM step in place of the replayed graph,
+        on whichever cache beam_cache_plan chose."""
         B, T, _ = embeds.shape
         BB, V, dev = B * beam_size, self.cfg.vocab, self.device
         off = disabled_switches()
@@ -1138,6 +1180,7 @@ class LlamaEngine:
         # pcy_kv_reorder, source map r -> r // beam).  PCY_DISABLE=beam_prefill_once, or one beam: the reference's replicated prefill, issued
         # as LlamaPostTokenization.forward issues it (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise).
         shared = beam_cache_plan(B, beam_size, T, max_new, off)["shared"]
+        gemm = self._use_decode_gemm(decode_gemm, BB, shared)
         rep = lambda x: x.repeat_interleave(beam_size, dim=0)
         if shared or (beam_size > 1 and "beam_prefill_once" not in off):
             cache = self.new_cache(B, T) if shared else self.new_cache(BB, T + max_new)
@@ -1165,9 +1208,12 @@ class LlamaEngine:
         while i < max_len and not ((i & 7) == 0 and int(bs.done)):
             if T + i > cache.capacity:
                 raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
-            if "beam_graph" in off:
+            if gemm or "beam_graph" in off:
                 n = 1
-                self.decode_graph(cache, st, BB)
+                if gemm:
+                    self.decode_gemm(cache, st, BB)
+                else:
+                    self.decode_graph(cache, st, BB)
                 rec[i].copy_(st.logits)
                 self.beam_step(st.logits, bs, group_size, diversity_penalty)
                 self.kv_reorder(cache, bs.src, T + i, t0=kv_t0)

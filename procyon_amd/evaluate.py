@@ -11,7 +11,9 @@ same return types, incl. the on-disk target-embedding cache of the retrieval plu
 scoring runs on the device (`pcy_retrieval_scores`) and returns the reference's float64 CPU matrix.
 
 Engine-specific, optional `model_config` keys (absent in the reference's YAML, ignored by it): "tokenizer" (a tokenizer object
-for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwargs" (dict forwarded to `from_pretrained`)."""
+for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwargs" (dict forwarded to `from_pretrained`),
+"decode_gemm" (caption plugin; False, True or "auto", default False: the decode steps of `generate` on the step that reads the weights
+once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step)."""
 from collections import defaultdict
 from collections.abc import Mapping
 
@@ -154,6 +156,7 @@ class ProcyonCaptionEval:
         self.num_captions = model_config.get("num_captions", 5)
         self.beam_group_size = model_config.get("beam_group_size", 2)
         self.beam_size = model_config.get("beam_size", self.num_captions * self.beam_group_size)
+        self.decode_gemm = model_config.get("decode_gemm", False)
 
     @torch.no_grad()
     def get_predictions(self, data_loader):
@@ -163,7 +166,8 @@ class ProcyonCaptionEval:
             model_inputs = move_inputs_to_device(model_inputs, self.device)
             _, _, _, captions = self.model.generate(model_inputs, max_len=self.max_len, aaseq_type=data_loader.dataset.aaseq_type,
                                                     return_all_internals=False, method=self.method, beam_size=self.beam_size,
-                                                    beam_group_size=self.beam_group_size, truncate_on_eos=True)
+                                                    beam_group_size=self.beam_group_size, truncate_on_eos=True,
+                                                    **({"decode_gemm": self.decode_gemm} if self.decode_gemm else {}))
             for i, indices in enumerate(model_inputs["reference_indices"]["input"]["seq"]):
                 for j in range(self.num_captions):
                     aaseq_indices.append(indices[-1])

@@ -917,7 +917,7 @@ class UnifiedProCyon:
 
     @torch.no_grad()
     def _generate_sampling(self, input_embeds, attn_masks, max_len=64, num_text_per_instance=1, temperature=1.0,
-                           greedy=False, nucleus_prob=None):
+                           greedy=False, nucleus_prob=None, decode_gemm=False):
         """`_generate_sampling` (model_unified.py:861-921).  Greedy runs entirely on the device (hipGraph-replayed
         decode steps, fused argmax + log-prob), and so does sampling: `pcy_llama_sample` forms the reference's pre-sampling
         probability vector (`_sampling_probs` below is its torch restatement) and draws by inverse CDF with uniform variates
@@ -929,8 +929,9 @@ class UnifiedProCyon:
         for _ in range(num_text_per_instance):
             # the whole loop on the device: decode launches + the pick (greedy: argmax; sampling: softmax, nucleus mask by histogram, inverse-CDF
             # draw with uniform variates from torch's device generator); the logits record goes to the host as it is produced
-            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True) if greedy else \
-                eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True)
+            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm) if greedy else \
+                eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True,
+                                      decode_gemm=decode_gemm)
             out_list.append(tok.cpu())
             lp_list.append(lp.cpu().clone())
             logit_list.append(lg.cpu())
@@ -941,7 +942,7 @@ class UnifiedProCyon:
 
     @torch.no_grad()
     def _generate_beam_search(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5,
-                              diversity_penalty=0.8):
+                              diversity_penalty=0.8, decode_gemm=False):
         """`_generate_beam_search` (model_unified.py:702-842): diverse beam search with the reference's exact
         bookkeeping (step-0 single-beam top-g, in-place Hamming penalty carried in the score, bf16 log-softmax +
         fp32 running score, EOS-anywhere stop).  The transformer steps run on the engine; the per-step
@@ -954,7 +955,7 @@ class UnifiedProCyon:
             raise ValueError("beam_size > 32 is not supported by the device-side beam step")
         enc = self.text_encoder
         flat = enc.engine.generate_beam(input_embeds, attn_mask, max_len, beam_size, beam_group_size, diversity_penalty,
-                                        self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len))
+                                        self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len), decode_gemm=decode_gemm)
         return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
 
     @contextmanager
@@ -1049,7 +1050,7 @@ class UnifiedProCyon:
     def generate(self, inputs, max_len=64, aaseq_type='protein', method="sampling", temperature=1.0, greedy=False,
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
-                 lookahead=0, lookahead_ngram=(3, 1)):
+                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1058,7 +1059,12 @@ class UnifiedProCyon:
         tokens per pass over the weights (`LlamaEngine.generate_lookahead`; drafts by looking the last `lookahead_ngram` = (longest, shortest)
         tokens up in the prompt and the text so far).  Same return values; with return_all_internals the dictionary gains "lookahead" =
         {passes, tokens, accepted, tokens_per_pass}.  Its tokens do not depend on the drafts, but are not promised equal to lookahead=0
-        where two logits tie within the arithmetic's noise."""
+        where two logits tie within the arithmetic's noise.
+        decode_gemm=True | "auto" (not in the reference; False, the default, is today's code): the cached decode steps of every method on the
+        step that reads the weights once whatever the row count (`LlamaEngine.decode_gemm`) -- for more than 32 rows per step
+        (prompts x beams); "auto" takes it from `engine.decode_gemm_plan`'s row count on.  Same return values; the tokens are not promised equal
+        to decode_gemm=False where two logits tie within the arithmetic's noise.  Not together with lookahead (ValueError: one prompt, one
+        row); not on the fp32 family (NotImplementedError)."""
         assert method in ["sampling", "temperature", "greedy", "beam", "nucleus"]
         self._require_bf16_or_fp32("generate")      # fp32 (a caller that never called .bfloat16()): the operator-by-operator fp32 loops below
         lookahead = int(lookahead)
@@ -1066,6 +1072,12 @@ class UnifiedProCyon:
             raise NotImplementedError("generate(lookahead=W) needs the bf16 engine (the fp32 family has no cache extension)")
         if lookahead and (lookahead < 2 or lookahead > 32):
             raise ValueError(f"generate: lookahead={lookahead}: 0 (off) or a window of 2..32 rows")
+        if decode_gemm not in (False, True, "auto"):
+            raise ValueError(f"generate: decode_gemm={decode_gemm!r}: False, True or 'auto'")
+        if decode_gemm and lookahead:
+            raise ValueError("generate: decode_gemm serves steps of many rows, lookahead one prompt: pass one of them")
+        if decode_gemm and self._f32:
+            raise NotImplementedError("generate(decode_gemm=...) needs the bf16 engine (the fp32 family has no GEMM decode step)")
         if method == "beam":
             num_text_per_instance = beam_size
         elif method == "greedy":
@@ -1097,11 +1109,11 @@ class UnifiedProCyon:
         elif method == "beam":
             tokens, log_probs, logits = (self._generate_beam_search_f32 if self._f32 else self._generate_beam_search)(
                 input_embeds, attn_masks, max_len=max_len, beam_size=beam_size, diversity_penalty=diversity_penalty,
-                beam_group_size=beam_group_size)
+                beam_group_size=beam_group_size, **({"decode_gemm": decode_gemm} if decode_gemm else {}))
         else:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,
-                temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob)
+                temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob, **({"decode_gemm": decode_gemm} if decode_gemm else {}))
         flattened = torch.flatten(tokens, start_dim=0, end_dim=1)
         text = self.tokenizer.batch_decode(flattened)
         if truncate_on_eos:
