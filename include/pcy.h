@@ -377,6 +377,30 @@ int pcy_llama_decode_gemm(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, 
 /* steps enqueued by pcy_llama_decode_gemm since the library was loaded.  A word of its own, as pcy_debug_look_count: the kinds of
  * pcy_debug_dispatch_count are pinned, and this step counts under none of the decode kinds. */
 unsigned long long pcy_debug_decode_gemm_count(void);
+/* Decode attention of ONE new token per row on layer `layer` of a shared-prefix cache, all rows of a prompt against ONE pass over its prefix
+ * (DESIGN.md 4.3d).  The operator is pcy_attn_decode's: ropes q and the new k at *pos (device scalar = LOGICAL cache length t), appends K, V
+ * at suffix slot t - prefix_T of the row's own panel, attends logical slots [0, t] -- slot j < prefix_T from prefix row b / rows_per_prefix,
+ * slot j >= prefix_T from the row's own panel -- with pcy_attn_decode's rounding points.  keep: optional [B, prefix_T + Tmax] bytes in logical
+ * slots read through the query's own row, non-zero = kept; slot t is always attended, bytes at and above t are not read.  The cache is passed
+ * as to pcy_attn_extend, everything else as to pcy_attn_decode.  head_dim 64 or 128, H / Hkv in 1, 2, 4, 8, rows_per_prefix >= 1.
+ * Work split: the K and V tiles of a (prompt, kv head) are staged once per 64 packed queries (rows x H / Hkv) and used by MFMA; the prefix is
+ * cut into key chunks whose count is a function of (B, rows_per_prefix, prefix_T, geometry); the chunks' fp32 partial sums are added in chunk
+ * order, the row's own slots last, and rounded once.  No atomics.
+ * Promised: a query's bits depend on its own row's logical contents and on the call's shape (B, prefix_T, t, geometry) only; equal calls give
+ * equal bits; the appended K / V have the bits pcy_attn_decode writes; the prefix is never written and of the suffix only slot t - prefix_T;
+ * slots above t never reach a result.  NOT promised: the bits of pcy_attn_decode's output (another order of the sums).
+ * t < prefix_T or t >= prefix_T + Tmax: nothing is written.  Argument errors (nothing launched, nothing written, no fallback): a plain cache,
+ * a grouped cache (rows_per_prefix == 0), an incomplete shared cache, B outside [1, cache rows], an unsupported head_dim or H / Hkv, rows of
+ * qkv / o that are not 16-byte aligned.  Workspace: the context's. */
+int pcy_attn_decode_shared(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos,
+                           const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh);
+/* pcy_llama_decode_gemm with the attention of every layer served by pcy_attn_decode_shared's kernels: the same contract word for word, on
+ * shared-prefix caches with rows_per_prefix >= 1 only (a plain cache, head_dim 32: argument errors as above).  The decode workspace keeps its
+ * carve; the attention's score rows and partial sums lie behind it.  NOT promised: the bits of pcy_llama_decode_gemm. */
+int pcy_llama_decode_gemm_mq(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* steps enqueued by pcy_llama_decode_gemm_mq since the library was loaded (each also counts in pcy_debug_decode_gemm_count, none under a
+ * decode kind of pcy_debug_dispatch_count). */
+unsigned long long pcy_debug_attn_mq_count(void);
 /* argmax of state->logits (lowest index on ties) -> next_tok / tokens_out[step], logprob, ++pos? no: ++step only
  * when advance_pos == 0 (used on the prefill logits), ++pos and ++step otherwise.  logprob += bf16 log_softmax(logits)[token]: fp32
  * statistics, one rounding.  -inf logits are allowed and mean "never chosen" (banned tokens, also whole runs of them); a row must hold

@@ -146,6 +146,9 @@ SIGNATURES = {
     "pcy_llama_decode_graph": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_llama_decode_gemm": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_debug_decode_gemm_count": (C.c_ulonglong, []),
+    "pcy_attn_decode_shared": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "pcy_llama_decode_gemm_mq": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_debug_attn_mq_count": (C.c_ulonglong, []),
     "pcy_greedy_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
     "pcy_look_draft": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
     "pcy_look_verify": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),

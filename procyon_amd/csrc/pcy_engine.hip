@@ -41,6 +41,8 @@ unsigned long long g_pcy_extend_grouped = 0;
 unsigned long long g_pcy_look[2] = {0, 0};
 // steps enqueued by pcy_llama_decode_gemm (pcy_debug_decode_gemm_count): a word of its own for the same reason
 unsigned long long g_pcy_decode_gemm = 0;
+// ... of which by pcy_llama_decode_gemm_mq (pcy_debug_attn_mq_count)
+unsigned long long g_pcy_attn_mq = 0;
 
 }  // namespace
 
@@ -1812,10 +1814,30 @@ int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cac
 // `linear`, the prefill's and the extension's dispatcher: MFMA tiles, the K-split finish and the RMSNorm fused into it, SwiGLU / residual
 // epilogues.  The attention is the loop's stand-alone launch (all rows, *pos and the keep mask from device memory, shared-prefix caches).
 // The workspace is the decode carve: the pick / sampling launches behind the step find their partials where they expect them.
-static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+
+// The many-queries attention (pcy_attn_mq.hip) on layer `layer` of a complete shared-prefix cache; ws: its score rows and partial
+// sums (mq_ws_bytes).  Built in ONE place for pcy_attn_decode_shared and the step of pcy_llama_decode_gemm_mq.
+static size_t mq_ws_bytes(const PcyMqPlan& p) { return align_up(p.sc_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
+static PcyMqAttnArgs mq_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
+                                  const bf16_t* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, char* ws) {
+  const PcyMqPlan p = pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T);
+  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh, prefix_layer_stride = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
+  PcyMqAttnArgs a{};
+  a.qkv = qkv; a.ld = ld; a.k_own = (bf16_t*)kv->k + layer * layer_stride; a.v_own = (bf16_t*)kv->v + layer * layer_stride;
+  a.k_pre = (const bf16_t*)kv->prefix_k + layer * prefix_layer_stride; a.v_pre = (const bf16_t*)kv->prefix_v + layer * prefix_layer_stride;
+  a.Town = kv->Tmax; a.Tp = kv->prefix_T; a.rows_per_prefix = kv->rows_per_prefix; a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t;
+  a.keep = keep; a.ld_keep = kv_cap(kv); a.B = B; a.H = H; a.Hkv = Hkv; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
+  Carver cv(ws);
+  a.sc = cv.take<bf16_t>(p.sc_bytes / sizeof(bf16_t)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
+  a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks; a.lds = p.lds;
+  return a;
+}
+// mq: the attention launch of every layer is the many-queries one, its buffers behind the decode carve (pcy_llama_decode_gemm_mq)
+static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq) {
   hipStream_t s = c->stream;
   const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
   const DecodeCx cx = decode_cx(c, m, kv, st, B);
+  char* mq_ws = c->ws + align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256);
   const DecodePlan p{};   // (the stand-alone attention: no key split, its own column cut)
   pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
   int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
@@ -1824,7 +1846,9 @@ static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_k
     if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
     xn_ready = 0;
     linear(s, cx.xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, cx.qkv, cx.qkvw, B, cx.qkvw, d, EPI_STORE, cx.sk_ws, cx.sk_bytes);
-    pcy_launch_attn_decode(s, attn_args(cx, p, l));
+    if (mq) pcy_launch_attn_mq(s, mq_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
+                                               B, H, m->n_kv_heads, dh, mq_ws));
+    else pcy_launch_attn_decode(s, attn_args(cx, p, l));
     linear(s, cx.ao, H * dh, (const bf16_t*)L.wo, nullptr, cx.x, d, cx.x, d, B, d, H * dh, EPI_RESID, cx.sk_ws, cx.sk_bytes,
            (const bf16_t*)L.ln2, cx.xn, &xn_ready, m->rms_eps, m->rms_cast, 1);   // (1: K splits that fill the chip at one or two row tiles)
     if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, B, d, m->rms_eps, m->rms_cast);
@@ -1836,11 +1860,23 @@ static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_k
   if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, B, d, m->rms_eps, m->rms_cast);
   linear(s, cx.xn, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)st->logits, m->vocab, B, m->vocab, d, EPI_STORE);
   ++g_pcy_decode_gemm;
+  if (mq) ++g_pcy_attn_mq;
 }
 
-int pcy_llama_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+// a complete shared-prefix cache with a uniform rows_per_prefix and a geometry the many-queries attention covers: anything else is the caller's error
+static int check_mq_cache(const pcy_kv_cache* kv, int B, int H, int Hkv, int dh, const char* what) {
+  if (!kv_shared(kv)) return fail(1, "%s: the cache has no shared prefix (plain caches: the decode attention)", what);
+  if (kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
+  if (int r = check_shared_cache(kv, B, what)) return r;
+  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (!pcy_attn_mq_covers(H, Hkv, dh, kv->Tmax)) return fail(1, "%s: the scores of %d suffix slots do not fit in LDS", what, kv->Tmax);
+  return 0;
+}
+
+static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq) {
   PCY_STICKY(c);
-  const char* what = "pcy_llama_decode_gemm";
+  const char* what = mq ? "pcy_llama_decode_gemm_mq" : "pcy_llama_decode_gemm";
   if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
   if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
@@ -1850,11 +1886,38 @@ int pcy_llama_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cach
   if (dh != 32 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (32/64/128)", what, dh);
   if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
   if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "%s: d, ffn, H*dh, Hkv*dh must be multiples of 64", what);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  enqueue_decode_gemm(c, m, kv, st, B);
+  size_t need = decode_ws_bytes(m, B, kv_cap(kv));
+  if (mq) {
+    if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
+    need = align_up(need, 256) + mq_ws_bytes(pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T));
+  }
+  if (int r = c->reserve(need)) return r;
+  enqueue_decode_gemm(c, m, kv, st, B, mq);
   return check_launch(what);
 }
+int pcy_llama_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  return decode_gemm_entry(c, m, kv, st, B, false);
+}
+int pcy_llama_decode_gemm_mq(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  return decode_gemm_entry(c, m, kv, st, B, true);
+}
 unsigned long long pcy_debug_decode_gemm_count(void) { return g_pcy_decode_gemm; }
+unsigned long long pcy_debug_attn_mq_count(void) { return g_pcy_attn_mq; }
+
+int pcy_attn_decode_shared(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
+                           const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh) {
+  PCY_STICKY(c);
+  const char* what = "pcy_attn_decode_shared";
+  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
+  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
+  if (int r = c->reserve(mq_ws_bytes(pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T)))) return r;
+  if (!pcy_launch_attn_mq(c->stream, mq_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
+                                                  B, H, Hkv, dh, c->ws)))
+    return fail(1, "%s: shape not covered", what);
+  return check_launch(what);
+}
 
 int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out) {

@@ -270,6 +270,30 @@ bool pcy_launch_attn_extend_packed(hipStream_t s, const PcyExtAttnArgs& a);
 void pcy_launch_ext_pos(hipStream_t s, int32_t* pos, int B, int S, int t_past);   // pos[b*S + s] = t_past + s
 // grouped sibling: pos[b*S + s] = g_len[g_row_grp[b]] + t_own + s
 void pcy_launch_ext_pos_grouped(hipStream_t s, int32_t* pos, int B, int S, int t_own, const int32_t* g_len, const int32_t* g_row_grp);
+// Many-queries decode attention on a shared-prefix cache (pcy_attn_mq.hip): the operator of pcy_launch_attn_decode on a shared
+// cache, with the prefix of a prompt staged once for all its rows x G queries and cut into key chunks across workgroups.
+struct PcyMqPlan {
+  int ntiles;                                  // 64-query tiles per (prompt, kv head)
+  int nchunk, cblocks;                         // key chunks of the prefix, 32-key blocks per chunk: functions of the call's shape only
+  int lds;                                     // elements per score row (prefix_T rounded up to 32)
+  size_t sc_bytes, part_bytes;                 // score rows [B*H][lds] bf16; partial o [nchunk + 1][B][H*dh] fp32
+};
+PcyMqPlan pcy_attn_mq_plan(int B, int rows_per_prefix, int H, int Hkv, int dh, int Tp);
+bool pcy_attn_mq_covers(int H, int Hkv, int dh, int Town);   // head_dim 64 / 128, H/Hkv 1 / 2 / 4 / 8, the own slots' scores fit in LDS
+struct PcyMqAttnArgs {
+  const bf16_t* qkv; int ld;                   // [B, (H+2Hkv)*dh] un-roped projections of the new token
+  bf16_t* k_own; bf16_t* v_own;                // THIS layer's suffix panels [rows, Hkv, Town, dh]: logical slot j >= Tp at j - Tp
+  const bf16_t* k_pre; const bf16_t* v_pre;    // THIS layer's prefix [prefix_B, Hkv, Tp, dh]; row b reads prefix row b / rows_per_prefix
+  int Town, Tp, rows_per_prefix;
+  bf16_t* o; int ldo;                          // [B, H*dh]
+  const int32_t* pos_dev;                      // device scalar: logical cache length t == rotary position of the new token
+  const bf16_t* cos_t; const bf16_t* sin_t;
+  const uint8_t* keep; int ld_keep;            // optional [B, ld_keep] key mask in logical slots, non-zero = kept
+  int B, H, Hkv, dh; float scale;
+  bf16_t* sc; float* part;                     // workspace (PcyMqPlan::sc_bytes / part_bytes), 256-byte aligned
+  int ntiles, nchunk, cblocks, lds;            // the plan of this shape
+};
+bool pcy_launch_attn_mq(hipStream_t s, const PcyMqAttnArgs& a);   // false = shape not covered, nothing launched
 struct PcyGemvArgs;
 // decode attention + o projection (EPI_RESID GEMV over the attention output) in one launch; false = shape not covered,
 // nothing launched.  epoch: device word that differs between consecutive calls on the same `flags` (max_flags words).

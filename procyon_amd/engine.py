@@ -174,6 +174,20 @@ class Context:
                                          _p(sin_t), _p(keep), B, H, Hkv, dh, Tmax), "pcy_attn_decode")
         return o
 
+    def attn_decode_shared(self, qkv, cache, layer, pos, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, out=None):
+        """pcy_attn_decode_shared: `attn_decode`'s operator on layer `layer` of a shared-prefix KVCache, all rows of a prompt against one pass
+        over its prefix.  qkv [B, (H+2Hkv)*dh] un-roped projections (B rows, default the cache's); pos int32 device scalar =
+        the LOGICAL cache length; appends K / V at suffix slot pos - prefix_T; -> o [B, H*dh].  keep: [B, cache.capacity] uint8 in logical
+        slots or None.  Anything but a complete shared-prefix cache with rows_per_prefix >= 1 is an error: there is no fallback."""
+        _chk_bf16(qkv)
+        B = cache.B if B is None else int(B)
+        if keep is not None:
+            assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, cache.capacity), (keep.shape, keep.dtype)
+        o = torch.empty(B, H * dh, dtype=BF16, device=qkv.device) if out is None else out
+        L.check(self.lib.pcy_attn_decode_shared(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), o.shape[1], _p(pos), _p(cos_t),
+                                                _p(sin_t), _p(keep), B, H, Hkv, dh), "pcy_attn_decode_shared")
+        return o
+
     def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, packed=False, groups=None):
         """pcy_attn_extend: qkv [B*S, (H+2Hkv)*dh] un-roped projections of S new tokens per row (row b*S+s; B rows, default the cache's);
         `cache` a KVCache (plain or shared-prefix) that holds t_past tokens per row.  Ropes q / k in place at t_past + s, appends K / V at
@@ -981,9 +995,13 @@ class LlamaEngine:
         """decode step as one replayed hipGraph (~190 launches otherwise): loops that select between steps on the device."""
         L.check(self.ctx.lib.pcy_llama_decode_graph(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_graph")
 
-    def decode_gemm(self, cache: KVCache, st: GenState, B):
+    def decode_gemm(self, cache: KVCache, st: GenState, B, shared_attn=False):
         """the decode step for more than 32 rows: every projection one GEMM over the B rows, one pass over the weights (pcy_llama_decode_gemm).
-        The contract of `decode`; not its bits."""
+        The contract of `decode`; not its bits.  shared_attn=True (pcy_llama_decode_gemm_mq): the attention scores all rows of a
+        prompt against one pass over its shared prefix -- a shared-prefix cache only, anything else is an error."""
+        if shared_attn:
+            L.check(self.ctx.lib.pcy_llama_decode_gemm_mq(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm_mq")
+            return
         L.check(self.ctx.lib.pcy_llama_decode_gemm(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm")
 
     def _use_decode_gemm(self, decode_gemm, rows, shared=False):
@@ -1161,7 +1179,8 @@ class LlamaEngine:
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
         return st.tokens_out.long(), st.logprob, la, (st, cache, look)
 
-    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new, decode_gemm=False):
+    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new, decode_gemm=False,
+                      shared_attn=False):
         """`_generate_beam_search` (model_unified.py:702-842): diverse beam search of B prompts x beam_size beams, at most max_len tokens, on
         a cache with room for max_new (>= max_len) generated ones.  Returns (tokens [BB,max_len] int64 and scores [BB] on the host, logits
         [BB,steps,V] in pinned host memory), BB = B * beam_size, row r = beam r % beam_size of prompt r // beam_size.
@@ -1170,7 +1189,10 @@ class LlamaEngine:
         step and re-indexed once at the end along the parent chain (the reference re-indexes the whole history in every group of every step,
         :827-829).  The EOS stop (:833) is decided on the device; the host looks at the flag every 8 steps.
         decode_gemm (False | True | "auto"): the four-call body with the one-pass GEMM step in place of the replayed graph,
-        on whichever cache beam_cache_plan chose."""
+        on whichever cache beam_cache_plan chose.
+        shared_attn (False | True): the GEMM step's attention scores all beams of a prompt against one pass over its shared prefix
+        (`decode_gemm(..., shared_attn=True)`).  ValueError unless this call runs the GEMM step AND beam_cache_plan chose the
+        shared cache: there is no fallback."""
         B, T, _ = embeds.shape
         BB, V, dev = B * beam_size, self.cfg.vocab, self.device
         off = disabled_switches()
@@ -1181,6 +1203,9 @@ class LlamaEngine:
         # as LlamaPostTokenization.forward issues it (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise).
         shared = beam_cache_plan(B, beam_size, T, max_new, off)["shared"]
         gemm = self._use_decode_gemm(decode_gemm, BB, shared)
+        if shared_attn and not (gemm and shared):
+            raise ValueError(f"generate_beam: shared_attn needs the GEMM decode step (decode_gemm={decode_gemm!r} -> {gemm}) on the shared-prefix "
+                             f"cache (beam_cache_plan -> shared={shared}) for {B} prompts x {beam_size} beams")
         rep = lambda x: x.repeat_interleave(beam_size, dim=0)
         if shared or (beam_size > 1 and "beam_prefill_once" not in off):
             cache = self.new_cache(B, T) if shared else self.new_cache(BB, T + max_new)
@@ -1211,7 +1236,7 @@ class LlamaEngine:
             if gemm or "beam_graph" in off:
                 n = 1
                 if gemm:
-                    self.decode_gemm(cache, st, BB)
+                    self.decode_gemm(cache, st, BB, **({"shared_attn": True} if shared_attn else {}))
                 else:
                     self.decode_graph(cache, st, BB)
                 rec[i].copy_(st.logits)

@@ -13,7 +13,9 @@ scoring runs on the device (`pcy_retrieval_scores`) and returns the reference's 
 Engine-specific, optional `model_config` keys (absent in the reference's YAML, ignored by it): "tokenizer" (a tokenizer object
 for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwargs" (dict forwarded to `from_pretrained`),
 "decode_gemm" (caption plugin; False, True or "auto", default False: the decode steps of `generate` on the step that reads the weights
-once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step)."""
+once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step),
+"shared_attn" (caption plugin; False or True, default False: beam search with "decode_gemm" only -- the step's attention scores all beams of a
+prompt against one pass over the K / V they share)."""
 from collections import defaultdict
 from collections.abc import Mapping
 
@@ -157,6 +159,7 @@ class ProcyonCaptionEval:
         self.beam_group_size = model_config.get("beam_group_size", 2)
         self.beam_size = model_config.get("beam_size", self.num_captions * self.beam_group_size)
         self.decode_gemm = model_config.get("decode_gemm", False)
+        self.shared_attn = model_config.get("shared_attn", False)
 
     @torch.no_grad()
     def get_predictions(self, data_loader):
@@ -167,7 +170,8 @@ class ProcyonCaptionEval:
             _, _, _, captions = self.model.generate(model_inputs, max_len=self.max_len, aaseq_type=data_loader.dataset.aaseq_type,
                                                     return_all_internals=False, method=self.method, beam_size=self.beam_size,
                                                     beam_group_size=self.beam_group_size, truncate_on_eos=True,
-                                                    **({"decode_gemm": self.decode_gemm} if self.decode_gemm else {}))
+                                                    **({"decode_gemm": self.decode_gemm} if self.decode_gemm else {}),
+                                                    **({"shared_attn": self.shared_attn} if self.shared_attn else {}))
             for i, indices in enumerate(model_inputs["reference_indices"]["input"]["seq"]):
                 for j in range(self.num_captions):
                     aaseq_indices.append(indices[-1])

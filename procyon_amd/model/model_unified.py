@@ -942,7 +942,7 @@ class UnifiedProCyon:
 
     @torch.no_grad()
     def _generate_beam_search(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5,
-                              diversity_penalty=0.8, decode_gemm=False):
+                              diversity_penalty=0.8, decode_gemm=False, shared_attn=False):
         """`_generate_beam_search` (model_unified.py:702-842): diverse beam search with the reference's exact
         bookkeeping (step-0 single-beam top-g, in-place Hamming penalty carried in the score, bf16 log-softmax +
         fp32 running score, EOS-anywhere stop).  The transformer steps run on the engine; the per-step
@@ -955,7 +955,8 @@ class UnifiedProCyon:
             raise ValueError("beam_size > 32 is not supported by the device-side beam step")
         enc = self.text_encoder
         flat = enc.engine.generate_beam(input_embeds, attn_mask, max_len, beam_size, beam_group_size, diversity_penalty,
-                                        self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len), decode_gemm=decode_gemm)
+                                        self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len), decode_gemm=decode_gemm,
+                                        **({"shared_attn": True} if shared_attn else {}))
         return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
 
     @contextmanager
@@ -1050,7 +1051,7 @@ class UnifiedProCyon:
     def generate(self, inputs, max_len=64, aaseq_type='protein', method="sampling", temperature=1.0, greedy=False,
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
-                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False):
+                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1064,7 +1065,11 @@ class UnifiedProCyon:
         step that reads the weights once whatever the row count (`LlamaEngine.decode_gemm`) -- for more than 32 rows per step
         (prompts x beams); "auto" takes it from `engine.decode_gemm_plan`'s row count on.  Same return values; the tokens are not promised equal
         to decode_gemm=False where two logits tie within the arithmetic's noise.  Not together with lookahead (ValueError: one prompt, one
-        row); not on the fp32 family (NotImplementedError)."""
+        row); not on the fp32 family (NotImplementedError).
+        shared_attn=True (not in the reference; False, the default, is today's code): beam search only, together with decode_gemm -- the
+        attention of the GEMM step scores all beams of a prompt against one pass over the K / V they share.  ValueError with
+        any other method, with lookahead, or (from the engine, before any decode step) where the call does not run the GEMM step on the
+        shared-prefix cache; NotImplementedError on the fp32 family.  Never a silent fallback."""
         assert method in ["sampling", "temperature", "greedy", "beam", "nucleus"]
         self._require_bf16_or_fp32("generate")      # fp32 (a caller that never called .bfloat16()): the operator-by-operator fp32 loops below
         lookahead = int(lookahead)
@@ -1078,6 +1083,12 @@ class UnifiedProCyon:
             raise ValueError("generate: decode_gemm serves steps of many rows, lookahead one prompt: pass one of them")
         if decode_gemm and self._f32:
             raise NotImplementedError("generate(decode_gemm=...) needs the bf16 engine (the fp32 family has no GEMM decode step)")
+        if shared_attn and self._f32:
+            raise NotImplementedError("generate(shared_attn=True) needs the bf16 engine (the fp32 family has no shared-prefix cache)")
+        if shared_attn and lookahead:
+            raise ValueError("generate: shared_attn serves the beams of a beam search, lookahead one greedy row: pass one of them")
+        if shared_attn and method != "beam":
+            raise ValueError(f"generate: shared_attn scores the beams of a prompt together: method='beam' only, got {method!r}")
         if method == "beam":
             num_text_per_instance = beam_size
         elif method == "greedy":
@@ -1109,7 +1120,8 @@ class UnifiedProCyon:
         elif method == "beam":
             tokens, log_probs, logits = (self._generate_beam_search_f32 if self._f32 else self._generate_beam_search)(
                 input_embeds, attn_masks, max_len=max_len, beam_size=beam_size, diversity_penalty=diversity_penalty,
-                beam_group_size=beam_group_size, **({"decode_gemm": decode_gemm} if decode_gemm else {}))
+                beam_group_size=beam_group_size, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
+                **({"shared_attn": True} if shared_attn else {}))
         else:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,

@@ -65,11 +65,13 @@ def _merge_dedup(inputs: List[dict]) -> dict:
 @torch.no_grad()
 def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_dataset: str = "uniprot", prompt_relation: str = "all",
                  max_len: int = 200, beam_size: int = 10, diversity_penalty: float = 0.8, save_path: Optional[str] = None,
-                 batch_size: int = 8, save_frequency: int = 5, device=None, decode_gemm=False) -> pd.DataFrame:
+                 batch_size: int = 8, save_frequency: int = 5, device=None, decode_gemm=False,
+                 shared_attn=False) -> pd.DataFrame:
     """-> DataFrame(uniprot_id, response0 .. response{beam_size // 2 - 1}); `save_path` receives the running table as a pickle
     whenever the one-by-one loop would have written it (after protein i for every i % save_frequency == 0, i > 0) and the final
     table as CSV (caption_bulk.py:99-148).  decode_gemm (False | True | "auto"): `generate`'s option of the same name -- batch_size x beam_size
-    rows per decode step (8 x 10 = 80) on the step that reads the weights once."""
+    rows per decode step (8 x 10 = 80) on the step that reads the weights once.  shared_attn (False | True): `generate`'s
+    option of the same name, with decode_gemm only -- the beams of a protein are scored against one pass over their shared K / V (4.3d)."""
     from procyon.data.inference_utils import create_caption_input_simple, uniprot_id_to_index
     assert "drug" not in prompt_dataset, "DrugBank not supported in this script"
     model.eval()
@@ -86,7 +88,8 @@ def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_da
                                               icl_example_number=1, device=device) for u in ids]
         _, _, _, out_text = model.generate(inputs=_merge_dedup(inputs), aaseq_type="protein", max_len=max_len, method="beam",
                                            return_all_internals=False, beam_size=beam_size, beam_group_size=2,
-                                           diversity_penalty=diversity_penalty, **({"decode_gemm": decode_gemm} if decode_gemm else {}))
+                                           diversity_penalty=diversity_penalty, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
+                                           **({"shared_attn": shared_attn} if shared_attn else {}))
         for b, u in enumerate(ids):
             results["uniprot_id"].append(u)
             for j, t in enumerate(out_text[b]):
