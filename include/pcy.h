@@ -208,7 +208,8 @@ typedef struct {
 /* optional e4m3 copies of the four projection matrices (same row order / interleave as the bf16 ones) and their per-row
  * scales (pcy_quant_rows_fp8).  When pcy_llama_desc.layers_fp8 != NULL, pcy_llama_prefill quantises the input of every
  * projection per token and runs it through pcy_gemm_fp8; norms, rope, attention, residuals, lm_head and the whole
- * decode path stay bf16. */
+ * decode path stay bf16.  (The opt-in step pcy_llama_decode_w8 below streams the same copies in cached decode; it takes them as an
+ * argument of its own and does not look at layers_fp8.) */
 typedef struct {
   const void *wqkv, *wo, *wgu, *wdown;
   const float *sqkv, *so, *sgu, *sdown;
@@ -401,6 +402,38 @@ int pcy_llama_decode_gemm_mq(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache
 /* steps enqueued by pcy_llama_decode_gemm_mq since the library was loaded (each also counts in pcy_debug_decode_gemm_count, none under a
  * decode kind of pcy_debug_dispatch_count). */
 unsigned long long pcy_debug_attn_mq_count(void);
+/* ---- cached decode that streams e4m3 weights: weight-only fp8 projections for 1..8 rows ----
+ * The operator.  y[b][n] = epi( (sum_k x[b][k] * f32(W8[n][k])) * scale[n] ): W8 [N,K] OCP e4m3 codes and scale [N] fp32 as pcy_quant_rows_fp8
+ * makes them per output channel (EPI_SWIGLU: [2N,K] / [2N] in the 16-row gate/up interleave, y is [B,N]); x, resid, y, rms_w bf16.  The
+ * activations stay bf16 and nothing is quantised per call.  fp32 accumulation, the scale ONCE on the finished sum, then pcy_gemv's rounding
+ * points: STORE bf16(v); RESID bf16(bf16(v) + resid) (resid may alias y); SWIGLU bf16(bf16(silu(bf16(g))) * bf16(u)); rms_w != NULL fuses
+ * RMSNorm(x) * rms_w in front (STORE / SWIGLU; rms_cast as pcy_gemv).  Up to 4 rows share a pass over the matrix, 5..8 rows take two.
+ * The order of a (row, output) sum is a function of the output row and K alone: row b of a B-row call has the bits of the one-row call on it.
+ * Argument errors (nothing launched): epi outside STORE / RESID / SWIGLU, B outside [1, 8], K % 16, ldx % 8, W8 / x not 16-byte aligned,
+ * SWIGLU with N % 16, RESID without resid or with rms_w, a NULL tensor, a K whose x row does not fit the LDS of a CU. */
+int pcy_gemv_w8(pcy_ctx*, const void* W8, const float* scale, const void* x, int ldx, const void* resid, void* y, int ldy, const void* rms_w,
+                float rms_eps, int rms_cast, int N, int K, int B, int epi);
+/* One decode step on the e4m3 copies of the projections.  Opt-in, beside pcy_llama_decode, with its contract: next_tok -> logits in
+ * state->logits, K / V of the new token appended at slot *pos of every row; does not pick, does not advance; next_tok, *pos and keep are read
+ * from device memory.  w8: HOST array [n_layers] of the e4m3 matrices and their per-row scales (same row order / interleave as the bf16 ones),
+ * passed explicitly: desc->layers_fp8 keeps meaning "fp8 prefill" and is not read here.  One launch per stage on the context's stream: per
+ * layer qkv (ln1 fused) -> the stand-alone decode attention -> o (+ residual) -> gate/up (ln2 fused, SwiGLU) -> down (+ residual), each a
+ * pcy_gemv_w8 launch; norms, rope, attention, residuals stay bf16, and lm_head stays bf16 on the streaming GEMV with the final norm fused.
+ * The workspace is the decode carve.  A model whose bf16 projection weights ARE dequant(w8) computes here what pcy_llama_decode computes, up
+ * to the order of the sums.
+ * Argument errors (nothing launched, nothing written): w8 NULL or a layer with a NULL pointer; B outside [1, min(8, cache rows)]; a
+ * shared-prefix or grouped cache; d, ffn, H*dh or (H+2Hkv)*dh not multiples of 16; head_dim outside 32 / 64 / 128 or H / Hkv outside
+ * 1, 2, 4, 8; d > 8192.
+ * Promised: a row's logits and appended K / V depend on that row's inputs alone, not on B (1..8) nor on its batch mates; equal calls give
+ * equal bits; pcy_llama_greedy_w8's graph replay and its eager loop give equal bits.  NOT promised: the bits of pcy_llama_decode. */
+int pcy_llama_decode_w8(pcy_ctx*, const pcy_llama_desc*, const pcy_llama_layer_fp8* w8, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* n_steps x (pcy_llama_decode_w8 + greedy pick) with no host synchronisation; use_graph != 0 replays ONE captured hipGraph per step (about
+ * 160 launches per step of a 32-layer model make the eager loop host-bound at one row). */
+int pcy_llama_greedy_w8(pcy_ctx*, const pcy_llama_desc*, const pcy_llama_layer_fp8* w8, const pcy_kv_cache*, const pcy_gen_state*, int B,
+                        int n_steps, int use_graph);
+/* steps enqueued by pcy_llama_decode_w8 / pcy_llama_greedy_w8 outside a graph replay (an eager step, or the capture of a graph).  A word of
+ * its own, as pcy_debug_decode_gemm_count: this step counts under none of the decode kinds of pcy_debug_dispatch_count. */
+unsigned long long pcy_debug_decode_w8_count(void);
 /* argmax of state->logits (lowest index on ties) -> next_tok / tokens_out[step], logprob, ++pos? no: ++step only
  * when advance_pos == 0 (used on the prefill logits), ++pos and ++step otherwise.  logprob += bf16 log_softmax(logits)[token]: fp32
  * statistics, one rounding.  -inf logits are allowed and mean "never chosen" (banned tokens, also whole runs of them); a row must hold

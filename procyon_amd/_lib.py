@@ -149,6 +149,10 @@ SIGNATURES = {
     "pcy_attn_decode_shared": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci]),
     "pcy_llama_decode_gemm_mq": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_debug_attn_mq_count": (C.c_ulonglong, []),
+    "pcy_gemv_w8": (ci, [vp, vp, vp, vp, ci, vp, vp, ci, vp, C.c_float, ci, ci, ci, ci, ci]),
+    "pcy_llama_decode_w8": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LlamaLayerFp8), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_llama_greedy_w8": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LlamaLayerFp8), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci]),
+    "pcy_debug_decode_w8_count": (C.c_ulonglong, []),
     "pcy_greedy_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci]),
     "pcy_look_draft": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
     "pcy_look_verify": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),

@@ -43,6 +43,8 @@ unsigned long long g_pcy_look[2] = {0, 0};
 unsigned long long g_pcy_decode_gemm = 0;
 // ... of which by pcy_llama_decode_gemm_mq (pcy_debug_attn_mq_count)
 unsigned long long g_pcy_attn_mq = 0;
+// steps enqueued by pcy_llama_decode_w8 / pcy_llama_greedy_w8 outside a graph replay (pcy_debug_decode_w8_count): a word of its own as well
+unsigned long long g_pcy_decode_w8 = 0;
 
 }  // namespace
 
@@ -60,7 +62,8 @@ void pcy_set_error(const char* fmt, ...) {
 // arguments), the context's buffers that are baked into the launches, and the switch snapshot the launches were chosen under.  Zero-filled
 // before it is filled in (decode_graph_key) and compared with memcmp: no packing, no hashing.
 struct DecodeGraphKey {
-  int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps)
+  int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps),
+                                      // 3: decode on e4m3 weights + greedy pick (pcy_llama_greedy_w8)
   int B;
   PcySwitches sw;
   const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
@@ -75,6 +78,8 @@ struct DecodeGraphKey {
   const void *logits_rec, *beam_ws;
   int beam, group_size, kv_t0;
   uint32_t penalty_bits;
+  const void* w8;                                  // kind 3: the host array of e4m3 layers and a fingerprint of the device pointers it holds
+  uint64_t w8_fp;
 };
 
 struct pcy_ctx {
@@ -1903,6 +1908,127 @@ int pcy_llama_decode_gemm_mq(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_c
 }
 unsigned long long pcy_debug_decode_gemm_count(void) { return g_pcy_decode_gemm; }
 unsigned long long pcy_debug_attn_mq_count(void) { return g_pcy_attn_mq; }
+
+// ---- the decode step that streams e4m3 weights: weight-only fp8 projections, 1..8 rows ----
+// One launch per stage, built the way enqueue_decode_gemm is: the four projections of a layer are pcy_launch_gemv_w8 launches (RMSNorm fused
+// into qkv and gate/up, residual epilogue on o and down), the attention is the loop's stand-alone launch, lm_head stays bf16 on the streaming
+// GEMV with the final norm fused.  The workspace is the decode carve.
+static PcyGemvW8Args w8_args(const void* W, const float* scale, const bf16_t* x, int K, bf16_t* y, int N, int B, int epi, const void* ln,
+                             const pcy_llama_desc* m) {
+  PcyGemvW8Args g{};
+  g.W = (const uint8_t*)W; g.scale = scale; g.x = x; g.y = y; g.N = N; g.K = K; g.B = B; g.ldx = K; g.ldy = N; g.epi = epi;
+  if (epi == EPI_RESID) g.resid = y;
+  else { g.rms_w = (const bf16_t*)ln; g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast; }
+  return g;
+}
+static uint64_t w8_fingerprint(const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8) {   // FNV-1a, as layers_fingerprint
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](const void* p) { h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull; };
+  mix(m->final_norm); mix(m->lm_head); mix(m->rope_cos); mix(m->rope_sin);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer_fp8& Q = w8[l];
+    mix(Q.wqkv); mix(Q.wo); mix(Q.wgu); mix(Q.wdown); mix(Q.sqkv); mix(Q.so); mix(Q.sgu); mix(Q.sdown);
+  }
+  return h;
+}
+static void enqueue_decode_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  hipStream_t s = c->stream;
+  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
+  const DecodeCx cx = decode_cx(c, m, kv, st, B);
+  DecodePlan p{};   // (the stand-alone attention: no key split)
+  // Its column cut is the one a ONE-row step gets, whatever B: the launcher otherwise widens the cut with Hkv * B, and the order of a row's
+  // sums with it -- a row's bits would depend on the batch it sits in (head_dim 128; the other head sizes have one cut).
+  p.force_ds = m->n_kv_heads >= 128 ? 128 : m->n_kv_heads >= 32 ? 64 : 16;
+  pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer& L = m->layers[l];
+    const pcy_llama_layer_fp8& Q = w8[l];
+    pcy_launch_gemv_w8(s, w8_args(Q.wqkv, Q.sqkv, cx.x, d, cx.qkv, cx.qkvw, B, EPI_STORE, L.ln1, m));
+    pcy_launch_attn_decode(s, attn_args(cx, p, l));
+    pcy_launch_gemv_w8(s, w8_args(Q.wo, Q.so, cx.ao, H * dh, cx.x, d, B, EPI_RESID, nullptr, m));
+    pcy_launch_gemv_w8(s, w8_args(Q.wgu, Q.sgu, cx.x, d, cx.act, F, B, EPI_SWIGLU, L.ln2, m));
+    pcy_launch_gemv_w8(s, w8_args(Q.wdown, Q.sdown, cx.act, F, cx.x, d, B, EPI_RESID, nullptr, m));
+  }
+  PcyGemvArgs h{};
+  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
+  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = B; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
+  h.force_stream = 1;   // (the fused norm selects the streaming kernel anyway, rows in groups of <= 4: a row's bits do not depend on B)
+  pcy_launch_gemv(s, h);
+  ++g_pcy_decode_w8;
+}
+// everything pcy_llama_decode_w8 / pcy_llama_greedy_w8 refuse; reserves the workspace behind the checks
+static int decode_w8_check(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B,
+                           const char* what) {
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits || !m->layers) return fail(1, "%s: model, cache or state incomplete", what);
+  if (!w8) return fail(1, "%s: w8 is NULL (the e4m3 copies of the projections are passed explicitly)", what);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer_fp8& Q = w8[l];
+    if (!Q.wqkv || !Q.wo || !Q.wgu || !Q.wdown || !Q.sqkv || !Q.so || !Q.sgu || !Q.sdown) return fail(1, "%s: w8 layer %d holds a NULL pointer", what, l);
+    if (((uintptr_t)Q.wqkv | (uintptr_t)Q.wo | (uintptr_t)Q.wgu | (uintptr_t)Q.wdown) & 15) return fail(1, "%s: w8 layer %d: matrices must be 16-byte aligned", what, l);
+  }
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  const int bmax = kv->B < 8 ? kv->B : 8;
+  if (B < 1 || B > bmax) return fail(1, "%s: B=%d outside [1, min(8, cache rows %d)]", what, B, kv->B);
+  if (kv_shared(kv)) return fail(1, "%s: a shared-prefix or grouped cache is not served by this step (plain caches only)", what);
+  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (32/64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (d % 16 || F % 16 || (H * dh) % 16 || ((H + 2 * Hkv) * dh) % 16) return fail(1, "%s: d, ffn, H*dh, (H+2Hkv)*dh must be multiples of 16", what);
+  if ((size_t)d * 2 * 4 > 65536) return fail(1, "%s: d=%d: the fused final norm of lm_head needs 4 rows of x in 64 KiB of LDS", what, d);
+  if (pcy_gemv_w8_rows_per_pass(d) < 1 || pcy_gemv_w8_rows_per_pass(F) < 1 || pcy_gemv_w8_rows_per_pass(H * dh) < 1)
+    return fail(1, "%s: a row of x (d, ffn or H*dh elements) does not fit in LDS", what);
+  return c->reserve(decode_ws_bytes(m, B, kv_cap(kv)));
+}
+int pcy_llama_decode_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  PCY_STICKY(c);
+  if (int r = decode_w8_check(c, m, w8, kv, st, B, "pcy_llama_decode_w8")) return r;
+  enqueue_decode_w8(c, m, w8, kv, st, B);
+  return check_launch("pcy_llama_decode_w8");
+}
+int pcy_llama_greedy_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B,
+                        int n_steps, int use_graph) {
+  PCY_STICKY(c);
+  if (int r = decode_w8_check(c, m, w8, kv, st, B, "pcy_llama_greedy_w8")) return r;
+  if (!st->step || !st->tokens_out || !st->logprob) return fail(1, "pcy_llama_greedy_w8: generation state incomplete");
+  if (!use_graph) {
+    for (int i = 0; i < n_steps; ++i) {
+      enqueue_decode_w8(c, m, w8, kv, st, B);
+      enqueue_pick(c, m, st, B, 1, kv_cap(kv));
+    }
+    return check_launch("pcy_llama_greedy_w8");
+  }
+  // (this step reads no switch: the key's snapshot stays zero, and the weight pointers of every layer go in through their fingerprint)
+  DecodeGraphKey key;
+  decode_graph_key(key, c, m, kv, st, B, 3, PcySwitches{});
+  key.mc_tags = key.mb_flags = key.nb_tags = key.dev_layers = nullptr;   // (the fused steps' buffers: not read here)
+  key.layers_fp = layers_fingerprint(m);   // (ln1 / ln2 of every layer)
+  key.w8 = w8; key.w8_fp = w8_fingerprint(m, w8);
+  key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps;
+  return replay_graph(c, key, n_steps, "decode-w8-step", [&] {
+    enqueue_decode_w8(c, m, w8, kv, st, B);
+    enqueue_pick(c, m, st, B, 1, kv_cap(kv));
+  });
+}
+unsigned long long pcy_debug_decode_w8_count(void) { return g_pcy_decode_w8; }
+
+int pcy_gemv_w8(pcy_ctx* c, const void* W8, const float* scale, const void* x, int ldx, const void* resid, void* y, int ldy, const void* rms_w,
+                float rms_eps, int rms_cast, int N, int K, int B, int epi) {
+  PCY_STICKY(c);
+  if (!W8 || !scale || !x || !y) return fail(1, "pcy_gemv_w8: W8, scale, x or y is NULL");
+  if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return fail(1, "pcy_gemv_w8: epi=%d (STORE, RESID or SWIGLU)", epi);
+  if (B < 1 || B > 8) return fail(1, "pcy_gemv_w8: B=%d outside [1, 8]", B);
+  if (N < 1 || K < 16 || K % 16) return fail(1, "pcy_gemv_w8: N=%d K=%d (N >= 1, K a positive multiple of 16)", N, K);
+  if (ldx % 8 || ldx < K || ldy < N) return fail(1, "pcy_gemv_w8: ldx=%d ldy=%d (ldx %% 8 == 0, rows must hold K / N elements)", ldx, ldy);
+  if (((uintptr_t)W8 | (uintptr_t)x) & 15) return fail(1, "pcy_gemv_w8: W8 and x must be 16-byte aligned");
+  if (epi == EPI_SWIGLU && N % 16) return fail(1, "pcy_gemv_w8: SWIGLU needs N %% 16 == 0 features (16-row gate/up interleave), got %d", N);
+  if (epi == EPI_RESID && (!resid || rms_w)) return fail(1, "pcy_gemv_w8: RESID needs resid and takes no fused RMSNorm");
+  if (rms_w && ((uintptr_t)rms_w & 15)) return fail(1, "pcy_gemv_w8: rms_w must be 16-byte aligned");
+  if (pcy_gemv_w8_rows_per_pass(K) < 1) return fail(1, "pcy_gemv_w8: K=%d: a row of x does not fit in LDS", K);
+  PcyGemvW8Args g{};
+  g.W = (const uint8_t*)W8; g.scale = scale; g.x = (const bf16_t*)x; g.y = (bf16_t*)y; g.resid = epi == EPI_RESID ? (const bf16_t*)resid : nullptr;
+  g.rms_w = (const bf16_t*)rms_w; g.rms_eps = rms_eps; g.rms_cast = rms_cast; g.N = N; g.K = K; g.B = B; g.ldx = ldx; g.ldy = ldy; g.epi = epi;
+  if (!pcy_launch_gemv_w8(c->stream, g)) return fail(1, "pcy_gemv_w8: the device refused the LDS size for K=%d", K);
+  return check_launch("pcy_gemv_w8");
+}
 
 int pcy_attn_decode_shared(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
                            const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh) {

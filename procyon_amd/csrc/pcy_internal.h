@@ -38,6 +38,23 @@ struct PcyGemvArgs {
 };
 void pcy_launch_gemv(hipStream_t s, const PcyGemvArgs& a);
 
+// Weight-only fp8 streaming GEMV (pcy_gemv_w8.hip): y = epi((x . f32(W8)^T) * scale), activations bf16.
+struct PcyGemvW8Args {
+  const uint8_t* W;     // [N,K] OCP e4m3 codes, row-major, 16-byte aligned rows (K % 16 == 0); EPI_SWIGLU: [2N,K], 16-row gate/up interleave
+  const float* scale;   // [N] ([2N] for EPI_SWIGLU, in weight-row order): power-of-two dequantisation scale per weight row
+  const bf16_t* x;      // [B,K] (ldx elements between rows, ldx % 8 == 0)
+  bf16_t* y;            // [B,N] (ldy)
+  const bf16_t* resid;  // [B,N] (ldy), EPI_RESID; may alias y
+  const bf16_t* rms_w;  // non-null: RMSNorm(x) * rms_w fused in the prologue (STORE / SWIGLU)
+  float rms_eps;
+  int rms_cast;
+  int N, K, B, ldx, ldy, epi;   // 1 <= B <= 8; epi in STORE / RESID / SWIGLU
+};
+// rows of x one pass over the matrix serves (min(4, what fits the LDS of a CU beside the reduction words); 0: K too large)
+int pcy_gemv_w8_rows_per_pass(int K);
+// false = shape not covered (nothing launched): the caller checks the arguments first
+bool pcy_launch_gemv_w8(hipStream_t s, const PcyGemvW8Args& a);
+
 // Rotated K order of the batched GEMVs (round 6).  Every workgroup of these kernels walks ITS K range front to back in step with all the
 // others, so at any moment every wave of the chip reads the same 256-byte window of its rows -- and with a power-of-two row stride (K = 4096:
 // 8 KB) those windows fall on the same few HBM channels: tools/probes/stream_rows.hip measures the gate/up stream at 4.86 TB/s, and 6.26 TB/s

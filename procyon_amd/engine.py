@@ -84,6 +84,17 @@ class Context:
                                   N, K, B, epi), "pcy_gemv")
         return out
 
+    def gemv_w8(self, W8, scale, x, resid=None, epi=L.EPI_STORE, rms_w=None, rms_eps=1e-5, rms_cast=0, out=None):
+        """Weight-only fp8 GEMV (pcy_gemv_w8): epi((x . f32(W8)^T) * scale) -> bf16; W8 [N,K] uint8 (e4m3 bits) and scale [N] fp32 as
+        `quant_rows_fp8` makes them, x [B,K] bf16 with 1 <= B <= 8; epi STORE / RESID / SWIGLU (W8 in the gate/up interleave)."""
+        _chk_bf16(x, resid, rms_w)
+        B, K = x.shape
+        N = W8.shape[0] // 2 if epi == L.EPI_SWIGLU else W8.shape[0]
+        out = torch.empty(B, N, dtype=BF16, device=x.device) if out is None else out
+        L.check(self.lib.pcy_gemv_w8(self.h, _p(W8), _p(scale), _p(x), x.stride(0), _p(resid), _p(out), out.stride(0), _p(rms_w), rms_eps,
+                                     rms_cast, N, K, B, epi), "pcy_gemv_w8")
+        return out
+
     def lm_head_xent(self, x, W, targets, want_parts=False):
         """Teacher-forced scoring operator (pcy_lm_head_xent): per row m of x [M, d] (final-normed, bf16) against W [V, d] (lm_head),
         nll[m] = logsumexp(bf16 logits of the row) - bf16 logit of targets[m], HF's causal-LM loss term -- the [M, V] logits stay in
@@ -770,6 +781,11 @@ class LlamaEngine:
 
     def quantize_fp8(self):
         """e4m3 copies + per-row scales of wqkv / wo / wgu / wdown (8 GB on top of the 16 GB of a Llama-3-8B), fp8 path on."""
+        self._ensure_fp8_copies()
+        self.set_fp8(True)
+
+    def _ensure_fp8_copies(self):
+        """the e4m3 copies + per-row scales, built once; `desc.layers_fp8` (the prefill's switch) is not touched"""
         if self._arr8 is None:
             self._keep8 = []
             arr8 = (L.LlamaLayerFp8 * self.cfg.n_layers)()
@@ -778,7 +794,7 @@ class LlamaEngine:
                 self._keep8.append(qs)
                 arr8[l] = L.LlamaLayerFp8(*[q.data_ptr() for q, _ in qs], *[sc.data_ptr() for _, sc in qs])
             self._arr8 = arr8
-        self.set_fp8(True)
+        return self._arr8
 
     def set_fp8(self, on):
         if on and self._arr8 is None:
@@ -1004,6 +1020,30 @@ class LlamaEngine:
             return
         L.check(self.ctx.lib.pcy_llama_decode_gemm(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm")
 
+    def decode_w8(self, cache: KVCache, st: GenState, B):
+        """the decode step that streams the e4m3 copies of the projections (pcy_llama_decode_w8): weight-only fp8, 1..8 rows,
+        plain caches.  The contract of `decode`; not its bits.  The copies are made on first use; the prefill stays what `set_fp8` says."""
+        L.check(self.ctx.lib.pcy_llama_decode_w8(self.ctx.h, C.byref(self.desc), self._ensure_fp8_copies(), C.byref(cache.c), C.byref(st.c), B),
+                "pcy_llama_decode_w8")
+
+    def greedy_steps_w8(self, cache, st, B, n_steps, use_graph=True):
+        """n_steps x (decode_w8 + pick) with no host synchronisation; use_graph: one replayed hipGraph per step (pcy_llama_greedy_w8)"""
+        L.check(self.ctx.lib.pcy_llama_greedy_w8(self.ctx.h, C.byref(self.desc), self._ensure_fp8_copies(), C.byref(cache.c), C.byref(st.c), B,
+                                                 n_steps, int(use_graph)), "pcy_llama_greedy_w8")
+
+    @staticmethod
+    def _use_decode_w8(decode_w8, rows, decode_gemm=False):
+        """What a driver's `decode_w8=False | True` means; ValueError for what the e4m3 step does not serve."""
+        if decode_w8 is False:
+            return False
+        if decode_w8 is not True:
+            raise ValueError(f"decode_w8={decode_w8!r}: False or True")
+        if not (decode_gemm is False or decode_gemm is None):
+            raise ValueError("decode_w8 and decode_gemm are two different decode steps: choose one")
+        if rows > 8:
+            raise ValueError(f"decode_w8 serves 1..8 rows, not {rows}")
+        return True
+
     def _use_decode_gemm(self, decode_gemm, rows, shared=False):
         """What a driver's `decode_gemm=False | True | "auto"` means for `rows` decode rows."""
         if decode_gemm is False or decode_gemm is None:
@@ -1055,19 +1095,23 @@ class LlamaEngine:
         st.pos.fill_(T)
         return cache, st
 
-    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, decode_gemm=False):
+    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, decode_gemm=False,
+                          decode_w8=False):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) entirely on the device: prefill, then per step the
         decode launches + the sampling kernels (pcy_llama_sample); the uniform variates of all steps are drawn up front from
         torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state).
-        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + sample_pick per step."""
+        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + sample_pick per step.
+        decode_w8 (False | True): the steps on the e4m3 weight stream, one decode_w8 + sample_pick per step."""
         B = embeds.shape[0]
+        w8 = self._use_decode_w8(decode_w8, B, decode_gemm)
         gemm = self._use_decode_gemm(decode_gemm, B)
         u = torch.rand(max_len * B, device=self.device, dtype=torch.float32) if uniforms is None else uniforms.to(self.device, torch.float32).contiguous()
         cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits)
         self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
-        if gemm:
+        if gemm or w8:
+            step = self.decode_w8 if w8 else self.decode_gemm
             for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
-                self.decode_gemm(cache, st, B)
+                step(cache, st, B)
                 self.sample_pick(cache, st, B, True, u, temperature, nucleus_prob)
         elif max_len > 1:
             self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob)
@@ -1080,12 +1124,15 @@ class LlamaEngine:
         src = src_rows.to(self.device, torch.int32).contiguous()
         L.check(self.ctx.lib.pcy_kv_reorder_range(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(src), src.numel(), int(t0), t), "pcy_kv_reorder")
 
-    def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, clean_decode_mask=False, use_graph=True, decode_gemm=False):
+    def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, clean_decode_mask=False, use_graph=True, decode_gemm=False,
+                        decode_w8=False):
         """`_generate_sampling(greedy=True)` (model_unified.py:861-921): prefill, then max_len-1 cached decode
         steps with no mask and position = cache length (Q1/Q2); no EOS stop.  Everything stays on the device;
         returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,max_len,V] bf16 | None, state).
-        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + pick per step."""
+        decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + pick per step.
+        decode_w8 (False | True): the steps on the e4m3 weight stream (`use_graph` as for the default step)."""
         B, T, _ = embeds.shape
+        w8 = self._use_decode_w8(decode_w8, B, decode_gemm)
         gemm = self._use_decode_gemm(decode_gemm, B)
         keep = None
         if clean_decode_mask and attn_mask is not None:
@@ -1097,6 +1144,8 @@ class LlamaEngine:
             for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
                 self.decode_gemm(cache, st, B)
                 self.pick(cache, st, B, advance_pos=True)
+        elif max_len > 1 and w8:
+            self.greedy_steps_w8(cache, st, B, max_len - 1, use_graph)
         elif max_len > 1:
             self.greedy_steps(cache, st, B, max_len - 1, use_graph)
         # complete before anything is handed out: the logits record may live in host memory, and a watchdog that fired inside a

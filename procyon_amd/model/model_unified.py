@@ -917,7 +917,7 @@ class UnifiedProCyon:
 
     @torch.no_grad()
     def _generate_sampling(self, input_embeds, attn_masks, max_len=64, num_text_per_instance=1, temperature=1.0,
-                           greedy=False, nucleus_prob=None, decode_gemm=False):
+                           greedy=False, nucleus_prob=None, decode_gemm=False, decode_w8=False):
         """`_generate_sampling` (model_unified.py:861-921).  Greedy runs entirely on the device (hipGraph-replayed
         decode steps, fused argmax + log-prob), and so does sampling: `pcy_llama_sample` forms the reference's pre-sampling
         probability vector (`_sampling_probs` below is its torch restatement) and draws by inverse CDF with uniform variates
@@ -929,9 +929,10 @@ class UnifiedProCyon:
         for _ in range(num_text_per_instance):
             # the whole loop on the device: decode launches + the pick (greedy: argmax; sampling: softmax, nucleus mask by histogram, inverse-CDF
             # draw with uniform variates from torch's device generator); the logits record goes to the host as it is produced
-            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm) if greedy else \
+            w8 = {"decode_w8": True} if decode_w8 else {}
+            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm, **w8) if greedy else \
                 eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True,
-                                      decode_gemm=decode_gemm)
+                                      decode_gemm=decode_gemm, **w8)
             out_list.append(tok.cpu())
             lp_list.append(lp.cpu().clone())
             logit_list.append(lg.cpu())
@@ -1051,7 +1052,7 @@ class UnifiedProCyon:
     def generate(self, inputs, max_len=64, aaseq_type='protein', method="sampling", temperature=1.0, greedy=False,
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
-                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False):
+                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1069,7 +1070,12 @@ class UnifiedProCyon:
         shared_attn=True (not in the reference; False, the default, is today's code): beam search only, together with decode_gemm -- the
         attention of the GEMM step scores all beams of a prompt against one pass over the K / V they share.  ValueError with
         any other method, with lookahead, or (from the engine, before any decode step) where the call does not run the GEMM step on the
-        shared-prefix cache; NotImplementedError on the fp32 family.  Never a silent fallback."""
+        shared-prefix cache; NotImplementedError on the fp32 family.  Never a silent fallback.
+        decode_w8=True (not in the reference; False, the default, is today's code): greedy and sampling methods only, up to 8 prompts -- the
+        cached decode steps stream the e4m3 copies of the projection weights (`LlamaEngine.decode_w8`, DESIGN.md 4.3e: weight-only fp8, half
+        the weight bytes per step; the prefill stays what the engine's `set_fp8` says).  The tokens are those of a model whose projection
+        weights are rounded to e4m3 per output channel, not those of decode_w8=False.  ValueError together with lookahead, decode_gemm or
+        method="beam", with more than 8 rows, or with anything but False / True; NotImplementedError on the fp32 family."""
         assert method in ["sampling", "temperature", "greedy", "beam", "nucleus"]
         self._require_bf16_or_fp32("generate")      # fp32 (a caller that never called .bfloat16()): the operator-by-operator fp32 loops below
         lookahead = int(lookahead)
@@ -1089,6 +1095,16 @@ class UnifiedProCyon:
             raise ValueError("generate: shared_attn serves the beams of a beam search, lookahead one greedy row: pass one of them")
         if shared_attn and method != "beam":
             raise ValueError(f"generate: shared_attn scores the beams of a prompt together: method='beam' only, got {method!r}")
+        if decode_w8 is not False:
+            if decode_w8 is not True:
+                raise ValueError(f"generate: decode_w8={decode_w8!r}: False or True")
+            if self._f32:
+                raise NotImplementedError("generate(decode_w8=True) needs the bf16 engine (the fp32 family has no e4m3 decode step)")
+            if lookahead or decode_gemm or method == "beam":
+                raise ValueError("generate: decode_w8 serves the greedy and sampling steps of up to 8 rows: not together with lookahead, decode_gemm or method='beam'")
+            n_rows = len(inputs.get("instructions") or ()) if isinstance(inputs, dict) else 0
+            if n_rows > 8:
+                raise ValueError(f"generate: decode_w8 serves 1..8 rows, got {n_rows} prompts")
         if method == "beam":
             num_text_per_instance = beam_size
         elif method == "greedy":
@@ -1125,7 +1141,8 @@ class UnifiedProCyon:
         else:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,
-                temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob, **({"decode_gemm": decode_gemm} if decode_gemm else {}))
+                temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
+                **({"decode_w8": True} if decode_w8 else {}))
         flattened = torch.flatten(tokens, start_dim=0, end_dim=1)
         text = self.tokenizer.batch_decode(flattened)
         if truncate_on_eos:
