@@ -538,7 +538,8 @@ int pcy_llama_beam_steps(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, c
  * /root/reference/scripts/caption_bulk.py:72-73.  Every pointer is a DEVICE pointer to fp32 (ids / pos / cu: int32, keep: uint8);
  * calls enqueue on the context's stream.  The host side (procyon_amd/engine_f32.py) strings these together op for op like the fp32
  * evaluation of the reference's modules: ESM2 encoder (esm.py:504-538) -> ProteinPooler (:131-173) -> create_mlp projectors
- * (model_utils.py:13-41) -> splice (model_unified.py:1135-1175) -> Llama prefill (pmc_llama.py:546-596).  Cached decode stays bf16. */
+ * (model_utils.py:13-41) -> splice (model_unified.py:1135-1175) -> Llama prefill (pmc_llama.py:546-596) -> cached decode steps
+ * of an fp32 generation (pcy_f32_attn_decode below). */
 /* C[M,N] = act(A[M,K] . W[N,K]^T + bias[N]) (+ resid[M,N]); W is nn.Linear's [out, in]; act 0 = none, 1 = gelu
  * x * 0.5 * (1 + erf(x / sqrt 2)) (nn.GELU and the ESM gelu coincide in fp32).  bias / resid may be NULL; resid may alias C.
  * Matrix cores on exact fp32 products (v_mfma_f32_16x16x4_f32) when K % 16 == 0 and rows are 16-byte aligned, a plain kernel otherwise. */
@@ -560,7 +561,10 @@ int pcy_f32_acc_rows(pcy_ctx*, const float* src, int ld, const int32_t* rows, fl
 /* ProteinPooler over token ranges, arguments as pcy_pool (mode 0 mean, 1 mean of x[1:-1], 2 max) */
 int pcy_f32_pool(pcy_ctx*, const float* hidden, int d, const int32_t* seg, const int32_t* rng, int nprot, int mode, float* out);
 /* softmax((q . k) * scale + mask) . v over packed sequences (cu), grouped heads (Hkv | H), exact fp32 softmax; causal = 1: keys <= query;
- * keep (may be NULL): one byte per packed token, 0 = the key is masked out.  q / k / v are column windows of row-major buffers. */
+ * keep (may be NULL): one byte per packed token, 0 = the key is masked out.  q / k / v are column windows of row-major buffers.
+ * A query row without any kept key (a left-pad row) gets the reference's value, the softmax of a row that is finfo.min throughout:
+ * the plain average of V over ALL keys of its sequence, causal or not, masked and later keys included.  The cached decode reads what
+ * the next layers make of such rows (no mask after the prefill), so the value is part of the contract. */
 int pcy_f32_attention(pcy_ctx*, const float* q, int ldq, int qcol0, const float* k, int ldk, int kcol0, const float* v, int ldv, int vcol0,
                       float* o, int ldo, const int32_t* cu, const uint8_t* keep, int nseq, int max_len, int H, int Hkv, int dh, int causal,
                       float scale);

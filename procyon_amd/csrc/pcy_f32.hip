@@ -2,11 +2,12 @@
 //   /root/reference/examples/paper_analyses/protpep_qa_scores.py:55-58 (the loop that defines BASELINE configs[4]),
 //   /root/reference/scripts/qa_filter_captions.py:17-18, /root/reference/scripts/caption_bulk.py:72-73.
 // Their model holds fp32 weights and every torch op runs in fp32; the bf16 engine cannot reproduce that to better than 1e-2.  This
-// file is the fp32 operator family those paths need -- encoder, pooler, projectors, splice, decoder PREFILL (QA scoring and retrieval
-// read one forward pass; cached decode stays bf16-only) -- written for correctness first:
+// file is the fp32 operator family those paths need -- encoder, pooler, projectors, splice, decoder prefill (QA scoring and retrieval
+// read one forward pass) and the cached decode step of an fp32 generation (pcy_f32_attn_decode) -- written for correctness first:
 //   * Linear on the f32-input matrix cores (v_mfma_f32_16x16x4_f32: exact fp32 products, fp32 accumulation in ascending k == an fmaf
 //     chain; 155 TFLOP/s peak, 1/16 of the bf16 rate), 128 x 128 x 16 tiles, register-staged double buffer;
 //   * attention as one wave per (sequence, head, query row): exact softmax in fp32 (scores in LDS), GQA, causal / key-keep masks;
+//     decode attention as one wave per (row, head) over every slot of a token-major fp32 K / V cache;
 //   * LayerNorm / RMSNorm / rotary / embedding / ESM token-dropout embedding / pooling / SiLU-mul as plain fp32 kernels.
 // The Python side (procyon_amd/engine_f32.py) strings them together exactly as the oracle's fp32 evaluation does (oracle/esm_ref.py,
 // oracle/llama_ref.py); tests hold every op and the stacks to <= 1e-4 of it.
@@ -241,8 +242,10 @@ __global__ __launch_bounds__(NT) void pool_f32_kernel(const float* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------ attention
 // One wave per (query row i, head h, sequence q).  Packed rows: token t0 + j of sequence q.  keys j < (causal ? i + 1 : len), dropped
-// where keep[t0 + j] == 0.  scores = (q . k) * scale in LDS, exact softmax, o = P . V.  A row without any kept key writes zeros (only
-// pad query rows: the reference's value there -- a uniform average over every key -- is never read on the prefill-only path).
+// where keep[t0 + j] == 0.  scores = (q . k) * scale in LDS, exact softmax, o = P . V.  A query row without any kept key (a pad query
+// row) writes the reference's value: the plain average of V over ALL `len` keys of its sequence, causal or not, pads and later keys
+// included -- the softmax of a row whose every entry is finfo.min (oracle/llama_ref.py::build_additive_mask).  The cached decode
+// attends every slot without a mask, so the K / V that the next layers compute from these rows are read (LlamaEngineF32.decode).
 __global__ __launch_bounds__(64) void attn_f32_kernel(const float* __restrict__ q, int ldq, int qcol0, const float* __restrict__ k, int ldk, int kcol0,
                                                       const float* __restrict__ v, int ldv, int vcol0, float* __restrict__ o, int ldo,
                                                       const int32_t* __restrict__ cu, const uint8_t* __restrict__ keep, int H, int Hkv, int dh,
@@ -277,7 +280,13 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(const float* __restrict__ 
   mx = wave_max(mx);
   float* orow = o + (size_t)(t0 + i) * ldo + h * dh;
   if (mx == -INFINITY) {
-    for (int e = lane; e < dh; e += 64) orow[e] = 0.f;
+    const float u = 1.0f / (float)len;
+    for (int e = lane; e < dh; e += 64) {
+      float a = 0.f;
+      const float* vc = v + (size_t)t0 * ldv + vcol0 + hk * dh + e;
+      for (int j = 0; j < len; ++j) a = fmaf(u, vc[(size_t)j * ldv], a);
+      orow[e] = a;
+    }
     return;
   }
   float sum = 0.f;

@@ -7,10 +7,13 @@ include/pcy.h; procyon_amd/csrc/pcy_f32.hip) together op for op like the referen
 
   EsmEngineF32    ESM2 encoder over packed sequences + ProteinPooler            (/root/reference/procyon/model/esm.py:131-173,504-538)
   MlpEngineF32    `create_mlp` projectors                                        (/root/reference/procyon/model/model_utils.py:13-41)
-  LlamaEngineF32  token embedding + soft-token splice, decoder PREFILL, logits   (/root/reference/procyon/model/pmc_llama.py:546-596,
-                  at chosen rows, final hidden states, the L+1-state sum          /root/reference/procyon/model/model_unified.py:556-581)
+  LlamaEngineF32  token embedding + soft-token splice, decoder prefill, logits   (/root/reference/procyon/model/pmc_llama.py:546-596,
+                  at chosen rows, final hidden states, the L+1-state sum;         /root/reference/procyon/model/model_unified.py:556-581)
+                  with a KVCacheF32 also the cached decode step of an fp32
+                  generation (`decode`, pcy_f32_attn_decode)
 
-Cached decode is not built in fp32 (generation stays a bf16 path; the model mirror raises a clear error).  PyTorch holds the device
+The cached decode attends every slot without a mask, as the reference does after the prefill, so it reads the K / V that the prefill
+computed from left-pad rows: pcy_f32_attention gives those rows the reference's value (include/pcy.h).  PyTorch holds the device
 memory and does index bookkeeping only; every floating-point operation is a HIP kernel behind the C ABI.
 """
 from __future__ import annotations
@@ -77,6 +80,9 @@ class F32Ops:
     def attn_decode(self, q, kcache, vcache, nkeys, H, Hkv, dh, scale):
         """q [B, H*dh] (a view with row stride q.stride(0) is fine) against slots [0, nkeys) of token-major caches [B, Tmax, Hkv*dh]"""
         _chk(kcache, vcache)
+        if q.dtype != F32 or not q.is_cuda or q.dim() != 2 or q.stride(1) != 1 or q.stride(0) % 4:
+            raise TypeError(f"fp32 engine: q must be an fp32 device matrix with unit inner stride and a row stride that is a multiple of 4 "
+                            f"floats, got {q.dtype} {q.device} strides {tuple(q.stride())}")
         B = q.shape[0]
         o = torch.empty(B, H * dh, dtype=F32, device=q.device)
         L.check(self.lib.pcy_f32_attn_decode(self.h, _p(q), q.stride(0), _p(kcache), _p(vcache), kcache.shape[2], kcache.shape[1], _p(o), H * dh, B,

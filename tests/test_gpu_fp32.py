@@ -66,7 +66,8 @@ def test_f32_norms_rope_silu(ops):
 
 @pytest.mark.parametrize("causal,H,Hkv,dh", [(True, 8, 2, 16), (False, 4, 4, 64), (True, 4, 4, 128)])
 def test_f32_attention(ops, causal, H, Hkv, dh):
-    """packed sequences of ragged length, grouped heads, causal / bidirectional, a key-keep mask (left pads)"""
+    """packed sequences of ragged length, grouped heads, causal / bidirectional, a key-keep mask (left pads); the causal pad query rows
+    have no kept key and hold the reference's uniform average of V over every key of their sequence"""
     lens = [33, 1, 70, 128]
     cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32)
     ntok = int(cu[-1])
@@ -85,10 +86,12 @@ def test_f32_attention(ops, causal, H, Hkv, dh):
         if causal:
             allowed &= torch.tril(torch.ones(n, n, dtype=torch.bool))[None]
         sc = sc.masked_fill(~allowed, float("-inf"))
-        ref = (sc.softmax(-1).nan_to_num(0.0) @ v).transpose(0, 1).reshape(n, H * dh)
-        live = allowed[0].any(-1)                   # rows with at least one kept key (pad query rows write zeros)
+        live = allowed[0].any(-1)                   # rows with at least one kept key
+        sc[:, ~live] = 0.0                          # a pad query row: the reference's softmax of a finfo.min row, uniform over ALL n keys
+        ref = (sc.softmax(-1) @ v).transpose(0, 1).reshape(n, H * dh)
         assert rel_err(out[t0:t0 + n][live], ref[live]) < 2e-6, s_
-        assert bool((out[t0:t0 + n][~live] == 0).all())
+        if bool((~live).any()):
+            assert rel_err(out[t0:t0 + n][~live], ref[~live]) < 2e-6, s_
 
 
 def test_f32_esm_engine_vs_oracle():
@@ -226,3 +229,140 @@ def test_fp32_model_runs_as_the_unchanged_fp32_callers_drive_it():
     assert ob["shared"].dtype == torch.bfloat16 and rel_err(ob["shared"].float().cpu(), ref["shared"]) < 2e-2
     with pytest.raises(RuntimeError, match="fp32"):      # the fp32 weights are gone: .float() says so at once
         m.float()
+
+
+# ---- padded generation in fp32: the cached decode attends every slot without a mask (reference quirk Q1), so it reads the K / V that the
+# prefill computed from LEFT-PAD rows; those rows have no kept key and take the reference's uniform average (include/pcy.h,
+# pcy_f32_attention).  tests/test_f32_ref_cpu.py keeps it permanent that these inputs see a prefill that zeroes them instead.
+@pytest.fixture(scope="module")
+def padded_gen():
+    """the fp32 Llama of the engine test (3 layers, GQA 4/2, head_dim 64), B = 3 prompts of T = 12 with left pads {0, 5, 1}; the oracle's
+    prefill K / V and its 6 greedy steps, computed once"""
+    import f32_ref as R
+    from oracle import llama_ref as LR
+    from procyon_amd import synth
+    from procyon_amd.engine import LlamaConfig
+    from procyon_amd.engine_f32 import LlamaEngineF32
+    sd = synth.llama_state_dict(**R.GEN_GEOM, dtype=F32)
+    geom = LR.LlamaGeom(**R.GEN_GEOM)
+    eng = LlamaEngineF32(sd, LlamaConfig(**R.GEN_GEOM, max_pos=256))
+    ids, mask = R.gen_case()
+    emb = F.embedding(ids, sd["model.embed_tokens.weight"])
+    past = LR.llama_forward(sd, geom, inputs_embeds=emb, attn_mask=mask, logits_rows="last")["past_kv"]
+    toks, logits, _ = LR.greedy_generate(sd, geom, emb, mask, R.GEN_STEPS, clean_decode_mask=False)
+    return dict(sd=sd, geom=geom, eng=eng, ids=ids, mask=mask, emb=emb, past=past, toks=toks, logits=logits, pads=R.GEN_PADS, steps=R.GEN_STEPS)
+
+
+def test_f32_padded_greedy_engine_vs_oracle(padded_gen):
+    """LlamaEngineF32.prefill(cache=...) + decode, 6 greedy tokens: the K / V of the pad slots of every layer after the prefill, the
+    tokens, and the logits of every step on EVERY row (the padded ones included) vs the oracle's loop, <= 1e-4"""
+    g = padded_gen
+    eng, ids, mask = g["eng"], g["ids"], g["mask"]
+    B, T = ids.shape
+    cache = eng.new_cache(B, T + g["steps"])
+    emb = eng.embed_tokens(ids)
+    assert torch.equal(emb.cpu(), g["emb"])
+    logits, _ = eng.prefill(emb, mask, "last", cache=cache)
+    e_pad = {"k": 0.0, "v": 0.0}
+    for l, (k_ref, v_ref) in enumerate(g["past"]):                  # [B, Hkv, T, dh]
+        for b, p in enumerate(g["pads"]):
+            if p == 0:
+                continue
+            for name, got, ref in (("k", cache.k, k_ref), ("v", cache.v, v_ref)):
+                e = rel_err(got[l, b, :p].cpu(), ref[b, :, :p].transpose(0, 1).reshape(p, -1))
+                print(f"pad-slot {name} layer {l} row {b}: {e:.3e}")
+                e_pad[name] = max(e_pad[name], e)
+    toks, errs = [], []
+    for i in range(g["steps"]):
+        if i:
+            logits = eng.decode(cache, toks[-1], T + i - 1)
+        lg = logits.cpu()
+        errs.append([rel_err(lg[b], g["logits"][b, i]) for b in range(B)])
+        print(f"step {i}: per-row logits error {['%.3e' % e for e in errs[-1]]}")
+        toks.append(lg.argmax(-1))
+    toks = torch.stack(toks, 1)
+    e_lg = max(max(r) for r in errs)
+    record_parity("fp32/llama_padded_greedy", err_pad_slot_k=e_pad["k"], err_pad_slot_v=e_pad["v"], err_logits_worst_row_step=e_lg,
+                  tokens_equal=bool(torch.equal(toks, g["toks"])))
+    assert e_pad["k"] < 1e-4 and e_pad["v"] < 1e-4, e_pad
+    assert torch.equal(toks, g["toks"]), (toks, g["toks"])
+    assert e_lg < 1e-4, errs
+
+
+def test_f32_padded_beam_engine_vs_oracle(padded_gen):
+    """diverse beam search (beam 4 / group 2 / penalty 0.8, 5 steps) over B = 2 prompts, one left-padded: the oracle's own loop
+    (llama_ref.beam_search, as the model test drives it) once over the oracle's text encoder and once over an adapter that runs
+    LlamaEngineF32 prefill / decode and hands the loop the engine's K / V caches to re-index -- same tokens, scores, logits <= 1e-4"""
+    from oracle import llama_ref as LR
+    g = padded_gen
+    eng = g["eng"]
+    emb, mask = g["emb"][:2], g["mask"][:2]
+    assert g["pads"][0] == 0 and g["pads"][1] > 0
+    kw = dict(vocab_size=g["geom"].vocab, eos_id=2, max_len=5, beam_size=4, beam_group_size=2, diversity_penalty=0.8)
+    t_ref, s_ref, l_ref = LR.beam_search(LR.make_text_encoder(g["sd"], g["geom"]), emb, mask, **kw)
+    state = {}
+
+    def enc(input_embeds=None, input_ids=None, attn_masks=None, past_key_values=None):
+        if past_key_values is None:
+            BB, T, _ = input_embeds.shape
+            state["cache"], state["t"] = eng.new_cache(BB, T + kw["max_len"]), T
+            logits, _ = eng.prefill(input_embeds, attn_masks, "last", cache=state["cache"])
+        else:
+            logits = eng.decode(state["cache"], input_ids.view(-1), state["t"])
+            state["t"] += 1
+        c = state["cache"]
+        # (views of the engine's caches, batch first: the loop's in-place `layer[0][gs:ge] = layer[0][orig]` moves the engine's rows)
+        return logits.cpu()[:, None, :], [[c.k[l], c.v[l]] for l in range(c.k.shape[0])]
+
+    t, s, lg = LR.beam_search(enc, emb, mask, **kw)
+    e = rel_err(lg, l_ref)
+    e_rows = [rel_err(lg[b], l_ref[b]) for b in range(2)]
+    print(f"beam logits error {e:.3e}, per prompt {e_rows}")
+    record_parity("fp32/llama_padded_beam", err_logits=e, err_logits_padded_prompt=e_rows[1], tokens_equal=bool(torch.equal(t, t_ref)))
+    assert torch.equal(t, t_ref), (t, t_ref)
+    assert torch.allclose(s, s_ref, atol=1e-3), (s, s_ref)
+    assert max(e_rows) < 1e-4, e_rows
+
+
+def test_fp32_model_generates_from_left_padded_prompts():
+    """`UnifiedProCyon.generate(method="greedy")` on the small synthetic fp32 model (never cast) with two instructions of different token
+    length, so that one row is left-padded: tokens and logits of every row vs the oracle pipeline in fp32, as the single-prompt block of
+    the test above compares them; the same batch through method="beam" (the engine's cache re-ordering under a padded row)"""
+    from oracle import esm_ref as ER
+    from oracle import llama_ref as LR
+    from oracle import procyon_ref as PR
+    from procyon_amd import synth
+    from procyon_amd import synthetic_model as SM
+    m, w = SM.build("small", device="cuda", return_weights=True, max_new_tokens=8, dtype=F32, as_loaded=True)
+    m.eval()
+    lgeom, egeom = LR.LlamaGeom(**w["geom"]["llama"]), ER.EsmGeom(**w["geom"]["esm"])
+    prot = synth.protein_tokens([90, 41], seed=3)
+    mk = lambda instr, seq, slots: {
+        "data": {"seq": seq, "seq_idx": torch.arange(seq.shape[0]), "text": [], "drug": None},
+        "input": {"seq": slots, "text": [[] for _ in instr], "drug": None},
+        "target": {"seq": None, "text": None, "drug": None}, "instructions": list(instr)}
+    ginstr = ["w4 <|protein|> w5 [ANSWER]", "w1 w2 w3 w6 <|protein|> is w7 w8 ? [ANSWER]"]
+    gslots = [[1], [0]]
+    gids, gmask = m._prepare_text_inputs_and_tokenize(list(ginstr), [[], []], crop_off=True, no_pad=True, left_pad=True)
+    npad = (gmask == 0).sum(1)
+    assert int(npad[0]) > 0 and int(npad[1]) == 0 and bool((gmask[0, :int(npad[0])] == 0).all())        # row 0 is left-padded
+    z = PR.esm_plm_forward(w["esm"], egeom, prot, pooling="mean")
+    gsoft = PR.mlp_forward(z[[1, 0]], w["projs"]["aaseq"])
+    gemb, _ = PR.prepare_input_embeddings(w["llama"]["model.embed_tokens.weight"], gids.long(), m.prot_replacement_idx, gsoft, ret_idx=m.prot_retrieval_idx)
+    t_ref, lg_ref, _ = LR.greedy_generate(w["llama"], lgeom, gemb, gmask, 6)
+    toks, lp, lg, _ = m.generate(mk(ginstr, prot, gslots), max_len=6, method="greedy")
+    e_rows = [rel_err(lg[b, 0].float(), lg_ref[b]) for b in range(2)]
+    print(f"greedy logits error per row {e_rows}")
+    enc = LR.make_text_encoder(w["llama"], lgeom)
+    tb_ref, sb_ref, lb_ref = LR.beam_search(enc, gemb, gmask, vocab_size=lgeom.vocab, eos_id=m.tokenizer.eos_token_id, max_len=5,
+                                            beam_size=4, beam_group_size=2, diversity_penalty=0.8)
+    tb, sb, lb, _ = m.generate(mk(ginstr, prot, gslots), max_len=5, method="beam", beam_size=4, beam_group_size=2, diversity_penalty=0.8)
+    eb_rows = [rel_err(lb[b].float(), lb_ref[b]) for b in range(2)]
+    print(f"beam logits error per prompt {eb_rows}")
+    record_parity("fp32/model_small_generate_padded", err_greedy_logits_padded_row=e_rows[0], err_greedy_logits_full_row=e_rows[1],
+                  err_beam_logits_padded_row=eb_rows[0], err_beam_logits_full_row=eb_rows[1],
+                  greedy_tokens_equal=bool(torch.equal(toks[:, 0], t_ref)), beam_tokens_equal=bool(torch.equal(tb, tb_ref)))
+    assert lg.dtype == F32 and torch.equal(toks[:, 0], t_ref), (toks, t_ref)
+    assert max(e_rows) < 1e-4, e_rows
+    assert torch.equal(tb, tb_ref) and torch.allclose(sb, sb_ref, atol=1e-3), (tb, tb_ref, sb, sb_ref)
+    assert max(eb_rows) < 1e-4, eb_rows
