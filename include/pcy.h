@@ -90,6 +90,12 @@ int pcy_rope(pcy_ctx*, void* buf, int ld, int col0, int nh, int dh, const int32_
 int pcy_attention(pcy_ctx*, const void* q, int ldq, int qcol0, const void* k, int ldk, int kcol0, const void* v, int ldv,
                   int vcol0, void* o, int ldo, const int32_t* cu, const int32_t* vt_cu, const uint8_t* keep, int nseq,
                   int max_len, int vt_total, int H, int Hkv, int dh, int causal, float scale);
+/* Test instrumentation: launches of the two-pass prefill attention since the library was loaded, by the kernel that the launcher chose
+ * (pcy_attention, pcy_esm_encode, pcy_llama_prefill and every other caller of it) -- 0: head_dim 32; 1: head_dim 64; 2: head_dim 128, one
+ * 16-row query tile per wave; 3: head_dim 128, two query tiles per wave (large grids); anything else reads 0.  The single-pass ESM kernel
+ * counts as kind 6 of pcy_debug_dispatch_count and under none of these.  Words of their own, as pcy_debug_look_count: the kinds of
+ * pcy_debug_dispatch_count are pinned.  Kernels 2 and 3 give one sequence the same bits (same key-block order, same rounding points). */
+unsigned long long pcy_debug_attn_route_count(int which);
 /* Decode attention of ONE new token per row against the [B,Hkv,Tmax,dh] cache: ropes q and the new k at position
  * *pos (device scalar = cache length), appends K,V at slot *pos, attends slots [0,*pos] (keep: optional [B,Tmax]
  * key mask, NULL = the reference's unmasked decode, quirk Q1).  qkv [B,(H+2Hkv)*dh] un-roped projections.

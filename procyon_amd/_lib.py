@@ -19,6 +19,8 @@ ABI_VERSION = 13
 # which way a decode step was served (one count per step enqueued outside a graph replay; pcy_internal.h PCY_DISPATCH_DEC_*)
 DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STEP_MHA, layer=DISPATCH_DEC_LAYER, step_nb=DISPATCH_DEC_STEP_NB,
                        step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
+# pcy_debug_attn_route_count words: which two-pass prefill attention kernel the launcher chose
+ATTN_ROUTE_DH32, ATTN_ROUTE_DH64, ATTN_ROUTE_LDS128_1, ATTN_ROUTE_LDS128_2 = range(4)
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -102,6 +104,7 @@ SIGNATURES = {
     "pcy_embed_splice": (ci, [vp, vp, vp, vp, vp, vp, ci, ci]),
     "pcy_rope": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, ci, C.c_float]),
     "pcy_attention": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, C.c_float]),
+    "pcy_debug_attn_route_count": (C.c_ulonglong, [ci]),
     "pcy_attn_decode": (ci, [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend_packed": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),

@@ -273,7 +273,10 @@ __global__ __launch_bounds__(256) void attn_kernel(PcyAttnArgs a) {
 // 32-key block of K ([32][DH]) and Vt ([DH][32]) is fetched from L2 ONCE per workgroup (one or two 16-byte loads per
 // thread), staged in a double-buffered, XOR-swizzled LDS image and read back as MFMA fragments with ds_read_b128.
 // The per-wave global fragment loads of attn_kernel made the kernel L2-bandwidth bound (5.6 GB of fragment traffic per
-// ESM layer at batch 32); this cuts it 4x.  Arithmetic and rounding are identical to attn_kernel.
+// ESM layer at batch 32); this cuts it 4x.  The bf16 rounding points are those of attn_kernel (the fp32 softmax steps between them differ:
+// the log2e fold is a multiplication here, an fma there).  QT = 1 and QT = 2 give a sequence the same bits: the same key blocks in the same
+// order per row, and the blocks that only the wider causal range or the retry of a 128-row workgroup adds carry weight exactly 0 for a row with an allowed key, and
+// a row without one walks all keys of its sequence in both (tests/test_gpu_attn_prefill.py::test_route_independence holds the two to that).
 template <int DH, int QT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void attn_lds_kernel(PcyAttnArgs a) {
   constexpr int KB = DH / 32, NT = DH / 16, QROWS = QT * 16;
@@ -1108,6 +1111,8 @@ bool pcy_attn_fast_eligible(int dh, int causal, bool has_keep, float scale, int 
 }
 // ... and for reading V token-major where the projection wrote it (PCY_DISABLE=fa_vrow: from the transposed copy)
 bool pcy_attn_fast_vrow(int ldv, int vcol0) { return !pcy_off("fa_vrow") && ((ldv | vcol0) % 8) == 0; }
+// launches per two-pass kernel, counted where the launch is decided (pcy_debug_attn_route_count)
+unsigned long long g_pcy_attn_route[PCY_ATTN_ROUTE_N] = {};
 void pcy_launch_attn(hipStream_t s, const PcyAttnArgs& a) {
   if (a.nseq <= 0) return;
   if (a.vt_pad64 && pcy_attn_fast_eligible(a.dh, a.causal, a.keep != nullptr, a.scale, a.H, a.Hkv, a.ldq, a.qcol0, a.ldk, a.kcol0, a.ldo) &&
@@ -1125,6 +1130,7 @@ void pcy_launch_attn(hipStream_t s, const PcyAttnArgs& a) {
     // ... but a small grid (one 512-token prompt: 4 x 32 workgroups of two tiles) is a latency chain per workgroup: keep one
     // tile per wave until two-tile workgroups alone fill the chip twice
     const long wg2 = (long)((a.max_len + 127) / 128) * a.H * a.nseq;
+    ++g_pcy_attn_route[wg2 >= 512 ? PCY_ATTN_ROUTE_LDS128_2 : PCY_ATTN_ROUTE_LDS128_1];
     if (wg2 >= 512) hipLaunchKernelGGL((attn_lds_kernel<128, 2>), dim3((a.max_len + 127) / 128, a.H, a.nseq), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_lds_kernel<128, 1>), dim3((a.max_len + 63) / 64, a.H, a.nseq), dim3(256), 0, s, a);
     return;
@@ -1140,6 +1146,7 @@ void pcy_launch_attn(hipStream_t s, const PcyAttnArgs& a) {
     if (scaled) hipLaunchKernelGGL((attn_kernel<DHV, QTV, true, true>), grid, dim3(256), 0, s, a);                         \
     else hipLaunchKernelGGL((attn_kernel<DHV, QTV, true, false>), grid, dim3(256), 0, s, a);                               \
   } while (0)
+  ++g_pcy_attn_route[a.dh == 64 ? PCY_ATTN_ROUTE_DH64 : PCY_ATTN_ROUTE_DH32];
   if (a.dh == 64) PCY_ATTN_LAUNCH(64, 3, 192);
   else PCY_ATTN_LAUNCH(32, 2, 128);
 #undef PCY_ATTN_LAUNCH

@@ -757,6 +757,7 @@ hipStream_t pcy_ctx_stream(pcy_ctx* c) { return c->stream; }
 extern "C" {
 int pcy_abi_version(void) { return PCY_ABI_VERSION; }
 unsigned long long pcy_debug_dispatch_count(int kind) { return (kind >= 0 && kind < PCY_DISPATCH_N) ? g_pcy_dispatch[kind] : 0; }
+unsigned long long pcy_debug_attn_route_count(int which) { return (which >= 0 && which < PCY_ATTN_ROUTE_N) ? g_pcy_attn_route[which] : 0; }
 const char* pcy_last_error(void) { return g_err; }
 
 int pcy_ctx_create(int device_id, void* stream, pcy_ctx** out) {

@@ -162,6 +162,14 @@ enum { PCY_DISPATCH_GEMM_128 = 0, PCY_DISPATCH_GEMM_64 = 1, PCY_DISPATCH_GEMM_BI
        PCY_DISPATCH_EXTEND_PACKED = 19,   // one pcy_llama_extend_packed call (in addition to PCY_DISPATCH_EXTEND)
        PCY_DISPATCH_N = 20 };
 extern unsigned long long g_pcy_dispatch[PCY_DISPATCH_N];
+// which two-pass kernel pcy_launch_attn chose (pcy_debug_attn_route_count): words of their own, the kinds above are pinned.  The single-pass
+// kernel stays PCY_DISPATCH_ATTN_FAST.
+enum { PCY_ATTN_ROUTE_DH32 = 0,       // attn_kernel<32, 2>
+       PCY_ATTN_ROUTE_DH64 = 1,       // attn_kernel<64, 3>
+       PCY_ATTN_ROUTE_LDS128_1 = 2,   // attn_lds_kernel<128, 1>
+       PCY_ATTN_ROUTE_LDS128_2 = 3,   // attn_lds_kernel<128, 2>
+       PCY_ATTN_ROUTE_N = 4 };
+extern unsigned long long g_pcy_attn_route[PCY_ATTN_ROUTE_N];
 
 // lm_head x cross-entropy without logits in memory (pcy_xent.hip): nll[m] = logsumexp_n(bf16(x[m] . W[n])) - bf16(x[m] . W[targets[m]]).
 // x [M, d] bf16 (ldx, rows 16-byte aligned), W [V, d], d % 64 == 0, targets [M] int32 in [0, V) (anything else: nll = NaN).  lse / row_max /

@@ -162,9 +162,18 @@ class Context:
                                   mode, prescale), "pcy_rope")
         return buf
 
-    def attention(self, q, k, v, lens, H, Hkv, dh, causal, scale, keep=None):
-        """q [ntok,H*dh], k,v [ntok,Hkv*dh] packed sequences of lengths `lens` (list)."""
+    def attention(self, q, k, v, lens, H, Hkv, dh, causal, scale, keep=None, ld=None, col0=None):
+        """q [ntok,H*dh], k,v [ntok,Hkv*dh] packed sequences of lengths `lens` (list).
+        ld / col0: q, k, v as column windows of wider token-major buffers -- ld = the row stride in elements (one int for all three, or
+        (ldq, ldk, ldv)), col0 = (qcol0, kcol0, vcol0), the column of head 0 in each.  The fused QKV buffer of the Llama prefill is
+        q = k = v = buf [ntok, (H+2Hkv)*dh], ld = (H+2Hkv)*dh, col0 = (0, H*dh, (H+Hkv)*dh).  Default: the tensors' own width, column 0."""
         _chk_bf16(q, k, v)
+        lds = (q.shape[1], k.shape[1], v.shape[1]) if ld is None else ((ld,) * 3 if isinstance(ld, int) else tuple(ld))
+        c0 = (0, 0, 0) if col0 is None else tuple(col0)
+        if ld is not None or col0 is not None:      # the kernels trust ld / col0: every window must lie inside its tensor
+            for t, l_, c_, w in ((q, lds[0], c0[0], H * dh), (k, lds[1], c0[1], Hkv * dh), (v, lds[2], c0[2], Hkv * dh)):
+                if not (t.is_contiguous() and c_ >= 0 and c_ + w <= l_ and t.numel() >= (sum(lens) - 1) * l_ + c_ + w):
+                    raise ValueError("attention: column window outside its buffer")
         lens_t = torch.tensor(lens, dtype=torch.int64)
         cu = torch.zeros(len(lens) + 1, dtype=torch.int64)
         cu[1:] = lens_t.cumsum(0)
@@ -172,7 +181,7 @@ class Context:
         vt_cu[1:] = ((lens_t + 31) // 32 * 32).cumsum(0)
         cu_d, vt_d = cu.to(q.device, torch.int32), vt_cu.to(q.device, torch.int32)
         o = torch.empty(q.shape[0], H * dh, dtype=BF16, device=q.device)
-        L.check(self.lib.pcy_attention(self.h, _p(q), q.shape[1], 0, _p(k), k.shape[1], 0, _p(v), v.shape[1], 0, _p(o), H * dh,
+        L.check(self.lib.pcy_attention(self.h, _p(q), lds[0], c0[0], _p(k), lds[1], c0[1], _p(v), lds[2], c0[2], _p(o), H * dh,
                                        _p(cu_d), _p(vt_d), _p(keep), len(lens), int(lens_t.max()), int(vt_cu[-1]), H, Hkv, dh,
                                        int(causal), scale), "pcy_attention")
         return o
