@@ -485,6 +485,41 @@ int pcy_look_verify(pcy_ctx*, const pcy_llama_desc*, const pcy_look_state*, cons
 /* calls since the library was loaded -- 0: pcy_look_draft, 1: pcy_look_verify (= passes); anything else reads 0.  Words of their own, as
  * pcy_debug_extend_grouped_count: the kinds of pcy_debug_dispatch_count are pinned. */
 unsigned long long pcy_debug_look_count(int which);
+/* ---- the lookahead pass on the decode loop ----
+ * Window attention: W consecutive tokens of cache row 0 on layer `layer` of a PLAIN cache with kv->B == 1.  The operator is pcy_attn_extend's
+ * with B = 1, S = W, t_past = *pos and no keep mask, *pos (device scalar) being read on the device: qkv [W, ld] holds the un-roped projections
+ * (read only: the roped queries go to the workspace); q and k of row i are roped at position *pos + i, K / V of row i are written to slot
+ * *pos + i, o[i] is the causal attention of query i over slots [0, *pos + i], with pcy_attn_extend's rounding points (bf16 scores, the scale
+ * on the rounded score, probabilities normalised in fp32 before their rounding, fp32 P.V rounded once).  cos_t / sin_t hold at least Tmax
+ * rows.  head_dim 64 or 128, H / Hkv in 1, 2, 4, 8, 2 <= W <= 32.
+ * Work split: the W x H / Hkv queries of a kv head are packed into 16-wide MFMA tiles; the keys are cut into chunks of
+ * pcy_attn_window_chunk() keys, one workgroup per (chunk, kv head, 64 packed queries), the grid sized from the capacity; a launch writes the
+ * chunks' (max, sum), a second one their fp32 P.V under the query's global (max, sum), a third adds the chunks in chunk order.  No atomics.
+ * Promised: query i's bits depend on the logical contents of slots [0, *pos + i], on i, *pos, W and the geometry only -- not on rows > i of
+ * qkv (NaN included), not on what slots above *pos + i held, not on Tmax; a masked key contributes exactly 0 (select, not multiply); equal
+ * calls give equal bits; the appended K / V have the bits pcy_attn_extend writes; slots below *pos and above *pos + W - 1 are never written.
+ * *pos < 0 or *pos + W > Tmax: nothing is written.  NOT promised: the bits of pcy_attn_extend's or pcy_attn_decode's output.
+ * Argument errors (nothing launched, nothing written): a shared-prefix or grouped cache, kv->B != 1, W outside [2, 32], Tmax < W, an
+ * unsupported head_dim or H / Hkv, rows of qkv / o that are not 16-byte aligned.  Workspace: the context's. */
+int pcy_attn_window(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
+                    const void* sin_t, int W, int H, int Hkv, int dh);
+/* keys per chunk of pcy_attn_window: a constant of the library, a multiple of 32 */
+int pcy_attn_window_chunk(void);
+/* One lookahead pass on the batched decode loop.  embeds [W, d] bf16 (what pcy_look_draft writes) -> logits_out [W, vocab] bf16; K / V of
+ * row i appended at slot *pos + i of the one cache row.  Reads state->pos on the device and does not advance it (pcy_look_verify does); of
+ * the state only pos and keep are read.  One launch per stage, always: per layer qkv -> pcy_attn_window -> o (+ residual) -> gate/up
+ * (SwiGLU) -> down (+ residual), then the final norm and the lm_head GEMV for all W rows -- the launch-per-stage loop of pcy_llama_decode at
+ * B = W (skinny-MFMA GEMVs with the RMSNorm fused into the K-split finish from W = the MFMA GEMVs' smallest batch on when d % 128 == 0 and
+ * ffn % 128 == 0, the streaming GEMVs otherwise), never a fused one-launch step whatever the switches say, and with the GEMV's own finish
+ * launch behind the qkv projection.  The decode workspace keeps its carve; the attention's buffers lie behind it.
+ * Promised: row i's logits and appended K / V depend on rows <= i of embeds, on *pos, W and the cache below *pos only; equal calls give equal
+ * bits.  NOT promised: the bits of pcy_llama_extend or pcy_llama_decode.
+ * Argument errors (nothing launched, nothing written): state->keep != NULL, fp8 layers (desc->layers_fp8), everything pcy_attn_window
+ * refuses, d, ffn, H*dh or (H+2Hkv)*dh not multiples of 16. */
+int pcy_llama_decode_window(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, const void* embeds, int W,
+                            void* logits_out);
+/* calls of pcy_llama_decode_window since the library was loaded: a word of its own, as pcy_debug_decode_gemm_count */
+unsigned long long pcy_debug_decode_window_count(void);
 /* n_steps x (decode + pick) with no host synchronisation; use_graph != 0 replays a captured hipGraph */
 int pcy_llama_greedy(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int n_steps,
                      int use_graph);

@@ -160,6 +160,10 @@ SIGNATURES = {
     "pcy_look_draft": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
     "pcy_look_verify": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LookState), C.POINTER(GenState), vp]),
     "pcy_debug_look_count": (C.c_ulonglong, [ci]),
+    "pcy_attn_window": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, vp, vp, vp, ci, ci, ci, ci]),
+    "pcy_attn_window_chunk": (ci, []),
+    "pcy_llama_decode_window": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), vp, ci, vp]),
+    "pcy_debug_decode_window_count": (C.c_ulonglong, []),
     "pcy_llama_greedy": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci]),
     "pcy_sample_pick": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp, vp]),
     "pcy_llama_sample": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp]),

@@ -45,6 +45,8 @@ unsigned long long g_pcy_decode_gemm = 0;
 unsigned long long g_pcy_attn_mq = 0;
 // steps enqueued by pcy_llama_decode_w8 / pcy_llama_greedy_w8 outside a graph replay (pcy_debug_decode_w8_count): a word of its own as well
 unsigned long long g_pcy_decode_w8 = 0;
+// calls of pcy_llama_decode_window (pcy_debug_decode_window_count): a word of its own as well
+unsigned long long g_pcy_decode_window = 0;
 
 }  // namespace
 
@@ -2029,6 +2031,101 @@ int pcy_gemv_w8(pcy_ctx* c, const void* W8, const float* scale, const void* x, i
   g.rms_w = (const bf16_t*)rms_w; g.rms_eps = rms_eps; g.rms_cast = rms_cast; g.N = N; g.K = K; g.B = B; g.ldx = ldx; g.ldy = ldy; g.epi = epi;
   if (!pcy_launch_gemv_w8(c->stream, g)) return fail(1, "pcy_gemv_w8: the device refused the LDS size for K=%d", K);
   return check_launch("pcy_gemv_w8");
+}
+
+// ---- the lookahead pass on the decode loop: W consecutive tokens of ONE cache row ----
+// The window attention (pcy_attn_win.hip) on layer `layer` of a plain one-row cache; ws: its roped queries, chunk statistics and partial sums
+// (win_ws_bytes).  Built in ONE place for pcy_attn_window and the step of pcy_llama_decode_window.
+static size_t win_ws_bytes(const PcyWinPlan& p) { return align_up(p.qr_bytes, 256) + align_up(p.stats_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
+static PcyWinAttnArgs win_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
+                                    const bf16_t* sin_t, int W, int H, int Hkv, int dh, char* ws) {
+  const PcyWinPlan p = pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax);
+  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
+  PcyWinAttnArgs a{};
+  a.qkv = qkv; a.ld = ld; a.kcache = (bf16_t*)kv->k + layer * layer_stride; a.vcache = (bf16_t*)kv->v + layer * layer_stride;
+  a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t; a.W = W; a.H = H; a.Hkv = Hkv; a.dh = dh; a.Tmax = kv->Tmax;
+  a.scale = 1.0f / sqrtf((float)dh);
+  Carver cv(ws);
+  a.qr = cv.take<bf16_t>(p.qr_bytes / sizeof(bf16_t)); a.stats = cv.take<float2>(p.stats_bytes / sizeof(float2)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
+  a.nchunk = p.nchunk;
+  return a;
+}
+// what the operator refuses, for the operator entry and the step alike
+static int check_win_call(const pcy_kv_cache* kv, int W, int H, int Hkv, int dh, const char* what) {
+  if (kv_shared(kv)) return fail(1, "%s: a shared-prefix or grouped cache is not served by the window attention (plain caches only)", what);
+  if (kv->B != 1) return fail(1, "%s: the cache holds %d rows (the window is W tokens of ONE row: kv->B == 1)", what, kv->B);
+  if (W < 2 || W > 32) return fail(1, "%s: W=%d outside [2, 32]", what, W);
+  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (Hkv < 1 || H < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (kv->Tmax < W) return fail(1, "%s: the cache holds %d slots, fewer than the %d of a window", what, kv->Tmax, W);
+  if (((uintptr_t)kv->k | (uintptr_t)kv->v) & 15) return fail(1, "%s: the cache must be 16-byte aligned", what);
+  return 0;
+}
+// The loop of enqueue_decode at B = W (its helpers, unchanged: proj_args, the K-split finish with the fused next norm, SwiGLU, the final norm +
+// lm_head GEMV), never a fused step, with the window attention in the place of the decode attention and the GEMV's own finish launch.
+static void enqueue_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int W, void* logits_out) {
+  hipStream_t s = c->stream;
+  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
+  const DecodeCx cx = decode_cx(c, m, kv, st, W);
+  char* win_ws = c->ws + align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256);
+  DecodePlan p{};   // (the loop alone: no fused step, no deferred qkv finish, no rotated K order, no key split)
+  p.batched_head = W >= pcy_mfma_min_batch() && d % 128 == 0 && F % 128 == 0;
+  p.batched = p.batched_head;
+  int xn_ready = 0;
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_llama_layer& L = m->layers[l];
+    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, W, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    pcy_launch_gemv(s, proj_args(cx, p, L.wqkv, L.ln1, cx.x, d, cx.qkv, cx.qkvw, EPI_STORE, true, 0, nullptr));
+    pcy_launch_attn_window(s, win_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, W, H,
+                                            m->n_kv_heads, dh, win_ws));
+    pcy_launch_gemv(s, proj_args(cx, p, L.wo, L.ln2, cx.ao, H * dh, cx.x, d, EPI_RESID, true, 0, &xn_ready));
+    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, W, d, m->rms_eps, m->rms_cast);
+    xn_ready = 0;
+    pcy_launch_gemv(s, proj_args(cx, p, L.wgu, L.ln2, cx.x, d, cx.act, F, EPI_SWIGLU, false, 0, nullptr));
+    pcy_launch_gemv(s, proj_args(cx, p, L.wdown, l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm, cx.act, F, cx.x, d, EPI_RESID, true, 0, &xn_ready));
+  }
+  PcyGemvArgs h{};
+  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)logits_out; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
+  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = W; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
+  if (p.batched_head) {
+    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, W, d, m->rms_eps, m->rms_cast);
+    h.x = cx.xn; h.rms_w = nullptr;
+  }
+  pcy_launch_gemv(s, h);
+  ++g_pcy_decode_window;
+}
+int pcy_llama_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, const void* embeds, int W,
+                            void* logits_out) {
+  PCY_STICKY(c);
+  const char* what = "pcy_llama_decode_window";
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !m->layers || !embeds || !logits_out) return fail(1, "%s: model, cache, state, embeds or logits_out incomplete", what);
+  if (st->keep) return fail(1, "%s: a keep mask is not supported (lookahead prompts are unpadded)", what);
+  if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  if (int r = check_win_call(kv, W, H, Hkv, dh, what)) return r;
+  if (d % 16 || F % 16 || (H * dh) % 16 || ((H + 2 * Hkv) * dh) % 16) return fail(1, "%s: d, ffn, H*dh, (H+2Hkv)*dh must be multiples of 16", what);
+  const size_t need = align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256) + win_ws_bytes(pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax));
+  if (int r = c->reserve(need)) return r;
+  HIP_TRY(hipMemcpyAsync(carve_decode_ws(c->ws, m, W, kv_cap(kv)).x, embeds, (size_t)W * d * 2, hipMemcpyDeviceToDevice, c->stream));
+  enqueue_decode_window(c, m, kv, st, W, logits_out);
+  return check_launch(what);
+}
+unsigned long long pcy_debug_decode_window_count(void) { return g_pcy_decode_window; }
+int pcy_attn_window_chunk(void) { return pcy_attn_win_chunk(); }
+
+int pcy_attn_window(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
+                    const void* sin_t, int W, int H, int Hkv, int dh) {
+  PCY_STICKY(c);
+  const char* what = "pcy_attn_window";
+  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
+  if (int r = check_win_call(kv, W, H, Hkv, dh, what)) return r;
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
+  if (int r = c->reserve(win_ws_bytes(pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax)))) return r;
+  if (!pcy_launch_attn_window(c->stream, win_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t,
+                                                       W, H, Hkv, dh, c->ws)))
+    return fail(1, "%s: shape not covered", what);
+  return check_launch(what);
 }
 
 int pcy_attn_decode_shared(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,

@@ -319,6 +319,28 @@ struct PcyMqAttnArgs {
   int ntiles, nchunk, cblocks, lds;            // the plan of this shape
 };
 bool pcy_launch_attn_mq(hipStream_t s, const PcyMqAttnArgs& a);   // false = shape not covered, nothing launched
+// Window attention (pcy_attn_win.hip): W consecutive tokens of cache row 0 of a plain one-row cache -- a lookahead pass --
+// with the keys cut into chunks of PCY_WIN_CHUNK across workgroups and the position read on the device.  Four launches: rope + append,
+// per-chunk (max, sum), per-chunk P.V under the global (max, sum), the sum of the chunks in chunk order.
+#define PCY_WIN_CHUNK 128                      // keys per chunk: a constant of the plan, a multiple of 32
+struct PcyWinPlan {
+  int nchunk;                                  // chunks the CAPACITY is cut into (the grid); the live ones are those below *pos + W
+  size_t qr_bytes, stats_bytes, part_bytes;    // roped q [W][H*dh] bf16; (m, l) [nchunk][Hkv][W*G] float2; partial o [nchunk][W][H*dh] fp32
+};
+int pcy_attn_win_chunk();
+bool pcy_attn_win_covers(int W, int H, int Hkv, int dh);   // 2 <= W <= 32, head_dim 64 / 128, H/Hkv 1 / 2 / 4 / 8
+PcyWinPlan pcy_attn_win_plan(int W, int H, int Hkv, int dh, int Tmax);
+struct PcyWinAttnArgs {
+  const bf16_t* qkv; int ld;                   // [W, (H+2Hkv)*dh] un-roped projections of the W tokens (not written)
+  bf16_t* kcache; bf16_t* vcache;              // THIS layer's panels [Hkv, Tmax, dh] of the one cache row
+  bf16_t* o; int ldo;                          // [W, H*dh], rows 8-byte aligned
+  const int32_t* pos_dev;                      // device scalar: the slot (and rotary position) of row 0
+  const bf16_t* cos_t; const bf16_t* sin_t;    // [>= Tmax, dh]
+  int W, H, Hkv, dh, Tmax; float scale;
+  bf16_t* qr; float2* stats; float* part;      // workspace (PcyWinPlan), 256-byte aligned
+  int nchunk;                                  // the plan of this capacity
+};
+bool pcy_launch_attn_window(hipStream_t s, const PcyWinAttnArgs& a);   // false = shape not covered, nothing launched
 struct PcyGemvArgs;
 // decode attention + o projection (EPI_RESID GEMV over the attention output) in one launch; false = shape not covered,
 // nothing launched.  epoch: device word that differs between consecutive calls on the same `flags` (max_flags words).

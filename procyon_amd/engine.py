@@ -232,6 +232,22 @@ class Context:
                    B, S, H, Hkv, dh), "pcy_attn_extend")
         return o
 
+    def attn_window(self, qkv, cache, layer, pos, cos_t, sin_t, H, Hkv, dh, out=None):
+        """pcy_attn_window: qkv [W, (H+2Hkv)*dh] un-roped projections of W consecutive tokens of the ONE row of a plain KVCache (DESIGN.md 4.9a);
+        pos int32 device scalar = the slot of row 0, read on the device.  Ropes q / k of row i at pos + i (qkv itself is not written), writes
+        K / V to slot pos + i of layer `layer`, -> o [W, H*dh], o[i] = the causal attention of query i over slots [0, pos + i].  2 <= W <= 32;
+        a shared-prefix or grouped cache, or more than one cache row, is an error: there is no fallback."""
+        _chk_bf16(qkv)
+        W = qkv.shape[0]
+        o = torch.empty(W, H * dh, dtype=BF16, device=qkv.device) if out is None else out
+        L.check(self.lib.pcy_attn_window(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), o.shape[1], _p(pos), _p(cos_t),
+                                         _p(sin_t), W, H, Hkv, dh), "pcy_attn_window")
+        return o
+
+    def attn_window_chunk(self):
+        """keys per chunk of `attn_window` (a constant of the library)"""
+        return int(self.lib.pcy_attn_window_chunk())
+
     def retrieval_scores(self, query, targets):
         """cosine similarities [Q,N] (bf16) as `ProcyonRetrievalEval.get_predictions` forms them (procyon.py:400-406)."""
         _chk_bf16(query, targets)
@@ -1163,6 +1179,16 @@ class LlamaEngine:
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
         return st.tokens_out.long(), st.logprob, la, (st, cache)
 
+    def decode_window(self, cache: KVCache, st: GenState, embeds, logits):
+        """one lookahead pass on the batched decode loop (pcy_llama_decode_window): embeds [W, d] (or [1, W, d]) bf16 -> logits
+        [W, V] bf16, K / V of row i appended at slot st.pos + i of the one cache row; st.pos is read on the device and not advanced."""
+        _chk_bf16(embeds, logits)
+        W = logits.shape[0]
+        if embeds.numel() != W * self.cfg.d or tuple(logits.shape) != (W, self.cfg.vocab) or not (embeds.is_contiguous() and logits.is_contiguous()):
+            raise ValueError(f"decode_window: embeds {tuple(embeds.shape)} / logits {tuple(logits.shape)} for d {self.cfg.d}, vocab {self.cfg.vocab}")
+        L.check(self.ctx.lib.pcy_llama_decode_window(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), _p(embeds), W, _p(logits)),
+                "pcy_llama_decode_window")
+
     def look_draft(self, look: "LookState", st: GenState, embeds_out):
         """window[1..W) by prompt lookup + the W embedding rows of the window -> embeds_out [W, d] (pcy_look_draft)"""
         L.check(self.ctx.lib.pcy_look_draft(self.ctx.h, C.byref(self.desc), C.byref(look.c), C.byref(st.c), _p(embeds_out)), "pcy_look_draft")
@@ -1172,7 +1198,7 @@ class LlamaEngine:
         _chk_bf16(logits)
         L.check(self.ctx.lib.pcy_look_verify(self.ctx.h, C.byref(self.desc), C.byref(look.c), C.byref(st.c), _p(logits)), "pcy_look_verify")
 
-    def generate_lookahead(self, embeds, input_ids, max_len, window, ngram=(3, 1), forced=None, keep_logits=False):
+    def generate_lookahead(self, embeds, input_ids, max_len, window, ngram=(3, 1), forced=None, keep_logits=False, step="extend"):
         """Greedy generation of ONE prompt with `window - 1` drafted tokens checked per pass over the weights: prefill, token 0
         from its logits as in `generate_greedy`, then passes of draft (prompt lookup over `input_ids` + the text so far, pcy_look_draft) ->
         `extend` of exactly `window` rows at the cache length -> verify + commit (pcy_look_verify) until max_len tokens are committed; no EOS
@@ -1181,7 +1207,12 @@ class LlamaEngine:
         replaces the draft of output token i (tests, measurements).  Returns what `generate_greedy` returns: (tokens [1,max_len] int64,
         logprob [1] fp32, logits [1,max_len,V] bf16 | None, (state, cache, look state)).
         At a fixed window the tokens, the log-prob, the logits record and the K / V of every committed slot do not depend on the drafts; they
-        are NOT promised bit-equal to `generate_greedy` (a window-row pass and a one-row decode step are different arithmetic)."""
+        are NOT promised bit-equal to `generate_greedy` (a window-row pass and a one-row decode step are different arithmetic).
+        step: what a pass runs on -- "extend" (the default: `extend`, the prefill's launch-per-stage loop) or "window" (`decode_window`, the
+        batched decode loop with the window attention; the position is then read on the device).  The two are different
+        arithmetic: each is independent of the drafts, they are not promised bit-equal to each other."""
+        if step not in ("extend", "window"):
+            raise ValueError(f"generate_lookahead: step={step!r}: 'extend' or 'window'")
         if embeds.dim() != 3 or embeds.shape[0] != 1:
             raise ValueError(f"generate_lookahead: one prompt at a time, embeds {tuple(embeds.shape)}")
         if embeds.dtype != BF16:
@@ -1221,14 +1252,19 @@ class LlamaEngine:
         emb = torch.empty(1, W, d, dtype=BF16, device=dev)
         rows = torch.arange(W, dtype=torch.int32, device=dev)
         logits = torch.empty(W, V, dtype=BF16, device=dev)
+        on_window = step == "window"      # (`step` counts the committed tokens from here on)
         pos, step = T, 1
         while step < max_len:
             self.look_draft(look, st, emb)
             # rows of rejected drafts left K / V in slots [pos, pos + W - 1 - accepted) of the previous pass's range: this pass starts at pos,
             # has W rows and so rewrites every one of them before any of its queries reads it (a query at slot p reads [0, p] only)
-            self._extend_call(cache, emb, None, pos, False, rows, logits)
+            if on_window:
+                self.decode_window(cache, st, emb, logits)
+            else:
+                self._extend_call(cache, emb, None, pos, False, rows, logits)
             self.look_verify(look, st, logits)
-            # the one host read of a pass: `extend` takes t_past from the host (DESIGN.md 4.9 names the follow-up)
+            # the one host read of a pass: `extend` takes t_past from the host, and either step needs `step` to know when to stop
+            # 
             _, n, step0, pos0 = look.last.tolist()
             if n < 1:
                 raise L.PcyError(f"generate_lookahead: a pass committed nothing at step {step0}")

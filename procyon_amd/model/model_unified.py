@@ -1052,7 +1052,7 @@ class UnifiedProCyon:
     def generate(self, inputs, max_len=64, aaseq_type='protein', method="sampling", temperature=1.0, greedy=False,
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
-                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False):
+                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False, lookahead_step="extend"):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1062,6 +1062,10 @@ class UnifiedProCyon:
         tokens up in the prompt and the text so far).  Same return values; with return_all_internals the dictionary gains "lookahead" =
         {passes, tokens, accepted, tokens_per_pass}.  Its tokens do not depend on the drafts, but are not promised equal to lookahead=0
         where two logits tie within the arithmetic's noise.
+        lookahead_step="extend" | "window" (with lookahead only; "extend", the default, is today's code): what a pass runs on -- the cache
+        extension, or the batched decode loop with the window attention (`LlamaEngine.decode_window`).  The internals'
+        "lookahead" dictionary names a step other than the default under "step".  ValueError for any other value, or for "window" without lookahead;
+        NotImplementedError on the fp32 family.
         decode_gemm=True | "auto" (not in the reference; False, the default, is today's code): the cached decode steps of every method on the
         step that reads the weights once whatever the row count (`LlamaEngine.decode_gemm`) -- for more than 32 rows per step
         (prompts x beams); "auto" takes it from `engine.decode_gemm_plan`'s row count on.  Same return values; the tokens are not promised equal
@@ -1083,6 +1087,12 @@ class UnifiedProCyon:
             raise NotImplementedError("generate(lookahead=W) needs the bf16 engine (the fp32 family has no cache extension)")
         if lookahead and (lookahead < 2 or lookahead > 32):
             raise ValueError(f"generate: lookahead={lookahead}: 0 (off) or a window of 2..32 rows")
+        if lookahead_step not in ("extend", "window"):
+            raise ValueError(f"generate: lookahead_step={lookahead_step!r}: 'extend' or 'window'")
+        if lookahead_step != "extend" and self._f32:
+            raise NotImplementedError("generate(lookahead_step=...) needs the bf16 engine (the fp32 family has no lookahead)")
+        if lookahead_step != "extend" and not lookahead:
+            raise ValueError(f"generate: lookahead_step={lookahead_step!r} chooses the pass of lookahead=W: pass a window too")
         if decode_gemm not in (False, True, "auto"):
             raise ValueError(f"generate: decode_gemm={decode_gemm!r}: False, True or 'auto'")
         if decode_gemm and lookahead:
@@ -1130,9 +1140,10 @@ class UnifiedProCyon:
             for i in (self.prot_replacement_idx, self.struct_idx, self.drug_idx):
                 hist_ids[hist_ids == i] = -1
             tok, lp, lg, (_, _, look) = self.text_encoder.engine.generate_lookahead(input_embeds, hist_ids, max_len, lookahead, ngram=lookahead_ngram,
-                                                                                    keep_logits=True)
+                                                                                    keep_logits=True, **({} if lookahead_step == "extend" else {"step": lookahead_step}))
             tokens, log_probs, logits = tok.cpu().unsqueeze(1), lp.cpu().clone().unsqueeze(0).T, lg.cpu().unsqueeze(1)
-            look_stats = look.stats()
+            # ("step" is named only where it was chosen: the default call returns the dictionary it always returned)
+            look_stats = look.stats() if lookahead_step == "extend" else dict(look.stats(), step=lookahead_step)
         elif method == "beam":
             tokens, log_probs, logits = (self._generate_beam_search_f32 if self._f32 else self._generate_beam_search)(
                 input_embeds, attn_masks, max_len=max_len, beam_size=beam_size, diversity_penalty=diversity_penalty,
