@@ -616,6 +616,30 @@ int pcy_f32_attention(pcy_ctx*, const float* q, int ldq, int qcol0, const float*
 int pcy_f32_attn_decode(pcy_ctx*, const float* q, int ldq, const float* kcache, const float* vcache, int ldkv, int Tmax, float* o, int ldo, int B,
                         int H, int Hkv, int dh, int nkeys, float scale);
 
+/* fp32 cache extension (HF's forward(input_ids [B,S], past_key_values) on an fp32 model; shared-prefix candidate scoring): S new query rows
+ * per row.  qkv [B*S, ld] roped, row b*S + s: q at column 0, the new K at H*dh, the new V at (H+Hkv)*dh.  Query s of row b attends slots
+ * [0, t_past) of cache row cache_row[b] (NULL = b; token-major caches [rows][Tmax][Hkv*dh], row stride ldkv floats) and then the new keys
+ * 0..s of its own row, read from qkv -- never from the cache, so rows may share a prefix row, and slots >= t_past are not read.  keep
+ * (may be NULL) [B, ldkeep >= t_past + S] bytes: 0 = the key is masked, old and new alike.  Exact fp32 softmax, keys in ascending slot
+ * order; o [B*S, ldo].  A query row without any kept key gets the family's value (pcy_f32_attention): the plain average of V over ALL
+ * t_past + S keys of its row.  S == 1 without keep / cache_row: bit-equal to pcy_f32_attn_decode on the same cache with the new K / V at
+ * slot t_past.  t_past == 0 is a causal prefill of the new tokens.  dh + t_past + S floats of LDS: larger sizes are refused (code 1). */
+int pcy_f32_attn_extend(pcy_ctx*, const float* qkv, int ld, const float* kcache, const float* vcache, int ldkv, int Tmax,
+                        const int32_t* cache_row, const uint8_t* keep, int ldkeep, float* o, int ldo, int B, int S, int t_past, int H, int Hkv,
+                        int dh, float scale);
+
+/* fp32 lm_head x cross-entropy without the [M, V] logits: nll[m] = lse[m] - l[m][targets[m]], lse = max + log sum exp(l - max), where
+ * l[m][n] is the fp32 value pcy_f32_linear(x, W) stores from its matrix-core kernel (same main loop: label_logit_out and row_max_out are
+ * bit-equal to the corresponding entries of that product).  x [M, d] final-normed, ldx floats between rows; W [V, d] in natural row order;
+ * rows 16-byte aligned and d % 16 == 0 (the conditions of pcy_f32_linear's matrix-core path; anything else is code 1, never a slow
+ * path).  targets [M] in [0, V): a target outside gives NaN in that row.  lse_out / row_max_out / label_logit_out may be NULL.  M == 0
+ * returns 0 without a launch.  No atomics; the column partition and every merge order are functions of V alone: a row's bits depend
+ * neither on M nor on the other rows, and two runs are bit-equal.  Workspace (the context's): rows are processed at most 1024 at a
+ * time, pcy_f32_lm_head_xent_ws_bytes = min(M, 1024) * (n_col_blocks(V) * 8 + 4) bytes -- host arithmetic, callable without a device. */
+int pcy_f32_lm_head_xent(pcy_ctx*, const float* x, int ldx, const float* W, int M, int V, int d, const int32_t* targets, float* nll_out,
+                         float* lse_out, float* row_max_out, float* label_logit_out);
+size_t pcy_f32_lm_head_xent_ws_bytes(int M, int V);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,9 @@ SIGNATURES = {
     "pcy_f32_pool": (ci, [vp, vp, ci, vp, vp, ci, ci, vp]),
     "pcy_f32_attention": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, C.c_float]),
     "pcy_f32_attn_decode": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ci, C.c_float]),
+    "pcy_f32_attn_extend": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, C.c_float]),
+    "pcy_f32_lm_head_xent": (ci, [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
+    "pcy_f32_lm_head_xent_ws_bytes": (C.c_size_t, [ci, ci]),
     "pcy_quant_rows_fp8": (ci, [vp, vp, ci, ci, ci, vp, vp]),
     "pcy_gemm_fp8": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci]),
     "pcy_mlp_forward": (ci, [vp, C.POINTER(MlpDesc), vp, ci, vp]),

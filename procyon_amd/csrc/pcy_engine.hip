@@ -756,6 +756,7 @@ extern "C" {
 
 }  // extern "C"
 hipStream_t pcy_ctx_stream(pcy_ctx* c) { return c->stream; }
+void* pcy_ctx_reserve(pcy_ctx* c, size_t bytes) { return c->reserve(bytes) == 0 ? c->ws : nullptr; }
 extern "C" {
 int pcy_abi_version(void) { return PCY_ABI_VERSION; }
 unsigned long long pcy_debug_dispatch_count(int kind) { return (kind >= 0 && kind < PCY_DISPATCH_N) ? g_pcy_dispatch[kind] : 0; }

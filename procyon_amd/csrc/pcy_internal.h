@@ -137,6 +137,7 @@ struct PcyGemmArgs {
 struct pcy_ctx;
 hipStream_t pcy_ctx_stream(pcy_ctx* c);               // the context's stream (pcy_engine.hip owns the struct)
 void pcy_set_error(const char* fmt, ...);             // sets the text pcy_last_error() returns
+void* pcy_ctx_reserve(pcy_ctx* c, size_t bytes);      // the context's workspace grown to >= bytes (256-byte aligned); nullptr + error text on failure
 void pcy_launch_gemm(hipStream_t s, const PcyGemmArgs& a);
 // builds the one-time device tables of the GEMM epilogues (the ESM GELU table) on `s` if this device has none yet -- callers that
 // CAPTURE a chain of launches call it first, so that the build is not recorded into the graph

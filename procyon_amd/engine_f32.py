@@ -10,7 +10,9 @@ include/pcy.h; procyon_amd/csrc/pcy_f32.hip) together op for op like the referen
   LlamaEngineF32  token embedding + soft-token splice, decoder prefill, logits   (/root/reference/procyon/model/pmc_llama.py:546-596,
                   at chosen rows, final hidden states, the L+1-state sum;         /root/reference/procyon/model/model_unified.py:556-581)
                   with a KVCacheF32 also the cached decode step of an fp32
-                  generation (`decode`, pcy_f32_attn_decode)
+                  generation (`decode`, pcy_f32_attn_decode), the many-token
+                  cache extension (`extend`, `extend_behind`, pcy_f32_attn_extend)
+                  and HF's causal-LM loss (`score`, pcy_f32_lm_head_xent)
 
 The cached decode attends every slot without a mask, as the reference does after the prefill, so it reads the K / V that the prefill
 computed from left-pad rows: pcy_f32_attention gives those rows the reference's value (include/pcy.h).  PyTorch holds the device
@@ -23,7 +25,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Context, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq
+from .engine import Context, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, score_plan, uniform_keep
 
 F32 = torch.float32
 
@@ -88,6 +90,66 @@ class F32Ops:
         L.check(self.lib.pcy_f32_attn_decode(self.h, _p(q), q.stride(0), _p(kcache), _p(vcache), kcache.shape[2], kcache.shape[1], _p(o), H * dh, B,
                                              H, Hkv, dh, nkeys, scale), "pcy_f32_attn_decode")
         return o
+
+    @staticmethod
+    def _chk_rows(t, what, min_cols=0):
+        """an fp32 device matrix whose rows the 16-byte loads can read: unit inner stride, row stride and base address multiples of 4 floats"""
+        if (not isinstance(t, torch.Tensor) or t.dtype != F32 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4
+                or t.data_ptr() % 16 or t.shape[1] < min_cols):
+            raise TypeError(f"fp32 engine: {what} must be an fp32 device matrix with unit inner stride, a row stride that is a multiple of 4 floats and a "
+                            f"16-byte aligned base, got {getattr(t, 'dtype', type(t))} {getattr(t, 'device', None)} shape "
+                            f"{tuple(getattr(t, 'shape', ()))} strides {tuple(t.stride()) if isinstance(t, torch.Tensor) else None}")
+
+    def attn_extend(self, qkv, S, kcache, vcache, t_past, H, Hkv, dh, scale, keep=None, cache_rows=None):
+        """S new query rows per row: qkv [B*S, >= (H + 2 Hkv) dh] roped (q | new K | new V, row b*S + s; a view with a row stride is fine)
+        against slots [0, t_past) of token-major caches [rows, Tmax, Hkv*dh] and the new keys 0..s of the row itself.  keep uint8
+        [B, >= t_past + S] (0 = masked key) or None; cache_rows int32 [B] (row b reads cache row cache_rows[b]) or None = b.  -> o [B*S, H*dh]"""
+        _chk(kcache, vcache)
+        self._chk_rows(qkv, "qkv", (H + 2 * Hkv) * dh)
+        S = int(S)
+        if S < 1 or qkv.shape[0] % S:
+            raise ValueError(f"qkv holds {qkv.shape[0]} rows: not a multiple of S = {S}")
+        B = qkv.shape[0] // S
+        ld = qkv.stride(0) if qkv.shape[0] > 1 else qkv.shape[1]
+        if kcache.dim() != 3 or kcache.shape != vcache.shape or kcache.shape[2] != Hkv * dh:
+            raise TypeError(f"fp32 engine: caches must be [rows, Tmax, {Hkv * dh}], got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
+        nrows, Tmax = kcache.shape[0], kcache.shape[1]
+        if cache_rows is not None:
+            if cache_rows.dtype != torch.int32 or not cache_rows.is_cuda or not cache_rows.is_contiguous() or cache_rows.numel() != B:
+                raise TypeError("fp32 engine: cache_rows must be a contiguous int32 device tensor [B]")
+            if B and (int(cache_rows.min()) < 0 or int(cache_rows.max()) >= nrows):
+                raise ValueError(f"cache_rows outside the {nrows} rows of the cache")
+        elif B > nrows:
+            raise ValueError(f"{B} rows on a cache of {nrows}")
+        ldkeep = 0
+        if keep is not None:
+            if keep.dtype != torch.uint8 or not keep.is_cuda or keep.dim() != 2 or keep.stride(1) != 1 or keep.shape[0] != B or keep.shape[1] < t_past + S:
+                raise TypeError(f"fp32 engine: keep must be a uint8 device matrix [{B}, >= {t_past + S}] with unit inner stride")
+            ldkeep = keep.stride(0) if B > 1 else keep.shape[1]
+        o = torch.empty(B * S, H * dh, dtype=F32, device=qkv.device)
+        L.check(self.lib.pcy_f32_attn_extend(self.h, _p(qkv), ld, _p(kcache), _p(vcache), kcache.shape[2], Tmax, _p(cache_rows), _p(keep), ldkeep,
+                                             _p(o), H * dh, B, S, int(t_past), H, Hkv, dh, scale), "pcy_f32_attn_extend")
+        return o
+
+    def lm_head_xent(self, x, W, targets, want_parts=False):
+        """nll [M] fp32 = logsumexp(x . W^T) - (x . W^T)[targets] without the [M, V] logits (pcy_f32_lm_head_xent); x [M, d] fp32 (a view with
+        a row stride is fine), W [V, d], targets int32 [M] on the device.  want_parts: (nll, lse, row_max, label_logit)."""
+        _chk(W)
+        self._chk_rows(x, "x")
+        if W.dim() != 2 or W.shape[1] != x.shape[1]:
+            raise TypeError(f"fp32 engine: W {tuple(W.shape)} does not match x {tuple(x.shape)}")
+        M, d = x.shape
+        V = W.shape[0]
+        if targets.dtype != torch.int32 or not targets.is_cuda or not targets.is_contiguous() or targets.numel() != M:
+            raise TypeError("fp32 engine: targets must be a contiguous int32 device tensor [M]")
+        outs = [torch.empty(M, dtype=F32, device=x.device) for _ in range(4 if want_parts else 1)]
+        ldx = x.stride(0) if M > 1 else d
+        L.check(self.lib.pcy_f32_lm_head_xent(self.h, _p(x), ldx, _p(W), M, V, d, _p(targets), *[_p(t) for t in outs], *([None] * (4 - len(outs)))),
+                "pcy_f32_lm_head_xent")
+        return tuple(outs) if want_parts else outs[0]
+
+    def lm_head_xent_ws_bytes(self, M, V):
+        return int(self.lib.pcy_f32_lm_head_xent_ws_bytes(int(M), int(V)))
 
     def embed(self, table, ids, soft=None, soft_map=None):
         _chk(table, soft)
@@ -290,9 +352,32 @@ class LlamaEngineF32:
             x = ops.linear(act, lw["wd"], resid=x)
         return ops.linear(ops.rmsnorm(x, self.final_norm, cfg.rms_eps), self.lm_head)
 
-    def prefill(self, embeds, attn_mask=None, logit_rows="last", want_hidden=False, sum_rows=None, cache=None):
-        """embeds [B,T,d] fp32; attn_mask [B,T] 0/1 or None -> (logits [n,V] fp32, final-normed hidden [B,T,d] | None[, sum over the
-        L+1 hidden states at `sum_rows` (flat b*T+t) [n,d]]) -- the return contract of `LlamaEngine.prefill`"""
+    def _rows(self, spec, B, T):
+        """flat token rows b*T+t (int64, on the device) of a logit_rows argument: "last", "all", None or a tensor"""
+        if isinstance(spec, str) and spec == "last":
+            return (torch.arange(B, dtype=torch.int64, device=self.device) + 1) * T - 1
+        if isinstance(spec, str) and spec == "all":
+            return torch.arange(B * T, dtype=torch.int64, device=self.device)
+        if spec is None:
+            return torch.zeros(0, dtype=torch.int64, device=self.device)
+        if isinstance(spec, str):
+            raise ValueError(f'logit_rows={spec!r}: expected "all", "last", None or a tensor of flat rows')
+        return spec.to(self.device, torch.int64)
+
+    def _logits(self, hn, rows):
+        logits = torch.empty(rows.numel(), self.cfg.vocab, dtype=F32, device=self.device)
+        if rows.numel():
+            self.ops.linear(hn.index_select(0, rows).contiguous(), self.lm_head, out=logits)
+        return logits
+
+    def _mlp(self, x, lw):
+        ops, cfg = self.ops, self.cfg
+        xn = ops.rmsnorm(x, lw["ln2"], cfg.rms_eps)
+        act = ops.silu_mul(ops.linear(xn, lw["wg"]), ops.linear(xn, lw["wu"]))
+        return ops.linear(act, lw["wd"], resid=x)
+
+    def _trunk(self, embeds, attn_mask, sum_rows=None, cache=None):
+        """the decoder over a whole batch -> (final-normed hidden [B*T, d], sum over the L+1 hidden states at `sum_rows` | None)"""
         ops, cfg = self.ops, self.cfg
         B, T, d = embeds.shape
         _no_shared_prefix(cache)
@@ -322,24 +407,112 @@ class LlamaEngineF32:
                 cache.v[li, :B, :T] = qkv[:, qw + kw:].view(B, T, kw)
             ao = ops.attention(qkv, 0, qkv, qw, qkv, qw + kw, cu, keep, B, T, H, Hkv, dh, True, dh ** -0.5)
             x = ops.linear(ao, lw["wo"], resid=x)
-            xn = ops.rmsnorm(x, lw["ln2"], cfg.rms_eps)
-            act = ops.silu_mul(ops.linear(xn, lw["wg"]), ops.linear(xn, lw["wu"]))
-            x = ops.linear(act, lw["wd"], resid=x)
+            x = self._mlp(x, lw)
         hn = ops.rmsnorm(x, self.final_norm, cfg.rms_eps)
         if hsum is not None:
             ops.acc_rows(hsum, hn, srows)
-        if isinstance(logit_rows, str) and logit_rows == "last":
-            rows = (torch.arange(B, dtype=torch.int64, device=self.device) + 1) * T - 1
-        elif isinstance(logit_rows, str) and logit_rows == "all":
-            rows = torch.arange(B * T, dtype=torch.int64, device=self.device)
-        elif logit_rows is None:
-            rows = torch.zeros(0, dtype=torch.int64, device=self.device)
-        else:
-            rows = logit_rows.to(self.device, torch.int64)
-        logits = torch.empty(rows.numel(), cfg.vocab, dtype=F32, device=self.device)
-        if rows.numel():
-            ops.linear(hn.index_select(0, rows).contiguous(), self.lm_head, out=logits)
+        return hn, hsum
+
+    def prefill(self, embeds, attn_mask=None, logit_rows="last", want_hidden=False, sum_rows=None, cache=None):
+        """embeds [B,T,d] fp32; attn_mask [B,T] 0/1 or None -> (logits [n,V] fp32, final-normed hidden [B,T,d] | None[, sum over the
+        L+1 hidden states at `sum_rows` (flat b*T+t) [n,d]]) -- the return contract of `LlamaEngine.prefill`"""
+        B, T, d = embeds.shape
+        hn, hsum = self._trunk(embeds, attn_mask, sum_rows, cache)
+        logits = self._logits(hn, self._rows(logit_rows, B, T))
         hidden = hn.view(B, T, d) if want_hidden else None
         if sum_rows is not None:
             return logits, hidden, hsum
         return logits, hidden
+
+    def _score_rows(self, hn, labels, B, T):
+        """HF's shifted causal-LM loss over the rows of hn [B*T, d] (engine.score_plan) -> (token_nll [B,T] fp32, n_tokens): the scored rows
+        of the final-normed hidden state are gathered and go through the fused lm_head x cross-entropy; no [n, V] logits"""
+        rows_c, tg_c, bt = labels
+        n = int(rows_c.numel())
+        token_nll = torch.zeros(B, T, dtype=F32, device=self.device)
+        if n:
+            rows_d, tg_d, bt_d = _h2d_many([rows_c, tg_c, bt.to(torch.int32)], self.device)
+            nll = self.ops.lm_head_xent(hn.index_select(0, rows_d.long()).contiguous(), self.lm_head, tg_d)
+            token_nll[bt_d[:, 0].long(), bt_d[:, 1].long() + 1] = nll      # row (b, t) scores the token at t + 1
+        return token_nll, n
+
+    def score(self, embeds, attn_mask, full_labels, cache=None, logit_rows=None):
+        """Teacher-forced scoring in ONE prefill pass, the return contract of `LlamaEngine.score`: embeds [B,T,d] fp32, attn_mask [B,T] or None,
+        full_labels [B,>=T] (HF's `labels`: -100 = not scored; a label outside [0, V) is a ValueError) -> (token_nll [B,T] fp32, n_tokens,
+        logits | None).  token_nll[b, t+1] = -log p(token t+1 | tokens <= t) where full_labels[b, t+1] is a label, 0 elsewhere; logits [n,V]
+        for `logit_rows` (the bits of `prefill`) or None.  Nothing is launched when there is nothing to do."""
+        B, T, _ = embeds.shape
+        plan = score_plan(full_labels, T, self.cfg.vocab)
+        if plan[0].numel() == 0 and logit_rows is None:
+            return torch.zeros(B, T, dtype=F32, device=self.device), 0, None
+        hn, _ = self._trunk(embeds, attn_mask, None, cache)
+        logits = self._logits(hn, self._rows(logit_rows, B, T)) if logit_rows is not None else None
+        token_nll, n = self._score_rows(hn, plan, B, T)
+        return token_nll, n, logits
+
+    def extend(self, cache: KVCacheF32, embeds, t_past, keep=None, logit_rows=None, labels=None, want_hidden=False, cache_rows=None):
+        """S more tokens per row against a cache that holds t_past tokens (HF's forward(inputs_embeds [B,S], past_key_values)), the return tuple of
+        `LlamaEngine.extend`: embeds [B,S,d] fp32 at rotary positions t_past .. t_past+S-1 for every row; keep [B, >= t_past+S] (0 = masked key,
+        old and new alike) or None; logit_rows "all" / "last" / flat rows b*S+s / None; labels [B,S] in HF's convention (-100 = not scored).
+        cache_rows None: the cache is the rows' own -- row b attends its slots [0, t_past) and the new K / V are written to [t_past, t_past+S).
+        cache_rows [B]: row b attends slots [0, t_past) of cache row cache_rows[b] (a shared prefix) and nothing is written.
+        -> (logits [n,V] | None, hidden [B,S,d] | None, token_nll [B,S] fp32 | None, n_tokens)"""
+        ops, cfg = self.ops, self.cfg
+        B, S, d = embeds.shape
+        t_past = int(t_past)
+        _no_shared_prefix(cache)
+        if t_past < 0 or t_past > cache.Tmax or (cache_rows is None and (t_past + S > cache.Tmax or B > cache.B)):
+            raise ValueError(f"KV cache capacity ({cache.B} rows x {cache.Tmax} slots) exhausted by {B} rows x ({t_past} + {S}) tokens; raise max_new_tokens")
+        if t_past + S > cfg.max_pos:
+            raise ValueError(f"t_past + S = {t_past + S} exceeds the rotary table ({cfg.max_pos})")
+        plan = None if labels is None else score_plan(labels, S, cfg.vocab)
+        H, Hkv, dh = cfg.n_heads, cfg.n_kv_heads, cfg.head_dim
+        keep_d = None
+        if keep is not None:
+            kp = torch.as_tensor(keep) != 0
+            if kp.dim() != 2 or kp.shape[0] != B or kp.shape[1] < t_past + S:
+                raise ValueError(f"keep {tuple(kp.shape)}: expected [{B}, >= {t_past + S}]")
+            if not bool(kp[:, :t_past + S].all()):
+                keep_d = kp[:, :t_past + S].to(self.device, torch.uint8).contiguous()
+        crows = None
+        if cache_rows is not None:
+            cr = torch.as_tensor(cache_rows).reshape(-1).cpu()
+            if cr.numel() != B or int(cr.min()) < 0 or int(cr.max()) >= cache.B:
+                raise ValueError(f"cache_rows: expected {B} rows of a cache of {cache.B}")
+            crows, = _h2d_many([cr.to(torch.int32)], self.device)
+        x = embeds.to(self.device, F32).reshape(B * S, d).contiguous().clone()
+        pos = (torch.arange(S, dtype=torch.int32, device=self.device) + t_past).repeat(B)
+        qw, kw = H * dh, Hkv * dh
+        for li, lw in enumerate(self.layers):
+            xn = ops.rmsnorm(x, lw["ln1"], cfg.rms_eps)
+            qkv = ops.linear(xn, lw["wqkv"])
+            ops.rope(qkv, 0, H, dh, pos, self.cos, self.sin)
+            ops.rope(qkv, qw, Hkv, dh, pos, self.cos, self.sin)
+            if cache_rows is None:
+                cache.k[li, :B, t_past:t_past + S] = qkv[:, qw:qw + kw].view(B, S, kw)
+                cache.v[li, :B, t_past:t_past + S] = qkv[:, qw + kw:].view(B, S, kw)
+            ao = ops.attn_extend(qkv, S, cache.k[li], cache.v[li], t_past, H, Hkv, dh, dh ** -0.5, keep=keep_d, cache_rows=crows)
+            x = ops.linear(ao, lw["wo"], resid=x)
+            x = self._mlp(x, lw)
+        hn = ops.rmsnorm(x, self.final_norm, cfg.rms_eps)
+        logits = self._logits(hn, self._rows(logit_rows, B, S)) if logit_rows is not None else None
+        token_nll, n = self._score_rows(hn, plan, B, S) if plan is not None else (None, 0)
+        return logits, (hn.view(B, S, d) if want_hidden else None), token_nll, n
+
+    def extend_behind(self, prefix_emb, prefix_mask, suffix_emb, suffix_mask, rows_per_prefix, **what):
+        """Prefill P prefixes ONCE and run the R = P * rows_per_prefix rows behind them as ONE `extend` on the prefixes' cache (row r reads
+        prefix r // rows_per_prefix; the shared-prefix form of `LlamaEngine.extend_behind`): prefix_emb [P,Tp,d], prefix_mask [P,Tp] with the
+        pads on the LEFT or None; suffix_emb [R,S,d], suffix_mask [R,S] (0 on the right pads).  what: logit_rows / labels / want_hidden of
+        `extend`.  -> (*what `extend` returns, the prefix cache)"""
+        if "groups" in what or "packed" in what:
+            raise TypeError("LlamaEngineF32.extend_behind: the fp32 family has the shared-prefix form only (no groups=, no packed=)")
+        P, Tp, _ = prefix_emb.shape
+        R = suffix_emb.shape[0]
+        n = int(rows_per_prefix)
+        if n < 1 or R != P * n:
+            raise ValueError(f"extend_behind: {R} rows are not {P} prefixes x {n} rows")
+        cache = self.new_cache(P, Tp)
+        self.prefill(prefix_emb, prefix_mask, logit_rows=None, cache=cache)
+        full = bool(torch.as_tensor(suffix_mask).all())
+        keep = None if full and prefix_mask is None else uniform_keep(prefix_mask, torch.as_tensor(suffix_mask).long(), Tp)
+        return (*self.extend(cache, suffix_emb, Tp, keep=keep, cache_rows=torch.arange(R) // n, **what), cache)

@@ -667,9 +667,9 @@ class UnifiedProCyon:
         out["answer_positions"] are the engine's own handle on the answer rows.  Retrieval: contrastive_out["positive"]["text"] [B, D].
         full_logits=True (not in the reference's signature): outputs.logits is a plain [B, T_real, V] tensor from the start (the reference pads
         every row to max_text_len and materialises [B, 2048, V]; the trailing all-pad columns are not computed here).
-        `outputs.loss` (non-retrieval, bf16): the reference's causal-LM loss over `full_labels` (trainIT.py reads it for the validation loss and
-        perplexity), with `outputs.token_nll` / `outputs.n_tokens` -- computed on first access, or in this pass with compute_loss=True
-        (LlamaPostTokenization.forward); None for retrieval and on the fp32 path.
+        `outputs.loss` (non-retrieval, bf16 and fp32): the reference's causal-LM loss over `full_labels` (trainIT.py reads it for the validation
+        loss and perplexity), with `outputs.token_nll` / `outputs.n_tokens` -- computed on first access, or in this pass with compute_loss=True
+        (LlamaPostTokenization.forward); None for retrieval.
         share_prefix=True (QA, bf16; not in the reference's signature): the columns every row of the batch shares -- in-context examples, the
         receptor -- are prefilled ONCE and the rows' differing ends run as one `LlamaEngine.extend` call on a cache whose rows share that
         prefix (`shared_prefix_plan`; `packed`: with the packed extension attention, read only here).  Same dictionary, plus
@@ -819,8 +819,6 @@ class UnifiedProCyon:
         "loss" = seq_nll.sum() / n_tokens.sum() (HF's batch mean), "perplexity" = exp(loss)}.  One prefill pass, no [B, T, V] logits."""
         out = self.forward(inputs, aaseq_type=aaseq_type, crop_off=crop_off, get_full_labels=True, compute_loss=True)
         o = out['outputs']
-        if o.loss is None:
-            raise NotImplementedError("score_text needs the bf16 engine (the fp32 path computes no loss)")
         tn = o.token_nll
         n_tok = (out['full_labels'][:, 1:tn.shape[1]] != -100).sum(1)
         loss = o.loss
@@ -840,9 +838,18 @@ class UnifiedProCyon:
         `score_text` gives it and no pad column runs in front of it -- and the suffixes run as one grouped `extend`.  The results are padded to
         Nmax = the longest list: "n_candidates" [P]; in the padding token_nll = 0, n_tokens = 0, seq_nll = mean_nll = +inf, so that "order"
         (stable argsort) puts it last.
-        Not on the fp32 family, with structure tokens or with fp8 weights (NotImplementedError, the refusals of `forward(share_prefix=True)`)."""
+        Not with structure tokens or with fp8 weights (NotImplementedError, the refusals of `forward(share_prefix=True)`).  On an fp32 model the
+        suffixes run through `LlamaEngineF32.extend_behind` (the prompts' fp32 cache, read by every row behind it; "cache" is that prefix cache);
+        `packed` is accepted and ignored (there is one fp32 attention), ragged=True is NotImplementedError."""
         self._require_bf16_or_fp32("score_candidates")
-        self._require_cache_extension("score_candidates", inputs)
+        if self._f32:       # the fp32 family has the shared-prefix form of the extension only (LlamaEngineF32.extend_behind); one attention: `packed` is not read
+            if ragged:
+                raise NotImplementedError("score_candidates(ragged=True) needs the bf16 engine (the fp32 family has no grouped cache)")
+            if self.config.use_protein_struct and inputs["input"]["seq"]:
+                raise NotImplementedError("score_candidates: structure tokens are dropped at random per call (struct_dropout_prob), so rows that read "
+                                          "alike need not share a prefix; score such batches with the ordinary forward / score_text")
+        else:
+            self._require_cache_extension("score_candidates", inputs)
         if any(len(t) for t in inputs["input"]["text"]):
             raise NotImplementedError("score_candidates: [EXT] text slots are not supported; write the text into the instruction")
         tokenize = lambda texts: self._prepare_text_inputs_and_tokenize(texts, [[] for _ in texts], crop_off=True)
@@ -852,10 +859,12 @@ class UnifiedProCyon:
             raise ValueError("score_candidates: a candidate holds a soft-token slot")
         _, protein_soft_tokens, drug_soft_tokens = self._soft_tokens(inputs, aaseq_type)
         prefix_emb, _ = self._prepare_input_embeddings(plan["prefix_ids"], protein_soft_tokens=protein_soft_tokens, drug_soft_tokens=drug_soft_tokens)
-        eng = self.text_encoder.engine
+        eng = self.text_encoder.engine_f32 if self._f32 else self.text_encoder.engine
         rows = dict(groups=(plan["group_rows"], plan["group_len"])) if ragged else dict(rows_per_prefix=plan["N"])
+        if not self._f32:
+            rows["packed"] = bool(packed)
         _, _, row_nll, _, cache = eng.extend_behind(prefix_emb, plan["prefix_mask"], eng.embed_tokens(plan["suffix_ids"]), plan["suffix_mask"],
-                                                    labels=plan["suffix_labels"], packed=bool(packed), **rows)
+                                                    labels=plan["suffix_labels"], **rows)
         n_tokens = plan["n_tokens"].to(row_nll.device)
         if not ragged:
             token_nll = row_nll.view(plan["P"], plan["N"], plan["S"])

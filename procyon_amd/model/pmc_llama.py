@@ -121,14 +121,16 @@ class LlamaPostTokenization:
         scores in this call (one pass together with the logits when `lazy_hidden=True` and no hidden-state sum is asked for; the hidden
         states then come from a second pass if they are read).  With the default `compute_loss=False` nothing extra runs here: `.loss` is
         computed on first access by a second, deterministic scoring pass (same bits) and cached, so callers that never read it pay nothing.
-        Without `full_labels`, on the fp32 path (fp32 `input_embeds`) and on the one-token cached decode `.loss` stays None.
+        The fp32 path (fp32 `input_embeds`) does the same on the fp32 family (`LlamaEngineF32.score`, pcy_f32_lm_head_xent; one pass with
+        `compute_loss=True` whenever no hidden-state sum is asked for).  Without `full_labels` and on the one-token cached decode `.loss` stays None.
       * past_key_values with MORE than one new token (HF's `forward(input_ids [B,S], past_key_values=...)`): `input_ids` [B,S] with S > 1, or
         bf16 `input_embeds` [B,S,d] at any S, extend the filled cache by S tokens per row in one pass (`LlamaEngine.extend`): positions
         t .. t+S-1, causal among the new tokens, every cached key attended.  `attn_masks` None or [B, t+S] (cached AND new keys; 0 = masked),
         `full_labels` [B,S] label the NEW tokens (token_nll[b, s+1] = NLL of new token s+1 given everything before it, the cache included),
         `logit_positions` [B] index the new tokens.  Returns `.logits` [B,S,V] (or [B,1,V]), `.past_key_values` of t+S tokens,
         `hidden_states[-1]` when `want_hidden`, `.loss / .token_nll / .n_tokens` as above (in the same pass with `compute_loss=True`).
-        `input_ids` [B,1] stays the decode step, bit for bit.  The fp32 family has no extension: an fp32 past takes `input_ids` [B,1] only.
+        `input_ids` [B,1] stays the decode step, bit for bit.  An fp32 past (the past of an fp32 forward) takes `input_ids` [B,S] or fp32
+        `input_embeds` [B,S,d] the same way (`LlamaEngineF32.extend`, pcy_f32_attn_extend); fp32 embeds with a bf16 past are an error.
       * output_attentions: not computed.
       * max_new_tokens: KV capacity reserved beyond the prompt when use_cache=True.
     """
@@ -168,13 +170,18 @@ class LlamaPostTokenization:
                 use_cache=False, output_attentions=None, logit_positions=None, want_hidden=True, hidden_sum_positions=None,
                 output_hidden_states=False, lazy_hidden=False, compute_loss=False):
         assert (input_embeds is not None) != (input_ids is not None), "Only one of input_embeds or input_ids can be provided"
-        if isinstance(past_key_values, _PastF32):      # cached decode of an fp32 generation
-            assert input_ids is not None and input_ids.shape[1] == 1, "cached decode takes input_ids [B,1]"
+        if isinstance(past_key_values, _PastF32):      # fp32 generation: the cached decode step, or the many-token extension
+            if input_embeds is not None and input_embeds.dtype != torch.float32:
+                raise RuntimeError("an fp32 past takes input_ids or fp32 input_embeds")
+            if input_embeds is not None or input_ids.shape[1] != 1:
+                return self._forward_extend_f32(input_embeds, input_ids, attn_masks, full_labels, past_key_values, logit_positions, want_hidden,
+                                                compute_loss)
             cache, t = past_key_values.cache, past_key_values.t
             logits = self.engine_f32.decode(cache, input_ids.view(-1), t)
             return CausalLMOutput(logits.view(input_ids.shape[0], 1, -1), _PastF32(cache, t + 1))
         if input_embeds is not None and input_embeds.dtype == torch.float32:
-            return self._forward_f32(input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions)
+            return self._forward_f32(input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions,
+                                     full_labels, compute_loss)
         eng = self.engine
         if past_key_values is None:
             if input_embeds is None:
@@ -267,22 +274,67 @@ class LlamaPostTokenization:
         hs = _HiddenStates(L1, hidden, no_tuple) if want_hidden else None
         return CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _Past(cache, t + S), hs, None, scorer=scorer, scored=scored)
 
-    def _forward_f32(self, input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions):
+    def _forward_f32(self, input_embeds, attn_masks, past_key_values, use_cache, logit_positions, want_hidden, hidden_sum_positions,
+                     full_labels=None, compute_loss=False):
         """fp32 embeddings in -> the fp32 prefill (the callers that never call `.bfloat16()`); use_cache=True keeps the K / V rows in an fp32
-        cache for the cached decode steps of an fp32 generation (/root/reference/scripts/caption_bulk.py:70-73, 123-132)"""
+        cache for the cached decode steps of an fp32 generation (/root/reference/scripts/caption_bulk.py:70-73, 123-132).  With full_labels:
+        `.loss` / `.token_nll` / `.n_tokens` from `LlamaEngineF32.score` -- in this pass together with the logits when compute_loss (and no
+        hidden-state sum is asked for), else on first access by a second, deterministic pass."""
         if past_key_values is not None:
-            raise RuntimeError("a prefill with input_embeds takes no past_key_values")
+            raise RuntimeError("fp32 input_embeds take an fp32 past (the past_key_values of an fp32 forward with use_cache=True) or none")
         eng = self.engine_f32
         B, T, _ = input_embeds.shape
         cache = eng.new_cache(B, T + self.max_new_tokens) if use_cache else None
         rows = "all" if logit_positions is None else (torch.arange(B) * T + logit_positions.cpu().long())
         hsum = None
-        if hidden_sum_positions is not None:
+        no_tuple = lambda: (_ for _ in ()).throw(RuntimeError("the fp32 path keeps the final hidden state only (hidden_states[-1])"))
+        L1 = self.cfg.n_layers + 1
+        scorer = scored = None
+        if full_labels is not None:
+            labels = torch.as_tensor(full_labels)[:, :T]      # columns beyond T are not run (the reference's trailing pads: all -100)
+            scorer = lambda: eng.score(input_embeds, attn_masks, labels)[:2]
+        if scorer is not None and compute_loss and hidden_sum_positions is None:
+            # loss and logits from ONE pass; the final hidden state comes from a second pass if it is read
+            token_nll, n_tok, logits = eng.score(input_embeds, attn_masks, labels, cache=cache, logit_rows=rows)
+            scored, scorer = (token_nll, n_tok), None
+            hs = _HiddenStates(L1, None, lambda: [None] * (L1 - 1) + [eng.prefill(input_embeds, attn_masks, None, want_hidden=True)[1]])
+        elif hidden_sum_positions is not None:
             logits, hidden, hsum = eng.prefill(input_embeds, attn_masks, rows, want_hidden=True, sum_rows=hidden_sum_positions, cache=cache)
+            hs = _HiddenStates(L1, hidden, no_tuple)
         else:
             logits, hidden = eng.prefill(input_embeds, attn_masks, rows, want_hidden=True, cache=cache)
-        hs = _HiddenStates(self.cfg.n_layers + 1, hidden, lambda: (_ for _ in ()).throw(
-            RuntimeError("the fp32 path keeps the final hidden state only (hidden_states[-1])")))
-        return CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _PastF32(cache, T) if use_cache else None, hs, hsum)
+            hs = _HiddenStates(L1, hidden, no_tuple)
+        out = CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _PastF32(cache, T) if use_cache else None, hs, hsum, scorer=scorer, scored=scored)
+        if compute_loss:
+            out._score()
+        return out
+
+    def _forward_extend_f32(self, input_embeds, input_ids, attn_masks, full_labels, past_key_values, logit_positions, want_hidden, compute_loss):
+        """S new tokens per row against the filled fp32 cache of `past_key_values` (see the class docstring): one `LlamaEngineF32.extend` pass"""
+        eng = self.engine_f32
+        cache, t = past_key_values.cache, past_key_values.t
+        if input_embeds is None:
+            input_embeds = eng.embed_tokens(input_ids)
+        B, S, _ = input_embeds.shape
+        if t + S > cache.Tmax:
+            raise ValueError(f"KV cache capacity {cache.Tmax} exhausted; raise max_new_tokens")
+        if attn_masks is not None:
+            attn_masks = torch.as_tensor(attn_masks)
+            assert tuple(attn_masks.shape) == (B, t + S), f"attn_masks {tuple(attn_masks.shape)}: the cached and the new keys, [{B}, {t + S}]"
+        rows = "all" if logit_positions is None else (torch.arange(B) * S + logit_positions.cpu().long())
+        labels = None if full_labels is None else torch.as_tensor(full_labels)[:, :S]
+
+        def no_tuple():
+            raise RuntimeError("the cached multi-token forward keeps the final hidden state only (hidden_states[-1])")
+
+        if labels is not None and not compute_loss:
+            # `.loss` on first access: the new tokens' K / V are in the cache by then, so the scoring pass rewrites the same slots with the same bits
+            logits, hidden, _, _ = eng.extend(cache, input_embeds, t, keep=attn_masks, logit_rows=rows, want_hidden=want_hidden)
+            scorer, scored = (lambda: tuple(eng.extend(cache, input_embeds, t, keep=attn_masks, labels=labels)[2:])), None
+        else:
+            logits, hidden, token_nll, n_tok = eng.extend(cache, input_embeds, t, keep=attn_masks, logit_rows=rows, labels=labels, want_hidden=want_hidden)
+            scorer, scored = None, (None if labels is None else (token_nll, n_tok))
+        hs = _HiddenStates(self.cfg.n_layers + 1, hidden, no_tuple) if want_hidden else None
+        return CausalLMOutput(logits.view(B, -1, self.cfg.vocab), _PastF32(cache, t + S), hs, None, scorer=scorer, scored=scored)
 
     __call__ = forward
