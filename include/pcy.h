@@ -408,6 +408,36 @@ int pcy_llama_decode_gemm_mq(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache
 /* steps enqueued by pcy_llama_decode_gemm_mq since the library was loaded (each also counts in pcy_debug_decode_gemm_count, none under a
  * decode kind of pcy_debug_dispatch_count). */
 unsigned long long pcy_debug_attn_mq_count(void);
+/* ---- split-key decode attention on a shared-prefix cache ----
+ * pcy_attn_decode_shared's operator, arguments, coverage and argument errors word for word; another arithmetic and another work split.
+ * Arithmetic: s_j = bf16(bf16(q.k) * scale), a masked s_j = the bf16 minimum.  The prefix is cut into chunks of pcy_attn_split_chunk_keys()
+ * keys; the row's own slots [prefix_T, t] are the last chunk.  Per chunk c: m_c = max s_j, e_j = exp(s_j - m_c) in fp32, l_c = sum e_j in fp32,
+ * p_j = bf16(e_j), o_c = sum p_j * v_j in fp32.  Then m = max_c m_c, w_c = exp(m_c - m), o = bf16((sum_c w_c * o_c) / (sum_c w_c * l_c)),
+ * both sums in chunk order, rounded once.  A chunk whose keys are all masked for a query has w_c == 0 exactly (slot t is never masked).
+ * This gives up the reference's rounding point p = bf16(exp(s - m) / l) under the global (m, l); against float64 it is no worse.
+ * Work split: two launches.  The first holds row workgroups (kv head, row: rope, append, the own slots) and prefix workgroups (key chunk x 64
+ * packed queries, kv head, prompt: each K and each V tile staged once, S and P.V by MFMA, S never leaves the chip) and writes o_c and
+ * (m_c, l_c); the second combines.  No atomics, no waiting between workgroups, no score rows in memory; the plan never depends on t.
+ * Promised: a query's bits depend on its own row's logical contents and on the call's shape (B, rows_per_prefix, prefix_T, geometry) only;
+ * equal calls give equal bits, equal rows in other tiles or prompts give equal bits; the appended K / V have the bits pcy_attn_decode writes;
+ * the prefix is never written and of the suffix only slot t - prefix_T; slots above t never reach a result.  NOT promised: the bits of
+ * pcy_attn_decode or of pcy_attn_decode_shared.  t < prefix_T or t >= prefix_T + Tmax: nothing is written.  Workspace: the context's. */
+int pcy_attn_decode_split(pcy_ctx*, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos,
+                          const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh);
+/* host arithmetic only: the keys per prefix chunk of pcy_attn_decode_split's plan for this shape (a positive multiple of 32; 0 for arguments
+ * below 1).  A function of these six values and nothing else. */
+int pcy_attn_split_chunk_keys(int B, int rows_per_prefix, int H, int Hkv, int dh, int prefix_T);
+/* pcy_llama_decode's contract on the default batched loop, with the attention of every layer served by pcy_attn_decode_split's launches
+ * (qkv projection with its own K-split finish -> attention -> o projection).  Eager.  Shared-prefix caches with rows_per_prefix >= 1 and a
+ * row count the batched loop serves only; a plain or grouped cache, an uncovered geometry, fp8 layers: argument errors before any launch.
+ * The attention's partial sums lie behind the decode carve and the K/V reorder scratch of pcy_llama_beam_steps.  NOT promised: the bits of
+ * pcy_llama_decode. */
+int pcy_llama_decode_split(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* pcy_llama_decode_gemm_mq with pcy_attn_decode_split's two launches in place of the four. */
+int pcy_llama_decode_gemm_split(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
+/* steps enqueued with the split-key attention since the library was loaded: by pcy_llama_decode_split, by pcy_llama_decode_gemm_split (which
+ * also counts in pcy_debug_decode_gemm_count) and, once per captured chain, by pcy_llama_beam_steps_split. */
+unsigned long long pcy_debug_attn_split_count(void);
 /* ---- cached decode that streams e4m3 weights: weight-only fp8 projections for 1..8 rows ----
  * The operator.  y[b][n] = epi( (sum_k x[b][k] * f32(W8[n][k])) * scale[n] ): W8 [N,K] OCP e4m3 codes and scale [N] fp32 as pcy_quant_rows_fp8
  * makes them per output channel (EPI_SWIGLU: [2N,K] / [2N] in the 16-row gate/up interleave, y is [B,N]); x, resid, y, rms_w bf16.  The
@@ -572,6 +602,10 @@ int pcy_kv_reorder_range(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, c
  * results as pcy_llama_decode_graph + a copy + pcy_beam_step + pcy_kv_reorder per step. */
 int pcy_llama_beam_steps(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int beam, int group_size,
                          float diversity_penalty, const pcy_beam_state* state, void* logits_rec, int n_steps, int kv_t0);
+/* ... with pcy_llama_decode_split's step inside (its cache rules; the same bits as the four calls around pcy_llama_decode_split).  A chain
+ * captured with this attention and one without never share a graph. */
+int pcy_llama_beam_steps_split(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B, int beam, int group_size,
+                               float diversity_penalty, const pcy_beam_state* state, void* logits_rec, int n_steps, int kv_t0);
 
 /* ---- fp32 operator family: the arithmetic of the reference's callers that never call `.bfloat16()` ----
  * /root/reference/examples/paper_analyses/protpep_qa_scores.py:55-58 (`model.eval().to(device)`: fp32 weights, every torch op in

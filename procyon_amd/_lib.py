@@ -155,6 +155,11 @@ SIGNATURES = {
     "pcy_attn_decode_shared": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci]),
     "pcy_llama_decode_gemm_mq": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_debug_attn_mq_count": (C.c_ulonglong, []),
+    "pcy_attn_decode_split": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci]),
+    "pcy_attn_split_chunk_keys": (ci, [ci, ci, ci, ci, ci, ci]),
+    "pcy_llama_decode_split": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_llama_decode_gemm_split": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci]),
+    "pcy_debug_attn_split_count": (C.c_ulonglong, []),
     "pcy_gemv_w8": (ci, [vp, vp, vp, vp, ci, vp, vp, ci, vp, C.c_float, ci, ci, ci, ci, ci]),
     "pcy_llama_decode_w8": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LlamaLayerFp8), C.POINTER(KvCache), C.POINTER(GenState), ci]),
     "pcy_llama_greedy_w8": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(LlamaLayerFp8), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci]),
@@ -174,6 +179,7 @@ SIGNATURES = {
     "pcy_kv_reorder": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, ci, ci]),
     "pcy_kv_reorder_range": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), vp, ci, ci, ci]),
     "pcy_llama_beam_steps": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci, C.c_float, C.POINTER(BeamState), vp, ci, ci]),
+    "pcy_llama_beam_steps_split": (ci, [vp, C.POINTER(LlamaDesc), C.POINTER(KvCache), C.POINTER(GenState), ci, ci, ci, C.c_float, C.POINTER(BeamState), vp, ci, ci]),
 }
 
 _lib = None

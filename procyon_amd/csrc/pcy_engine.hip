@@ -43,6 +43,8 @@ unsigned long long g_pcy_look[2] = {0, 0};
 unsigned long long g_pcy_decode_gemm = 0;
 // ... of which by pcy_llama_decode_gemm_mq (pcy_debug_attn_mq_count)
 unsigned long long g_pcy_attn_mq = 0;
+// steps enqueued with the split-key attention (pcy_llama_decode_split / _beam_steps_split / _decode_gemm_split; pcy_debug_attn_split_count)
+unsigned long long g_pcy_attn_split = 0;
 // steps enqueued by pcy_llama_decode_w8 / pcy_llama_greedy_w8 outside a graph replay (pcy_debug_decode_w8_count): a word of its own as well
 unsigned long long g_pcy_decode_w8 = 0;
 // calls of pcy_llama_decode_window (pcy_debug_decode_window_count): a word of its own as well
@@ -82,6 +84,7 @@ struct DecodeGraphKey {
   uint32_t penalty_bits;
   const void* w8;                                  // kind 3: the host array of e4m3 layers and a fingerprint of the device pointers it holds
   uint64_t w8_fp;
+  int attn_split;                                  // 1: every layer's attention is the split-key one (pcy_attn_split.hip); never shares a graph with 0
 };
 
 struct pcy_ctx {
@@ -526,13 +529,47 @@ PcyGemvArgs proj_args(const DecodeCx& cx, const DecodePlan& p, const void* W, co
   return g;
 }
 
+// The split-key attention (pcy_attn_split.hip) on layer `layer` of a complete shared-prefix cache; ws: its partial sums and
+// statistics (split_ws_bytes).  Built in ONE place for pcy_attn_decode_split and the three steps that use it.
+size_t split_ws_bytes(const PcySplitPlan& p) { return align_up(p.part_bytes, 256) + align_up(p.stat_bytes, 256) + 256; }
+// Where a STEP keeps them: behind the decode carve AND the K/V reorder scratch of a beam-search chain (pcy_kv_reorder_range, pcy_llama_beam_steps),
+// so that the eager step, the replayed chain and the GEMM step agree on one offset and a reorder between two steps never meets them.
+size_t reorder_scratch_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
+  return align_up((size_t)2 * m->n_layers * B * m->n_kv_heads * kv->Tmax * m->head_dim * 2, 256) + 4096;
+}
+size_t split_ws_offset(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
+  return align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256) + reorder_scratch_bytes(m, kv, B);
+}
+size_t split_step_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
+  return split_ws_offset(m, kv, B) + split_ws_bytes(pcy_attn_split_plan(B, kv->rows_per_prefix, m->n_heads, m->n_kv_heads, m->head_dim, kv->prefix_T));
+}
+PcySplitAttnArgs split_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
+                                 const bf16_t* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, char* ws) {
+  const PcySplitPlan p = pcy_attn_split_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T);
+  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh, prefix_layer_stride = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
+  PcySplitAttnArgs a{};
+  a.qkv = qkv; a.ld = ld; a.k_own = (bf16_t*)kv->k + layer * layer_stride; a.v_own = (bf16_t*)kv->v + layer * layer_stride;
+  a.k_pre = (const bf16_t*)kv->prefix_k + layer * prefix_layer_stride; a.v_pre = (const bf16_t*)kv->prefix_v + layer * prefix_layer_stride;
+  a.Town = kv->Tmax; a.Tp = kv->prefix_T; a.rows_per_prefix = kv->rows_per_prefix; a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t;
+  a.keep = keep; a.ld_keep = kv_cap(kv); a.B = B; a.H = H; a.Hkv = Hkv; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
+  Carver cv(ws);
+  a.part = cv.take<float>(p.part_bytes / sizeof(float)); a.stat = cv.take<float2>(p.stat_bytes / sizeof(float2));
+  a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks;
+  return a;
+}
+
 // layers_only (measurement, pcy_llama_decode_layers): the decoder layers without the token embedding (the residual stream is whatever
 // the workspace holds) and without lm_head; the hand-over counters are advanced by one-thread launches instead.
-void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const PcySwitches& sw, bool layers_only = false) {
+// split (the batched loop on a shared-prefix cache only -- the callers have checked both): every layer's attention is the split-key one, its
+// buffers at split_ws_offset; it reads FINISHED qkv, so the projection runs its own K-split finish, and the o projection is a launch of its own.
+void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const PcySwitches& sw, bool layers_only = false,
+                    bool split = false) {
   hipStream_t s = c->stream;
   const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
   const DecodeCx cx = decode_cx(c, m, kv, st, B);
-  const DecodePlan p = plan_decode(c, m, kv, B, sw);
+  DecodePlan p = plan_decode(c, m, kv, B, sw);
+  if (split) { p.defer_qkv_finish = false; p.attn_o = false; }
+  char* split_ws = split ? c->ws + split_ws_offset(m, kv, B) : nullptr;
   if (layers_only) {
     if (p.epoch_word) pcy_launch_bump(s, p.epoch_word);
     if (p.tag_word) pcy_launch_bump(s, p.tag_word);
@@ -587,7 +624,11 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
     pcy_launch_gemv(s, g);
     if (qkv_splits > 1) { t.qkv_partials = cx.sk_ws; t.qkv_splits = qkv_splits; }
     const PcyGemvArgs o = proj_args(cx, p, L.wo, L.ln2, cx.ao, H * dh, cx.x, d, EPI_RESID, true, p.krot, &xn_ready);
-    if (!(p.attn_o && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err, xflags))) {
+    if (split) {
+      pcy_launch_attn_split(s, split_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
+                                               B, H, m->n_kv_heads, dh, split_ws));
+      pcy_launch_gemv(s, o);
+    } else if (!(p.attn_o && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err, xflags))) {
       t.xmin = 0;   // (no key split in the stand-alone attention)
       pcy_launch_attn_decode(s, t);
       pcy_launch_gemv(s, o);
@@ -600,6 +641,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
     pcy_launch_gemv(s, w);
   }
   if (layers_only) return;
+  if (split) ++g_pcy_attn_split;
   PcyGemvArgs h{};
   h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
   h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = B; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
@@ -1842,11 +1884,13 @@ static PcyMqAttnArgs mq_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache*
   return a;
 }
 // mq: the attention launch of every layer is the many-queries one, its buffers behind the decode carve (pcy_llama_decode_gemm_mq)
-static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq) {
+// split: ... the split-key one, its buffers at split_ws_offset (pcy_llama_decode_gemm_split)
+static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq, bool split = false) {
   hipStream_t s = c->stream;
   const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
   const DecodeCx cx = decode_cx(c, m, kv, st, B);
   char* mq_ws = c->ws + align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256);
+  char* split_ws = split ? c->ws + split_ws_offset(m, kv, B) : nullptr;
   const DecodePlan p{};   // (the stand-alone attention: no key split, its own column cut)
   pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
   int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
@@ -1855,7 +1899,9 @@ static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_k
     if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
     xn_ready = 0;
     linear(s, cx.xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, cx.qkv, cx.qkvw, B, cx.qkvw, d, EPI_STORE, cx.sk_ws, cx.sk_bytes);
-    if (mq) pcy_launch_attn_mq(s, mq_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
+    if (split) pcy_launch_attn_split(s, split_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
+                                                        st->keep, B, H, m->n_kv_heads, dh, split_ws));
+    else if (mq) pcy_launch_attn_mq(s, mq_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
                                                B, H, m->n_kv_heads, dh, mq_ws));
     else pcy_launch_attn_decode(s, attn_args(cx, p, l));
     linear(s, cx.ao, H * dh, (const bf16_t*)L.wo, nullptr, cx.x, d, cx.x, d, B, d, H * dh, EPI_RESID, cx.sk_ws, cx.sk_bytes,
@@ -1870,6 +1916,7 @@ static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_k
   linear(s, cx.xn, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)st->logits, m->vocab, B, m->vocab, d, EPI_STORE);
   ++g_pcy_decode_gemm;
   if (mq) ++g_pcy_attn_mq;
+  if (split) ++g_pcy_attn_split;
 }
 
 // a complete shared-prefix cache with a uniform rows_per_prefix and a geometry the many-queries attention covers: anything else is the caller's error
@@ -1883,9 +1930,9 @@ static int check_mq_cache(const pcy_kv_cache* kv, int B, int H, int Hkv, int dh,
   return 0;
 }
 
-static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq) {
+static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq, bool split = false) {
   PCY_STICKY(c);
-  const char* what = mq ? "pcy_llama_decode_gemm_mq" : "pcy_llama_decode_gemm";
+  const char* what = split ? "pcy_llama_decode_gemm_split" : mq ? "pcy_llama_decode_gemm_mq" : "pcy_llama_decode_gemm";
   if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
   if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
@@ -1900,9 +1947,21 @@ static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_c
     if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
     need = align_up(need, 256) + mq_ws_bytes(pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T));
   }
+  if (split) {   // (the same cache and geometry rules as the many-queries attention)
+    if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
+    need = split_step_ws_bytes(m, kv, B);
+  }
   if (int r = c->reserve(need)) return r;
-  enqueue_decode_gemm(c, m, kv, st, B, mq);
+  enqueue_decode_gemm(c, m, kv, st, B, mq, split);
   return check_launch(what);
+}
+int pcy_llama_decode_gemm_split(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  return decode_gemm_entry(c, m, kv, st, B, false, true);
+}
+unsigned long long pcy_debug_attn_split_count(void) { return g_pcy_attn_split; }
+int pcy_attn_split_chunk_keys(int B, int rows_per_prefix, int H, int Hkv, int dh, int prefix_T) {
+  if (B < 1 || rows_per_prefix < 1 || Hkv < 1 || H < Hkv || prefix_T < 1) return 0;
+  return pcy_attn_split_plan(B, rows_per_prefix, H, Hkv, dh, prefix_T).cblocks * 32;
 }
 int pcy_llama_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   return decode_gemm_entry(c, m, kv, st, B, false);
@@ -2144,6 +2203,44 @@ int pcy_attn_decode_shared(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv
   return check_launch(what);
 }
 
+int pcy_attn_decode_split(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
+                          const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh) {
+  PCY_STICKY(c);
+  const char* what = "pcy_attn_decode_split";
+  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
+  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
+  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
+  if (int r = c->reserve(split_ws_bytes(pcy_attn_split_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T)))) return r;
+  if (!pcy_launch_attn_split(c->stream, split_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
+                                                        B, H, Hkv, dh, c->ws)))
+    return fail(1, "%s: shape not covered", what);
+  return check_launch(what);
+}
+
+// What the steps on the split-key attention ask of the call beyond check_decode_cache: a complete shared-prefix cache with a uniform
+// rows_per_prefix >= 1, a geometry the attention covers, and the batched loop (DEC_LOOP_MFMA) as the step's plan.  No launch before it.
+static int check_split_step(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw, const char* what) {
+  if (int r = check_mq_cache(kv, B, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, sw, what)) return r;
+  if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
+  return 0;
+}
+
+int pcy_llama_decode_split(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+  PCY_STICKY(c);
+  const char* what = "pcy_llama_decode_split";
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
+  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  if (int r = check_mq_cache(kv, B, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
+  if (int r = c->reserve(split_step_ws_bytes(m, kv, B))) return r;
+  const PcySwitches sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, sw)) return r;
+  if (int r = check_split_step(c, m, kv, B, sw, what)) return r;
+  enqueue_decode(c, m, kv, st, B, sw, false, true);
+  return check_launch(what);
+}
+
 int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out) {
   PCY_STICKY(c);
@@ -2220,8 +2317,9 @@ int pcy_kv_reorder_range(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
 // -> record of the step's logits (row (step, b) of logits_rec, step read from the device) -> pcy_beam_step -> pcy_kv_reorder over the
 // slots the position counter names.  Same kernels, same order, same bits as the four calls (PCY_DISABLE=beam_graph: the callers keep
 // them); it removes the ~12 launch boundaries of a step (3.43 -> see DESIGN.md ms per step at beam 5).
-int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
-                         float diversity_penalty, const pcy_beam_state* bs, void* logits_rec, int n_steps, int kv_t0) {
+// split: the decode step of the chain is pcy_llama_decode_split's (pcy_llama_beam_steps_split); the error texts keep the default entry's name
+static int beam_steps_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
+                            float diversity_penalty, const pcy_beam_state* bs, void* logits_rec, int n_steps, int kv_t0, bool split) {
   PCY_STICKY(c);
   if (kv_t0 < 0 || (kv_t0 * m->head_dim) % 8) return fail(1, "pcy_llama_beam_steps: kv_t0 = %d (>= 0, kv_t0 * head_dim a multiple of 8)", kv_t0);
   const int BB = B * beam;
@@ -2231,14 +2329,18 @@ int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
   if (m->vocab <= 0 || m->vocab > 163840) return fail(1, "pcy_llama_beam_steps: vocab %d unsupported (<= 163840)", m->vocab);
   if (st->pos != bs->pos || st->next_tok != bs->next_tok) return fail(1, "pcy_llama_beam_steps: the decode state must read the beam state's position and tokens");
   if ((kv->Tmax * m->head_dim) % 8) return fail(1, "pcy_llama_beam_steps: Tmax * head_dim must be a multiple of 8");
+  if (split) {
+    if (int r = check_mq_cache(kv, BB, m->n_heads, m->n_kv_heads, m->head_dim, "pcy_llama_beam_steps_split")) return r;
+  }
   if (n_steps <= 0) return 0;
-  // everything the chain allocates, before the capture: decode workspace + the reorder scratch behind it, beam scratch, decode state
+  // everything the chain allocates, before the capture: decode workspace + the reorder scratch behind it (+ behind that the partial sums and
+  // statistics of the split-key attention), beam scratch, decode state
   const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
   const size_t tmp_elems = (size_t)2 * L * BB * Hkv * kv->Tmax * dh;
-  if (int r = c->reserve(decode_ws_bytes(m, BB, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
+  if (int r = c->reserve(split ? split_step_ws_bytes(m, kv, BB) : decode_ws_bytes(m, BB, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
   const PcySwitches sw = pcy_read_switches();
   if (int r = ensure_decode_state(c, m, BB, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, BB, sw, "pcy_llama_beam_steps")) return r;
+  if (int r = split ? check_split_step(c, m, kv, BB, sw, "pcy_llama_beam_steps_split") : check_decode_cache(c, m, kv, BB, sw, "pcy_llama_beam_steps")) return r;
   // (a shared-prefix cache: the rows own their suffix slots only -- the reorder starts at the first of them, and counts them from prefix_T)
   const int t_off = kv_shared(kv) ? kv->prefix_T : 0;
   const int sfx_t0 = (kv_t0 > t_off ? kv_t0 : t_off) - t_off;
@@ -2247,10 +2349,11 @@ int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
   decode_graph_key(key, c, m, kv, st, BB, 2, sw);
   memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
   memcpy(&key.penalty_bits, &diversity_penalty, 4);
+  key.attn_split = split ? 1 : 0;
   return replay_graph(c, key, n_steps, "beam-step", [&] {
     bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, BB, kv_cap(kv)), 256));
     hipStream_t s = c->stream;
-    enqueue_decode(c, m, kv, st, BB, sw);
+    enqueue_decode(c, m, kv, st, BB, sw, false, split);
     enqueue_store_logits(s, st->logits, logits_rec, 0, bs->step, BB, m->vocab);
     pcy_launch_beam_step(s, (const bf16_t*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
     if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, sfx_t0, t_off)) {
@@ -2261,6 +2364,14 @@ int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
                          (const int32_t*)bs->pos, sfx_t0, t_off);
     }
   });
+}
+int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
+                         float diversity_penalty, const pcy_beam_state* bs, void* logits_rec, int n_steps, int kv_t0) {
+  return beam_steps_entry(c, m, kv, st, B, beam, group_size, diversity_penalty, bs, logits_rec, n_steps, kv_t0, false);
+}
+int pcy_llama_beam_steps_split(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
+                               float diversity_penalty, const pcy_beam_state* bs, void* logits_rec, int n_steps, int kv_t0) {
+  return beam_steps_entry(c, m, kv, st, B, beam, group_size, diversity_penalty, bs, logits_rec, n_steps, kv_t0, true);
 }
 
 }  // extern "C"

@@ -320,6 +320,29 @@ struct PcyMqAttnArgs {
   int ntiles, nchunk, cblocks, lds;            // the plan of this shape
 };
 bool pcy_launch_attn_mq(hipStream_t s, const PcyMqAttnArgs& a);   // false = shape not covered, nothing launched
+// Split-key decode attention on a shared-prefix cache (pcy_attn_split.hip): the same operator in two launches, the softmax
+// statistics kept per key chunk and folded in a fixed-order combine; no score rows in memory.  The plan never depends on the position.
+struct PcySplitPlan {
+  int ntiles;                                  // 64-query tiles per (prompt, kv head)
+  int nchunk, cblocks;                         // key chunks of the prefix, 32-key blocks per chunk (<= 4): functions of the call's shape only
+  size_t part_bytes, stat_bytes;               // partial o [nchunk + 1][B][H*dh] fp32; (m_c, l_c) [nchunk + 1][B][H] float2 -- the own slots last
+};
+PcySplitPlan pcy_attn_split_plan(int B, int rows_per_prefix, int H, int Hkv, int dh, int Tp);
+bool pcy_attn_split_covers(int H, int Hkv, int dh, int Town);   // pcy_attn_mq_covers'
+struct PcySplitAttnArgs {
+  const bf16_t* qkv; int ld;                   // [B, (H+2Hkv)*dh] un-roped projections of the new token
+  bf16_t* k_own; bf16_t* v_own;                // THIS layer's suffix panels [rows, Hkv, Town, dh]: logical slot j >= Tp at j - Tp
+  const bf16_t* k_pre; const bf16_t* v_pre;    // THIS layer's prefix [prefix_B, Hkv, Tp, dh]; row b reads prefix row b / rows_per_prefix
+  int Town, Tp, rows_per_prefix;
+  bf16_t* o; int ldo;                          // [B, H*dh]
+  const int32_t* pos_dev;                      // device scalar: logical cache length t == rotary position of the new token
+  const bf16_t* cos_t; const bf16_t* sin_t;
+  const uint8_t* keep; int ld_keep;            // optional [B, ld_keep] key mask in logical slots, non-zero = kept
+  int B, H, Hkv, dh; float scale;
+  float* part; float2* stat;                   // workspace (PcySplitPlan::part_bytes / stat_bytes), 256-byte aligned
+  int ntiles, nchunk, cblocks;                 // the plan of this shape
+};
+bool pcy_launch_attn_split(hipStream_t s, const PcySplitAttnArgs& a);   // false = shape not covered, nothing launched
 // Window attention (pcy_attn_win.hip): W consecutive tokens of cache row 0 of a plain one-row cache -- a lookahead pass --
 // with the keys cut into chunks of PCY_WIN_CHUNK across workgroups and the position read on the device.  Four launches: rope + append,
 // per-chunk (max, sum), per-chunk P.V under the global (max, sum), the sum of the chunks in chunk order.

@@ -208,6 +208,22 @@ class Context:
                                                 _p(sin_t), _p(keep), B, H, Hkv, dh), "pcy_attn_decode_shared")
         return o
 
+    def attn_decode_split(self, qkv, cache, layer, pos, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, out=None):
+        """pcy_attn_decode_split: `attn_decode_shared`'s operator, arguments and errors on the split-key kernels: two launches,
+        softmax statistics per key chunk (`attn_split_chunk_keys`) folded in a fixed-order combine.  Not the bits of `attn_decode_shared`."""
+        _chk_bf16(qkv)
+        B = cache.B if B is None else int(B)
+        if keep is not None:
+            assert keep.dtype == torch.uint8 and keep.is_contiguous() and tuple(keep.shape) == (B, cache.capacity), (keep.shape, keep.dtype)
+        o = torch.empty(B, H * dh, dtype=BF16, device=qkv.device) if out is None else out
+        L.check(self.lib.pcy_attn_decode_split(self.h, _p(qkv), qkv.shape[1], C.byref(cache.c), int(layer), _p(o), o.shape[1], _p(pos), _p(cos_t),
+                                               _p(sin_t), _p(keep), B, H, Hkv, dh), "pcy_attn_decode_split")
+        return o
+
+    def attn_split_chunk_keys(self, B, rows_per_prefix, H, Hkv, dh, prefix_T):
+        """keys per prefix chunk of `attn_decode_split`'s plan: host arithmetic on these six values only"""
+        return int(self.lib.pcy_attn_split_chunk_keys(int(B), int(rows_per_prefix), int(H), int(Hkv), int(dh), int(prefix_T)))
+
     def attn_extend(self, qkv, cache, layer, t_past, cos_t, sin_t, H, Hkv, dh, keep=None, B=None, packed=False, groups=None):
         """pcy_attn_extend: qkv [B*S, (H+2Hkv)*dh] un-roped projections of S new tokens per row (row b*S+s; B rows, default the cache's);
         `cache` a KVCache (plain or shared-prefix) that holds t_past tokens per row.  Ropes q / k in place at t_past + s, appends K / V at
@@ -614,6 +630,16 @@ def decode_gemm_plan(rows, shared=False, mha=False):
     prefix; mha: the multi-head geometry class (Llama-2-7B / ProCyon-Split) instead of the grouped-query one (Llama-3-8B).  Pure: the one
     place that decides what "auto" means.  The measurement gave the same threshold for both classes and both cache layouts."""
     return int(rows) >= max(33, DECODE_GEMM_MIN_ROWS)
+
+
+def check_shared_attn(shared_attn):
+    """-> False, True or "split": the values of the `shared_attn` option, anything else a ValueError.  False: the per-row decode attention;
+    True: the many-queries attention of the GEMM step; "split": the split-key attention, beam search only."""
+    if shared_attn is False or shared_attn is True:
+        return shared_attn
+    if isinstance(shared_attn, str) and shared_attn == "split":
+        return "split"
+    raise ValueError(f"shared_attn={shared_attn!r}: False, True or 'split'")
 
 
 def disabled_switches():
@@ -1039,11 +1065,21 @@ class LlamaEngine:
     def decode_gemm(self, cache: KVCache, st: GenState, B, shared_attn=False):
         """the decode step for more than 32 rows: every projection one GEMM over the B rows, one pass over the weights (pcy_llama_decode_gemm).
         The contract of `decode`; not its bits.  shared_attn=True (pcy_llama_decode_gemm_mq): the attention scores all rows of a
-        prompt against one pass over its shared prefix -- a shared-prefix cache only, anything else is an error."""
+        prompt against one pass over its shared prefix -- a shared-prefix cache only, anything else is an error.  shared_attn="split"
+        (pcy_llama_decode_gemm_split): the same on the split-key attention's two launches."""
+        if check_shared_attn(shared_attn) == "split":
+            L.check(self.ctx.lib.pcy_llama_decode_gemm_split(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm_split")
+            return
         if shared_attn:
             L.check(self.ctx.lib.pcy_llama_decode_gemm_mq(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm_mq")
             return
         L.check(self.ctx.lib.pcy_llama_decode_gemm(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_gemm")
+
+    def decode_split(self, cache: KVCache, st: GenState, B):
+        """`decode` on the default batched loop with every layer's attention served by the split-key launches (pcy_llama_decode_split, DESIGN.md
+        4.3f): a shared-prefix cache with rows_per_prefix >= 1 and a row count the batched loop serves; anything else is an error.  The
+        contract of `decode`; not its bits."""
+        L.check(self.ctx.lib.pcy_llama_decode_split(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B), "pcy_llama_decode_split")
 
     def decode_w8(self, cache: KVCache, st: GenState, B):
         """the decode step that streams the e4m3 copies of the projections (pcy_llama_decode_w8): weight-only fp8, 1..8 rows,
@@ -1085,12 +1121,14 @@ class LlamaEngine:
         L.check(self.ctx.lib.pcy_beam_step(self.ctx.h, _p(logits), logits.shape[1], bs.B, bs.beam, group_size, float(diversity_penalty),
                                            C.byref(bs.c)), "pcy_beam_step")
 
-    def beam_steps(self, cache: KVCache, st: GenState, bs: "BeamState", group_size, diversity_penalty, logits_rec, n_steps, kv_t0=0):
+    def beam_steps(self, cache: KVCache, st: GenState, bs: "BeamState", group_size, diversity_penalty, logits_rec, n_steps, kv_t0=0, split=False):
         """n_steps iterations of decode -> record -> beam step -> KV reorder, each ONE replayed launch chain
         (pcy_llama_beam_steps); st.pos / st.next_tok are the beam state's arrays.  kv_t0: first cache slot the reorder moves (the prompt
-        length when the beams of a prompt hold the same prefix rows)."""
-        L.check(self.ctx.lib.pcy_llama_beam_steps(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), bs.B, bs.beam, group_size,
-                                                  float(diversity_penalty), C.byref(bs.c), _p(logits_rec), n_steps, int(kv_t0)), "pcy_llama_beam_steps")
+        length when the beams of a prompt hold the same prefix rows).  split: the chain's decode step is `decode_split`'s
+        (pcy_llama_beam_steps_split)."""
+        name = "pcy_llama_beam_steps_split" if split else "pcy_llama_beam_steps"
+        L.check(getattr(self.ctx.lib, name)(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), bs.B, bs.beam, group_size,
+                                            float(diversity_penalty), C.byref(bs.c), _p(logits_rec), n_steps, int(kv_t0)), name)
 
     def pick(self, cache: KVCache, st: GenState, B, advance_pos):
         L.check(self.ctx.lib.pcy_greedy_pick(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B, int(advance_pos)),
@@ -1286,9 +1324,13 @@ class LlamaEngine:
         on whichever cache beam_cache_plan chose.
         shared_attn (False | True): the GEMM step's attention scores all beams of a prompt against one pass over its shared prefix
         (`decode_gemm(..., shared_attn=True)`).  ValueError unless this call runs the GEMM step AND beam_cache_plan chose the
-        shared cache: there is no fallback."""
+        shared cache: there is no fallback.
+        shared_attn="split": the split-key attention in whichever step this call runs -- the replayed chain
+        (pcy_llama_beam_steps_split), under PCY_DISABLE=beam_graph the four-call body with `decode_split` (same kernels, same bits), with the
+        GEMM step `decode_gemm(..., shared_attn="split")`.  ValueError unless beam_cache_plan chose the shared cache: there is no fallback."""
         B, T, _ = embeds.shape
         BB, V, dev = B * beam_size, self.cfg.vocab, self.device
+        split = check_shared_attn(shared_attn) == "split"
         off = disabled_switches()
         # Three cache layouts (DESIGN.md 4.3b).  Each prompt is prefilled ONCE (the reference replicates it x beam before the prefill, :751-752)
         # and its last-row logits repeated: where beam_cache_plan says so into a B-row cache of exactly T slots that the BB rows share, owning
@@ -1297,7 +1339,10 @@ class LlamaEngine:
         # as LlamaPostTokenization.forward issues it (a BB-row batch may take other GEMM tiles than a B-row one: equal to bf16 noise).
         shared = beam_cache_plan(B, beam_size, T, max_new, off)["shared"]
         gemm = self._use_decode_gemm(decode_gemm, BB, shared)
-        if shared_attn and not (gemm and shared):
+        if split and not shared:
+            raise ValueError(f"generate_beam: shared_attn='split' needs the shared-prefix cache (beam_cache_plan -> shared={shared}) for {B} prompts "
+                             f"x {beam_size} beams")
+        if shared_attn and not split and not (gemm and shared):
             raise ValueError(f"generate_beam: shared_attn needs the GEMM decode step (decode_gemm={decode_gemm!r} -> {gemm}) on the shared-prefix "
                              f"cache (beam_cache_plan -> shared={shared}) for {B} prompts x {beam_size} beams")
         rep = lambda x: x.repeat_interleave(beam_size, dim=0)
@@ -1330,7 +1375,9 @@ class LlamaEngine:
             if gemm or "beam_graph" in off:
                 n = 1
                 if gemm:
-                    self.decode_gemm(cache, st, BB, **({"shared_attn": True} if shared_attn else {}))
+                    self.decode_gemm(cache, st, BB, **({"shared_attn": shared_attn} if shared_attn else {}))
+                elif split:
+                    self.decode_split(cache, st, BB)
                 else:
                     self.decode_graph(cache, st, BB)
                 rec[i].copy_(st.logits)
@@ -1338,7 +1385,7 @@ class LlamaEngine:
                 self.kv_reorder(cache, bs.src, T + i, t0=kv_t0)
             else:
                 n = min(8 - (i & 7), max_len - i, cache.capacity - T - i + 1)
-                self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=kv_t0)
+                self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=kv_t0, **({"split": True} if split else {}))
             i += n
         out, steps = bs.tokens()                                   # synchronises
         anc = bs.anc[:steps].long()

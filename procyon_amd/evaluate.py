@@ -15,7 +15,8 @@ for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwar
 "decode_gemm" (caption plugin; False, True or "auto", default False: the decode steps of `generate` on the step that reads the weights
 once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step),
 "shared_attn" (caption plugin; False or True, default False: beam search with "decode_gemm" only -- the step's attention scores all beams of a
-prompt against one pass over the K / V they share)."""
+prompt against one pass over the K / V they share; DESIGN.md 4.3d -- or "split": the split-key attention in every beam-search step, with or
+without "decode_gemm")."""
 from collections import defaultdict
 from collections.abc import Mapping
 

@@ -966,7 +966,7 @@ class UnifiedProCyon:
         enc = self.text_encoder
         flat = enc.engine.generate_beam(input_embeds, attn_mask, max_len, beam_size, beam_group_size, diversity_penalty,
                                         self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len), decode_gemm=decode_gemm,
-                                        **({"shared_attn": True} if shared_attn else {}))
+                                        **({"shared_attn": shared_attn} if shared_attn else {}))
         return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
 
     @contextmanager
@@ -1084,6 +1084,11 @@ class UnifiedProCyon:
         attention of the GEMM step scores all beams of a prompt against one pass over the K / V they share.  ValueError with
         any other method, with lookahead, or (from the engine, before any decode step) where the call does not run the GEMM step on the
         shared-prefix cache; NotImplementedError on the fp32 family.  Never a silent fallback.
+        shared_attn="split" (not in the reference): beam search only, with or without decode_gemm -- every decode step's attention is the
+        split-key one: the beams of a prompt share one pass over its K / V, softmax statistics per key chunk, two launches per
+        layer.  Another rounding order than shared_attn=False (no worse against float64), so tokens may differ where two logits tie within the
+        noise.  ValueError with any other method, with lookahead or decode_w8, or (from the engine, before any decode step) where the beams do
+        not run on the shared-prefix cache; NotImplementedError on the fp32 family.  Any value but False, True or "split" is a ValueError.
         decode_w8=True (not in the reference; False, the default, is today's code): greedy and sampling methods only, up to 8 prompts -- the
         cached decode steps stream the e4m3 copies of the projection weights (`LlamaEngine.decode_w8`, DESIGN.md 4.3e: weight-only fp8, half
         the weight bytes per step; the prefill stays what the engine's `set_fp8` says).  The tokens are those of a model whose projection
@@ -1108,6 +1113,10 @@ class UnifiedProCyon:
             raise ValueError("generate: decode_gemm serves steps of many rows, lookahead one prompt: pass one of them")
         if decode_gemm and self._f32:
             raise NotImplementedError("generate(decode_gemm=...) needs the bf16 engine (the fp32 family has no GEMM decode step)")
+        if not (shared_attn is False or shared_attn is True or (isinstance(shared_attn, str) and shared_attn == "split")):
+            raise ValueError(f"generate: shared_attn={shared_attn!r}: False, True or 'split'")
+        if shared_attn == "split" and decode_w8 is not False:
+            raise ValueError("generate: shared_attn='split' serves beam search, decode_w8 the greedy and sampling steps: pass one of them")
         if shared_attn and self._f32:
             raise NotImplementedError("generate(shared_attn=True) needs the bf16 engine (the fp32 family has no shared-prefix cache)")
         if shared_attn and lookahead:
@@ -1157,7 +1166,7 @@ class UnifiedProCyon:
             tokens, log_probs, logits = (self._generate_beam_search_f32 if self._f32 else self._generate_beam_search)(
                 input_embeds, attn_masks, max_len=max_len, beam_size=beam_size, diversity_penalty=diversity_penalty,
                 beam_group_size=beam_group_size, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
-                **({"shared_attn": True} if shared_attn else {}))
+                **({"shared_attn": shared_attn} if shared_attn else {}))
         else:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,

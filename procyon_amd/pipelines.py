@@ -71,7 +71,8 @@ def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_da
     whenever the one-by-one loop would have written it (after protein i for every i % save_frequency == 0, i > 0) and the final
     table as CSV (caption_bulk.py:99-148).  decode_gemm (False | True | "auto"): `generate`'s option of the same name -- batch_size x beam_size
     rows per decode step (8 x 10 = 80) on the step that reads the weights once.  shared_attn (False | True): `generate`'s
-    option of the same name, with decode_gemm only -- the beams of a protein are scored against one pass over their shared K / V (4.3d)."""
+    option of the same name, with decode_gemm only -- the beams of a protein are scored against one pass over their shared K / V (4.3d);
+    "split": the split-key attention in every step, with or without decode_gemm (4.3f)."""
     from procyon.data.inference_utils import create_caption_input_simple, uniprot_id_to_index
     assert "drug" not in prompt_dataset, "DrugBank not supported in this script"
     model.eval()
