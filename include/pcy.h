@@ -674,6 +674,81 @@ int pcy_f32_lm_head_xent(pcy_ctx*, const float* x, int ldx, const float* W, int 
                          float* lse_out, float* row_max_out, float* label_logit_out);
 size_t pcy_f32_lm_head_xent_ws_bytes(int M, int V);
 
+/* ---- fp32 generation on a streaming GEMV and a device-resident decode step ----
+ * Opt-in, beside the operator-per-launch step that LlamaEngineF32.decode strings together from the entries above.
+ *
+ * The streaming GEMV.  y[b][n] = epi(sum_k x[b][k] * W[n][k]): W [N, K] fp32 in nn.Linear's natural layout (rows of K floats, 16-byte
+ * aligned), x [B, ldx], y [B, ldy], resid [B, ldr] fp32, 1 <= B.  epi: 0 STORE y = v; 1 RESID y = v + resid (resid may alias y);
+ * 4 SWIGLU y = silu(g) * u with g from W and u from W2 [N, K] (two separate matrices; x / (1 + exp(-x)) as pcy_f32_silu_mul).  W2 is read
+ * for SWIGLU only.  Exact fp32 products and fp32 accumulation on the fp32-input matrix cores (a chain of fused multiply-adds per output).
+ * Weight traffic: one pass over the matrix serves up to 32 rows of x (17..32 rows take ONE pass, two 16-row tiles against every weight
+ * register); the launcher loops passes of 32 rows for larger B.
+ * Order of a (row, output) sum: a function of K, the epilogue (SWIGLU cuts K over half as many waves) and the 16-row group of the OUTPUT
+ * row (its workgroup walks the K range rotated by that group, so that the workgroups of a launch do not read the same window of their
+ * rows -- rows of 4096 floats are a power-of-two stride -- at the same moment).  It depends neither on B, nor on the pass or tile the row
+ * sits in, nor on what the other rows hold: row b of a B-row call has the bits of the one-row call on that row, NaN in another row does
+ * not reach it, and equal calls give equal bits.  No atomics; the partial sums of a workgroup's waves are added in wave order.
+ * Argument errors (code 1, nothing launched): a NULL W / x / y, W2 NULL with SWIGLU, resid NULL with RESID, an epi outside the three,
+ * B < 1, N < 1, K < 4 or K % 4, ldx < K or ldx % 4, ldy < N, RESID with ldr < N, W / W2 / x not 16-byte aligned. */
+int pcy_f32_gemv(pcy_ctx*, const float* W, const float* W2, const float* x, int ldx, const float* resid, int ldr, float* y, int ldy,
+                 int N, int K, int B, int epi);
+/* Decode attention of ONE new token per row that reads its position on the device.  qkv [B, ld]: the un-roped projections of the new
+ * token (q heads | k heads | v heads; not written).  *pos (device scalar) = the cache length t = the rotary position of the new token for
+ * EVERY row.  The launch ropes q and the new k at t (pcy_f32_rope's formula on cos_t / sin_t [>= Tmax, dh]), writes the roped K and V to
+ * slot t of the token-major caches [B, Tmax, ldkv] and attends slots [0, t] without a mask, with pcy_f32_attn_decode's exact softmax:
+ * scores (q . k) * scale in LDS, max, exp, sum, p / sum, o = sum p v in fp32.  One workgroup per (row, kv head): its H / Hkv query heads
+ * (four at a time when there are more) share every K and V read; the waves of the workgroup split the keys, their partial o is added in
+ * wave order.
+ * Promised: a row's bits are a function of (*pos, the geometry) and the row's own qkv and cache contents; equal calls give equal bits;
+ * slots above *pos never reach a result; only slot *pos of the caches is written; *pos < 0 or *pos >= Tmax writes nothing at all.
+ * NOT promised: the bits of pcy_f32_rope + pcy_f32_attn_decode (another order of the sums).
+ * Argument errors (code 1, nothing launched): a NULL pointer, B < 1, head_dim outside 16 / 64 / 128, Hkv < 1 or H % Hkv, ld / ldkv /
+ * ldo shorter than their rows or not multiples of 4, qkv / caches not 16-byte aligned, and a capacity whose score rows exceed the LDS of
+ * a CU: (min(H / Hkv, 4) * (Tmax + 9 * dh) + 2 * dh + 64) * 4 bytes > 159 KiB (the rule of pcy_f32_attn_decode, for the heads that share
+ * a workgroup and sized by the capacity, since the host does not know *pos). */
+int pcy_f32_attn_decode_pos(pcy_ctx*, const float* qkv, int ld, float* kcache, float* vcache, int ldkv, int Tmax, float* o, int ldo,
+                            const int32_t* pos, const float* cos_t, const float* sin_t, int B, int H, int Hkv, int dh, float scale);
+/* The fp32 decoder as the step reads it: every pointer is fp32 device memory in HF's layout; wqkv = [q; k; v] rows stacked, gate and up
+ * stay separate matrices; rope_cos / rope_sin [max_pos, head_dim].  layers is a HOST array [n_layers]. */
+typedef struct {
+  const float *wqkv, *wo, *wg, *wu, *wd, *ln1, *ln2;
+} pcy_f32_llama_layer;
+typedef struct {
+  int32_t vocab, d, n_layers, n_heads, n_kv_heads, head_dim, ffn, max_pos;
+  float rms_eps;
+  const float *embed, *final_norm, *lm_head, *rope_cos, *rope_sin;
+  const pcy_f32_llama_layer* layers;
+} pcy_f32_llama_desc;
+/* token-major fp32 K (roped) / V caches [n_layers][B][Tmax][n_kv_heads * head_dim] (KVCacheF32) */
+typedef struct {
+  float *k, *v;
+  int32_t B, Tmax;
+} pcy_f32_kv_cache;
+/* One decode step, pcy_llama_decode's contract in fp32: next_tok -> logits in state->logits ([B, vocab] fp32), K / V of the new token
+ * appended at slot *pos of rows [0, B) of every layer; no pick, no advance; next_tok and *pos are read from device memory, no host read,
+ * no synchronisation.  The state is a pcy_gen_state whose logits / logits_all hold fp32; keep must be NULL (the reference passes no mask
+ * after the prefill).  Launch chain, all ordinary grids on the context's stream: token gather; per layer RMSNorm -> qkv GEMV ->
+ * pcy_f32_attn_decode_pos -> o GEMV (+ residual) -> RMSNorm -> gate / up GEMV (SwiGLU) -> down GEMV (+ residual), seven launches; final
+ * RMSNorm and the lm_head GEMV.  The workspace is the context's.  A row's logits and appended K / V depend on that row's inputs alone.
+ * NOT promised: the bits of the operator-per-launch step.
+ * Argument errors (code 1, nothing launched, nothing written): an incomplete descriptor / cache / state, keep != NULL, B outside
+ * [1, cache rows], d / ffn / H * dh not multiples of 4, whatever pcy_f32_attn_decode_pos refuses for this geometry and capacity,
+ * Tmax > max_pos. */
+int pcy_f32_llama_decode(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B);
+/* the same step, same bits, as ONE replayed hipGraph: a linear chain on one stream without parallel branches, captured on first use per
+ * (descriptor and its weight pointers, cache, state, B) -- for host-driven loops (sampling, beam search) that write next_tok and *pos on
+ * the device between steps */
+int pcy_f32_llama_decode_graph(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B);
+/* argmax of state->logits (fp32; lowest index on ties) -> next_tok / tokens_out[b][*step]; logprob[b] += fp32 log_softmax(logits)[token];
+ * then ++*step and, when advance_pos != 0, ++*pos -- pcy_greedy_pick's rules.  Writes row *step of the optional fp32 record logits_all
+ * ([max_steps, B, logits_all_ld or vocab]; may be pinned host memory) first.  -inf logits mean "never chosen"; NaN is outside the contract. */
+int pcy_f32_greedy_pick(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B, int advance_pos);
+/* n_steps x (pcy_f32_llama_decode + pcy_f32_greedy_pick with advance) with no host synchronisation; use_graph != 0 replays one captured
+ * graph per step.  Eager and replayed runs give equal bits.  The caller keeps *step + n_steps <= max_steps and *pos + n_steps <= Tmax. */
+int pcy_f32_llama_greedy(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B, int n_steps, int use_graph);
+/* steps enqueued by the three entries above outside a graph replay (an eager step, or the capture of a graph) since the library was loaded */
+unsigned long long pcy_debug_f32_stream_count(void);
+
 #ifdef __cplusplus
 }
 #endif

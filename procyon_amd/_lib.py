@@ -56,6 +56,21 @@ class LlamaDesc(C.Structure):
                 ("layers_fp8", C.POINTER(LlamaLayerFp8))]
 
 
+class LlamaLayerF32(C.Structure):
+    # (pcy_f32_llama_layer: the fp32 decoder layer of the stream step; gate and up stay separate matrices)
+    _fields_ = [(n, vp) for n in ("wqkv", "wo", "wg", "wu", "wd", "ln1", "ln2")]
+
+
+class LlamaDescF32(C.Structure):
+    _fields_ = [("vocab", i32), ("d", i32), ("n_layers", i32), ("n_heads", i32), ("n_kv_heads", i32), ("head_dim", i32), ("ffn", i32),
+                ("max_pos", i32), ("rms_eps", C.c_float), ("embed", vp), ("final_norm", vp), ("lm_head", vp), ("rope_cos", vp), ("rope_sin", vp),
+                ("layers", C.POINTER(LlamaLayerF32))]
+
+
+class KvCacheF32(C.Structure):
+    _fields_ = [("k", vp), ("v", vp), ("B", i32), ("Tmax", i32)]
+
+
 class KvCache(C.Structure):
     # (the trailing fields: an optional shared prefix, all zero = a plain cache -- include/pcy.h)
     _fields_ = [("k", vp), ("v", vp), ("B", i32), ("Tmax", i32), ("prefix_k", vp), ("prefix_v", vp), ("prefix_B", i32), ("prefix_T", i32),
@@ -134,6 +149,14 @@ SIGNATURES = {
     "pcy_f32_attn_extend": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, vp, ci, vp, ci, ci, ci, ci, ci, ci, ci, C.c_float]),
     "pcy_f32_lm_head_xent": (ci, [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]),
     "pcy_f32_lm_head_xent_ws_bytes": (C.c_size_t, [ci, ci]),
+    # fp32 generation on the streaming GEMV (include/pcy.h)
+    "pcy_f32_gemv": (ci, [vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, ci, ci, ci]),
+    "pcy_f32_attn_decode_pos": (ci, [vp, vp, ci, vp, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, C.c_float]),
+    "pcy_f32_llama_decode": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci]),
+    "pcy_f32_llama_decode_graph": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci]),
+    "pcy_f32_greedy_pick": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci]),
+    "pcy_f32_llama_greedy": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci, ci]),
+    "pcy_debug_f32_stream_count": (C.c_ulonglong, []),
     "pcy_quant_rows_fp8": (ci, [vp, vp, ci, ci, ci, vp, vp]),
     "pcy_gemm_fp8": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci]),
     "pcy_mlp_forward": (ci, [vp, C.POINTER(MlpDesc), vp, ci, vp]),

@@ -49,6 +49,8 @@ unsigned long long g_pcy_attn_split = 0;
 unsigned long long g_pcy_decode_w8 = 0;
 // calls of pcy_llama_decode_window (pcy_debug_decode_window_count): a word of its own as well
 unsigned long long g_pcy_decode_window = 0;
+// steps enqueued by the fp32 stream step (pcy_f32_llama_decode / _decode_graph / _greedy) outside a graph replay (pcy_debug_f32_stream_count)
+unsigned long long g_pcy_f32_stream = 0;
 
 }  // namespace
 
@@ -68,6 +70,7 @@ void pcy_set_error(const char* fmt, ...) {
 struct DecodeGraphKey {
   int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps),
                                       // 3: decode on e4m3 weights + greedy pick (pcy_llama_greedy_w8)
+                                      // 4 / 5: the fp32 stream step alone / with its greedy pick (model = the pcy_f32_llama_desc)
   int B;
   PcySwitches sw;
   const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
@@ -2072,6 +2075,139 @@ int pcy_llama_greedy_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_lay
   });
 }
 unsigned long long pcy_debug_decode_w8_count(void) { return g_pcy_decode_w8; }
+
+// ---- fp32 generation: the device-resident decode step on the streaming fp32 GEMV (kernels: pcy_f32_gemv.hip) ----
+// One launch per stage, every kernel an ordinary grid: token gather; per layer RMSNorm -> qkv -> attention (rope + append + softmax at *pos)
+// -> o (+ residual) -> RMSNorm -> gate / up (SwiGLU) -> down (+ residual); final RMSNorm; lm_head.  next_tok and *pos come from device memory,
+// so the chain can be captured once and replayed.
+struct F32StreamCx { float *x, *xn, *qkv, *ao, *act; };
+static F32StreamCx f32_stream_carve(char* ws, const pcy_f32_llama_desc* m, int B) {
+  Carver cv(ws);
+  F32StreamCx cx;
+  cx.x = cv.take<float>((size_t)B * m->d);
+  cx.xn = cv.take<float>((size_t)B * m->d);
+  cx.qkv = cv.take<float>((size_t)B * (m->n_heads + 2 * m->n_kv_heads) * m->head_dim);
+  cx.ao = cv.take<float>((size_t)B * m->n_heads * m->head_dim);
+  cx.act = cv.take<float>((size_t)B * m->ffn);
+  return cx;
+}
+static size_t f32_stream_ws_bytes(const pcy_f32_llama_desc* m, int B) {
+  const size_t f = (size_t)B * (2 * (size_t)m->d + (size_t)(2 * m->n_heads + 2 * m->n_kv_heads) * m->head_dim + (size_t)m->ffn) * sizeof(float);
+  return f + 8 * 256;
+}
+static uint64_t f32_stream_fingerprint(const pcy_f32_llama_desc* m) {   // FNV-1a over every weight pointer the step reads, as layers_fingerprint
+  uint64_t h = 1469598103934665603ull;
+  auto mix = [&](const void* p) { h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull; };
+  mix(m->embed); mix(m->final_norm); mix(m->lm_head); mix(m->rope_cos); mix(m->rope_sin);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_f32_llama_layer& L = m->layers[l];
+    mix(L.wqkv); mix(L.wo); mix(L.wg); mix(L.wu); mix(L.wd); mix(L.ln1); mix(L.ln2);
+  }
+  return h;
+}
+static PcyF32GemvArgs f32_gemv_args(const float* W, const float* W2, const float* x, int K, float* y, int N, int B, int epi) {
+  PcyF32GemvArgs g{};
+  g.W = W; g.W2 = W2; g.x = x; g.y = y; g.N = N; g.K = K; g.B = B; g.ldx = K; g.ldy = N; g.ldr = N; g.epi = epi;
+  if (epi == EPI_RESID) g.resid = y;
+  return g;
+}
+static void enqueue_decode_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B) {
+  hipStream_t s = c->stream;
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  const int qkvw = (H + 2 * Hkv) * dh, kw = Hkv * dh;
+  const F32StreamCx cx = f32_stream_carve(c->ws, m, B);
+  const size_t layer_stride = (size_t)kv->B * kv->Tmax * kw;
+  const float scale = 1.0f / sqrtf((float)dh);
+  pcy_launch_f32_embed_dev(s, m->embed, st->next_tok, cx.x, B, d);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_f32_llama_layer& L = m->layers[l];
+    pcy_launch_f32_rmsnorm(s, cx.x, L.ln1, cx.xn, B, d, m->rms_eps);
+    pcy_launch_f32_gemv(s, f32_gemv_args(L.wqkv, nullptr, cx.xn, d, cx.qkv, qkvw, B, EPI_STORE));
+    pcy_launch_f32_attn_decode_pos(s, cx.qkv, qkvw, kv->k + l * layer_stride, kv->v + l * layer_stride, kw, kv->Tmax, cx.ao, H * dh, st->pos, m->rope_cos,
+                                   m->rope_sin, B, H, Hkv, dh, scale);
+    pcy_launch_f32_gemv(s, f32_gemv_args(L.wo, nullptr, cx.ao, H * dh, cx.x, d, B, EPI_RESID));
+    pcy_launch_f32_rmsnorm(s, cx.x, L.ln2, cx.xn, B, d, m->rms_eps);
+    pcy_launch_f32_gemv(s, f32_gemv_args(L.wg, L.wu, cx.xn, d, cx.act, F, B, EPI_SWIGLU));
+    pcy_launch_f32_gemv(s, f32_gemv_args(L.wd, nullptr, cx.act, F, cx.x, d, B, EPI_RESID));
+  }
+  pcy_launch_f32_rmsnorm(s, cx.x, m->final_norm, cx.xn, B, d, m->rms_eps);
+  pcy_launch_f32_gemv(s, f32_gemv_args(m->lm_head, nullptr, cx.xn, d, (float*)st->logits, m->vocab, B, EPI_STORE));
+  ++g_pcy_f32_stream;
+}
+static void enqueue_pick_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos) {
+  pcy_launch_f32_pick(c->stream, (const float*)st->logits, B, m->vocab, st->next_tok, st->tokens_out, st->max_steps, st->logprob, st->pos, st->step,
+                      advance_pos, (float*)st->logits_all, st->logits_all_ld);
+}
+// everything the fp32 step entries refuse; reserves the workspace behind the checks
+static int f32_stream_check(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, bool pick, const char* what) {
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits || !m->layers || !m->embed || !m->final_norm || !m->lm_head ||
+      !m->rope_cos || !m->rope_sin)
+    return fail(1, "%s: model, cache or state incomplete", what);
+  if (pick && (!st->step || !st->tokens_out || !st->logprob || st->max_steps < 1)) return fail(1, "%s: generation state incomplete", what);
+  if (st->keep) return fail(1, "%s: keep must be NULL (the fp32 step attends every slot, as the reference does after the prefill)", what);
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  if (m->n_layers < 1 || m->vocab < 1 || d < 4 || F < 4) return fail(1, "%s: geometry incomplete", what);
+  for (int l = 0; l < m->n_layers; ++l) {
+    const pcy_f32_llama_layer& L = m->layers[l];
+    if (!L.wqkv || !L.wo || !L.wg || !L.wu || !L.wd || !L.ln1 || !L.ln2) return fail(1, "%s: layer %d holds a NULL pointer", what, l);
+    if (((uintptr_t)L.wqkv | (uintptr_t)L.wo | (uintptr_t)L.wg | (uintptr_t)L.wu | (uintptr_t)L.wd) & 15) return fail(1, "%s: layer %d: matrices must be 16-byte aligned", what, l);
+  }
+  if (((uintptr_t)m->lm_head | (uintptr_t)kv->k | (uintptr_t)kv->v) & 15) return fail(1, "%s: lm_head and the caches must be 16-byte aligned", what);
+  if (B < 1 || B > kv->B || B > 65535) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  if (dh != 16 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (16/64/128)", what, dh);
+  if (Hkv < 1 || H < 1 || H % Hkv) return fail(1, "%s: Hkv | H required", what);
+  if (d % 4 || F % 4 || (H * dh) % 4) return fail(1, "%s: d, ffn and H*dh must be multiples of 4", what);
+  if (kv->Tmax < 1 || kv->Tmax > m->max_pos) return fail(1, "%s: cache capacity %d outside the rotary table (%d)", what, kv->Tmax, m->max_pos);
+  if (pcy_f32_attn_pos_lds(H, Hkv, dh, kv->Tmax) > 160 * 1024 - 1024) return fail(1, "%s: %d slots exceed the LDS score buffer of the attention", what, kv->Tmax);
+  return c->reserve(f32_stream_ws_bytes(m, B));
+}
+static void f32_stream_key(DecodeGraphKey& key, const pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int kind) {
+  memset(&key, 0, sizeof(key));
+  key.kind = kind; key.B = B;
+  key.model = m; key.layers = m->layers; key.embed = m->embed; key.kv_k = kv->k; key.kv_v = kv->v; key.Tmax = kv->Tmax; key.kv_B = kv->B;
+  key.pos = st->pos; key.step = st->step; key.next_tok = st->next_tok; key.logits = st->logits;
+  key.ws = c->ws; key.layers_fp = f32_stream_fingerprint(m);
+  if (kind == 5) { key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps; }
+}
+int pcy_f32_llama_decode(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B) {
+  PCY_STICKY(c);
+  if (int r = f32_stream_check(c, m, kv, st, B, false, "pcy_f32_llama_decode")) return r;
+  enqueue_decode_f32(c, m, kv, st, B);
+  return check_launch("pcy_f32_llama_decode");
+}
+int pcy_f32_llama_decode_graph(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B) {
+  PCY_STICKY(c);
+  if (int r = f32_stream_check(c, m, kv, st, B, false, "pcy_f32_llama_decode_graph")) return r;
+  DecodeGraphKey key;
+  f32_stream_key(key, c, m, kv, st, B, 4);   // kind 4: the fp32 step alone; 5: with the greedy pick
+  return replay_graph(c, key, 1, "decode-f32-step", [&] { enqueue_decode_f32(c, m, kv, st, B); });
+}
+int pcy_f32_greedy_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos) {
+  PCY_STICKY(c);
+  if (!m || !st || !st->logits || !st->pos || !st->step || !st->next_tok || !st->tokens_out || !st->logprob || st->max_steps < 1)
+    return fail(1, "pcy_f32_greedy_pick: generation state incomplete");
+  if (B < 1 || B > 65535 || m->vocab < 1 || (kv && B > kv->B)) return fail(1, "pcy_f32_greedy_pick: B=%d", B);
+  enqueue_pick_f32(c, m, st, B, advance_pos);
+  return check_launch("pcy_f32_greedy_pick");
+}
+int pcy_f32_llama_greedy(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps, int use_graph) {
+  PCY_STICKY(c);
+  if (int r = f32_stream_check(c, m, kv, st, B, true, "pcy_f32_llama_greedy")) return r;
+  if (!use_graph) {
+    for (int i = 0; i < n_steps; ++i) {
+      enqueue_decode_f32(c, m, kv, st, B);
+      enqueue_pick_f32(c, m, st, B, 1);
+    }
+    return check_launch("pcy_f32_llama_greedy");
+  }
+  DecodeGraphKey key;
+  f32_stream_key(key, c, m, kv, st, B, 5);
+  return replay_graph(c, key, n_steps, "decode-f32-step", [&] {
+    enqueue_decode_f32(c, m, kv, st, B);
+    enqueue_pick_f32(c, m, st, B, 1);
+  });
+}
+unsigned long long pcy_debug_f32_stream_count(void) { return g_pcy_f32_stream; }
 
 int pcy_gemv_w8(pcy_ctx* c, const void* W8, const float* scale, const void* x, int ldx, const void* resid, void* y, int ldy, const void* rms_w,
                 float rms_eps, int rms_cast, int N, int K, int B, int epi) {

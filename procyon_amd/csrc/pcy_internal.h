@@ -55,6 +55,25 @@ int pcy_gemv_w8_rows_per_pass(int K);
 // false = shape not covered (nothing launched): the caller checks the arguments first
 bool pcy_launch_gemv_w8(hipStream_t s, const PcyGemvW8Args& a);
 
+// fp32 streaming GEMV and the launches of the device-resident fp32 decode step (pcy_f32_gemv.hip)
+struct PcyF32GemvArgs {
+  const float* W;       // [N,K] fp32, natural nn.Linear layout
+  const float* W2;      // EPI_SWIGLU: the up matrix [N,K] (W is the gate); not read otherwise
+  const float* x;       // [B,K] (ldx)
+  const float* resid;   // [B,N] (ldr), EPI_RESID; may alias y
+  float* y;             // [B,N] (ldy)
+  int N, K, B, ldx, ldr, ldy, epi;   // epi in STORE / RESID / SWIGLU
+};
+bool pcy_launch_f32_gemv(hipStream_t s, const PcyF32GemvArgs& a);   // false = the device refused the LDS size (nothing launched)
+size_t pcy_f32_attn_pos_lds(int H, int Hkv, int dh, int Tmax);      // dynamic LDS of the launch below, bytes
+bool pcy_launch_f32_attn_decode_pos(hipStream_t s, const float* qkv, int ld, float* kc, float* vc, int ldkv, int Tmax, float* o, int ldo,
+                                    const int32_t* pos, const float* cos_t, const float* sin_t, int B, int H, int Hkv, int dh, float scale);
+void pcy_launch_f32_embed_dev(hipStream_t s, const float* table, const int32_t* ids, float* out, int rows, int d);
+void pcy_launch_f32_rmsnorm(hipStream_t s, const float* x, const float* w, float* y, int rows, int d, float eps);
+// record row *step of logits_all (optional), then the pick and the counters (pcy.h, the fp32 greedy pick)
+void pcy_launch_f32_pick(hipStream_t s, const float* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
+                         int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld);
+
 // Rotated K order of the batched GEMVs (round 6).  Every workgroup of these kernels walks ITS K range front to back in step with all the
 // others, so at any moment every wave of the chip reads the same 256-byte window of its rows -- and with a power-of-two row stride (K = 4096:
 // 8 KB) those windows fall on the same few HBM channels: tools/probes/stream_rows.hip measures the gate/up stream at 4.86 TB/s, and 6.26 TB/s

@@ -12,7 +12,9 @@ include/pcy.h; procyon_amd/csrc/pcy_f32.hip) together op for op like the referen
                   with a KVCacheF32 also the cached decode step of an fp32
                   generation (`decode`, pcy_f32_attn_decode), the many-token
                   cache extension (`extend`, `extend_behind`, pcy_f32_attn_extend)
-                  and HF's causal-LM loss (`score`, pcy_f32_lm_head_xent)
+                  and HF's causal-LM loss (`score`, pcy_f32_lm_head_xent); opt-in,
+                  the device-resident decode step on the streaming fp32 GEMV
+                  (`decode_stream`, `greedy_steps`: pcy_f32_llama_decode)
 
 The cached decode attends every slot without a mask, as the reference does after the prefill, so it reads the K / V that the prefill
 computed from left-pad rows: pcy_f32_attention gives those rows the reference's value (include/pcy.h).  PyTorch holds the device
@@ -89,6 +91,41 @@ class F32Ops:
         o = torch.empty(B, H * dh, dtype=F32, device=q.device)
         L.check(self.lib.pcy_f32_attn_decode(self.h, _p(q), q.stride(0), _p(kcache), _p(vcache), kcache.shape[2], kcache.shape[1], _p(o), H * dh, B,
                                              H, Hkv, dh, nkeys, scale), "pcy_f32_attn_decode")
+        return o
+
+    def gemv(self, x, w, w2=None, resid=None, epi=L.EPI_STORE, out=None):
+        """the streaming fp32 GEMV (pcy_f32_gemv): y[b] = epi(x[b] . w^T); x [B, K], out / resid [B, N] may be column windows of wider
+        buffers (row strides that are multiples of 4 floats for x); w [N, K]; epi EPI_STORE, EPI_RESID (y = v + resid, resid may be `out`) or
+        EPI_SWIGLU (y = silu(x . w^T) * (x . w2^T), two separate matrices)"""
+        _chk(w, w2)
+        self._chk_rows(x, "x")
+        B, K = x.shape
+        N = w.shape[0]
+        if w.dim() != 2 or w.shape[1] != K or (w2 is not None and w2.shape != w.shape):
+            raise TypeError(f"fp32 engine: w {tuple(w.shape)} / w2 {None if w2 is None else tuple(w2.shape)} do not match x {tuple(x.shape)}")
+        out = torch.empty(B, N, dtype=F32, device=x.device) if out is None else out
+        for t, what in ((out, "out"), (resid, "resid")):
+            if t is not None and (t.dtype != F32 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or tuple(t.shape) != (B, N)):
+                raise TypeError(f"fp32 engine: {what} must be an fp32 device matrix [{B}, {N}] with unit inner stride")
+        ld = lambda t: t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+        L.check(self.lib.pcy_f32_gemv(self.h, _p(w), _p(w2), _p(x), ld(x), _p(resid), 0 if resid is None else ld(resid), _p(out), ld(out), N, K, B,
+                                      int(epi)), "pcy_f32_gemv")
+        return out
+
+    def attn_decode_pos(self, qkv, kcache, vcache, pos, cos, sin, H, Hkv, dh, scale, out=None):
+        """pcy_f32_attn_decode_pos: qkv [B, >= (H + 2 Hkv) dh] un-roped (not written), token-major caches [B, Tmax, Hkv*dh], pos an int32
+        device scalar = cache length = rotary position: ropes q / the new k, appends K / V at slot *pos, attends slots [0, *pos] -> o [B, H*dh]"""
+        _chk(kcache, vcache, cos, sin)
+        self._chk_rows(qkv, "qkv", (H + 2 * Hkv) * dh)
+        if pos.dtype != torch.int32 or not pos.is_cuda or pos.numel() != 1:
+            raise TypeError("fp32 engine: pos must be an int32 device scalar")
+        if kcache.dim() != 3 or kcache.shape != vcache.shape or kcache.shape[0] < qkv.shape[0]:
+            raise TypeError(f"fp32 engine: caches must be [>= {qkv.shape[0]}, Tmax, ldkv], got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
+        B = qkv.shape[0]
+        o = torch.empty(B, H * dh, dtype=F32, device=qkv.device) if out is None else out
+        ld = qkv.stride(0) if B > 1 else max(qkv.stride(0), qkv.shape[1])
+        L.check(self.lib.pcy_f32_attn_decode_pos(self.h, _p(qkv), ld, _p(kcache), _p(vcache), kcache.shape[2], kcache.shape[1], _p(o), o.stride(0) if B > 1 else H * dh,
+                                                 _p(pos), _p(cos), _p(sin), B, H, Hkv, dh, scale), "pcy_f32_attn_decode_pos")
         return o
 
     @staticmethod
@@ -292,9 +329,36 @@ class KVCacheF32:
             c[:, moved, :t] = c[:, idx[moved], :t]       # (advanced indexing on the right gathers into a temporary first: sources are read before any write)
 
 
+class GenStateF32:
+    """device state of the fp32 stream step (a pcy_gen_state whose logits hold fp32): pos / step int32 scalars, next_tok [B], tokens_out
+    [B, max_steps], logprob [B], logits [B, V], optionally the record logits_all [max_steps, B, V]"""
+
+    def __init__(self, B, vocab, max_steps, device, keep_logits=False):
+        i32 = dict(dtype=torch.int32, device=device)
+        self.B, self.vocab, self.max_steps = B, vocab, max_steps
+        self.pos, self.step = torch.zeros(1, **i32), torch.zeros(1, **i32)
+        self.next_tok = torch.zeros(B, **i32)
+        self.tokens_out = torch.zeros(B, max_steps, **i32)
+        self.logprob = torch.zeros(B, dtype=F32, device=device)
+        self.logits = torch.zeros(B, vocab, dtype=F32, device=device)
+        self.logits_all = torch.zeros(max_steps, B, vocab, dtype=F32, device=device) if keep_logits else None
+        self.c = L.GenState(_p(self.pos), _p(self.step), _p(self.next_tok), _p(self.tokens_out), _p(self.logprob), _p(self.logits), _p(self.logits_all),
+                            None, max_steps, 0)
+
+    def set(self, pos=None, step=None, next_tok=None):
+        """device-side writes only (a fill / a copy on the stream: nothing is read back)"""
+        if pos is not None:
+            self.pos.fill_(int(pos))
+        if step is not None:
+            self.step.fill_(int(step))
+        if next_tok is not None:
+            self.next_tok.copy_(next_tok.reshape(-1).to(torch.int32), non_blocking=True)
+
+
 class LlamaEngineF32:
     """Llama decoder in fp32 (HF layout state dict): embedding + splice, L layers, final norm, logits at chosen rows; with a cache also
-    the KV-cached decode step (one launch per operator: a compatibility path for callers that generate without .bfloat16(), not a fast one)."""
+    the KV-cached decode step (`decode`: one launch per operator, 82 ms per step at full size) and, opt-in, the device-resident step that streams
+    the fp32 weights once per step and is replayed as a graph (`decode_stream` / `greedy_steps`, 8.4-13.7 ms; other bits than `decode`)."""
 
     def __init__(self, sd, cfg: LlamaConfig, device=None, ctx=None):
         self.ops = F32Ops(ctx, device)
@@ -351,6 +415,44 @@ class LlamaEngineF32:
             act = ops.silu_mul(ops.linear(xn, lw["wg"]), ops.linear(xn, lw["wu"]))
             x = ops.linear(act, lw["wd"], resid=x)
         return ops.linear(ops.rmsnorm(x, self.final_norm, cfg.rms_eps), self.lm_head)
+
+    # ---- the device-resident step on the streaming fp32 GEMV (pcy_f32_llama_decode): opt-in beside `decode`, other bits
+    def _stream_desc(self):
+        if getattr(self, "_sdesc", None) is None:
+            cfg = self.cfg
+            arr = (L.LlamaLayerF32 * cfg.n_layers)(*[L.LlamaLayerF32(*[lw[n].data_ptr() for n in ("wqkv", "wo", "wg", "wu", "wd", "ln1", "ln2")])
+                                                     for lw in self.layers])
+            self._sdesc_layers = arr       # (the descriptor points into it: kept alive with the engine)
+            self._sdesc = L.LlamaDescF32(cfg.vocab, cfg.d, cfg.n_layers, cfg.n_heads, cfg.n_kv_heads, cfg.head_dim, cfg.ffn, cfg.max_pos, cfg.rms_eps,
+                                         self.embed.data_ptr(), self.final_norm.data_ptr(), self.lm_head.data_ptr(), self.cos.data_ptr(),
+                                         self.sin.data_ptr(), arr)
+        return self._sdesc
+
+    def new_gen_state(self, B, max_steps, keep_logits=False):
+        return GenStateF32(B, self.cfg.vocab, max_steps, self.device, keep_logits)
+
+    @staticmethod
+    def _stream_cache(cache):
+        _no_shared_prefix(cache)
+        c = L.KvCacheF32(cache.k.data_ptr(), cache.v.data_ptr(), cache.B, cache.Tmax)
+        return c
+
+    def decode_stream(self, cache: KVCacheF32, st: GenStateF32, B, graph=True):
+        """one step for rows [0, B): st.next_tok at position *st.pos (both read on the device) -> st.logits [B, V] fp32, K / V appended at slot
+        *st.pos; no pick, no advance, no host read.  graph: replay the captured chain (same bits as the eager launches)."""
+        fn = self.ops.lib.pcy_f32_llama_decode_graph if graph else self.ops.lib.pcy_f32_llama_decode
+        L.check(fn(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B)),
+                "pcy_f32_llama_decode_graph" if graph else "pcy_f32_llama_decode")
+        return st.logits[:B]
+
+    def greedy_pick(self, cache, st, B, advance_pos=True):
+        L.check(self.ops.lib.pcy_f32_greedy_pick(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B),
+                                                 int(bool(advance_pos))), "pcy_f32_greedy_pick")
+
+    def greedy_steps(self, cache: KVCacheF32, st: GenStateF32, B, n_steps, graph=True):
+        """n_steps x (step + greedy pick + advance) on the device without a host synchronisation (pcy_f32_llama_greedy)"""
+        L.check(self.ops.lib.pcy_f32_llama_greedy(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B),
+                                                  int(n_steps), int(bool(graph))), "pcy_f32_llama_greedy")
 
     def _rows(self, spec, B, T):
         """flat token rows b*T+t (int64, on the device) of a logit_rows argument: "last", "all", None or a tensor"""

@@ -16,7 +16,8 @@ for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwar
 once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step),
 "shared_attn" (caption plugin; False or True, default False: beam search with "decode_gemm" only -- the step's attention scores all beams of a
 prompt against one pass over the K / V they share; DESIGN.md 4.3d -- or "split": the split-key attention in every beam-search step, with or
-without "decode_gemm")."""
+without "decode_gemm"), "decode_f32" (caption plugin; "ops" or "stream", default "ops": `generate`'s option of the same name --
+"stream" runs the cached steps of an fp32 model on the device-resident fp32 step; a ValueError on a bf16 model)."""
 from collections import defaultdict
 from collections.abc import Mapping
 
@@ -161,6 +162,7 @@ class ProcyonCaptionEval:
         self.beam_size = model_config.get("beam_size", self.num_captions * self.beam_group_size)
         self.decode_gemm = model_config.get("decode_gemm", False)
         self.shared_attn = model_config.get("shared_attn", False)
+        self.decode_f32 = model_config.get("decode_f32", "ops")
 
     @torch.no_grad()
     def get_predictions(self, data_loader):
@@ -172,7 +174,8 @@ class ProcyonCaptionEval:
                                                     return_all_internals=False, method=self.method, beam_size=self.beam_size,
                                                     beam_group_size=self.beam_group_size, truncate_on_eos=True,
                                                     **({"decode_gemm": self.decode_gemm} if self.decode_gemm else {}),
-                                                    **({"shared_attn": self.shared_attn} if self.shared_attn else {}))
+                                                    **({"shared_attn": self.shared_attn} if self.shared_attn else {}),
+                                                    **({"decode_f32": self.decode_f32} if self.decode_f32 != "ops" else {}))
             for i, indices in enumerate(model_inputs["reference_indices"]["input"]["seq"]):
                 for j in range(self.num_captions):
                     aaseq_indices.append(indices[-1])

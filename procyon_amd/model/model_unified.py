@@ -980,25 +980,45 @@ class UnifiedProCyon:
             enc.max_new_tokens = keep_new
 
     # ---- fp32 generation (/root/reference/scripts/caption_bulk.py:70-73 never casts the model and calls generate(method="beam")): the
-    # reference's own loops over the sub-module waist, every operator on the fp32 family (procyon_amd/engine_f32.py) -- a compatibility
-    # path, one launch per operator and a host round trip per step, not a fast one
+    # reference's own loops over the sub-module waist, every operator on the fp32 family (procyon_amd/engine_f32.py) -- by default a
+    # compatibility path, one launch per operator and a host round trip per step, not a fast one; decode_f32="stream" puts the cached steps
+    # on the device-resident step of DESIGN.md 4.10 (greedy: the whole loop on the device)
     @torch.no_grad()
     def _generate_sampling_f32(self, input_embeds, attn_masks, max_len=64, num_text_per_instance=1, temperature=1.0, greedy=False,
-                               nucleus_prob=None):
+                               nucleus_prob=None, decode_f32="ops"):
         """`_generate_sampling` (model_unified.py:861-921) in fp32: prefill, then max_len - 1 cached steps; greedy argmax, or multinomial
-        on softmax(logits / temperature) / the un-renormalised nucleus-masked softmax; chosen log-probabilities summed; no EOS stop."""
+        on softmax(logits / temperature) / the un-renormalised nucleus-masked softmax; chosen log-probabilities summed; no EOS stop.
+        decode_f32="stream": the cached steps on the device-resident step -- greedy entirely on the device
+        (`LlamaEngineF32.greedy_steps`), sampling with this loop's host-side selection around the replayed graph."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
         enc = self.text_encoder
         B = len(input_embeds)
+        stream = decode_f32 == "stream"
         with self._room_for(max_len):
             outs, lps, lgs = [], [], []
             for _ in range(num_text_per_instance):
                 toks, past, rec = None, None, []
                 total = torch.zeros(B, device=self.device)
+                if stream and greedy:
+                    eng = enc.engine_f32
+                    o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1))
+                    past = o.past_key_values
+                    st = eng.new_gen_state(B, max_len, keep_logits=True)
+                    st.logits.copy_(o.logits[:, -1, :])
+                    st.set(pos=past.t, step=0)
+                    eng.greedy_pick(past.cache, st, B, advance_pos=False)       # the prefill's logits: token 0, the position stays
+                    if max_len > 1:
+                        if past.t + max_len - 1 > past.cache.Tmax:
+                            raise ValueError(f"KV cache capacity {past.cache.Tmax} exhausted; raise max_new_tokens")
+                        eng.greedy_steps(past.cache, st, B, max_len - 1, graph=True)
+                    outs.append(st.tokens_out.long().cpu()); lps.append(st.logprob.cpu()); lgs.append(st.logits_all.transpose(0, 1).cpu())
+                    continue
                 for i in range(max_len):
                     o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1)) \
                         if i == 0 else enc(input_ids=toks[:, -1:], use_cache=True, past_key_values=past)
                     past = o.past_key_values
+                    if stream and past.state is None:
+                        past.state = enc.engine_f32.new_gen_state(B, max_len)
                     logits = o.logits[:, -1, :]
                     rec.append(logits.cpu())
                     lsm = logits.log_softmax(-1)
@@ -1009,7 +1029,7 @@ class UnifiedProCyon:
         return torch.stack(outs, 1), torch.stack(lps).T, torch.stack(lgs, 1)
 
     @torch.no_grad()
-    def _generate_beam_search_f32(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5, diversity_penalty=0.8):
+    def _generate_beam_search_f32(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5, diversity_penalty=0.8, decode_f32="ops"):
         """`_generate_beam_search` (model_unified.py:702-842) in fp32: the prompt repeated beam_size times before the prefill; step 0 extends
         beam 0 of every group only, later steps the group's g x V candidates; groups after the first lose penalty x (count of the tokens
         the earlier groups of the same input chose this step) IN the running score; outputs, scores, the logits record and the K / V rows
@@ -1032,6 +1052,8 @@ class UnifiedProCyon:
                 o = enc(input_embeds=emb, attn_masks=mask, use_cache=True, logit_positions=torch.full((BB,), T - 1)) if i == 0 else \
                     enc(input_ids=out[:, i - 1:i], use_cache=True, past_key_values=past)
                 past = o.past_key_values
+                if decode_f32 == "stream" and past.state is None:      # every cached step: the replayed graph of the stream step
+                    past.state = enc.engine_f32.new_gen_state(BB, max_len)
                 logits = o.logits[:, -1, :]
                 step_rec = logits.cpu().unsqueeze(1)
                 rec = step_rec if rec is None else torch.cat([rec, step_rec], 1)
@@ -1061,7 +1083,8 @@ class UnifiedProCyon:
     def generate(self, inputs, max_len=64, aaseq_type='protein', method="sampling", temperature=1.0, greedy=False,
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
-                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False, lookahead_step="extend"):
+                 lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False, lookahead_step="extend",
+                 decode_f32="ops"):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1093,7 +1116,16 @@ class UnifiedProCyon:
         cached decode steps stream the e4m3 copies of the projection weights (`LlamaEngine.decode_w8`, DESIGN.md 4.3e: weight-only fp8, half
         the weight bytes per step; the prefill stays what the engine's `set_fp8` says).  The tokens are those of a model whose projection
         weights are rounded to e4m3 per output channel, not those of decode_w8=False.  ValueError together with lookahead, decode_gemm or
-        method="beam", with more than 8 rows, or with anything but False / True; NotImplementedError on the fp32 family."""
+        method="beam", with more than 8 rows, or with anything but False / True; NotImplementedError on the fp32 family.
+        decode_f32="ops" | "stream" (fp32 models only; "ops", the default, is today's code): what the cached steps of an fp32 generation run
+        on.  "stream": the device-resident step on the streaming fp32 GEMV (`LlamaEngineF32.decode_stream`) -- greedy runs
+        entirely on the device, sampling / nucleus and beam keep their host-side selection around one replayed graph per step.  Same return
+        values; the sums run in another order than "ops", so tokens may part where two logits tie within fp32 noise.  ValueError for any
+        other value and for "stream" on a bf16 model: never a fallback."""
+        if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream")):
+            raise ValueError(f"generate: decode_f32={decode_f32!r}: 'ops' or 'stream'")
+        if decode_f32 == "stream" and not self._f32:
+            raise ValueError("generate(decode_f32='stream') is the decode step of the fp32 family: this model runs the bf16 engine")
         assert method in ["sampling", "temperature", "greedy", "beam", "nucleus"]
         self._require_bf16_or_fp32("generate")      # fp32 (a caller that never called .bfloat16()): the operator-by-operator fp32 loops below
         lookahead = int(lookahead)
@@ -1166,12 +1198,12 @@ class UnifiedProCyon:
             tokens, log_probs, logits = (self._generate_beam_search_f32 if self._f32 else self._generate_beam_search)(
                 input_embeds, attn_masks, max_len=max_len, beam_size=beam_size, diversity_penalty=diversity_penalty,
                 beam_group_size=beam_group_size, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
-                **({"shared_attn": shared_attn} if shared_attn else {}))
+                **({"shared_attn": shared_attn} if shared_attn else {}), **({"decode_f32": decode_f32} if decode_f32 != "ops" else {}))
         else:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,
                 temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
-                **({"decode_w8": True} if decode_w8 else {}))
+                **({"decode_w8": True} if decode_w8 else {}), **({"decode_f32": decode_f32} if decode_f32 != "ops" else {}))
         flattened = torch.flatten(tokens, start_dim=0, end_dim=1)
         text = self.tokenizer.batch_decode(flattened)
         if truncate_on_eos:

@@ -9,10 +9,11 @@ from ..engine import GenState, KVCache, LlamaConfig, LlamaEngine
 
 
 class _PastF32:
-    """fp32 KV cache handle of an fp32 generation: `.cache` (engine_f32.KVCacheF32), `.t` keys held"""
+    """fp32 KV cache handle of an fp32 generation: `.cache` (engine_f32.KVCacheF32), `.t` keys held; `.state` (engine_f32.GenStateF32 or
+    None): the device state of the stream step -- when set, the cached one-token steps run `LlamaEngineF32.decode_stream` on it"""
 
-    def __init__(self, cache, t):
-        self.cache, self.t = cache, t
+    def __init__(self, cache, t, state=None):
+        self.cache, self.t, self.state = cache, t, state
 
 
 class _Past:
@@ -177,6 +178,13 @@ class LlamaPostTokenization:
                 return self._forward_extend_f32(input_embeds, input_ids, attn_masks, full_labels, past_key_values, logit_positions, want_hidden,
                                                 compute_loss)
             cache, t = past_key_values.cache, past_key_values.t
+            st = past_key_values.state
+            if st is not None:      # the stream step (generate(decode_f32="stream")): token ids and position written on the device, replayed graph
+                if t + 1 > cache.Tmax:
+                    raise ValueError(f"KV cache capacity {cache.Tmax} exhausted; raise max_new_tokens")
+                st.set(pos=t, next_tok=input_ids.view(-1).to(self.engine_f32.device))
+                logits = self.engine_f32.decode_stream(cache, st, input_ids.shape[0], graph=True).clone()
+                return CausalLMOutput(logits.view(input_ids.shape[0], 1, -1), _PastF32(cache, t + 1, st))
             logits = self.engine_f32.decode(cache, input_ids.view(-1), t)
             return CausalLMOutput(logits.view(input_ids.shape[0], 1, -1), _PastF32(cache, t + 1))
         if input_embeds is not None and input_embeds.dtype == torch.float32:

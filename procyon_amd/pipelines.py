@@ -66,17 +66,22 @@ def _merge_dedup(inputs: List[dict]) -> dict:
 def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_dataset: str = "uniprot", prompt_relation: str = "all",
                  max_len: int = 200, beam_size: int = 10, diversity_penalty: float = 0.8, save_path: Optional[str] = None,
                  batch_size: int = 8, save_frequency: int = 5, device=None, decode_gemm=False,
-                 shared_attn=False) -> pd.DataFrame:
+                 shared_attn=False, decode_f32="ops") -> pd.DataFrame:
     """-> DataFrame(uniprot_id, response0 .. response{beam_size // 2 - 1}); `save_path` receives the running table as a pickle
     whenever the one-by-one loop would have written it (after protein i for every i % save_frequency == 0, i > 0) and the final
     table as CSV (caption_bulk.py:99-148).  decode_gemm (False | True | "auto"): `generate`'s option of the same name -- batch_size x beam_size
     rows per decode step (8 x 10 = 80) on the step that reads the weights once.  shared_attn (False | True): `generate`'s
     option of the same name, with decode_gemm only -- the beams of a protein are scored against one pass over their shared K / V (4.3d);
-    "split": the split-key attention in every step, with or without decode_gemm (4.3f)."""
+    "split": the split-key attention in every step, with or without decode_gemm (4.3f).  decode_f32 ("ops" | "stream"): `generate`'s option of
+    the same name; "stream" keeps the model in fp32 AS LOADED (no cast here) and runs every cached step of the beam search on the
+    device-resident fp32 step (4.10) -- a model that was cast to bf16 before is `generate`'s ValueError."""
     from procyon.data.inference_utils import create_caption_input_simple, uniprot_id_to_index
     assert "drug" not in prompt_dataset, "DrugBank not supported in this script"
+    if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream")):
+        raise ValueError(f"caption_bulk: decode_f32={decode_f32!r}: 'ops' or 'stream'")
     model.eval()
-    model.bfloat16()
+    if decode_f32 != "stream":
+        model.bfloat16()
     results = {"uniprot_id": []}
     results.update({f"response{i}": [] for i in range(beam_size // 2)})
     split_str = "<|end_of_text|>" if "llama-3" in getattr(model_args, "text_encoder_fname", "llama-3") else "</s>"
@@ -90,7 +95,8 @@ def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_da
         _, _, _, out_text = model.generate(inputs=_merge_dedup(inputs), aaseq_type="protein", max_len=max_len, method="beam",
                                            return_all_internals=False, beam_size=beam_size, beam_group_size=2,
                                            diversity_penalty=diversity_penalty, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
-                                           **({"shared_attn": shared_attn} if shared_attn else {}))
+                                           **({"shared_attn": shared_attn} if shared_attn else {}),
+                                           **({"decode_f32": decode_f32} if decode_f32 != "ops" else {}))
         for b, u in enumerate(ids):
             results["uniprot_id"].append(u)
             for j, t in enumerate(out_text[b]):
