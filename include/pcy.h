@@ -749,6 +749,66 @@ int pcy_f32_llama_greedy(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_c
 /* steps enqueued by the three entries above outside a graph replay (an eager step, or the capture of a graph) since the library was loaded */
 unsigned long long pcy_debug_f32_stream_count(void);
 
+/* ---- fp32 generation: beam search and sampling selection on the device ----
+ * Opt-in (generate(decode_f32="device")), beside the host-side selection that the "ops" and "stream" modes keep.  Every entry checks its
+ * arguments first and launches nothing when it refuses (code 1).  No floating-point atomics anywhere: equal calls give equal bits, and a
+ * replayed chain gives the bits of the separate calls.
+ *
+ * One step of the diverse beam search on fp32 logits [B * beam, vocab]: pcy_beam_step's contract and state (pcy_beam_state above; step 0
+ * extends beam 0 of a group only, top-g by rounds of arg-max with ties to the lowest flat index row * vocab + token, the penalty inside
+ * the running score, double-buffered histories, src / anc parents, next_tok, EOS flags and the eos_id == 0 rule, the last workgroup
+ * advances *step / *pos and raises *done, a launch with *done set changes nothing but src, which it sets to the identity so that the
+ * reorder behind it moves nothing) with ONE difference: the candidate score is
+ *   s(r, v) = ((x[r][v] - max_r) - lse_r) + cur[r] - penalty * #{earlier picks of this step == v},  lse_r = logf(sum expf(x - max_r)),
+ * in fp32 throughout -- nothing is rounded to bf16 (the reference takes log_softmax in the model dtype, fp32 here).  The row statistics
+ * come from 16 slices per row, combined in slice order; an all -inf slice or row gives (max = -inf, sum = 0), never a NaN.
+ * beam <= 32, vocab <= 163840. */
+int pcy_f32_beam_step(pcy_ctx*, const float* logits, int vocab, int B, int beam, int group_size, float diversity_penalty,
+                      const pcy_beam_state* state);
+/* K / V rows of a beam search on the token-major fp32 caches: row b of rows [0, B) takes slots [t0, t) of row src_rows[b] (device int32
+ * [B]; any row of the cache), every layer, K and V, in place.  Correct for any map (cycles, one source for many rows): two launches, a
+ * gather into the context's workspace and the write back; rows that keep their place are skipped; slots outside [t0, t), rows >= B and the
+ * rows of a source outside the cache are not touched.  The scratch is sized for the suffix capacity Tmax - t0, not for t.  t <= t0: nothing. */
+int pcy_f32_kv_reorder_range(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache* kv, const int32_t* src_rows, int B, int t0, int t);
+/* out of place: row r of dst_kv, r in [0, B), takes slots [0, t) of row src_rows[r] of src_kv (another cache of the same model; its own
+ * row count and capacity): replicates a B-row prefill into B * beam rows with the map r / beam.  Nothing else of dst_kv is written. */
+int pcy_f32_kv_copy_rows(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache* dst_kv, const pcy_f32_kv_cache* src_kv, const int32_t* src_rows,
+                         int B, int t);
+/* n_steps iterations (steps >= 1) of an fp32 beam search for the B * beam rows: pcy_f32_llama_decode -> logits_rec[*step][row][vocab] = the
+ * step's logits (NULL: no record) -> pcy_f32_beam_step -> the reorder of slots [kv_t0, *pos), *pos read on the device behind the beam step.
+ * Each iteration is ONE replayed linear launch chain (no parallel branches), captured on first use per (descriptor and its weights, cache,
+ * both states, every argument).  gen_state->pos / next_tok must be the beam state's arrays.  The kernels and the bits of
+ * pcy_f32_llama_decode_graph + a copy + pcy_f32_beam_step + pcy_f32_kv_reorder_range(t0 = kv_t0, t = *pos).  The caller keeps
+ * *step + n_steps <= max_len and *pos + n_steps <= Tmax.  Refuses what those entries refuse, and kv_t0 outside [0, Tmax]. */
+int pcy_f32_llama_beam_steps(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache* kv, const pcy_gen_state*, int B, int beam, int group_size,
+                             float diversity_penalty, const pcy_beam_state* state, float* logits_rec, int n_steps, int kv_t0);
+/* Sampling / nucleus selection (`_generate_sampling` without greedy, model_unified.py:896-906) on state->logits [B, vocab] fp32:
+ *   probs = softmax(logits / temperature) in fp32 (the correctly rounded quotient, then exp(. - max) / sum);
+ *   nucleus_prob in (0, 1): probs = softmax(logits) (no temperature) times the mask of the tokens whose ascending cumulative probability
+ *   has reached 1 - nucleus_prob -- equal probabilities in token order (a stable sort: the lower index counts as the smaller), the kept
+ *   mass not renormalised, everything kept when nothing reaches the threshold; nucleus_prob <= 0: no mask;
+ *   token = first index in vocabulary order whose cumulative kept probability exceeds uniforms[*step * B + b] * total (the CALLER's
+ *   variates in [0, 1), device fp32 [max_steps * B]; the last kept token when a variate >= 1 pushes the draw past the end);
+ *   logprob[b] += fp32 log_softmax(unscaled logits)[token]; next_tok / tokens_out[b][*step]; row *step of the optional fp32 record
+ *   logits_all first; then ++*step and, when advance_pos != 0, ++*pos.  probs_out: optional [B, vocab] fp32, the masked vector.
+ * The nucleus threshold is found by a radix select over the bit patterns of the probabilities (12 + 12 + 8 bits; non-negative floats order
+ * like their patterns); bucket masses, the kept total and the CDF are sums of trunc(p * 2^44) in 64-bit integers, so the token is a
+ * deterministic function of (logits, variate): a mass differs from the exact sum of the fp32 probabilities by less than vocab * 2^-44
+ * (a threshold that the row's mass misses by no more than that counts as reached by the largest token).  The fp32 probabilities of a row
+ * sum to 1 only within fp32 rounding, about 2^-22: a nucleus_prob below that is accepted but not resolved -- whether 1 - nucleus_prob is
+ * reached (the top token alone is kept) or not (everything is kept) then depends on that rounding.
+ * -inf logits mean "never chosen" (probability exactly 0); a row must hold a finite logit; NaN is outside the contract.  *step outside
+ * [0, max_steps) selects nothing.  temperature > 0, nucleus_prob < 1, vocab <= 163840. */
+int pcy_f32_sample_pick(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B, int advance_pos, float temperature,
+                        float nucleus_prob, const float* uniforms, float* probs_out);
+/* n_steps x (pcy_f32_llama_decode + pcy_f32_sample_pick with advance) with no host synchronisation; use_graph != 0 replays one captured
+ * chain per step.  Eager and replayed runs give equal bits.  The caller keeps *step + n_steps <= max_steps and *pos + n_steps <= Tmax. */
+int pcy_f32_llama_sample(pcy_ctx*, const pcy_f32_llama_desc*, const pcy_f32_kv_cache*, const pcy_gen_state*, int B, int n_steps, float temperature,
+                         float nucleus_prob, const float* uniforms, int use_graph);
+/* steps enqueued by the entries above since the library was loaded (eager, captured or replayed) -- 0: beam steps (pcy_f32_beam_step,
+ * pcy_f32_llama_beam_steps), 1: sampling steps (pcy_f32_sample_pick, pcy_f32_llama_sample); anything else reads 0 */
+unsigned long long pcy_debug_f32_select_count(int which);
+
 #ifdef __cplusplus
 }
 #endif

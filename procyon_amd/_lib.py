@@ -157,6 +157,15 @@ SIGNATURES = {
     "pcy_f32_greedy_pick": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci]),
     "pcy_f32_llama_greedy": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci, ci]),
     "pcy_debug_f32_stream_count": (C.c_ulonglong, []),
+    # fp32 selection on the device (include/pcy.h)
+    "pcy_f32_beam_step": (ci, [vp, vp, ci, ci, ci, ci, C.c_float, C.POINTER(BeamState)]),
+    "pcy_f32_kv_reorder_range": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), vp, ci, ci, ci]),
+    "pcy_f32_kv_copy_rows": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(KvCacheF32), vp, ci, ci]),
+    "pcy_f32_llama_beam_steps": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci, ci, C.c_float,
+                                      C.POINTER(BeamState), vp, ci, ci]),
+    "pcy_f32_sample_pick": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp, vp]),
+    "pcy_f32_llama_sample": (ci, [vp, C.POINTER(LlamaDescF32), C.POINTER(KvCacheF32), C.POINTER(GenState), ci, ci, C.c_float, C.c_float, vp, ci]),
+    "pcy_debug_f32_select_count": (C.c_ulonglong, [ci]),
     "pcy_quant_rows_fp8": (ci, [vp, vp, ci, ci, ci, vp, vp]),
     "pcy_gemm_fp8": (ci, [vp, vp, vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, ci]),
     "pcy_mlp_forward": (ci, [vp, C.POINTER(MlpDesc), vp, ci, vp]),

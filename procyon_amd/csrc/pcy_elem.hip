@@ -1016,17 +1016,24 @@ __device__ __forceinline__ bool beam_better(float s, int c, float bs, int bc) { 
 // max and sum of exp(x - max) of one of BEAM_NCH slices of every logits row: grid (BB, BEAM_NCH).  (A single workgroup doing this
 // for its `beam` rows with one dependent 2-byte load per iteration took 0.8 of the 1.27 ms of the first version of the step.)
 constexpr int BEAM_NCH = 16;
-__global__ __launch_bounds__(256) void beam_rowstats_kernel(const bf16_t* __restrict__ logits, int V, float2* __restrict__ part) {
+// The logits type of the step: bf16 (the model dtype of the bf16 engine: the log-softmax value is rounded to it) or fp32 (the fp32 family,
+// pcy_f32_beam_step: the reference's log_softmax runs in fp32 there, nothing is rounded to bf16).  Everything else is the same code.
+__device__ __forceinline__ float beam_ld(const bf16_t* x, int v) { return bf2f(x[v]); }
+__device__ __forceinline__ float beam_ld(const float* x, int v) { return x[v]; }
+__device__ __forceinline__ float beam_lsm(const bf16_t*, float v) { return rbf(v); }
+__device__ __forceinline__ float beam_lsm(const float*, float v) { return v; }
+template <typename T>
+__global__ __launch_bounds__(256) void beam_rowstats_kernel(const T* __restrict__ logits, int V, float2* __restrict__ part) {
   __shared__ float red[4];
   const int row = blockIdx.x, c = blockIdx.y;
   const int chunk = (V + BEAM_NCH - 1) / BEAM_NCH;
   const int lo = c * chunk, hi = (lo + chunk) < V ? (lo + chunk) : V;
-  const bf16_t* x = logits + (size_t)row * V;
+  const T* x = logits + (size_t)row * V;
   float m = -INFINITY;
   for (int v0 = lo + threadIdx.x; v0 < hi; v0 += 256 * 8) {
     float xs[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) { const int v = v0 + u * 256; xs[u] = v < hi ? bf2f(x[v]) : -INFINITY; }
+    for (int u = 0; u < 8; ++u) { const int v = v0 + u * 256; xs[u] = v < hi ? beam_ld(x, v) : -INFINITY; }
 #pragma unroll
     for (int u = 0; u < 8; ++u) m = fmaxf(m, xs[u]);
   }
@@ -1036,7 +1043,7 @@ __global__ __launch_bounds__(256) void beam_rowstats_kernel(const bf16_t* __rest
     for (int v0 = lo + threadIdx.x; v0 < hi; v0 += 256 * 8) {
       float xs[8];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) { const int v = v0 + u * 256; xs[u] = v < hi ? bf2f(x[v]) : -INFINITY; }
+      for (int u = 0; u < 8; ++u) { const int v = v0 + u * 256; xs[u] = v < hi ? beam_ld(x, v) : -INFINITY; }
 #pragma unroll
       for (int u = 0; u < 8; ++u) se += expf(xs[u] - m);
     }
@@ -1047,11 +1054,12 @@ __global__ __launch_bounds__(256) void beam_rowstats_kernel(const bf16_t* __rest
 }
 
 // Per (row, slice): the `n` best candidates of the slice in the order (log-probability descending, token ascending), as
-// (bf16-rounded log-softmax value, token).  A group's final picks lie among the `beam` best unpenalised candidates of each of
+// (log-softmax value -- rounded to bf16 for bf16 logits --, token).  A group's final picks lie among the `beam` best unpenalised candidates of each of
 // its rows (the Hamming penalty lowers at most beam - g tokens), so the sequential per-group logic only ever looks at these
 // BB x BEAM_NCH x n entries instead of scanning V logits per round on ONE CU (0.84 ms per step, a CU pulls ~30 GB/s).
 struct BeamCand { float s; int v; };
-__global__ __launch_bounds__(256) void beam_topn_kernel(const bf16_t* __restrict__ logits, int V, const float2* __restrict__ part, int n,
+template <typename T>
+__global__ __launch_bounds__(256) void beam_topn_kernel(const T* __restrict__ logits, int V, const float2* __restrict__ part, int n,
                                                         BeamCand* __restrict__ cand) {
   __shared__ float red_s[4];
   __shared__ int red_v[4], red_t[4];
@@ -1066,11 +1074,11 @@ __global__ __launch_bounds__(256) void beam_topn_kernel(const bf16_t* __restrict
   const float l = logf(se);
   const int chunk = (V + BEAM_NCH - 1) / BEAM_NCH;
   const int lo = c * chunk, hi = (lo + chunk) < V ? (lo + chunk) : V;
-  const bf16_t* x = logits + (size_t)row * V;
+  const T* x = logits + (size_t)row * V;
   constexpr int EPT = 40;                      // elements per thread: slices of up to 10240 logits (V <= 163840)
   float xs[EPT];
 #pragma unroll
-  for (int u = 0; u < EPT; ++u) { const int v = lo + tid + u * 256; xs[u] = v < hi ? rbf((bf2f(x[v]) - m) - l) : -INFINITY; }
+  for (int u = 0; u < EPT; ++u) { const int v = lo + tid + u * 256; xs[u] = v < hi ? beam_lsm(x, (beam_ld(x, v) - m) - l) : -INFINITY; }
   unsigned long long taken = 0;
   for (int j = 0; j < n; ++j) {
     float bs = -INFINITY;
@@ -1102,7 +1110,7 @@ __global__ __launch_bounds__(256) void beam_topn_kernel(const bf16_t* __restrict
   }
 }
 
-__global__ __launch_bounds__(1024) void beam_step_kernel(const bf16_t* __restrict__ logits, int V, int beam, int g, float penalty,
+__global__ __launch_bounds__(1024) void beam_step_kernel(int V, int beam, int g, float penalty,
                                                          PcyBeamState st, int B, const float2* __restrict__ st_part,
                                                          const BeamCand* __restrict__ cand, int ncand) {
   extern __shared__ __attribute__((aligned(16))) char bsm[];
@@ -1493,12 +1501,20 @@ void pcy_launch_retrieval_rank_f32(hipStream_t s, const float* sims, int Q, int 
 size_t pcy_beam_ws_bytes(int B, int beam) {
   return (size_t)B * beam * BEAM_NCH * sizeof(float2) + 256 + (size_t)B * beam * BEAM_NCH * beam * sizeof(BeamCand);
 }
-void pcy_launch_beam_step(hipStream_t s, const bf16_t* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st,
-                          void* ws) {
+template <typename T>
+static void launch_beam_step(hipStream_t s, const T* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st, void* ws) {
   const size_t smem = (size_t)((V + 31) / 32) * 4;
   float2* part = reinterpret_cast<float2*>(ws);
   BeamCand* cand = reinterpret_cast<BeamCand*>(reinterpret_cast<char*>(ws) + ((size_t)B * beam * BEAM_NCH * sizeof(float2) + 255) / 256 * 256);
-  hipLaunchKernelGGL(beam_rowstats_kernel, dim3(B * beam, BEAM_NCH), dim3(256), 0, s, logits, V, part);
-  hipLaunchKernelGGL(beam_topn_kernel, dim3(B * beam, BEAM_NCH), dim3(256), 0, s, logits, V, part, beam, cand);
-  hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(1024), smem, s, logits, V, beam, g, penalty, st, B, part, cand, beam);
+  hipLaunchKernelGGL(beam_rowstats_kernel<T>, dim3(B * beam, BEAM_NCH), dim3(256), 0, s, logits, V, part);
+  hipLaunchKernelGGL(beam_topn_kernel<T>, dim3(B * beam, BEAM_NCH), dim3(256), 0, s, logits, V, part, beam, cand);
+  hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(1024), smem, s, V, beam, g, penalty, st, B, part, cand, beam);   // (reads the candidates only)
+}
+void pcy_launch_beam_step(hipStream_t s, const bf16_t* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st,
+                          void* ws) {
+  launch_beam_step(s, logits, V, B, beam, g, penalty, st, ws);
+}
+void pcy_launch_f32_beam_step(hipStream_t s, const float* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st,
+                              void* ws) {
+  launch_beam_step(s, logits, V, B, beam, g, penalty, st, ws);
 }

@@ -51,6 +51,8 @@ unsigned long long g_pcy_decode_w8 = 0;
 unsigned long long g_pcy_decode_window = 0;
 // steps enqueued by the fp32 stream step (pcy_f32_llama_decode / _decode_graph / _greedy) outside a graph replay (pcy_debug_f32_stream_count)
 unsigned long long g_pcy_f32_stream = 0;
+// steps enqueued by the fp32 selection entries (pcy_debug_f32_select_count) -- 0: beam steps, 1: sampling steps; eager, captured or replayed
+unsigned long long g_pcy_f32_select[2] = {0, 0};
 
 }  // namespace
 
@@ -71,6 +73,7 @@ struct DecodeGraphKey {
   int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps),
                                       // 3: decode on e4m3 weights + greedy pick (pcy_llama_greedy_w8)
                                       // 4 / 5: the fp32 stream step alone / with its greedy pick (model = the pcy_f32_llama_desc)
+                                      // 6: an fp32 beam-search step (pcy_f32_llama_beam_steps), 7: the fp32 step with its sampling pick
   int B;
   PcySwitches sw;
   const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
@@ -88,6 +91,8 @@ struct DecodeGraphKey {
   const void* w8;                                  // kind 3: the host array of e4m3 layers and a fingerprint of the device pointers it holds
   uint64_t w8_fp;
   int attn_split;                                  // 1: every layer's attention is the split-key one (pcy_attn_split.hip); never shares a graph with 0
+  const void* uniforms;                            // kind 7: the variates and the two parameters of the sampling pick
+  uint32_t temperature_bits, nucleus_bits;
 };
 
 struct pcy_ctx {
@@ -2208,6 +2213,144 @@ int pcy_f32_llama_greedy(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_
   });
 }
 unsigned long long pcy_debug_f32_stream_count(void) { return g_pcy_f32_stream; }
+
+// ---- fp32 selection on the device (pcy_f32_select.hip): beam search and sampling of an fp32 generation without a host
+// round trip.  Workspace of the context: [the stream step's carve for the rows][behind it, from a 256-byte boundary: the K / V reorder
+// scratch of a beam search, or the partials and probability rows of a sampling step].  Everything is reserved before a capture.
+static int f32_beam_check(const char* what, const void* logits_or_state, int vocab, int B, int beam, int group_size, const pcy_beam_state* bs) {
+  if (!logits_or_state || !bs || !bs->out || !bs->cur || !bs->cur_new || !bs->next_tok || !bs->src || !bs->has_eos || !bs->blk_eos || !bs->ticket ||
+      !bs->pos || !bs->step || !bs->done || bs->max_len < 1)
+    return fail(1, "%s: logits or beam state incomplete", what);
+  if (B <= 0 || B > 65535 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
+    return fail(1, "%s: B=%d, beam=%d (1..32) must be a multiple of group_size=%d", what, B, beam, group_size);
+  if (vocab <= 0 || vocab > 163840) return fail(1, "%s: vocab %d unsupported (<= 163840)", what, vocab);
+  return 0;
+}
+int pcy_f32_beam_step(pcy_ctx* c, const float* logits, int vocab, int B, int beam, int group_size, float diversity_penalty, const pcy_beam_state* bs) {
+  PCY_STICKY(c);
+  if (int r = f32_beam_check("pcy_f32_beam_step", logits, vocab, B, beam, group_size, bs)) return r;
+  if (int r = ensure_beam_ws(c, B, beam)) return r;
+  pcy_launch_f32_beam_step(c->stream, logits, vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
+  ++g_pcy_f32_select[0];
+  return check_launch("pcy_f32_beam_step");
+}
+static int f32_kv_check(const char* what, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv) {
+  if (!m || !kv || !kv->k || !kv->v || m->n_layers < 1 || m->n_kv_heads < 1 || m->head_dim < 1 || kv->B < 1 || kv->Tmax < 1)
+    return fail(1, "%s: model or cache incomplete", what);
+  if ((m->n_kv_heads * m->head_dim) % 4 || (((uintptr_t)kv->k | (uintptr_t)kv->v) & 15))
+    return fail(1, "%s: cache rows must be multiples of 4 floats and 16-byte aligned", what);
+  return 0;
+}
+static size_t f32_select_ws_offset(const pcy_f32_llama_desc* m, int B) { return align_up(f32_stream_ws_bytes(m, B), 256); }
+int pcy_f32_kv_reorder_range(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const int32_t* src_rows, int B, int t0, int t) {
+  PCY_STICKY(c);
+  if (int r = f32_kv_check("pcy_f32_kv_reorder_range", m, kv)) return r;
+  if (!src_rows || B < 1 || B > kv->B || B > 65535) return fail(1, "pcy_f32_kv_reorder_range: B=%d outside [1, cache rows %d] or no row map", B, kv->B);
+  if (t0 < 0 || t > kv->Tmax) return fail(1, "pcy_f32_kv_reorder_range: slots [%d, %d) outside the cache's %d", t0, t, kv->Tmax);
+  if (t <= t0) return 0;
+  const int kw = m->n_kv_heads * m->head_dim;
+  const size_t off = f32_select_ws_offset(m, B);
+  if (int r = c->reserve(off + pcy_f32_kv_reorder_tmp_bytes(m->n_layers, B, kv->Tmax, t0, kw))) return r;
+  pcy_launch_f32_kv_reorder(c->stream, kv->k, kv->v, reinterpret_cast<float*>(c->ws + off), src_rows, m->n_layers, B, kv->B, kv->Tmax, kw, t0, t, nullptr);
+  return check_launch("pcy_f32_kv_reorder_range");
+}
+int pcy_f32_kv_copy_rows(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* dst, const pcy_f32_kv_cache* src, const int32_t* src_rows,
+                         int B, int t) {
+  PCY_STICKY(c);
+  if (int r = f32_kv_check("pcy_f32_kv_copy_rows", m, dst)) return r;
+  if (int r = f32_kv_check("pcy_f32_kv_copy_rows", m, src)) return r;
+  if (dst->k == src->k || dst->v == src->v || dst->k == src->v || dst->v == src->k) return fail(1, "pcy_f32_kv_copy_rows: out of place only (pcy_f32_kv_reorder_range moves rows inside a cache)");
+  if (!src_rows || B < 1 || B > dst->B || B > 65535) return fail(1, "pcy_f32_kv_copy_rows: B=%d outside [1, destination rows %d] or no row map", B, dst->B);
+  if (t < 0 || t > dst->Tmax || t > src->Tmax) return fail(1, "pcy_f32_kv_copy_rows: %d slots exceed a cache (%d, %d)", t, dst->Tmax, src->Tmax);
+  if (t == 0) return 0;
+  pcy_launch_f32_kv_copy_rows(c->stream, dst->k, dst->v, dst->B, dst->Tmax, src->k, src->v, src->B, src->Tmax, src_rows, m->n_layers, B,
+                              m->n_kv_heads * m->head_dim, t);
+  return check_launch("pcy_f32_kv_copy_rows");
+}
+// n_steps x (fp32 step -> record row (*step, b) -> beam step -> reorder of slots [kv_t0, *pos)): ONE replayed linear launch chain per step, the
+// kernels and bits of pcy_f32_llama_decode_graph + a copy + pcy_f32_beam_step + pcy_f32_kv_reorder_range
+int pcy_f32_llama_beam_steps(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
+                             float diversity_penalty, const pcy_beam_state* bs, float* logits_rec, int n_steps, int kv_t0) {
+  PCY_STICKY(c);
+  const char* what = "pcy_f32_llama_beam_steps";
+  if (!m) return fail(1, "%s: model missing", what);
+  if (int r = f32_beam_check(what, st, m->vocab, B, beam, group_size, bs)) return r;
+  const int BB = B * beam;
+  if (int r = f32_stream_check(c, m, kv, st, BB, false, what)) return r;
+  if (st->pos != bs->pos || st->next_tok != bs->next_tok) return fail(1, "%s: the decode state must read the beam state's position and tokens", what);
+  if (kv_t0 < 0 || kv_t0 > kv->Tmax) return fail(1, "%s: kv_t0 = %d outside [0, %d]", what, kv_t0, kv->Tmax);
+  if (n_steps <= 0) return 0;
+  const int kw = m->n_kv_heads * m->head_dim;
+  const size_t off = f32_select_ws_offset(m, BB);
+  if (int r = c->reserve(off + pcy_f32_kv_reorder_tmp_bytes(m->n_layers, BB, kv->Tmax, kv_t0, kw))) return r;
+  if (int r = ensure_beam_ws(c, B, beam)) return r;
+  DecodeGraphKey key;
+  f32_stream_key(key, c, m, kv, st, BB, 6);
+  memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
+  memcpy(&key.penalty_bits, &diversity_penalty, 4);
+  g_pcy_f32_select[0] += (unsigned long long)n_steps;
+  return replay_graph(c, key, n_steps, "f32-beam-step", [&] {
+    hipStream_t s = c->stream;
+    enqueue_decode_f32(c, m, kv, st, BB);
+    pcy_launch_f32_record(s, (const float*)st->logits, logits_rec, bs->step, BB, m->vocab, 0);
+    pcy_launch_f32_beam_step(s, (const float*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
+    if (kv_t0 < kv->Tmax)
+      pcy_launch_f32_kv_reorder(s, kv->k, kv->v, reinterpret_cast<float*>(c->ws + off), bs->src, m->n_layers, BB, kv->B, kv->Tmax, kw, kv_t0, 0, bs->pos);
+  });
+}
+static int f32_sample_check(const char* what, const pcy_f32_llama_desc* m, float temperature, float nucleus_prob, const float* uniforms) {
+  if (!(temperature > 0.f)) return fail(1, "%s: temperature must be > 0 (greedy: pcy_f32_greedy_pick)", what);
+  if (!(nucleus_prob < 1.f)) return fail(1, "%s: nucleus_prob must be < 1 (<= 0 switches the nucleus mask off)", what);
+  if (!uniforms) return fail(1, "%s: no uniform variates", what);
+  if (m->vocab < 1 || m->vocab > 163840) return fail(1, "%s: vocab %d unsupported (<= 163840)", what, m->vocab);
+  return 0;
+}
+// record row *step -> the selection -> ++*step (/ ++*pos); the nucleus branch of the reference does not apply the temperature (model_unified.py:899-901)
+static void enqueue_sample_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos, float temperature,
+                               float nucleus_prob, const float* uniforms, float* probs_out) {
+  hipStream_t s = c->stream;
+  pcy_launch_f32_record(s, (const float*)st->logits, (float*)st->logits_all, st->step, B, m->vocab, st->logits_all_ld);
+  pcy_launch_f32_sample_step(s, (const float*)st->logits, B, m->vocab, nucleus_prob > 0.f ? 1.0f : temperature, nucleus_prob, uniforms, probs_out,
+                             st->next_tok, st->tokens_out, st->max_steps, st->logprob, st->step, c->ws + f32_select_ws_offset(m, B));
+  pcy_launch_f32_advance(s, st->step, st->pos, advance_pos);
+}
+int pcy_f32_sample_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
+                        float temperature, float nucleus_prob, const float* uniforms, float* probs_out) {
+  PCY_STICKY(c);
+  if (!m || !st || !st->logits || !st->pos || !st->step || !st->next_tok || !st->tokens_out || !st->logprob || st->max_steps < 1)
+    return fail(1, "pcy_f32_sample_pick: generation state incomplete");
+  if (B < 1 || B > 65535 || (kv && B > kv->B)) return fail(1, "pcy_f32_sample_pick: B=%d", B);
+  if (int r = f32_sample_check("pcy_f32_sample_pick", m, temperature, nucleus_prob, uniforms)) return r;
+  if (int r = c->reserve(f32_select_ws_offset(m, B) + pcy_f32_sample_ws_bytes(B, m->vocab))) return r;
+  enqueue_sample_f32(c, m, st, B, advance_pos, temperature, nucleus_prob, uniforms, probs_out);
+  ++g_pcy_f32_select[1];
+  return check_launch("pcy_f32_sample_pick");
+}
+int pcy_f32_llama_sample(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps,
+                         float temperature, float nucleus_prob, const float* uniforms, int use_graph) {
+  PCY_STICKY(c);
+  if (int r = f32_stream_check(c, m, kv, st, B, true, "pcy_f32_llama_sample")) return r;
+  if (int r = f32_sample_check("pcy_f32_llama_sample", m, temperature, nucleus_prob, uniforms)) return r;
+  if (n_steps <= 0) return 0;
+  if (int r = c->reserve(f32_select_ws_offset(m, B) + pcy_f32_sample_ws_bytes(B, m->vocab))) return r;
+  g_pcy_f32_select[1] += (unsigned long long)n_steps;
+  if (!use_graph) {
+    for (int i = 0; i < n_steps; ++i) {
+      enqueue_decode_f32(c, m, kv, st, B);
+      enqueue_sample_f32(c, m, st, B, 1, temperature, nucleus_prob, uniforms, nullptr);
+    }
+    return check_launch("pcy_f32_llama_sample");
+  }
+  DecodeGraphKey key;
+  f32_stream_key(key, c, m, kv, st, B, 5);
+  key.kind = 7; key.uniforms = uniforms;
+  memcpy(&key.temperature_bits, &temperature, 4); memcpy(&key.nucleus_bits, &nucleus_prob, 4);
+  return replay_graph(c, key, n_steps, "decode-f32-sample-step", [&] {
+    enqueue_decode_f32(c, m, kv, st, B);
+    enqueue_sample_f32(c, m, st, B, 1, temperature, nucleus_prob, uniforms, nullptr);
+  });
+}
+unsigned long long pcy_debug_f32_select_count(int which) { return (which == 0 || which == 1) ? g_pcy_f32_select[which] : 0; }
 
 int pcy_gemv_w8(pcy_ctx* c, const void* W8, const float* scale, const void* x, int ldx, const void* resid, void* y, int ldy, const void* rms_w,
                 float rms_eps, int rms_cast, int N, int K, int B, int epi) {

@@ -434,15 +434,20 @@ void pcy_launch_f32_embed_dev(hipStream_t s, const float* table, const int32_t* 
 void pcy_launch_f32_rmsnorm(hipStream_t s, const float* x, const float* w, float* y, int rows, int d, float eps) {
   hipLaunchKernelGGL(rmsnorm_stream_f32_kernel, dim3(rows), dim3(E_NT), 0, s, x, w, y, d, eps);
 }
+void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld) {
+  if (!logits_all) return;
+  int nb = (V + E_NT - 1) / E_NT;
+  nb = nb < 64 ? nb : 64;
+  hipLaunchKernelGGL(record_f32_kernel, dim3(nb, B), dim3(E_NT), 0, s, logits, logits_all, step_dev, B, V, ld > 0 ? ld : V);
+}
+void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos) {
+  hipLaunchKernelGGL(advance_f32_kernel, dim3(1), dim3(1), 0, s, step_dev, pos_dev, advance_pos);
+}
 void pcy_launch_f32_pick(hipStream_t s, const float* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
                          int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld) {
-  if (logits_all) {
-    int nb = (V + E_NT - 1) / E_NT;
-    nb = nb < 64 ? nb : 64;
-    hipLaunchKernelGGL(record_f32_kernel, dim3(nb, B), dim3(E_NT), 0, s, logits, logits_all, step_dev, B, V, logits_all_ld > 0 ? logits_all_ld : V);
-  }
+  pcy_launch_f32_record(s, logits, logits_all, step_dev, B, V, logits_all_ld);
   hipLaunchKernelGGL(pick_f32_kernel, dim3(B), dim3(P_NT), 0, s, logits, V, next_tok, tokens_out, max_steps, logprob, step_dev);
-  hipLaunchKernelGGL(advance_f32_kernel, dim3(1), dim3(1), 0, s, step_dev, pos_dev, advance_pos);
+  pcy_launch_f32_advance(s, step_dev, pos_dev, advance_pos);
 }
 
 extern "C" {

@@ -74,6 +74,26 @@ void pcy_launch_f32_rmsnorm(hipStream_t s, const float* x, const float* w, float
 void pcy_launch_f32_pick(hipStream_t s, const float* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
                          int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld);
 
+// the two ends of that chain on their own (the sampling and beam steps of pcy_f32_select.hip put another selection between them):
+// row (*step, b) of the record <- logits (logits_all == nullptr: nothing; ld <= 0: rows of V); ++*step and, on request, ++*pos
+void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld);
+void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos);
+
+// fp32 selection on the device (pcy_f32_select.hip; the beam step itself is pcy_launch_f32_beam_step below)
+// K / V reorder of the token-major fp32 caches [L][Bcache][Tmax][kw]: row b of rows [0, B) takes slots [t0, t) of row src_rows[b], in place,
+// through `tmp` (2 * L * B * (Tmax - t0) * kw floats: gather, then write back; any map).  t_dev != nullptr: t = *t_dev, read on the device.
+size_t pcy_f32_kv_reorder_tmp_bytes(int L, int B, int Tmax, int t0, int kw);
+void pcy_launch_f32_kv_reorder(hipStream_t s, float* k, float* v, float* tmp, const int32_t* src_rows, int L, int B, int Bcache, int Tmax, int kw,
+                               int t0, int t, const int32_t* t_dev);
+// dst row r (a cache of Bdst rows, Tdst slots) <- slots [0, t) of src row src_rows[r] (a cache of Bsrc rows, Tsrc slots), every layer, K and V
+void pcy_launch_f32_kv_copy_rows(hipStream_t s, float* dk, float* dv, int Bdst, int Tdst, const float* sk, const float* sv, int Bsrc, int Tsrc,
+                                 const int32_t* src_rows, int L, int B, int kw, int t);
+// sampling / nucleus selection of one step on fp32 logits [B, V] (pcy.h, pcy_f32_sample_pick); ws: pcy_f32_sample_ws_bytes(B, V)
+size_t pcy_f32_sample_ws_bytes(int B, int V);
+void pcy_launch_f32_sample_step(hipStream_t s, const float* logits, int B, int V, float temperature, float nucleus_p, const float* uniforms,
+                                float* probs_out, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob, const int32_t* step_dev,
+                                void* ws);
+
 // Rotated K order of the batched GEMVs (round 6).  Every workgroup of these kernels walks ITS K range front to back in step with all the
 // others, so at any moment every wave of the chip reads the same 256-byte window of its rows -- and with a power-of-two row stride (K = 4096:
 // 8 KB) those windows fall on the same few HBM channels: tools/probes/stream_rows.hip measures the gate/up stream at 4.86 TB/s, and 6.26 TB/s
@@ -519,6 +539,9 @@ struct PcyBeamState {
 size_t pcy_beam_ws_bytes(int B, int beam);   // scratch of pcy_launch_beam_step (row-statistics partials)
 void pcy_launch_beam_step(hipStream_t s, const bf16_t* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st,
                           void* ws);
+// the same step on fp32 logits (pcy_f32_beam_step): the log-softmax value is not rounded to bf16; same scratch
+void pcy_launch_f32_beam_step(hipStream_t s, const float* logits, int V, int B, int beam, int g, float penalty, const PcyBeamState& st,
+                              void* ws);
 void pcy_launch_copy_rows(hipStream_t s, const bf16_t* src, int lds, bf16_t* dst, int ldd, const int32_t* rows,
                           int nrows, int d);
 void pcy_launch_l2norm_rows(hipStream_t s, const bf16_t* x, bf16_t* y, int rows, int d, float eps);

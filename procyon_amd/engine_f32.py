@@ -15,6 +15,9 @@ include/pcy.h; procyon_amd/csrc/pcy_f32.hip) together op for op like the referen
                   and HF's causal-LM loss (`score`, pcy_f32_lm_head_xent); opt-in,
                   the device-resident decode step on the streaming fp32 GEMV
                   (`decode_stream`, `greedy_steps`: pcy_f32_llama_decode)
+                  and beam search / sampling whose selection runs on the device too
+                  (`generate_beam`, `generate_sampling`: pcy_f32_beam_step,
+                  pcy_f32_sample_pick and their replayed chains)
 
 The cached decode attends every slot without a mask, as the reference does after the prefill, so it reads the K / V that the prefill
 computed from left-pad rows: pcy_f32_attention gives those rows the reference's value (include/pcy.h).  PyTorch holds the device
@@ -27,7 +30,7 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import Context, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, score_plan, uniform_keep
+from .engine import BeamState, Context, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, score_plan, uniform_keep
 
 F32 = torch.float32
 
@@ -331,13 +334,14 @@ class KVCacheF32:
 
 class GenStateF32:
     """device state of the fp32 stream step (a pcy_gen_state whose logits hold fp32): pos / step int32 scalars, next_tok [B], tokens_out
-    [B, max_steps], logprob [B], logits [B, V], optionally the record logits_all [max_steps, B, V]"""
+    [B, max_steps], logprob [B], logits [B, V], optionally the record logits_all [max_steps, B, V].  pos / next_tok: arrays to share
+    instead of new ones (a beam search: the step reads what the beam step writes, as engine.BeamState.gen_state does for bf16)"""
 
-    def __init__(self, B, vocab, max_steps, device, keep_logits=False):
+    def __init__(self, B, vocab, max_steps, device, keep_logits=False, pos=None, next_tok=None):
         i32 = dict(dtype=torch.int32, device=device)
         self.B, self.vocab, self.max_steps = B, vocab, max_steps
-        self.pos, self.step = torch.zeros(1, **i32), torch.zeros(1, **i32)
-        self.next_tok = torch.zeros(B, **i32)
+        self.pos, self.step = torch.zeros(1, **i32) if pos is None else pos, torch.zeros(1, **i32)
+        self.next_tok = torch.zeros(B, **i32) if next_tok is None else next_tok
         self.tokens_out = torch.zeros(B, max_steps, **i32)
         self.logprob = torch.zeros(B, dtype=F32, device=device)
         self.logits = torch.zeros(B, vocab, dtype=F32, device=device)
@@ -453,6 +457,125 @@ class LlamaEngineF32:
         """n_steps x (step + greedy pick + advance) on the device without a host synchronisation (pcy_f32_llama_greedy)"""
         L.check(self.ops.lib.pcy_f32_llama_greedy(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B),
                                                   int(n_steps), int(bool(graph))), "pcy_f32_llama_greedy")
+
+    # ---- selection on the device (DESIGN.md 4.10a): the beam step, the K / V rows that follow the parents, the sampling pick, their chains
+    def beam_step(self, logits, bs: BeamState, group_size, diversity_penalty):
+        """one step of the diverse-beam bookkeeping on fp32 logits [BB, V] (pcy_f32_beam_step; engine.BeamState holds the state)"""
+        _chk(logits)
+        L.check(self.ops.lib.pcy_f32_beam_step(self.ops.h, _p(logits), logits.shape[1], bs.B, bs.beam, int(group_size), float(diversity_penalty),
+                                               C.byref(bs.c)), "pcy_f32_beam_step")
+
+    def kv_reorder(self, cache: KVCacheF32, src_rows, t, t0=0):
+        """cache[:, b] = cache[:, src_rows[b]] over slots [t0, t), in place, any map (pcy_f32_kv_reorder_range)"""
+        src = src_rows.to(self.device, torch.int32).contiguous()
+        L.check(self.ops.lib.pcy_f32_kv_reorder_range(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), _p(src),
+                                                      src.numel(), int(t0), int(t)), "pcy_f32_kv_reorder_range")
+
+    def kv_copy_rows(self, dst: KVCacheF32, src: KVCacheF32, src_rows, t):
+        """dst[:, r, :t] = src[:, src_rows[r], :t] for the rows of the map (pcy_f32_kv_copy_rows): a B-row prefill into B * beam rows"""
+        rows = src_rows.to(self.device, torch.int32).contiguous()
+        L.check(self.ops.lib.pcy_f32_kv_copy_rows(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(dst)),
+                                                  C.byref(self._stream_cache(src)), _p(rows), rows.numel(), int(t)), "pcy_f32_kv_copy_rows")
+
+    def beam_steps(self, cache: KVCacheF32, st: GenStateF32, bs: BeamState, group_size, diversity_penalty, logits_rec, n_steps, kv_t0=0):
+        """n_steps x (step -> record -> beam step -> reorder of [kv_t0, *pos)), each ONE replayed launch chain (pcy_f32_llama_beam_steps);
+        st.pos / st.next_tok are the beam state's arrays"""
+        _chk(logits_rec)
+        L.check(self.ops.lib.pcy_f32_llama_beam_steps(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c),
+                                                      bs.B, bs.beam, int(group_size), float(diversity_penalty), C.byref(bs.c), _p(logits_rec),
+                                                      int(n_steps), int(kv_t0)), "pcy_f32_llama_beam_steps")
+
+    def sample_pick(self, cache, st: GenStateF32, B, advance_pos, uniforms, temperature=1.0, nucleus_prob=None, probs_out=None):
+        """sampling / nucleus selection on st.logits with the variates uniforms[step * B + b] (pcy_f32_sample_pick)"""
+        _chk(uniforms, probs_out)
+        L.check(self.ops.lib.pcy_f32_sample_pick(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B),
+                                                 int(bool(advance_pos)), float(temperature), -1.0 if nucleus_prob is None else float(nucleus_prob),
+                                                 _p(uniforms), _p(probs_out)), "pcy_f32_sample_pick")
+
+    def sample_steps(self, cache, st: GenStateF32, B, n_steps, uniforms, temperature=1.0, nucleus_prob=None, graph=True):
+        """n_steps x (step + sampling pick + advance) on the device without a host synchronisation (pcy_f32_llama_sample)"""
+        _chk(uniforms)
+        L.check(self.ops.lib.pcy_f32_llama_sample(self.ops.h, C.byref(self._stream_desc()), C.byref(self._stream_cache(cache)), C.byref(st.c), int(B),
+                                                  int(n_steps), float(temperature), -1.0 if nucleus_prob is None else float(nucleus_prob),
+                                                  _p(uniforms), int(bool(graph))), "pcy_f32_llama_sample")
+
+    def select_count(self, which):
+        """steps enqueued by the selection entries -- 0: beam, 1: sampling (pcy_debug_f32_select_count)"""
+        return int(self.ops.lib.pcy_debug_f32_select_count(int(which)))
+
+    def _generation_capacity(self, T, max_len, max_new):
+        """slots of a cache for a T-token prompt and max_new generated tokens, inside the rotary table; ValueError when max_len tokens need more"""
+        Tmax = min(T + max(int(max_new), 1), self.cfg.max_pos)
+        if T + max_len - 1 > Tmax:
+            raise ValueError(f"KV cache capacity {Tmax} exhausted by a {T}-token prompt and {max_len} generated tokens; raise max_new_tokens")
+        return Tmax
+
+    def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new):
+        """`_generate_beam_search` (model_unified.py:702-842) of an fp32 model with nothing but the 8-step look at `done` on the host: diverse
+        beam search of B prompts x beam_size beams, at most max_len tokens, on a cache with room for max_new generated ones.  Returns what
+        `LlamaEngine.generate_beam` returns -- (tokens [BB, max_len] int64 and scores [BB] on the host, logits [BB, steps, V] fp32 in pinned
+        host memory), BB = B * beam_size, row r = beam r % beam_size of prompt r // beam_size.
+        ONE fp32 prefill of the B prompts into a B-row cache, its rows copied to the rows of their beams (kv_copy_rows, map r // beam; the
+        reference replicates the prompts before the prefill, :751-752); step 0 on the repeated prefill logits; then `beam_steps` up to the
+        next multiple of 8 steps.  The beams of a prompt hold the same K / V rows below slot T, so the per-step reorder starts there.  The
+        logits record is kept per slot on the device and re-indexed once along the parent chain at the end.  ValueError before any decode
+        step when max_len tokens do not fit the cache."""
+        B, T, _ = embeds.shape
+        BB, V, dev = B * beam_size, self.cfg.vocab, self.device
+        if beam_size > 32 or beam_size < 1 or group_size < 1 or beam_size % group_size:
+            raise ValueError(f"generate_beam: beam_size={beam_size} (1..32) must be a multiple of group_size={group_size}")
+        Tmax = self._generation_capacity(T, max_len, max_new)
+        small = self.new_cache(B, T)
+        lg_b, _ = self.prefill(embeds, attn_mask, "last", cache=small)
+        cache = self.new_cache(BB, Tmax)
+        self.kv_copy_rows(cache, small, torch.arange(BB, dtype=torch.int32) // beam_size, T)
+        logits = lg_b.repeat_interleave(beam_size, dim=0).contiguous()
+        bs = BeamState(B, beam_size, max_len, eos_id, prompt_len=T, device=dev)
+        st = GenStateF32(BB, V, 1, dev, pos=bs.pos, next_tok=bs.next_tok)
+        rec = torch.empty(max_len, BB, V, dtype=F32, device=dev)
+        rec[0].copy_(logits)
+        self.beam_step(logits, bs, group_size, diversity_penalty)      # (no reorder: every beam of a prompt still holds its prompt rows only)
+        i = 1
+        while i < max_len and not ((i & 7) == 0 and int(bs.done)):
+            n = min(8 - (i & 7), max_len - i)
+            self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=T)
+            i += n
+        out, steps = bs.tokens()                                       # synchronises
+        anc = bs.anc[:steps].long()
+        slot = torch.arange(BB, device=dev)
+        idx = torch.empty(steps, BB, dtype=torch.long, device=dev)
+        for s_ in range(steps - 1, -1, -1):                            # the record of step s is re-indexed by the parents of steps >= s
+            slot = anc[s_][slot]
+            idx[s_] = slot
+        out_logits_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
+        out_logits = torch.empty(out_logits_dev.shape, dtype=F32, pin_memory=True)
+        out_logits.copy_(out_logits_dev, non_blocking=True)
+        tokens, scores = torch.nn.functional.pad(out.cpu(), (0, max_len - steps)), bs.cur.cpu()      # (zeros behind an early EOS stop)
+        self.ops.ctx.sync()
+        return tokens, scores, out_logits
+
+    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, graph=True):
+        """`_generate_sampling(greedy=False)` (model_unified.py:861-921) of an fp32 model entirely on the device: the prefill, one pick on its
+        logits, then max_len - 1 x (step + pick) without a host synchronisation (`sample_steps`).  The uniform variates of all steps come
+        from ONE `torch.rand` on the device generator unless `uniforms` [max_len * B] injects them.  Returns what
+        `LlamaEngine.generate_sampling` returns: (tokens [B, max_len] int64, logprob [B], logits [B, max_len, V] fp32 | None, (state, cache,
+        variates)).  ValueError before any decode step when max_len tokens do not fit the cache."""
+        B, T, _ = embeds.shape
+        Tmax = self._generation_capacity(T, max_len, max_len)
+        u = torch.rand(max_len * B, device=self.device, dtype=F32) if uniforms is None else uniforms.to(self.device, F32).contiguous()
+        if u.numel() < max_len * B:
+            raise ValueError(f"generate_sampling: {u.numel()} uniform variates for {max_len} steps x {B} rows")
+        cache = self.new_cache(B, Tmax)
+        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits)
+        logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
+        st.logits.copy_(logits)
+        st.set(pos=T, step=0)
+        self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
+        if max_len > 1:
+            self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob, graph=graph)
+        self.ops.ctx.sync()
+        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        return st.tokens_out.long(), st.logprob, la, (st, cache, u)
 
     def _rows(self, spec, B, T):
         """flat token rows b*T+t (int64, on the device) of a logit_rows argument: "last", "all", None or a tensor"""

@@ -16,8 +16,9 @@ for boxes without Llama tokenizer files), "pretrained_weights_dir", "engine_kwar
 once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160 rows per step),
 "shared_attn" (caption plugin; False or True, default False: beam search with "decode_gemm" only -- the step's attention scores all beams of a
 prompt against one pass over the K / V they share; DESIGN.md 4.3d -- or "split": the split-key attention in every beam-search step, with or
-without "decode_gemm"), "decode_f32" (caption plugin; "ops" or "stream", default "ops": `generate`'s option of the same name --
-"stream" runs the cached steps of an fp32 model on the device-resident fp32 step; a ValueError on a bf16 model)."""
+without "decode_gemm"), "decode_f32" (caption plugin; "ops", "stream" or "device", default "ops": `generate`'s option of the same name --
+"stream" runs the cached steps of an fp32 model on the device-resident fp32 step; "device" the beam / sampling selection on
+the device as well; a ValueError on a bf16 model)."""
 from collections import defaultdict
 from collections.abc import Mapping
 

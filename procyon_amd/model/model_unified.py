@@ -989,16 +989,22 @@ class UnifiedProCyon:
         """`_generate_sampling` (model_unified.py:861-921) in fp32: prefill, then max_len - 1 cached steps; greedy argmax, or multinomial
         on softmax(logits / temperature) / the un-renormalised nucleus-masked softmax; chosen log-probabilities summed; no EOS stop.
         decode_f32="stream": the cached steps on the device-resident step -- greedy entirely on the device
-        (`LlamaEngineF32.greedy_steps`), sampling with this loop's host-side selection around the replayed graph."""
+        (`LlamaEngineF32.greedy_steps`), sampling with this loop's host-side selection around the replayed graph.
+        decode_f32="device": greedy as "stream"; sampling entirely on the device too (`LlamaEngineF32.generate_sampling`)."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
         enc = self.text_encoder
         B = len(input_embeds)
-        stream = decode_f32 == "stream"
+        stream = decode_f32 in ("stream", "device")
         with self._room_for(max_len):
             outs, lps, lgs = [], [], []
             for _ in range(num_text_per_instance):
                 toks, past, rec = None, None, []
                 total = torch.zeros(B, device=self.device)
+                if decode_f32 == "device" and not greedy:
+                    tok, lp, lg, _ = enc.engine_f32.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature,
+                                                                      nucleus_prob=nucleus_prob, keep_logits=True)
+                    outs.append(tok.cpu()); lps.append(lp.cpu()); lgs.append(lg.cpu())
+                    continue
                 if stream and greedy:
                     eng = enc.engine_f32
                     o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1))
@@ -1037,6 +1043,10 @@ class UnifiedProCyon:
         if beam_size % beam_group_size != 0:
             raise ValueError(f"beam_group_size must evenly divide beam_size, got: {beam_size} % {beam_group_size} != 0")
         enc = self.text_encoder
+        if decode_f32 == "device":      # the whole search on the device: one prefill per prompt, no host-side selection
+            flat = enc.engine_f32.generate_beam(input_embeds, attn_mask, max_len, beam_size, beam_group_size, diversity_penalty,
+                                                self.tokenizer.eos_token_id, max_new=max(enc.max_new_tokens, max_len))
+            return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
         dev = self.device
         B = input_embeds.shape[0]
         BB, V, T = B * beam_size, enc.cfg.vocab, input_embeds.shape[1]
@@ -1120,12 +1130,19 @@ class UnifiedProCyon:
         decode_f32="ops" | "stream" (fp32 models only; "ops", the default, is today's code): what the cached steps of an fp32 generation run
         on.  "stream": the device-resident step on the streaming fp32 GEMV (`LlamaEngineF32.decode_stream`) -- greedy runs
         entirely on the device, sampling / nucleus and beam keep their host-side selection around one replayed graph per step.  Same return
-        values; the sums run in another order than "ops", so tokens may part where two logits tie within fp32 noise.  ValueError for any
-        other value and for "stream" on a bf16 model: never a fallback."""
-        if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream")):
-            raise ValueError(f"generate: decode_f32={decode_f32!r}: 'ops' or 'stream'")
-        if decode_f32 == "stream" and not self._f32:
-            raise ValueError("generate(decode_f32='stream') is the decode step of the fp32 family: this model runs the bf16 engine")
+        values; the sums run in another order than "ops", so tokens may part where two logits tie within fp32 noise.
+        "device": the same step, and the selection on the device as well -- beam search is
+        `LlamaEngineF32.generate_beam` (one prefill per prompt, pcy_f32_beam_step, the K / V reorder of the generated suffix, one replayed
+        chain per step), sampling / temperature / nucleus `LlamaEngineF32.generate_sampling` (pcy_f32_sample_pick; the draw is the inverse
+        CDF on uniform variates from torch's device generator, not torch.multinomial's stream), greedy exactly the "stream" path.  Same
+        return values and shapes; beam_size <= 32.  ValueError for any other value, for "stream" / "device" on a bf16 model and for
+        beam_size > 32 with "device": never a fallback."""
+        if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream", "device")):
+            raise ValueError(f"generate: decode_f32={decode_f32!r}: 'ops', 'stream' or 'device'")
+        if decode_f32 != "ops" and not self._f32:
+            raise ValueError(f"generate(decode_f32={decode_f32!r}) is the decode step of the fp32 family: this model runs the bf16 engine")
+        if decode_f32 == "device" and method == "beam" and beam_size > 32:
+            raise ValueError("generate(decode_f32='device'): beam_size > 32 is not supported by the device-side beam step")
         assert method in ["sampling", "temperature", "greedy", "beam", "nucleus"]
         self._require_bf16_or_fp32("generate")      # fp32 (a caller that never called .bfloat16()): the operator-by-operator fp32 loops below
         lookahead = int(lookahead)

@@ -72,15 +72,16 @@ def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_da
     table as CSV (caption_bulk.py:99-148).  decode_gemm (False | True | "auto"): `generate`'s option of the same name -- batch_size x beam_size
     rows per decode step (8 x 10 = 80) on the step that reads the weights once.  shared_attn (False | True): `generate`'s
     option of the same name, with decode_gemm only -- the beams of a protein are scored against one pass over their shared K / V (4.3d);
-    "split": the split-key attention in every step, with or without decode_gemm (4.3f).  decode_f32 ("ops" | "stream"): `generate`'s option of
+    "split": the split-key attention in every step, with or without decode_gemm (4.3f).  decode_f32 ("ops" | "stream" | "device"): `generate`'s option of
     the same name; "stream" keeps the model in fp32 AS LOADED (no cast here) and runs every cached step of the beam search on the
-    device-resident fp32 step (4.10) -- a model that was cast to bf16 before is `generate`'s ValueError."""
+    device-resident fp32 step (4.10), "device" the whole search on the device as well (4.10a: one prefill per protein, the beam step and the
+    K / V reorder as kernels) -- a model that was cast to bf16 before is `generate`'s ValueError."""
     from procyon.data.inference_utils import create_caption_input_simple, uniprot_id_to_index
     assert "drug" not in prompt_dataset, "DrugBank not supported in this script"
-    if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream")):
-        raise ValueError(f"caption_bulk: decode_f32={decode_f32!r}: 'ops' or 'stream'")
+    if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream", "device")):
+        raise ValueError(f"caption_bulk: decode_f32={decode_f32!r}: 'ops', 'stream' or 'device'")
     model.eval()
-    if decode_f32 != "stream":
+    if decode_f32 == "ops":
         model.bfloat16()
     results = {"uniprot_id": []}
     results.update({f"response{i}": [] for i in range(beam_size // 2)})
