@@ -68,12 +68,20 @@ void pcy_set_error(const char* fmt, ...) {
 // cache / model the enqueue functions read AND the geometry (an allocator may hand a new state or a cache of another capacity the
 // addresses of the previous one while e.g. the `keep` mask or the token buffer differ -- a stale graph would then run with dangling
 // arguments), the context's buffers that are baked into the launches, and the switch snapshot the launches were chosen under.  Zero-filled
-// before it is filled in (decode_graph_key) and compared with memcmp: no packing, no hashing.
+// before it is filled in (key_base) and compared with memcmp: no packing, no hashing.
+// What a captured step is made of (the values are those of earlier logs: they stay)
+enum GraphKind {
+  KIND_GREEDY = 0,       // decode + greedy pick (pcy_llama_greedy)
+  KIND_DECODE = 1,       // decode only (pcy_llama_decode_graph)
+  KIND_BEAM = 2,         // a beam-search step (pcy_llama_beam_steps / _split)
+  KIND_GREEDY_W8 = 3,    // decode on e4m3 weights + greedy pick (pcy_llama_greedy_w8)
+  KIND_F32_DECODE = 4,   // the fp32 stream step alone (model = the pcy_f32_llama_desc, here and below)
+  KIND_F32_GREEDY = 5,   // ... with its greedy pick
+  KIND_F32_BEAM = 6,     // an fp32 beam-search step (pcy_f32_llama_beam_steps)
+  KIND_F32_SAMPLE = 7,   // the fp32 step with its sampling pick
+};
 struct DecodeGraphKey {
-  int kind;                           // 0: decode + greedy pick (pcy_llama_greedy), 1: decode only (pcy_llama_decode_graph), 2: a beam-search step (pcy_llama_beam_steps),
-                                      // 3: decode on e4m3 weights + greedy pick (pcy_llama_greedy_w8)
-                                      // 4 / 5: the fp32 stream step alone / with its greedy pick (model = the pcy_f32_llama_desc)
-                                      // 6: an fp32 beam-search step (pcy_f32_llama_beam_steps), 7: the fp32 step with its sampling pick
+  int kind;                           // a GraphKind
   int B;
   PcySwitches sw;
   const void *model, *layers, *embed, *kv_k, *kv_v, *pos, *step, *next_tok, *logits, *keep;
@@ -82,16 +90,16 @@ struct DecodeGraphKey {
   int kv_prefix_T, kv_prefix_B, kv_rows_per_prefix;
   const void *ws, *mc_tags, *mb_flags, *nb_tags, *dev_layers;
   uint64_t layers_fp;
-  const void *tokens_out, *logprob, *logits_all;   // kinds 0 and 1
+  const void *tokens_out, *logprob, *logits_all;   // key_record: what a pick behind the step writes
   int logits_all_ld, max_steps;
-  pcy_beam_state beam_state;                       // kind 2: every array of the beam state is baked into the chain
+  pcy_beam_state beam_state;                       // key_beam: every array of the beam state is baked into the chain
   const void *logits_rec, *beam_ws;
   int beam, group_size, kv_t0;
   uint32_t penalty_bits;
-  const void* w8;                                  // kind 3: the host array of e4m3 layers and a fingerprint of the device pointers it holds
+  const void* w8;                                  // KIND_GREEDY_W8: the host array of e4m3 layers and a fingerprint of the device pointers it holds
   uint64_t w8_fp;
   int attn_split;                                  // 1: every layer's attention is the split-key one (pcy_attn_split.hip); never shares a graph with 0
-  const void* uniforms;                            // kind 7: the variates and the two parameters of the sampling pick
+  const void* uniforms;                            // KIND_F32_SAMPLE: the variates and the two parameters of the sampling pick
   uint32_t temperature_bits, nucleus_bits;
 };
 
@@ -288,13 +296,17 @@ int ensure_sync_words(pcy_ctx* c) {
   }
   return 0;
 }
-uint64_t layers_fingerprint(const pcy_llama_desc* m) {   // FNV-1a over every weight pointer the fused decode launches read
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p) { h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull; };
-  mix(m->layers);
+// FNV-1a over pointers, in the order they are given: the fingerprint of a set of weights that a captured step bakes in
+uint64_t fnv1a(uint64_t h, std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs) h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull;
+  return h;
+}
+constexpr uint64_t FNV_BASIS = 1469598103934665603ull;
+uint64_t layers_fingerprint(const pcy_llama_desc* m) {   // every weight pointer the fused decode launches read
+  uint64_t h = fnv1a(FNV_BASIS, {m->layers});
   for (int l = 0; l < m->n_layers; ++l) {
     const pcy_llama_layer& L = m->layers[l];
-    mix(L.ln1); mix(L.wqkv); mix(L.wo); mix(L.ln2); mix(L.wgu); mix(L.wdown);
+    h = fnv1a(h, {L.ln1, L.wqkv, L.wo, L.ln2, L.wgu, L.wdown});
   }
   return h;
 }
@@ -540,14 +552,22 @@ PcyGemvArgs proj_args(const DecodeCx& cx, const DecodePlan& p, const void* W, co
 // The split-key attention (pcy_attn_split.hip) on layer `layer` of a complete shared-prefix cache; ws: its partial sums and
 // statistics (split_ws_bytes).  Built in ONE place for pcy_attn_decode_split and the three steps that use it.
 size_t split_ws_bytes(const PcySplitPlan& p) { return align_up(p.part_bytes, 256) + align_up(p.stat_bytes, 256) + 256; }
-// Where a STEP keeps them: behind the decode carve AND the K/V reorder scratch of a beam-search chain (pcy_kv_reorder_range, pcy_llama_beam_steps),
-// so that the eager step, the replayed chain and the GEMM step agree on one offset and a reorder between two steps never meets them.
+// The workspace of a step on B rows of a cache: [decode carve][K/V reorder scratch of a beam search][buffers of the split-key attention].
+// The scratch copy of the two-launch reorder (enqueue_kv_reorder; pcy_kv_reorder_range, the beam chains) is sized for the cache's capacity,
+// not for the slots in use: a workspace that grew step by step would be re-allocated, and the captured step dropped, several times per search.
+size_t step_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) { return decode_ws_bytes(m, B, kv_cap(kv)); }
 size_t reorder_scratch_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
   return align_up((size_t)2 * m->n_layers * B * m->n_kv_heads * kv->Tmax * m->head_dim * 2, 256) + 4096;
 }
-size_t split_ws_offset(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
-  return align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256) + reorder_scratch_bytes(m, kv, B);
+bf16_t* reorder_scratch(const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
+  return reinterpret_cast<bf16_t*>(c->ws + align_up(step_ws_bytes(m, kv, B), 256));
 }
+size_t reorder_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {   // the carve and the scratch
+  return align_up(step_ws_bytes(m, kv, B), 256) + reorder_scratch_bytes(m, kv, B);
+}
+// Where a STEP keeps the split-key buffers: behind BOTH, so that the eager step, the replayed chain and the GEMM step agree on one offset and a
+// reorder between two steps never meets them.
+size_t split_ws_offset(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) { return reorder_ws_bytes(m, kv, B); }
 size_t split_step_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
   return split_ws_offset(m, kv, B) + split_ws_bytes(pcy_attn_split_plan(B, kv->rows_per_prefix, m->n_heads, m->n_kv_heads, m->head_dim, kv->prefix_T));
 }
@@ -763,18 +783,6 @@ __global__ __launch_bounds__(128) void kv_permute_kernel(bf16_t* __restrict__ kb
     }
   }
 }
-// enqueue: the one-pass form for <= 32 rows (PCY_DISABLE=kv_permute: the two launches through the scratch copy; same result)
-static bool enqueue_kv_permute(hipStream_t s, const pcy_llama_desc* m, const pcy_kv_cache* kv, const int32_t* src_rows, int B, int t, const int32_t* t_dev,
-                               int t0, int t_off) {
-  if (B > 32 || pcy_off("kv_permute")) return false;
-  const dim3 grid(m->n_kv_heads, 2 * m->n_layers, 4);
-  if (B <= 8)
-    hipLaunchKernelGGL(kv_permute_kernel<8>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0, t_off);
-  else
-    hipLaunchKernelGGL(kv_permute_kernel<32>, grid, dim3(128), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, src_rows, B, kv->B, m->n_kv_heads, kv->Tmax, t, m->head_dim, t_dev, t0, t_off);
-  return true;
-}
-
 // t_dev != nullptr (the replayed beam step): the number of slots is read from the device (the position counter the beam step has just
 // advanced) and the scratch rows are Tmax slots apart -- nothing in the launch depends on the step.
 __global__ void kv_gather_kernel(bf16_t* __restrict__ kbase, bf16_t* __restrict__ vbase, bf16_t* __restrict__ tmp,
@@ -798,13 +806,25 @@ __global__ void kv_gather_kernel(bf16_t* __restrict__ kbase, bf16_t* __restrict_
   }
   for (size_t i = (size_t)t0 * dh / 8 + threadIdx.x; i < n8; i += blockDim.x) dp[i] = sp[i];
 }
+// The reorder of rows [0, B) over slots [t0, t) -- or [t0, *t_dev - t_off) -- of every layer: the one-pass form for <= 32 rows, else
+// (PCY_DISABLE=kv_permute too; same result) the two launches through the scratch copy `tmp` (reorder_scratch)
+void enqueue_kv_reorder(hipStream_t s, const pcy_llama_desc* m, const pcy_kv_cache* kv, const int32_t* rows, int B, int t, const int32_t* t_dev, int t0,
+                        int t_off, bf16_t* tmp) {
+  const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
+  bf16_t *k = (bf16_t*)kv->k, *v = (bf16_t*)kv->v;
+  if (B <= 32 && !pcy_off("kv_permute")) {
+    const dim3 grid(Hkv, 2 * L, 4);
+    if (B <= 8) hipLaunchKernelGGL(kv_permute_kernel<8>, grid, dim3(128), 0, s, k, v, rows, B, kv->B, Hkv, kv->Tmax, t, dh, t_dev, t0, t_off);
+    else hipLaunchKernelGGL(kv_permute_kernel<32>, grid, dim3(128), 0, s, k, v, rows, B, kv->B, Hkv, kv->Tmax, t, dh, t_dev, t0, t_off);
+    return;
+  }
+  for (int to_tmp = 1; to_tmp >= 0; --to_tmp)   // gather into the scratch copy, copy back
+    hipLaunchKernelGGL(kv_gather_kernel, dim3(B, Hkv, 2 * L), dim3(256), 0, s, k, v, tmp, rows, B, kv->B, Hkv, kv->Tmax, t, dh, to_tmp, t_dev, t0, t_off);
+}
 
 }  // namespace
 
 // ====================================================================================== C ABI
-extern "C" {
-
-}  // extern "C"
 hipStream_t pcy_ctx_stream(pcy_ctx* c) { return c->stream; }
 void* pcy_ctx_reserve(pcy_ctx* c, size_t bytes) { return c->reserve(bytes) == 0 ? c->ws : nullptr; }
 extern "C" {
@@ -1667,20 +1687,41 @@ int ensure_beam_ws(pcy_ctx* c, int B, int beam) {
   return 0;
 }
 
-// The part of a graph key that every kind shares: what enqueue_decode reads (call after ensure_decode_state: the context's buffers are final)
-// (filled in place behind a memset: the padding bytes take part in the comparison)
-void decode_graph_key(DecodeGraphKey& k, const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int kind, const PcySwitches& sw) {
+// The part of a graph key that EVERY kind shares, the bf16 steps and the fp32 ones (M / KV: their descriptor and cache; fp: the fingerprint
+// of the weight pointers the step reads).  Call it when the workspace is final.  Filled in place behind a memset: the padding bytes take
+// part in the comparison.
+template <typename M, typename KV>
+void key_base(DecodeGraphKey& k, GraphKind kind, int B, const M* m, const KV* kv, const pcy_gen_state* st, const pcy_ctx* c, uint64_t fp) {
   memset(&k, 0, sizeof(k));
-  k.kind = kind; k.B = B; k.sw = sw;
+  k.kind = kind; k.B = B;
   k.model = m; k.layers = m->layers; k.embed = m->embed; k.kv_k = kv->k; k.kv_v = kv->v; k.Tmax = kv->Tmax; k.kv_B = kv->B;
-  if (kv_shared(kv)) { k.kv_prefix_k = kv->prefix_k; k.kv_prefix_v = kv->prefix_v; k.kv_prefix_T = kv->prefix_T; k.kv_prefix_B = kv->prefix_B; k.kv_rows_per_prefix = kv->rows_per_prefix; }
-  k.pos = st->pos; k.step = st->step; k.next_tok = st->next_tok; k.logits = st->logits; k.keep = st->keep;
-  k.ws = c->ws; k.mc_tags = c->mc_tags; k.mb_flags = c->mb_flags; k.nb_tags = B <= 8 ? c->nb_tags[B] : nullptr; k.dev_layers = c->dev_layers;
-  k.layers_fp = c->layers_fp;
+  k.pos = st->pos; k.step = st->step; k.next_tok = st->next_tok; k.logits = st->logits;
+  k.ws = c->ws; k.layers_fp = fp;
 }
-// capture (once per key) and replay: `enqueue` puts the launches of ONE step on c->stream
+// ... and what enqueue_decode reads on top (call after ensure_decode_state: the context's buffers are final)
+void decode_graph_key(DecodeGraphKey& k, const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, GraphKind kind, const PcySwitches& sw) {
+  key_base(k, kind, B, m, kv, st, c, c->layers_fp);
+  k.sw = sw; k.keep = st->keep;
+  if (kv_shared(kv)) { k.kv_prefix_k = kv->prefix_k; k.kv_prefix_v = kv->prefix_v; k.kv_prefix_T = kv->prefix_T; k.kv_prefix_B = kv->prefix_B; k.kv_rows_per_prefix = kv->rows_per_prefix; }
+  k.mc_tags = c->mc_tags; k.mb_flags = c->mb_flags; k.nb_tags = B <= 8 ? c->nb_tags[B] : nullptr; k.dev_layers = c->dev_layers;
+}
+// a pick behind the step (greedy, sampling): where it records
+void key_record(DecodeGraphKey& k, const pcy_gen_state* st) {
+  k.tokens_out = st->tokens_out; k.logprob = st->logprob; k.logits_all = st->logits_all; k.logits_all_ld = st->logits_all_ld; k.max_steps = st->max_steps;
+}
+// a beam-search chain: the beam state by value, its record and scratch, its parameters
+void key_beam(DecodeGraphKey& k, const pcy_beam_state* bs, const void* logits_rec, const void* beam_ws, int beam, int group_size, int kv_t0, float penalty) {
+  memcpy(&k.beam_state, bs, sizeof(*bs)); k.logits_rec = logits_rec; k.beam_ws = beam_ws; k.beam = beam; k.group_size = group_size; k.kv_t0 = kv_t0;
+  memcpy(&k.penalty_bits, &penalty, 4);
+}
+// THE step driver: `enqueue` puts the launches of ONE step on c->stream.  Eager: n_steps times, launch by launch.  use_graph: captured once per
+// key, then replayed n_steps times.  Everything that allocates (workspace, beam scratch, sample state, sync words) happens before the call.
 template <typename Enqueue>
-int replay_graph(pcy_ctx* c, const DecodeGraphKey& key, int n_steps, const char* what, Enqueue&& enqueue) {
+int run_steps(pcy_ctx* c, int n_steps, bool use_graph, const char* what, const DecodeGraphKey& key, Enqueue&& enqueue) {
+  if (!use_graph) {
+    for (int i = 0; i < n_steps; ++i) enqueue();
+    return check_launch(what);
+  }
   if (!c->graph || memcmp(&key, &c->graph_key, sizeof(key)) != 0) {
     c->drop_graph();
     hipGraph_t g = nullptr;
@@ -1700,15 +1741,55 @@ int replay_graph(pcy_ctx* c, const DecodeGraphKey& key, int n_steps, const char*
   for (int i = 0; i < n_steps; ++i) HIP_TRY(hipGraphLaunch(c->graph, c->stream));
   return 0;
 }
-// kind 0 = decode + greedy pick, 1 = decode only
-int replay_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps, int kind, const PcySwitches& sw) {
-  DecodeGraphKey key;
-  decode_graph_key(key, c, m, kv, st, B, kind, sw);
-  key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps;
-  return replay_graph(c, key, n_steps, "decode-step", [&] {
-    enqueue_decode(c, m, kv, st, B, sw);
-    if (kind == 0) enqueue_pick(c, m, st, B, 1, kv_cap(kv));
-  });
+
+// ---- what the step entries refuse, each rule in ONE place; `what` names the entry that was called ----
+// the descriptors a step dereferences, and the rows
+int check_step_args(const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const char* what) {
+  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
+  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
+  return 0;
+}
+// a beam-search step, bf16 or fp32 logits
+int check_beam_args(const char* what, int B, int beam, int group_size, int vocab) {
+  if (B <= 0 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
+    return fail(1, "%s: B=%d, beam=%d (1..32) must be a multiple of group_size=%d", what, B, beam, group_size);
+  if (vocab <= 0 || vocab > 163840) return fail(1, "%s: vocab %d unsupported (<= 163840)", what, vocab);
+  return 0;
+}
+// a sampling pick (max_vocab: what its selection kernel covers); the comparisons refuse a NaN
+int check_sample_args(const char* what, int vocab, int max_vocab, float temperature, float nucleus_prob, const float* uniforms) {
+  if (!(temperature > 0.f)) return fail(1, "%s: temperature must be > 0 (the greedy pick is an entry of its own)", what);
+  if (!(nucleus_prob < 1.f)) return fail(1, "%s: nucleus_prob must be < 1 (<= 0 switches the nucleus mask off)", what);
+  if (!uniforms) return fail(1, "%s: no uniform variates", what);
+  if (vocab < 1 || vocab > max_vocab) return fail(1, "%s: vocab %d unsupported (<= %d)", what, vocab, max_vocab);
+  return 0;
+}
+// a complete shared-prefix cache with a uniform rows_per_prefix and a geometry the many-queries attention covers: anything else is the caller's error
+int check_mq_cache(const pcy_kv_cache* kv, int B, int H, int Hkv, int dh, const char* what) {
+  if (!kv_shared(kv)) return fail(1, "%s: the cache has no shared prefix (plain caches: the decode attention)", what);
+  if (kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
+  if (int r = check_shared_cache(kv, B, what)) return r;
+  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (!pcy_attn_mq_covers(H, Hkv, dh, kv->Tmax)) return fail(1, "%s: the scores of %d suffix slots do not fit in LDS", what, kv->Tmax);
+  return 0;
+}
+// THE prologue of the bf16 entries that enqueue the step (enqueue_decode), in this order -- plan_decode reads the context state that
+// ensure_decode_state builds: the call's descriptors and rows, the workspace (ws_bytes: step_ws_bytes, reorder_ws_bytes or split_step_ws_bytes),
+// ONE switch snapshot (*sw), the context state, what the cache asks of the step's plan.  No launch before it.
+// split (the steps on the split-key attention) asks beyond that for a complete shared-prefix cache with a uniform rows_per_prefix >= 1 and a
+// geometry the attention covers -- before the workspace, whose size is a function of them -- and for bf16 projections.
+int decode_prologue(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const char* what,
+                    size_t (*ws_bytes)(const pcy_llama_desc*, const pcy_kv_cache*, int), PcySwitches* sw, bool split = false) {
+  if (int r = check_step_args(m, kv, st, B, what)) return r;
+  if (split)
+    if (int r = check_mq_cache(kv, B, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
+  if (int r = c->reserve(ws_bytes(m, kv, B))) return r;
+  *sw = pcy_read_switches();
+  if (int r = ensure_decode_state(c, m, B, *sw)) return r;
+  if (int r = check_decode_cache(c, m, kv, B, *sw, what)) return r;
+  if (split && m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
+  return 0;
 }
 }  // namespace
 extern "C" {
@@ -1778,24 +1859,17 @@ int pcy_attn_extend_packed(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv
 
 int pcy_llama_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
-  if (B > kv->B) return fail(1, "pcy_llama_decode: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode")) return r;
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_decode", step_ws_bytes, &sw)) return r;
   enqueue_decode(c, m, kv, st, B, sw);
   return check_launch("pcy_llama_decode");
 }
 
 int pcy_llama_decode_layers(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int reps) {
   PCY_STICKY(c);
-  if (B > kv->B) return fail(1, "pcy_llama_decode_layers: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode_layers")) return r;
-  for (int i = 0; i < reps; ++i) enqueue_decode(c, m, kv, st, B, sw, true);
-  return check_launch("pcy_llama_decode_layers");
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_decode_layers", step_ws_bytes, &sw)) return r;
+  return run_steps(c, reps, false, "pcy_llama_decode_layers", DecodeGraphKey{}, [&] { enqueue_decode(c, m, kv, st, B, sw, true); });
 }
 
 int pcy_greedy_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos) {
@@ -1843,29 +1917,25 @@ unsigned long long pcy_debug_look_count(int which) { return (which == 0 || which
 int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps,
                      int use_graph) {
   PCY_STICKY(c);
-  if (B > kv->B) return fail(1, "pcy_llama_greedy: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_greedy")) return r;
-  if (!use_graph) {
-    for (int i = 0; i < n_steps; ++i) {
-      enqueue_decode(c, m, kv, st, B, sw);
-      enqueue_pick(c, m, st, B, 1, kv_cap(kv));
-    }
-    return check_launch("pcy_llama_greedy");
-  }
-  return replay_decode_graph(c, m, kv, st, B, n_steps, 0, sw);
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_greedy", step_ws_bytes, &sw)) return r;
+  DecodeGraphKey key;
+  decode_graph_key(key, c, m, kv, st, B, KIND_GREEDY, sw);
+  key_record(key, st);
+  return run_steps(c, n_steps, use_graph != 0, "pcy_llama_greedy", key, [&] {
+    enqueue_decode(c, m, kv, st, B, sw);
+    enqueue_pick(c, m, st, B, 1, kv_cap(kv));
+  });
 }
 
 int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
-  if (B > kv->B) return fail(1, "pcy_llama_decode_graph: B=%d exceeds cache rows %d", B, kv->B);
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_decode_graph")) return r;
-  return replay_decode_graph(c, m, kv, st, B, 1, 1, sw);
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_decode_graph", step_ws_bytes, &sw)) return r;
+  DecodeGraphKey key;
+  decode_graph_key(key, c, m, kv, st, B, KIND_DECODE, sw);
+  key_record(key, st);   // (no pick here: as every earlier key of this kind)
+  return run_steps(c, 1, true, "pcy_llama_decode_graph", key, [&] { enqueue_decode(c, m, kv, st, B, sw); });
 }
 
 // ---- the decode step for more than 32 rows: every projection is ONE GEMM over all B rows ----
@@ -1927,23 +1997,11 @@ static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_k
   if (split) ++g_pcy_attn_split;
 }
 
-// a complete shared-prefix cache with a uniform rows_per_prefix and a geometry the many-queries attention covers: anything else is the caller's error
-static int check_mq_cache(const pcy_kv_cache* kv, int B, int H, int Hkv, int dh, const char* what) {
-  if (!kv_shared(kv)) return fail(1, "%s: the cache has no shared prefix (plain caches: the decode attention)", what);
-  if (kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
-  if (int r = check_shared_cache(kv, B, what)) return r;
-  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
-  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
-  if (!pcy_attn_mq_covers(H, Hkv, dh, kv->Tmax)) return fail(1, "%s: the scores of %d suffix slots do not fit in LDS", what, kv->Tmax);
-  return 0;
-}
-
 static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq, bool split = false) {
   PCY_STICKY(c);
   const char* what = split ? "pcy_llama_decode_gemm_split" : mq ? "pcy_llama_decode_gemm_mq" : "pcy_llama_decode_gemm";
-  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
+  if (int r = check_step_args(m, kv, st, B, what)) return r;
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
-  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
   if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
   if (kv_shared(kv) && kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
   if (int r = check_shared_cache(kv, B, what)) return r;
@@ -1992,13 +2050,11 @@ static PcyGemvW8Args w8_args(const void* W, const float* scale, const bf16_t* x,
   else { g.rms_w = (const bf16_t*)ln; g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast; }
   return g;
 }
-static uint64_t w8_fingerprint(const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8) {   // FNV-1a, as layers_fingerprint
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p) { h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull; };
-  mix(m->final_norm); mix(m->lm_head); mix(m->rope_cos); mix(m->rope_sin);
+static uint64_t w8_fingerprint(const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8) {   // as layers_fingerprint
+  uint64_t h = fnv1a(FNV_BASIS, {m->final_norm, m->lm_head, m->rope_cos, m->rope_sin});
   for (int l = 0; l < m->n_layers; ++l) {
     const pcy_llama_layer_fp8& Q = w8[l];
-    mix(Q.wqkv); mix(Q.wo); mix(Q.wgu); mix(Q.wdown); mix(Q.sqkv); mix(Q.so); mix(Q.sgu); mix(Q.sdown);
+    h = fnv1a(h, {Q.wqkv, Q.wo, Q.wgu, Q.wdown, Q.sqkv, Q.so, Q.sgu, Q.sdown});
   }
   return h;
 }
@@ -2060,21 +2116,13 @@ int pcy_llama_greedy_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_lay
   PCY_STICKY(c);
   if (int r = decode_w8_check(c, m, w8, kv, st, B, "pcy_llama_greedy_w8")) return r;
   if (!st->step || !st->tokens_out || !st->logprob) return fail(1, "pcy_llama_greedy_w8: generation state incomplete");
-  if (!use_graph) {
-    for (int i = 0; i < n_steps; ++i) {
-      enqueue_decode_w8(c, m, w8, kv, st, B);
-      enqueue_pick(c, m, st, B, 1, kv_cap(kv));
-    }
-    return check_launch("pcy_llama_greedy_w8");
-  }
-  // (this step reads no switch: the key's snapshot stays zero, and the weight pointers of every layer go in through their fingerprint)
+  // (this step reads no switch and none of the fused steps' buffers: the base key, whose fingerprint holds ln1 / ln2 of every layer, the keep
+  // mask, and the e4m3 pointers through a fingerprint of their own; a shared-prefix cache never gets here)
   DecodeGraphKey key;
-  decode_graph_key(key, c, m, kv, st, B, 3, PcySwitches{});
-  key.mc_tags = key.mb_flags = key.nb_tags = key.dev_layers = nullptr;   // (the fused steps' buffers: not read here)
-  key.layers_fp = layers_fingerprint(m);   // (ln1 / ln2 of every layer)
-  key.w8 = w8; key.w8_fp = w8_fingerprint(m, w8);
-  key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps;
-  return replay_graph(c, key, n_steps, "decode-w8-step", [&] {
+  key_base(key, KIND_GREEDY_W8, B, m, kv, st, c, layers_fingerprint(m));
+  key.keep = st->keep; key.w8 = w8; key.w8_fp = w8_fingerprint(m, w8);
+  key_record(key, st);
+  return run_steps(c, n_steps, use_graph != 0, "pcy_llama_greedy_w8", key, [&] {
     enqueue_decode_w8(c, m, w8, kv, st, B);
     enqueue_pick(c, m, st, B, 1, kv_cap(kv));
   });
@@ -2100,13 +2148,11 @@ static size_t f32_stream_ws_bytes(const pcy_f32_llama_desc* m, int B) {
   const size_t f = (size_t)B * (2 * (size_t)m->d + (size_t)(2 * m->n_heads + 2 * m->n_kv_heads) * m->head_dim + (size_t)m->ffn) * sizeof(float);
   return f + 8 * 256;
 }
-static uint64_t f32_stream_fingerprint(const pcy_f32_llama_desc* m) {   // FNV-1a over every weight pointer the step reads, as layers_fingerprint
-  uint64_t h = 1469598103934665603ull;
-  auto mix = [&](const void* p) { h = (h ^ (uint64_t)(uintptr_t)p) * 1099511628211ull; };
-  mix(m->embed); mix(m->final_norm); mix(m->lm_head); mix(m->rope_cos); mix(m->rope_sin);
+static uint64_t f32_stream_fingerprint(const pcy_f32_llama_desc* m) {   // every weight pointer the step reads, as layers_fingerprint
+  uint64_t h = fnv1a(FNV_BASIS, {m->embed, m->final_norm, m->lm_head, m->rope_cos, m->rope_sin});
   for (int l = 0; l < m->n_layers; ++l) {
     const pcy_f32_llama_layer& L = m->layers[l];
-    mix(L.wqkv); mix(L.wo); mix(L.wg); mix(L.wu); mix(L.wd); mix(L.ln1); mix(L.ln2);
+    h = fnv1a(h, {L.wqkv, L.wo, L.wg, L.wu, L.wd, L.ln1, L.ln2});
   }
   return h;
 }
@@ -2166,13 +2212,10 @@ static int f32_stream_check(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f
   if (pcy_f32_attn_pos_lds(H, Hkv, dh, kv->Tmax) > 160 * 1024 - 1024) return fail(1, "%s: %d slots exceed the LDS score buffer of the attention", what, kv->Tmax);
   return c->reserve(f32_stream_ws_bytes(m, B));
 }
-static void f32_stream_key(DecodeGraphKey& key, const pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int kind) {
-  memset(&key, 0, sizeof(key));
-  key.kind = kind; key.B = B;
-  key.model = m; key.layers = m->layers; key.embed = m->embed; key.kv_k = kv->k; key.kv_v = kv->v; key.Tmax = kv->Tmax; key.kv_B = kv->B;
-  key.pos = st->pos; key.step = st->step; key.next_tok = st->next_tok; key.logits = st->logits;
-  key.ws = c->ws; key.layers_fp = f32_stream_fingerprint(m);
-  if (kind == 5) { key.tokens_out = st->tokens_out; key.logprob = st->logprob; key.logits_all = st->logits_all; key.logits_all_ld = st->logits_all_ld; key.max_steps = st->max_steps; }
+// the key of an fp32 step: the base, and where the pick behind it records (the greedy and the sampling pick)
+static void f32_stream_key(DecodeGraphKey& key, const pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, GraphKind kind) {
+  key_base(key, kind, B, m, kv, st, c, f32_stream_fingerprint(m));
+  if (kind == KIND_F32_GREEDY || kind == KIND_F32_SAMPLE) key_record(key, st);
 }
 int pcy_f32_llama_decode(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
@@ -2184,8 +2227,8 @@ int pcy_f32_llama_decode_graph(pcy_ctx* c, const pcy_f32_llama_desc* m, const pc
   PCY_STICKY(c);
   if (int r = f32_stream_check(c, m, kv, st, B, false, "pcy_f32_llama_decode_graph")) return r;
   DecodeGraphKey key;
-  f32_stream_key(key, c, m, kv, st, B, 4);   // kind 4: the fp32 step alone; 5: with the greedy pick
-  return replay_graph(c, key, 1, "decode-f32-step", [&] { enqueue_decode_f32(c, m, kv, st, B); });
+  f32_stream_key(key, c, m, kv, st, B, KIND_F32_DECODE);
+  return run_steps(c, 1, true, "pcy_f32_llama_decode_graph", key, [&] { enqueue_decode_f32(c, m, kv, st, B); });
 }
 int pcy_f32_greedy_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos) {
   PCY_STICKY(c);
@@ -2198,16 +2241,9 @@ int pcy_f32_greedy_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_k
 int pcy_f32_llama_greedy(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps, int use_graph) {
   PCY_STICKY(c);
   if (int r = f32_stream_check(c, m, kv, st, B, true, "pcy_f32_llama_greedy")) return r;
-  if (!use_graph) {
-    for (int i = 0; i < n_steps; ++i) {
-      enqueue_decode_f32(c, m, kv, st, B);
-      enqueue_pick_f32(c, m, st, B, 1);
-    }
-    return check_launch("pcy_f32_llama_greedy");
-  }
   DecodeGraphKey key;
-  f32_stream_key(key, c, m, kv, st, B, 5);
-  return replay_graph(c, key, n_steps, "decode-f32-step", [&] {
+  f32_stream_key(key, c, m, kv, st, B, KIND_F32_GREEDY);
+  return run_steps(c, n_steps, use_graph != 0, "pcy_f32_llama_greedy", key, [&] {
     enqueue_decode_f32(c, m, kv, st, B);
     enqueue_pick_f32(c, m, st, B, 1);
   });
@@ -2221,10 +2257,8 @@ static int f32_beam_check(const char* what, const void* logits_or_state, int voc
   if (!logits_or_state || !bs || !bs->out || !bs->cur || !bs->cur_new || !bs->next_tok || !bs->src || !bs->has_eos || !bs->blk_eos || !bs->ticket ||
       !bs->pos || !bs->step || !bs->done || bs->max_len < 1)
     return fail(1, "%s: logits or beam state incomplete", what);
-  if (B <= 0 || B > 65535 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
-    return fail(1, "%s: B=%d, beam=%d (1..32) must be a multiple of group_size=%d", what, B, beam, group_size);
-  if (vocab <= 0 || vocab > 163840) return fail(1, "%s: vocab %d unsupported (<= 163840)", what, vocab);
-  return 0;
+  if (B > 65535) return fail(1, "%s: B=%d exceeds the 65535 prompts of a launch", what, B);
+  return check_beam_args(what, B, beam, group_size, vocab);
 }
 int pcy_f32_beam_step(pcy_ctx* c, const float* logits, int vocab, int B, int beam, int group_size, float diversity_penalty, const pcy_beam_state* bs) {
   PCY_STICKY(c);
@@ -2285,11 +2319,10 @@ int pcy_f32_llama_beam_steps(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_
   if (int r = c->reserve(off + pcy_f32_kv_reorder_tmp_bytes(m->n_layers, BB, kv->Tmax, kv_t0, kw))) return r;
   if (int r = ensure_beam_ws(c, B, beam)) return r;
   DecodeGraphKey key;
-  f32_stream_key(key, c, m, kv, st, BB, 6);
-  memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
-  memcpy(&key.penalty_bits, &diversity_penalty, 4);
+  f32_stream_key(key, c, m, kv, st, BB, KIND_F32_BEAM);
+  key_beam(key, bs, logits_rec, c->beam_ws, beam, group_size, kv_t0, diversity_penalty);
   g_pcy_f32_select[0] += (unsigned long long)n_steps;
-  return replay_graph(c, key, n_steps, "f32-beam-step", [&] {
+  return run_steps(c, n_steps, true, what, key, [&] {
     hipStream_t s = c->stream;
     enqueue_decode_f32(c, m, kv, st, BB);
     pcy_launch_f32_record(s, (const float*)st->logits, logits_rec, bs->step, BB, m->vocab, 0);
@@ -2297,13 +2330,6 @@ int pcy_f32_llama_beam_steps(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_
     if (kv_t0 < kv->Tmax)
       pcy_launch_f32_kv_reorder(s, kv->k, kv->v, reinterpret_cast<float*>(c->ws + off), bs->src, m->n_layers, BB, kv->B, kv->Tmax, kw, kv_t0, 0, bs->pos);
   });
-}
-static int f32_sample_check(const char* what, const pcy_f32_llama_desc* m, float temperature, float nucleus_prob, const float* uniforms) {
-  if (!(temperature > 0.f)) return fail(1, "%s: temperature must be > 0 (greedy: pcy_f32_greedy_pick)", what);
-  if (!(nucleus_prob < 1.f)) return fail(1, "%s: nucleus_prob must be < 1 (<= 0 switches the nucleus mask off)", what);
-  if (!uniforms) return fail(1, "%s: no uniform variates", what);
-  if (m->vocab < 1 || m->vocab > 163840) return fail(1, "%s: vocab %d unsupported (<= 163840)", what, m->vocab);
-  return 0;
 }
 // record row *step -> the selection -> ++*step (/ ++*pos); the nucleus branch of the reference does not apply the temperature (model_unified.py:899-901)
 static void enqueue_sample_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos, float temperature,
@@ -2320,7 +2346,7 @@ int pcy_f32_sample_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_k
   if (!m || !st || !st->logits || !st->pos || !st->step || !st->next_tok || !st->tokens_out || !st->logprob || st->max_steps < 1)
     return fail(1, "pcy_f32_sample_pick: generation state incomplete");
   if (B < 1 || B > 65535 || (kv && B > kv->B)) return fail(1, "pcy_f32_sample_pick: B=%d", B);
-  if (int r = f32_sample_check("pcy_f32_sample_pick", m, temperature, nucleus_prob, uniforms)) return r;
+  if (int r = check_sample_args("pcy_f32_sample_pick", m->vocab, 163840, temperature, nucleus_prob, uniforms)) return r;
   if (int r = c->reserve(f32_select_ws_offset(m, B) + pcy_f32_sample_ws_bytes(B, m->vocab))) return r;
   enqueue_sample_f32(c, m, st, B, advance_pos, temperature, nucleus_prob, uniforms, probs_out);
   ++g_pcy_f32_select[1];
@@ -2330,22 +2356,15 @@ int pcy_f32_llama_sample(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_
                          float temperature, float nucleus_prob, const float* uniforms, int use_graph) {
   PCY_STICKY(c);
   if (int r = f32_stream_check(c, m, kv, st, B, true, "pcy_f32_llama_sample")) return r;
-  if (int r = f32_sample_check("pcy_f32_llama_sample", m, temperature, nucleus_prob, uniforms)) return r;
+  if (int r = check_sample_args("pcy_f32_llama_sample", m->vocab, 163840, temperature, nucleus_prob, uniforms)) return r;
   if (n_steps <= 0) return 0;
   if (int r = c->reserve(f32_select_ws_offset(m, B) + pcy_f32_sample_ws_bytes(B, m->vocab))) return r;
   g_pcy_f32_select[1] += (unsigned long long)n_steps;
-  if (!use_graph) {
-    for (int i = 0; i < n_steps; ++i) {
-      enqueue_decode_f32(c, m, kv, st, B);
-      enqueue_sample_f32(c, m, st, B, 1, temperature, nucleus_prob, uniforms, nullptr);
-    }
-    return check_launch("pcy_f32_llama_sample");
-  }
   DecodeGraphKey key;
-  f32_stream_key(key, c, m, kv, st, B, 5);
-  key.kind = 7; key.uniforms = uniforms;
+  f32_stream_key(key, c, m, kv, st, B, KIND_F32_SAMPLE);
+  key.uniforms = uniforms;
   memcpy(&key.temperature_bits, &temperature, 4); memcpy(&key.nucleus_bits, &nucleus_prob, 4);
-  return replay_graph(c, key, n_steps, "decode-f32-sample-step", [&] {
+  return run_steps(c, n_steps, use_graph != 0, "pcy_f32_llama_sample", key, [&] {
     enqueue_decode_f32(c, m, kv, st, B);
     enqueue_sample_f32(c, m, st, B, 1, temperature, nucleus_prob, uniforms, nullptr);
   });
@@ -2497,35 +2516,18 @@ int pcy_attn_decode_split(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv,
   return check_launch(what);
 }
 
-// What the steps on the split-key attention ask of the call beyond check_decode_cache: a complete shared-prefix cache with a uniform
-// rows_per_prefix >= 1, a geometry the attention covers, and the batched loop (DEC_LOOP_MFMA) as the step's plan.  No launch before it.
-static int check_split_step(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, int B, const PcySwitches& sw, const char* what) {
-  if (int r = check_mq_cache(kv, B, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, what)) return r;
-  if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
-  return 0;
-}
-
 int pcy_llama_decode_split(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
   PCY_STICKY(c);
-  const char* what = "pcy_llama_decode_split";
-  if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !st->next_tok || !st->logits) return fail(1, "%s: model, cache or state incomplete", what);
-  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
-  if (int r = check_mq_cache(kv, B, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
-  if (int r = c->reserve(split_step_ws_bytes(m, kv, B))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_split_step(c, m, kv, B, sw, what)) return r;
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_decode_split", split_step_ws_bytes, &sw, true)) return r;
   enqueue_decode(c, m, kv, st, B, sw, false, true);
-  return check_launch(what);
+  return check_launch("pcy_llama_decode_split");
 }
 
 int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out) {
   PCY_STICKY(c);
-  if (!(temperature > 0.f)) return fail(1, "pcy_sample_pick: temperature must be > 0 (greedy: pcy_greedy_pick)");
-  if (nucleus_prob >= 1.f) return fail(1, "pcy_sample_pick: nucleus_prob must be < 1 (<= 0 switches the nucleus mask off)");
-  if (m->vocab > pcy_sample_max_vocab()) return fail(1, "pcy_sample_pick: vocabulary %d unsupported (<= %d)", m->vocab, pcy_sample_max_vocab());
+  if (int r = check_sample_args("pcy_sample_pick", m->vocab, pcy_sample_max_vocab(), temperature, nucleus_prob, uniforms)) return r;
   if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
   enqueue_sample(c, m, st, B, advance_pos, kv_cap(kv), temperature, nucleus_prob, uniforms, (bf16_t*)probs_out);
@@ -2535,27 +2537,22 @@ int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
 int pcy_llama_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int n_steps,
                      float temperature, float nucleus_prob, const float* uniforms) {
   PCY_STICKY(c);
-  if (B > kv->B) return fail(1, "pcy_llama_sample: B=%d exceeds cache rows %d", B, kv->B);
-  if (!(temperature > 0.f) || nucleus_prob >= 1.f) return fail(1, "pcy_llama_sample: temperature > 0 and nucleus_prob < 1 required");
-  if (m->vocab > pcy_sample_max_vocab()) return fail(1, "pcy_llama_sample: vocabulary %d unsupported (<= %d)", m->vocab, pcy_sample_max_vocab());
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, B, sw)) return r;
-  if (int r = check_decode_cache(c, m, kv, B, sw, "pcy_llama_sample")) return r;
+  const char* what = "pcy_llama_sample";
+  if (int r = check_step_args(m, kv, st, B, what)) return r;   // (ahead of the prologue: the sampling arguments are refused before anything is allocated)
+  if (int r = check_sample_args(what, m->vocab, pcy_sample_max_vocab(), temperature, nucleus_prob, uniforms)) return r;
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, B, what, step_ws_bytes, &sw)) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
-  for (int i = 0; i < n_steps; ++i) {
+  return run_steps(c, n_steps, false, what, DecodeGraphKey{}, [&] {
     enqueue_decode(c, m, kv, st, B, sw);
     enqueue_sample(c, m, st, B, 1, kv_cap(kv), temperature, nucleus_prob, uniforms, nullptr);
-  }
-  return check_launch("pcy_llama_sample");
+  });
 }
 
 int pcy_beam_step(pcy_ctx* c, const void* logits, int vocab, int B, int beam, int group_size, float diversity_penalty,
                   const pcy_beam_state* st) {
   PCY_STICKY(c);
-  if (B <= 0 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
-    return fail(1, "pcy_beam_step: beam=%d (1..32) must be a multiple of group_size=%d", beam, group_size);
-  if (vocab <= 0 || vocab > 163840) return fail(1, "pcy_beam_step: vocab %d unsupported (<= 163840)", vocab);
+  if (int r = check_beam_args("pcy_beam_step", B, beam, group_size, vocab)) return r;
   if (int r = ensure_beam_ws(c, B, beam)) return r;
   pcy_launch_beam_step(c->stream, (const bf16_t*)logits, vocab, B, beam, group_size, diversity_penalty, beam_state_args(st), c->beam_ws);
   return check_launch("pcy_beam_step");
@@ -2566,7 +2563,7 @@ int pcy_kv_reorder(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, 
 }
 int pcy_kv_reorder_range(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const int32_t* src_rows, int B, int t0, int t) {
   PCY_STICKY(c);
-  const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
+  const int dh = m->head_dim;
   if (!kv_shared(kv) && (t <= 0 || t0 >= t)) return 0;
   if (t0 < 0) return fail(1, "pcy_kv_reorder_range: t0 < 0");
   if (kv_shared(kv)) {   // the rows own their suffix slots only: logical [max(t0, Tp), t) = suffix [max(t0, Tp) - Tp, t - Tp)
@@ -2578,17 +2575,8 @@ int pcy_kv_reorder_range(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
   }
   if (t <= 0 || t0 >= t) return 0;
   if ((t * dh) % 8 || (t0 * dh) % 8) return fail(1, "pcy_kv_reorder: t * head_dim (and t0 * head_dim) must be multiples of 8");
-  // scratch sized for the cache capacity, not for t: a workspace that grows step by step would be re-allocated (and the
-  // captured decode graph dropped) several times per beam search
-  const size_t tmp_elems = (size_t)2 * L * B * Hkv * kv->Tmax * dh;
-  if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
-  bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256));
-  if (enqueue_kv_permute(c->stream, m, kv, src_rows, B, t, nullptr, t0, 0)) return check_launch("pcy_kv_reorder");
-  const dim3 grid(B, Hkv, 2 * L);
-  hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, c->stream, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, src_rows, B, kv->B, Hkv,
-                     kv->Tmax, t, dh, 1, (const int32_t*)nullptr, t0, 0);
-  hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, c->stream, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, src_rows, B, kv->B, Hkv,
-                     kv->Tmax, t, dh, 0, (const int32_t*)nullptr, t0, 0);
+  if (int r = c->reserve(reorder_ws_bytes(m, kv, B))) return r;
+  enqueue_kv_reorder(c->stream, m, kv, src_rows, B, t, nullptr, t0, 0, reorder_scratch(c, m, kv, B));
   return check_launch("pcy_kv_reorder");
 }
 
@@ -2596,52 +2584,39 @@ int pcy_kv_reorder_range(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache
 // -> record of the step's logits (row (step, b) of logits_rec, step read from the device) -> pcy_beam_step -> pcy_kv_reorder over the
 // slots the position counter names.  Same kernels, same order, same bits as the four calls (PCY_DISABLE=beam_graph: the callers keep
 // them); it removes the ~12 launch boundaries of a step (3.43 -> see DESIGN.md ms per step at beam 5).
-// split: the decode step of the chain is pcy_llama_decode_split's (pcy_llama_beam_steps_split); the error texts keep the default entry's name
+// split: the decode step of the chain is pcy_llama_decode_split's (pcy_llama_beam_steps_split)
 static int beam_steps_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
                             float diversity_penalty, const pcy_beam_state* bs, void* logits_rec, int n_steps, int kv_t0, bool split) {
   PCY_STICKY(c);
-  if (kv_t0 < 0 || (kv_t0 * m->head_dim) % 8) return fail(1, "pcy_llama_beam_steps: kv_t0 = %d (>= 0, kv_t0 * head_dim a multiple of 8)", kv_t0);
+  const char* what = split ? "pcy_llama_beam_steps_split" : "pcy_llama_beam_steps";
+  if (!m || !kv || !st || !bs) return fail(1, "%s: model, cache or state incomplete", what);
+  if (kv_t0 < 0 || (kv_t0 * m->head_dim) % 8) return fail(1, "%s: kv_t0 = %d (>= 0, kv_t0 * head_dim a multiple of 8)", what, kv_t0);
+  if (int r = check_beam_args(what, B, beam, group_size, m->vocab)) return r;
   const int BB = B * beam;
-  if (B <= 0 || beam <= 0 || beam > 32 || group_size <= 0 || beam % group_size)
-    return fail(1, "pcy_llama_beam_steps: beam=%d (1..32) must be a multiple of group_size=%d", beam, group_size);
-  if (BB > kv->B) return fail(1, "pcy_llama_beam_steps: %d rows exceed cache rows %d", BB, kv->B);
-  if (m->vocab <= 0 || m->vocab > 163840) return fail(1, "pcy_llama_beam_steps: vocab %d unsupported (<= 163840)", m->vocab);
-  if (st->pos != bs->pos || st->next_tok != bs->next_tok) return fail(1, "pcy_llama_beam_steps: the decode state must read the beam state's position and tokens");
-  if ((kv->Tmax * m->head_dim) % 8) return fail(1, "pcy_llama_beam_steps: Tmax * head_dim must be a multiple of 8");
-  if (split) {
-    if (int r = check_mq_cache(kv, BB, m->n_heads, m->n_kv_heads, m->head_dim, "pcy_llama_beam_steps_split")) return r;
-  }
+  if (BB > kv->B) return fail(1, "%s: %d rows exceed cache rows %d", what, BB, kv->B);
+  if (st->pos != bs->pos || st->next_tok != bs->next_tok) return fail(1, "%s: the decode state must read the beam state's position and tokens", what);
+  if ((kv->Tmax * m->head_dim) % 8) return fail(1, "%s: Tmax * head_dim must be a multiple of 8", what);
+  if (split)   // (ahead of the prologue: refused for any n_steps)
+    if (int r = check_mq_cache(kv, BB, m->n_heads, m->n_kv_heads, m->head_dim, what)) return r;
   if (n_steps <= 0) return 0;
   // everything the chain allocates, before the capture: decode workspace + the reorder scratch behind it (+ behind that the partial sums and
-  // statistics of the split-key attention), beam scratch, decode state
-  const int Hkv = m->n_kv_heads, dh = m->head_dim, L = m->n_layers;
-  const size_t tmp_elems = (size_t)2 * L * BB * Hkv * kv->Tmax * dh;
-  if (int r = c->reserve(split ? split_step_ws_bytes(m, kv, BB) : decode_ws_bytes(m, BB, kv_cap(kv)) + align_up(tmp_elems * 2, 256) + 4096)) return r;
-  const PcySwitches sw = pcy_read_switches();
-  if (int r = ensure_decode_state(c, m, BB, sw)) return r;
-  if (int r = split ? check_split_step(c, m, kv, BB, sw, "pcy_llama_beam_steps_split") : check_decode_cache(c, m, kv, BB, sw, "pcy_llama_beam_steps")) return r;
+  // statistics of the split-key attention), decode state, beam scratch
+  PcySwitches sw;
+  if (int r = decode_prologue(c, m, kv, st, BB, what, split ? split_step_ws_bytes : reorder_ws_bytes, &sw, split)) return r;
+  if (int r = ensure_beam_ws(c, B, beam)) return r;
   // (a shared-prefix cache: the rows own their suffix slots only -- the reorder starts at the first of them, and counts them from prefix_T)
   const int t_off = kv_shared(kv) ? kv->prefix_T : 0;
   const int sfx_t0 = (kv_t0 > t_off ? kv_t0 : t_off) - t_off;
-  if (int r = ensure_beam_ws(c, B, beam)) return r;
   DecodeGraphKey key;
-  decode_graph_key(key, c, m, kv, st, BB, 2, sw);
-  memcpy(&key.beam_state, bs, sizeof(*bs)); key.logits_rec = logits_rec; key.beam_ws = c->beam_ws; key.beam = beam; key.group_size = group_size; key.kv_t0 = kv_t0;
-  memcpy(&key.penalty_bits, &diversity_penalty, 4);
+  decode_graph_key(key, c, m, kv, st, BB, KIND_BEAM, sw);
+  key_beam(key, bs, logits_rec, c->beam_ws, beam, group_size, kv_t0, diversity_penalty);
   key.attn_split = split ? 1 : 0;
-  return replay_graph(c, key, n_steps, "beam-step", [&] {
-    bf16_t* tmp = reinterpret_cast<bf16_t*>(c->ws + align_up(decode_ws_bytes(m, BB, kv_cap(kv)), 256));
+  return run_steps(c, n_steps, true, what, key, [&] {
     hipStream_t s = c->stream;
     enqueue_decode(c, m, kv, st, BB, sw, false, split);
     enqueue_store_logits(s, st->logits, logits_rec, 0, bs->step, BB, m->vocab);
     pcy_launch_beam_step(s, (const bf16_t*)st->logits, m->vocab, B, beam, group_size, diversity_penalty, beam_state_args(bs), c->beam_ws);
-    if (!enqueue_kv_permute(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, sfx_t0, t_off)) {
-      const dim3 grid(BB, Hkv, 2 * L);
-      hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 1,
-                         (const int32_t*)bs->pos, sfx_t0, t_off);
-      hipLaunchKernelGGL(kv_gather_kernel, grid, dim3(256), 0, s, (bf16_t*)kv->k, (bf16_t*)kv->v, tmp, bs->src, BB, kv->B, Hkv, kv->Tmax, 0, dh, 0,
-                         (const int32_t*)bs->pos, sfx_t0, t_off);
-    }
+    enqueue_kv_reorder(s, m, kv, bs->src, BB, 0, (const int32_t*)bs->pos, sfx_t0, t_off, reorder_scratch(c, m, kv, BB));
   });
 }
 int pcy_llama_beam_steps(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int beam, int group_size,
