@@ -81,7 +81,9 @@ int pcy_embed_splice(pcy_ctx*, const void* table, const int32_t* ids, const void
                      void* out, int rows, int d);
 /* In-place rotary on heads [0,nh) at column col0 of a token-major buffer [ntok, ld]; pos[tok] = position.
  * mode 0: (x*cos)+(rotate_half(x)*sin) with every op rounded to bf16 (HF Llama); mode 1: fp32, rounded once
- * (HF Esm).  prescale != 0 multiplies (and rounds) first: ESM's q * head_dim^-0.5. */
+ * (HF Esm).  prescale != 0 multiplies (and rounds) first: ESM's q * head_dim^-0.5.
+ * Refused with code 1 before any launch (buf untouched): dh % 16 != 0 (the kernel moves 8-element chunks of each half head),
+ * ld % 8 != 0 or col0 % 8 != 0 (16-byte accesses; buf, cos_t, sin_t 16-byte aligned), col0 + nh*dh > ld. */
 int pcy_rope(pcy_ctx*, void* buf, int ld, int col0, int nh, int dh, const int32_t* pos, const void* cos_t,
              const void* sin_t, int ntok, int mode, float prescale);
 /* Exact-rounding eager attention over packed sequences (cu/vt_cu as in pcy_esm_encode): q,k,v token-major with

@@ -984,7 +984,12 @@ int pcy_pool(pcy_ctx* c, const void* hidden, int d, const int32_t* seg, const in
 
 int pcy_rope(pcy_ctx* c, void* buf, int ld, int col0, int nh, int dh, const int32_t* pos, const void* cos_t, const void* sin_t,
              int ntok, int mode, float prescale) {
-  if (dh % 2) return fail(1, "pcy_rope: odd head_dim");
+  // rope_row moves 8 elements of each half head per 16-byte access: a head_dim that is no multiple of 16 would leave the tail of
+  // each half unrotated, a row stride or a first column off the 8-element grid would misalign every access
+  if (dh <= 0 || dh % 16) return fail(1, "pcy_rope: head_dim %d must be a positive multiple of 16", dh);
+  if (ld % 8 || col0 % 8) return fail(1, "pcy_rope: ld=%d and col0=%d must be multiples of 8", ld, col0);
+  if (nh < 0 || col0 < 0 || (long long)col0 + (long long)nh * dh > ld)
+    return fail(1, "pcy_rope: heads [%d, %d + %d*%d) do not fit a row of ld=%d", col0, col0, nh, dh, ld);
   pcy_launch_rope(c->stream, (bf16_t*)buf, ld, col0, nh, dh, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, ntok, mode, prescale);
   return check_launch("pcy_rope");
 }
