@@ -216,6 +216,22 @@ int check_launch(const char* what) {
   return 0;
 }
 
+// ---- the geometry rules of the attention and step entries, each in ONE place; `what` names the entry that was called ----
+// the head size (dh32: 32 is served too), and with it the query heads per K/V head
+int check_head_dim(const char* what, int dh, bool dh32) {
+  return dh == 64 || dh == 128 || (dh32 && dh == 32) ? 0 : fail(1, "%s: head_dim %d unsupported (%s64/128)", what, dh, dh32 ? "32/" : "");
+}
+int check_heads(const char* what, int H, int Hkv, int dh, bool dh32) {
+  if (int r = check_head_dim(what, dh, dh32)) return r;
+  return Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8) ? fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what) : 0;
+}
+// d, ffn, H*dh and the K/V columns (qkv_row: the whole qkv row) are multiples of `multiple`
+int check_widths(const char* what, const pcy_llama_desc* m, int multiple, bool qkv_row) {
+  const int HD = m->n_heads * m->head_dim, last = (qkv_row ? m->n_heads + 2 * m->n_kv_heads : m->n_kv_heads) * m->head_dim;
+  if (m->d % multiple == 0 && m->ffn % multiple == 0 && HD % multiple == 0 && last % multiple == 0) return 0;
+  return fail(1, "%s: d, ffn, H*dh, %s must be multiples of %d", what, qkv_row ? "(H+2Hkv)*dh" : "Hkv*dh", multiple);
+}
+
 // GEMM for any M: MFMA tiles when M is large enough to fill them, the streaming GEMV otherwise
 // next_w / next_xn / fused (optional): RMSNorm(C) * next_w -> next_xn inside the projection's finish launch where that exists
 // (*fused = 1), see PcyGemmArgs
@@ -405,11 +421,12 @@ struct DecodeCx : DecodeWs {
   pcy_ctx* c; const pcy_llama_desc* m; const pcy_kv_cache* kv; const pcy_gen_state* st; int B;
   int qkvw; size_t layer_stride;     // columns of the qkv projection; elements between the K (V) caches of consecutive layers
   size_t prefix_layer_stride;        // ... and between the layers of the shared prefix arrays (0: a plain cache)
+  const pcy_llama_layer_fp8* w8;     // the e4m3 layers of the step that streams them (nullptr for every other step)
 };
-DecodeCx decode_cx(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
+DecodeCx decode_cx(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const pcy_llama_layer_fp8* w8 = nullptr) {
   return DecodeCx{carve_decode_ws(c->ws, m, B, kv_cap(kv)), c, m, kv, st, B, (m->n_heads + 2 * m->n_kv_heads) * m->head_dim,
                   (size_t)kv->B * m->n_kv_heads * kv->Tmax * m->head_dim,
-                  kv_shared(kv) ? (size_t)kv->prefix_B * m->n_kv_heads * kv->prefix_T * m->head_dim : 0};
+                  kv_shared(kv) ? (size_t)kv->prefix_B * m->n_kv_heads * kv->prefix_T * m->head_dim : 0, w8};
 }
 
 // Which launches serve a step: decided once, from the context's state, the geometry, the batch size and the switch snapshot.  `path` is the
@@ -529,29 +546,98 @@ PcyDecodeStepArgs step_args(const DecodeCx& cx, uint32_t* tags, size_t tag_strid
   sa.x_lines = tags + (size_t)cx.m->n_layers * tag_stride; sa.x_lines_stride = line_stride;
   return sa;
 }
-// One projection of the loop: out[B][N] = epi(in[B][K] . W^T).  STORE / SWIGLU read the residual stream through RMSNorm * ln (fused into the
-// streaming launch; batched: xn, which the caller has filled); RESID adds onto the residual stream and, batched up to 32 rows, leaves
-// RMSNorm(x) * ln of the NEXT projection in xn from its K-split finish (*xn_ready = 1 where that happened).
-PcyGemvArgs proj_args(const DecodeCx& cx, const DecodePlan& p, const void* W, const void* ln, const bf16_t* in, int K, bf16_t* out, int N, int epi,
-                      bool splitk, int krot, int* xn_ready) {
+// WHAT the four projections of decoder layer l are, in ONE place: out[B][N] = epi(in[B][K] . W^T).  STORE / SWIGLU read the residual stream
+// through RMSNorm * ln; RESID adds onto the residual stream, and next_ln is the norm in front of the projection that reads it next (behind
+// the last layer's down projection: the final norm).  HOW a shape becomes a launch is the back-end's business (launch_proj).
+enum ProjSlot { PROJ_QKV, PROJ_O, PROJ_GATE_UP, PROJ_DOWN };
+struct ProjShape {
+  ProjSlot slot; int l;          // which matrix of which layer (the e4m3 back-end takes its copy and scales by these)
+  const void *W, *ln, *next_ln;  // ... its bf16 weights; the norms (above)
+  const bf16_t* in; int K;
+  bf16_t* out; int N;            // (SWIGLU: N features out of 2 N interleaved weight rows)
+  int epi; bool splitk;          // splitk: may split K over the step's partial-sum workspace
+};
+ProjShape proj_shape(const DecodeCx& cx, int l, ProjSlot slot) {
   const pcy_llama_desc* m = cx.m;
+  const pcy_llama_layer& L = m->layers[l];
+  switch (slot) {
+    case PROJ_QKV:     return {slot, l, L.wqkv, L.ln1, nullptr, cx.x, m->d, cx.qkv, cx.qkvw, EPI_STORE, true};
+    case PROJ_O:       return {slot, l, L.wo, nullptr, L.ln2, cx.ao, m->n_heads * m->head_dim, cx.x, m->d, EPI_RESID, true};
+    case PROJ_GATE_UP: return {slot, l, L.wgu, L.ln2, nullptr, cx.x, m->d, cx.act, m->ffn, EPI_SWIGLU, false};
+    default:           return {slot, l, L.wdown, nullptr, l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm, cx.act, m->ffn, cx.x, m->d, EPI_RESID, true};
+  }
+}
+// The three back-ends.  GEMV (the decode loop, the window pass): pcy_launch_gemv -- the norm fused into the streaming launch, or (p.batched)
+// xn, which the loop has filled; RESID, batched up to 32 rows, leaves RMSNorm(x) * next_ln in xn from its K-split finish (*xn_ready = 1 where
+// that happened).  GEMM (more than 32 rows): `linear` over all B rows, fed from xn, the next norm fused into the K-split finish.  W8: the
+// e4m3 streaming GEMV, the norm always fused.
+enum ProjBackend { BACKEND_GEMV, BACKEND_GEMM, BACKEND_W8 };
+PcyGemvArgs proj_args(const DecodeCx& cx, const DecodePlan& p, const ProjShape& sh, int* xn_ready) {
   PcyGemvArgs g{};
-  g.W = (const bf16_t*)W; g.x = in; g.y = out; g.N = N; g.K = K; g.B = cx.B; g.ldx = K; g.ldy = N; g.epi = epi;
-  g.force_stream = p.nb_on; g.krot = krot;
-  if (splitk) { g.splitk_ws = cx.sk_ws; g.splitk_ws_bytes = cx.sk_bytes; }
-  if (epi == EPI_RESID) {
-    g.resid = out;
-    if (p.batched && cx.B <= 32) { g.next_rms_w = (const bf16_t*)ln; g.next_xn = cx.xn; g.fused_next = xn_ready; g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast; }
+  g.W = (const bf16_t*)sh.W; g.x = sh.in; g.y = sh.out; g.N = sh.N; g.K = sh.K; g.B = cx.B; g.ldx = sh.K; g.ldy = sh.N; g.epi = sh.epi;
+  g.force_stream = p.nb_on; g.krot = sh.slot == PROJ_DOWN ? 0 : p.krot;   // (the rotated K order: the projections over d)
+  if (sh.splitk) { g.splitk_ws = cx.sk_ws; g.splitk_ws_bytes = cx.sk_bytes; }
+  if (sh.epi == EPI_RESID) {
+    g.resid = sh.out;
+    if (p.batched && cx.B <= 32) { g.next_rms_w = (const bf16_t*)sh.next_ln; g.next_xn = cx.xn; g.fused_next = xn_ready; g.rms_eps = cx.m->rms_eps; g.rms_cast = cx.m->rms_cast; }
   } else {
-    g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast;
-    if (p.batched) g.x = cx.xn; else g.rms_w = (const bf16_t*)ln;
+    g.rms_eps = cx.m->rms_eps; g.rms_cast = cx.m->rms_cast;
+    if (p.batched) g.x = cx.xn; else g.rms_w = (const bf16_t*)sh.ln;
   }
   return g;
 }
+PcyGemvW8Args w8_args(const DecodeCx& cx, const ProjShape& sh) {
+  const pcy_llama_layer_fp8& Q = cx.w8[sh.l];
+  const void* const W[4] = {Q.wqkv, Q.wo, Q.wgu, Q.wdown}; const float* const scale[4] = {Q.sqkv, Q.so, Q.sgu, Q.sdown};   // (by ProjSlot)
+  PcyGemvW8Args g{};
+  g.W = (const uint8_t*)W[sh.slot]; g.scale = scale[sh.slot]; g.x = sh.in; g.y = sh.out; g.N = sh.N; g.K = sh.K; g.B = cx.B; g.ldx = sh.K; g.ldy = sh.N; g.epi = sh.epi;
+  if (sh.epi == EPI_RESID) g.resid = sh.out;
+  else { g.rms_w = (const bf16_t*)sh.ln; g.rms_eps = cx.m->rms_eps; g.rms_cast = cx.m->rms_cast; }
+  return g;
+}
+// defer_splits (GEMV, the loop's qkv): the attention adds up the K-split partial sums, *defer_splits of them, instead of a finish launch
+void launch_proj(const DecodeCx& cx, const DecodePlan& p, ProjBackend backend, const ProjShape& sh, int* xn_ready, int* defer_splits = nullptr) {
+  hipStream_t s = cx.c->stream;
+  switch (backend) {
+    case BACKEND_GEMV: {
+      PcyGemvArgs g = proj_args(cx, p, sh, xn_ready);
+      g.defer_finish = defer_splits;
+      // (the four-way K split of the small-batch step's down projection)
+      if (!(sh.slot == PROJ_DOWN && p.nb_on && pcy_launch_gemv_kwin4(s, g))) pcy_launch_gemv(s, g);
+      return;
+    }
+    case BACKEND_GEMM: {
+      float* sk = sh.splitk ? cx.sk_ws : nullptr;
+      if (sh.epi == EPI_RESID)   // (1: K splits that fill the chip at one or two row tiles)
+        linear(s, sh.in, sh.K, (const bf16_t*)sh.W, nullptr, sh.out, sh.N, sh.out, sh.N, cx.B, sh.N, sh.K, sh.epi, sk, sk ? cx.sk_bytes : 0,
+               (const bf16_t*)sh.next_ln, cx.xn, xn_ready, cx.m->rms_eps, cx.m->rms_cast, 1);
+      else
+        linear(s, cx.xn, sh.K, (const bf16_t*)sh.W, nullptr, nullptr, 0, sh.out, sh.N, cx.B, sh.epi == EPI_SWIGLU ? 2 * sh.N : sh.N, sh.K, sh.epi, sk, sk ? cx.sk_bytes : 0);
+      return;
+    }
+    case BACKEND_W8:
+      pcy_launch_gemv_w8(s, w8_args(cx, sh));
+      return;
+  }
+}
 
-// The split-key attention (pcy_attn_split.hip) on layer `layer` of a complete shared-prefix cache; ws: its partial sums and
-// statistics (split_ws_bytes).  Built in ONE place for pcy_attn_decode_split and the three steps that use it.
-size_t split_ws_bytes(const PcySplitPlan& p) { return align_up(p.part_bytes, 256) + align_up(p.stat_bytes, 256) + 256; }
+// One call of an attention that has a workspace of its own -- split-key (pcy_attn_split.hip, DESIGN.md 4.3f: partial sums and statistics),
+// many-queries (pcy_attn_mq.hip, 4.3d: score rows and partial sums), both on a complete shared-prefix cache, and window (pcy_attn_win.hip,
+// 4.9a: roped queries, chunk statistics and partial sums; B = the W tokens of ONE row of a plain cache, no keep mask) -- on layer `layer`:
+// what the operator entries and the steps that use them pass alike.  ws: attn_ws_bytes.
+enum AttnKind { ATTN_DECODE, ATTN_SPLIT, ATTN_MQ, ATTN_WINDOW };   // (ATTN_DECODE: the decode attention, on the step's carve -- the loop's own)
+struct AttnCall {
+  const bf16_t* qkv; int ld; const pcy_kv_cache* kv; int layer; bf16_t* o; int ldo; const int32_t* pos; const bf16_t *cos_t, *sin_t; const uint8_t* keep;
+  int B, H, Hkv, dh; char* ws;
+};
+size_t attn_ws_bytes(AttnKind kind, const pcy_kv_cache* kv, int B, int H, int Hkv, int dh) {
+  switch (kind) {
+    case ATTN_WINDOW: { const PcyWinPlan p = pcy_attn_win_plan(B, H, Hkv, dh, kv->Tmax); return align_up(p.qr_bytes, 256) + align_up(p.stats_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
+    case ATTN_MQ:     { const PcyMqPlan p = pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T); return align_up(p.sc_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
+    case ATTN_SPLIT:  { const PcySplitPlan p = pcy_attn_split_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T); return align_up(p.part_bytes, 256) + align_up(p.stat_bytes, 256) + 256; }
+    default:          return 0;   // (ATTN_DECODE: nothing beyond the step's carve)
+  }
+}
 // The workspace of a step on B rows of a cache: [decode carve][K/V reorder scratch of a beam search][buffers of the split-key attention].
 // The scratch copy of the two-launch reorder (enqueue_kv_reorder; pcy_kv_reorder_range, the beam chains) is sized for the cache's capacity,
 // not for the slots in use: a workspace that grew step by step would be re-allocated, and the captured step dropped, several times per search.
@@ -569,21 +655,105 @@ size_t reorder_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) 
 // reorder between two steps never meets them.
 size_t split_ws_offset(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) { return reorder_ws_bytes(m, kv, B); }
 size_t split_step_ws_bytes(const pcy_llama_desc* m, const pcy_kv_cache* kv, int B) {
-  return split_ws_offset(m, kv, B) + split_ws_bytes(pcy_attn_split_plan(B, kv->rows_per_prefix, m->n_heads, m->n_kv_heads, m->head_dim, kv->prefix_T));
+  return split_ws_offset(m, kv, B) + attn_ws_bytes(ATTN_SPLIT, kv, B, m->n_heads, m->n_kv_heads, m->head_dim);
 }
-PcySplitAttnArgs split_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
-                                 const bf16_t* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, char* ws) {
-  const PcySplitPlan p = pcy_attn_split_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T);
-  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh, prefix_layer_stride = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
-  PcySplitAttnArgs a{};
-  a.qkv = qkv; a.ld = ld; a.k_own = (bf16_t*)kv->k + layer * layer_stride; a.v_own = (bf16_t*)kv->v + layer * layer_stride;
-  a.k_pre = (const bf16_t*)kv->prefix_k + layer * prefix_layer_stride; a.v_pre = (const bf16_t*)kv->prefix_v + layer * prefix_layer_stride;
-  a.Town = kv->Tmax; a.Tp = kv->prefix_T; a.rows_per_prefix = kv->rows_per_prefix; a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t;
-  a.keep = keep; a.ld_keep = kv_cap(kv); a.B = B; a.H = H; a.Hkv = Hkv; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
-  Carver cv(ws);
-  a.part = cv.take<float>(p.part_bytes / sizeof(float)); a.stat = cv.take<float2>(p.stat_bytes / sizeof(float2));
-  a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks;
+// the views of a layer of a complete shared-prefix cache, which the two attentions over it name alike
+template <typename Args>
+Args prefix_attn_args(const AttnCall& c) {
+  const pcy_kv_cache* kv = c.kv;
+  const size_t layer_stride = (size_t)kv->B * c.Hkv * kv->Tmax * c.dh, prefix_layer_stride = (size_t)kv->prefix_B * c.Hkv * kv->prefix_T * c.dh;
+  Args a{};
+  a.qkv = c.qkv; a.ld = c.ld; a.k_own = (bf16_t*)kv->k + c.layer * layer_stride; a.v_own = (bf16_t*)kv->v + c.layer * layer_stride;
+  a.k_pre = (const bf16_t*)kv->prefix_k + c.layer * prefix_layer_stride; a.v_pre = (const bf16_t*)kv->prefix_v + c.layer * prefix_layer_stride;
+  a.Town = kv->Tmax; a.Tp = kv->prefix_T; a.rows_per_prefix = kv->rows_per_prefix; a.o = c.o; a.ldo = c.ldo; a.pos_dev = c.pos; a.cos_t = c.cos_t; a.sin_t = c.sin_t;
+  a.keep = c.keep; a.ld_keep = kv_cap(kv); a.B = c.B; a.H = c.H; a.Hkv = c.Hkv; a.dh = c.dh; a.scale = 1.0f / sqrtf((float)c.dh);
   return a;
+}
+bool launch_attn(hipStream_t s, AttnKind kind, const AttnCall& c) {   // false = shape not covered, nothing launched
+  const pcy_kv_cache* kv = c.kv;
+  Carver cv(c.ws);
+  switch (kind) {
+    case ATTN_SPLIT: {
+      const PcySplitPlan p = pcy_attn_split_plan(c.B, kv->rows_per_prefix, c.H, c.Hkv, c.dh, kv->prefix_T);
+      PcySplitAttnArgs a = prefix_attn_args<PcySplitAttnArgs>(c);
+      a.part = cv.take<float>(p.part_bytes / sizeof(float)); a.stat = cv.take<float2>(p.stat_bytes / sizeof(float2));
+      a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks;
+      return pcy_launch_attn_split(s, a);
+    }
+    case ATTN_MQ: {
+      const PcyMqPlan p = pcy_attn_mq_plan(c.B, kv->rows_per_prefix, c.H, c.Hkv, c.dh, kv->prefix_T);
+      PcyMqAttnArgs a = prefix_attn_args<PcyMqAttnArgs>(c);
+      a.sc = cv.take<bf16_t>(p.sc_bytes / sizeof(bf16_t)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
+      a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks; a.lds = p.lds;
+      return pcy_launch_attn_mq(s, a);
+    }
+    case ATTN_WINDOW: {
+      const PcyWinPlan p = pcy_attn_win_plan(c.B, c.H, c.Hkv, c.dh, kv->Tmax);
+      const size_t layer_stride = (size_t)kv->B * c.Hkv * kv->Tmax * c.dh;
+      PcyWinAttnArgs a{};
+      a.qkv = c.qkv; a.ld = c.ld; a.kcache = (bf16_t*)kv->k + c.layer * layer_stride; a.vcache = (bf16_t*)kv->v + c.layer * layer_stride;
+      a.o = c.o; a.ldo = c.ldo; a.pos_dev = c.pos; a.cos_t = c.cos_t; a.sin_t = c.sin_t; a.W = c.B; a.H = c.H; a.Hkv = c.Hkv; a.dh = c.dh; a.Tmax = kv->Tmax;
+      a.scale = 1.0f / sqrtf((float)c.dh);
+      a.qr = cv.take<bf16_t>(p.qr_bytes / sizeof(bf16_t)); a.stats = cv.take<float2>(p.stats_bytes / sizeof(float2)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
+      a.nchunk = p.nchunk;
+      return pcy_launch_attn_window(s, a);
+    }
+    default: return false;
+  }
+}
+
+// *xn_ready: xn = RMSNorm(x) * (the norm of the NEXT projection) already stands in xn, written by a K-split finish (or by a fused step)
+void norm_if_needed(const DecodeCx& cx, bool feeds_xn, const void* ln, int* xn_ready) {
+  if (feeds_xn && !*xn_ready) pcy_launch_rmsnorm(cx.c->stream, cx.x, (const bf16_t*)ln, cx.xn, cx.B, cx.m->d, cx.m->rms_eps, cx.m->rms_cast);
+  *xn_ready = 0;
+}
+// THE layer loop of every launch-per-stage bf16 step, layers [l0, n_layers): norm if needed -> qkv -> attention -> o -> norm if needed ->
+// gate / up -> down.  The caller picks the projection back-end (BACKEND_W8: on cx.w8) and the attention (attn_ws: the workspace of a kind
+// other than ATTN_DECODE); the plan says what else happens -- attn_o (the decode attention and o in one launch where the launcher takes it),
+// defer_qkv_finish, krot, nb_on, batched, force_ds: all off in a zeroed plan.  *xn_ready: as above, on entry and on return.
+void enqueue_layers(const DecodeCx& cx, const DecodePlan& p, ProjBackend backend, AttnKind attn, char* attn_ws, int l0, int* xn_ready) {
+  pcy_ctx* c = cx.c;
+  const pcy_llama_desc* m = cx.m;
+  const bool feeds_xn = backend == BACKEND_GEMM || (backend == BACKEND_GEMV && p.batched);   // the projections over x read xn, not a fused norm
+  for (int l = l0; l < m->n_layers; ++l) {
+    const ProjShape qkv = proj_shape(cx, l, PROJ_QKV), o = proj_shape(cx, l, PROJ_O), gu = proj_shape(cx, l, PROJ_GATE_UP), down = proj_shape(cx, l, PROJ_DOWN);
+    norm_if_needed(cx, feeds_xn, qkv.ln, xn_ready);
+    int qkv_splits = 0;
+    launch_proj(cx, p, backend, qkv, nullptr, p.defer_qkv_finish ? &qkv_splits : nullptr);
+    bool o_done = false;
+    if (attn == ATTN_DECODE) {
+      PcyDecAttnArgs t = attn_args(cx, p, l);
+      if (qkv_splits > 1) { t.qkv_partials = cx.sk_ws; t.qkv_splits = qkv_splits; }
+      o_done = p.attn_o && pcy_launch_attn_o(c->stream, t, proj_args(cx, p, o, xn_ready), c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err,
+                                                     c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS);   // (the last: key-split flags of this layer's launch)
+      if (!o_done) { t.xmin = 0; pcy_launch_attn_decode(c->stream, t); }   // (no key split in the stand-alone attention)
+    } else {
+      launch_attn(c->stream, attn, AttnCall{cx.qkv, cx.qkvw, cx.kv, l, cx.ao, m->n_heads * m->head_dim, cx.st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, cx.st->keep,
+                                            cx.B, m->n_heads, m->n_kv_heads, m->head_dim, attn_ws});
+    }
+    if (!o_done) launch_proj(cx, p, backend, o, xn_ready);
+    norm_if_needed(cx, feeds_xn, gu.ln, xn_ready);
+    launch_proj(cx, p, backend, gu, nullptr);
+    launch_proj(cx, p, backend, down, xn_ready);
+  }
+}
+// THE lm_head tail of the GEMV steps, on cx.B rows: the streaming GEMV with the final norm fused, or norm + MFMA GEMV from xn (p.batched_head).
+// force_stream (and the small-batch arithmetic, p.nb_on): the fused norm on the streaming kernel whatever B -- rows in groups of <= 4, a
+// row's bits do not depend on the batch (the e4m3 step; the fused norm selects that kernel anyway).
+// (4 rows on the small-batch step: the streaming kernel -- one pass over the matrix for up to 4 rows -- instead of norm + MFMA GEMV: 3.178 ->
+// 3.153 ms per step; 5 and 8 rows would take two passes: 3.51 -> 3.65, 4.00 -> 4.15)
+void enqueue_lm_head(const DecodeCx& cx, const DecodePlan& p, void* logits_out, int xn_ready, bool force_stream = false) {
+  const pcy_llama_desc* m = cx.m;
+  PcyGemvArgs h{};
+  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)logits_out; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
+  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = m->d; h.B = cx.B; h.ldx = m->d; h.ldy = m->vocab; h.epi = EPI_STORE;
+  if (p.batched_head && !(p.nb_on && cx.B <= 4)) {
+    norm_if_needed(cx, true, m->final_norm, &xn_ready);
+    h.x = cx.xn; h.rms_w = nullptr;
+  } else {
+    h.force_stream = p.nb_on || force_stream;
+  }
+  pcy_launch_gemv(cx.c->stream, h);
 }
 
 // layers_only (measurement, pcy_llama_decode_layers): the decoder layers without the token embedding (the residual stream is whatever
@@ -593,11 +763,10 @@ PcySplitAttnArgs split_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* 
 void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, const PcySwitches& sw, bool layers_only = false,
                     bool split = false) {
   hipStream_t s = c->stream;
-  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
+  const int d = m->d, dh = m->head_dim;
   const DecodeCx cx = decode_cx(c, m, kv, st, B);
   DecodePlan p = plan_decode(c, m, kv, B, sw);
   if (split) { p.defer_qkv_finish = false; p.attn_o = false; }
-  char* split_ws = split ? c->ws + split_ws_offset(m, kv, B) : nullptr;
   if (layers_only) {
     if (p.epoch_word) pcy_launch_bump(s, p.epoch_word);
     if (p.tag_word) pcy_launch_bump(s, p.tag_word);
@@ -606,7 +775,7 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
   }
   const size_t tag_stride = tag_words_per_layer(m);
   bool step_done = false;
-  bool try_layer = p.path == DEC_STEP_GQA || p.path == DEC_STEP_MHA || p.path == DEC_LAYERS;   // one launch per decoder layer (behind a step that declines, too)
+  const bool try_layer = p.path == DEC_STEP_GQA || p.path == DEC_STEP_MHA || p.path == DEC_LAYERS;   // one launch per decoder layer (behind a step that declines, too)
   int xn_ready = 0;   // batched path: xn = RMSNorm(x) of the NEXT projection already produced by a fused finish kernel
   if (p.path == DEC_STEP_NB) {   // 2..8 rows, all layers in one launch
     const PcyDecodeStepArgs sa = step_args(cx, c->nb_tags[B], pcy_decode_nb_tag_words(B), 2 * AO_FLAGS, pcy_decode_nb_line_words(B));   // up to 128 attention units per layer
@@ -629,59 +798,23 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
     pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->layers[0].ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
     if (pcy_launch_decode_step_mb(s, c->device, ma, c->n_cu)) { step_done = true; xn_ready = 1; ++g_pcy_dispatch[PCY_DISPATCH_DEC_STEP_MB]; }
   }
-  for (int l = 0; l < (step_done ? 0 : m->n_layers); ++l) {
+  int l = step_done ? m->n_layers : 0;
+  for (; try_layer && l < m->n_layers; ++l) {   // the whole layer as one launch (a geometry it does not cover: the same for every layer)
     const pcy_llama_layer& L = m->layers[l];
-    PcyDecAttnArgs t = attn_args(cx, p, l);
-    unsigned* xflags = c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS;   // key-split flags of this layer's fused launch
-    if (try_layer) {   // the whole layer as one launch
-      uint32_t* tags = c->mc_tags + (size_t)l * tag_stride;
-      if (pcy_launch_decode_layer(s, t, block_args(cx, p.tag_word, mc_trace(sw, l), &L, tags), mlp_args(cx, p.tag_word, &L, tags), c->n_cu, c->ao_sync, xflags)) {
-        if (l == 0) ++g_pcy_dispatch[PCY_DISPATCH_DEC_LAYER];   // (one count per step)
-        continue;
-      }
-      try_layer = false;   // geometry not covered: the same for every layer
-    }
-    if (l == 0) ++g_pcy_dispatch[p.batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
-    if (l == 0 && kv_shared(kv)) ++g_pcy_dispatch[PCY_DISPATCH_SHARED_PREFIX];
-    // (batched: the previous layer's down projection may have written xn already, fused into its K-split finish)
-    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    PcyGemvArgs g = proj_args(cx, p, L.wqkv, L.ln1, cx.x, d, cx.qkv, cx.qkvw, EPI_STORE, true, p.krot, nullptr);
-    int qkv_splits = 0;
-    if (p.defer_qkv_finish) g.defer_finish = &qkv_splits;
-    pcy_launch_gemv(s, g);
-    if (qkv_splits > 1) { t.qkv_partials = cx.sk_ws; t.qkv_splits = qkv_splits; }
-    const PcyGemvArgs o = proj_args(cx, p, L.wo, L.ln2, cx.ao, H * dh, cx.x, d, EPI_RESID, true, p.krot, &xn_ready);
-    if (split) {
-      pcy_launch_attn_split(s, split_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
-                                               B, H, m->n_kv_heads, dh, split_ws));
-      pcy_launch_gemv(s, o);
-    } else if (!(p.attn_o && pcy_launch_attn_o(s, t, o, c->n_cu, c->ao_sync, c->ao_sync + 64 + l * AO_FLAGS, AO_FLAGS, c->xwg_err, xflags))) {
-      t.xmin = 0;   // (no key split in the stand-alone attention)
-      pcy_launch_attn_decode(s, t);
-      pcy_launch_gemv(s, o);
-    }
-    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, B, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    pcy_launch_gemv(s, proj_args(cx, p, L.wgu, L.ln2, cx.x, d, cx.act, F, EPI_SWIGLU, false, p.krot, nullptr));
-    const PcyGemvArgs w = proj_args(cx, p, L.wdown, l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm, cx.act, F, cx.x, d, EPI_RESID, true, 0, &xn_ready);
-    if (p.nb_on && pcy_launch_gemv_kwin4(s, w)) continue;   // (the four-way K split of the small-batch step's down projection)
-    pcy_launch_gemv(s, w);
+    uint32_t* tags = c->mc_tags + (size_t)l * tag_stride;
+    if (!pcy_launch_decode_layer(s, attn_args(cx, p, l), block_args(cx, p.tag_word, mc_trace(sw, l), &L, tags), mlp_args(cx, p.tag_word, &L, tags), c->n_cu,
+                                 c->ao_sync, c->ao_sync + 64 + (AO_MAX_LAYERS + l) * AO_FLAGS))   // (the last: key-split flags of this layer's launch)
+      break;
+    if (l == 0) ++g_pcy_dispatch[PCY_DISPATCH_DEC_LAYER];   // (one count per step)
   }
+  if (l == 0 && m->n_layers > 0) {
+    ++g_pcy_dispatch[p.batched ? PCY_DISPATCH_DEC_LOOP_MFMA : PCY_DISPATCH_DEC_LOOP_STREAM];
+    if (kv_shared(kv)) ++g_pcy_dispatch[PCY_DISPATCH_SHARED_PREFIX];
+  }
+  enqueue_layers(cx, p, BACKEND_GEMV, split ? ATTN_SPLIT : ATTN_DECODE, split ? c->ws + split_ws_offset(m, kv, B) : nullptr, l, &xn_ready);
   if (layers_only) return;
   if (split) ++g_pcy_attn_split;
-  PcyGemvArgs h{};
-  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
-  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = B; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
-  // (4 rows on the small-batch step: the streaming kernel with the final norm fused -- one pass over the matrix for up to 4 rows -- instead of
-  // norm + MFMA GEMV: 3.178 -> 3.153 ms per step; 5 and 8 rows would take two passes: 3.51 -> 3.65, 4.00 -> 4.15)
-  if (p.batched_head && !(p.nb_on && B <= 4)) {
-    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, B, d, m->rms_eps, m->rms_cast);
-    h.x = cx.xn; h.rms_w = nullptr;
-  } else if (p.nb_on) {
-    h.force_stream = 1;
-  }
-  pcy_launch_gemv(s, h);
+  enqueue_lm_head(cx, p, st->logits, xn_ready);
 }
 
 // Record of the per-step logits (the reference returns it on the CPU, model_unified.py:892,917-921).  `all` may be PINNED
@@ -997,7 +1130,7 @@ int pcy_rope(pcy_ctx* c, void* buf, int ld, int col0, int nh, int dh, const int3
 int pcy_attention(pcy_ctx* c, const void* q, int ldq, int qcol0, const void* k, int ldk, int kcol0, const void* v, int ldv,
                   int vcol0, void* o, int ldo, const int32_t* cu, const int32_t* vt_cu, const uint8_t* keep, int nseq,
                   int max_len, int vt_total, int H, int Hkv, int dh, int causal, float scale) {
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_attention: head_dim %d unsupported (32/64/128)", dh);
+  if (int r = check_head_dim("pcy_attention", dh, true)) return r;
   if ((Hkv * dh) % 64 || H % Hkv) return fail(1, "pcy_attention: Hkv*dh must be a multiple of 64 and Hkv | H");
   // the single-pass kernel wants every sequence's Vt slice zero-padded to a multiple of 64 keys: it lays Vt out itself (offsets
   // computed on the device from cu), whatever vt_cu / vt_total the caller passed
@@ -1029,9 +1162,7 @@ int pcy_attention(pcy_ctx* c, const void* q, int ldq, int qcol0, const void* k, 
 
 int pcy_attn_decode(pcy_ctx* c, void* qkv, int ld, void* kcache, void* vcache, void* o, int ldo, const int32_t* pos,
                     const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, int Tmax) {
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_attn_decode: head_dim %d unsupported (32/64/128)", dh);
-  const int G = H / Hkv;
-  if (H % Hkv || !(G == 1 || G == 2 || G == 4 || G == 8)) return fail(1, "pcy_attn_decode: H/Hkv must be 1, 2, 4 or 8");
+  if (int r = check_heads("pcy_attn_decode", H, Hkv, dh, true)) return r;
   PcyDecAttnArgs t{};
   t.qkv = (bf16_t*)qkv; t.ld = ld; t.kcache = (bf16_t*)kcache; t.vcache = (bf16_t*)vcache; t.o = (bf16_t*)o; t.ldo = ldo;
   t.pos_dev = pos; t.cos_t = (const bf16_t*)cos_t; t.sin_t = (const bf16_t*)sin_t; t.keep = keep; t.ld_keep = Tmax;
@@ -1298,7 +1429,7 @@ static int esm_encode_enqueue(pcy_ctx* c, const pcy_esm_desc* m, const int32_t* 
   const int d = m->d, H = m->n_heads, F = m->ffn;
   if (d % H) return fail(1, "pcy_esm_encode: d %% heads");
   const int dh = d / H;
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_esm_encode: head_dim %d unsupported (32/64/128)", dh);
+  if (int r = check_head_dim("pcy_esm_encode", dh, true)) return r;
   if (d % 64 || F % 64) return fail(1, "pcy_esm_encode: d and ffn must be multiples of 64");
   if (ntok <= 0) return 0;
   // single-pass attention (default at head_dim 64): Vt slices zero-padded to 64 keys, laid out by the engine itself
@@ -1445,11 +1576,11 @@ int check_prefix_groups(const pcy_kv_cache* kv, const pcy_prefix_groups* gr, int
 }
 int check_prefill_req(const pcy_llama_desc* m, const pcy_kv_cache* kv, const PrefillReq& r, int* g_max_rows) {   // g_max_rows: of a grouped extension
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn, B = r.B, T = r.T;
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "pcy_llama_prefill: head_dim %d unsupported (32/64/128)", dh);
-  if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "pcy_llama_prefill: d, ffn, H*dh, Hkv*dh must be multiples of 64");
+  if (int e = check_head_dim("pcy_llama_prefill", dh, true)) return e;
+  if (int e = check_widths("pcy_llama_prefill", m, 64, false)) return e;
   if (r.ext.on) {
     const int t_past = r.ext.t_past;
-    if (dh != 64 && dh != 128) return fail(1, "pcy_llama_extend: head_dim %d unsupported (64/128)", dh);
+    if (int e = check_head_dim("pcy_llama_extend", dh, false)) return e;
     if (H % Hkv) return fail(1, "pcy_llama_extend: H=%d is no multiple of Hkv=%d", H, Hkv);
     if (m->layers_fp8) return fail(1, "pcy_llama_extend: fp8 projections are not supported on the extension path");
     if (B < 1 || T < 1 || t_past < 0) return fail(1, "pcy_llama_extend: B=%d S=%d t_past=%d", B, T, t_past);
@@ -1657,7 +1788,7 @@ int attn_extend_entry(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, con
                       const void* cos_t, const void* sin_t, const uint8_t* keep, int B, int S, int H, int Hkv, int dh, bool packed) {
   PCY_STICKY(c);
   const char* what = grp ? "pcy_attn_extend_grouped" : "pcy_attn_extend";
-  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
+  if (int r = check_head_dim(what, dh, false)) return r;
   if (Hkv < 1 || H % Hkv) return fail(1, "%s: H=%d is no multiple of Hkv=%d", what, H, Hkv);
   if (layer < 0 || (!grp && (!kv || !kv->k || !kv->v || B < 1 || S < 1 || t_past < 0)))   // (a grouped call: check_prefix_groups has words of its own)
     return fail(1, "%s: B=%d S=%d t_past=%d layer=%d", what, B, S, t_past, layer);
@@ -1774,8 +1905,7 @@ int check_mq_cache(const pcy_kv_cache* kv, int B, int H, int Hkv, int dh, const 
   if (!kv_shared(kv)) return fail(1, "%s: the cache has no shared prefix (plain caches: the decode attention)", what);
   if (kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
   if (int r = check_shared_cache(kv, B, what)) return r;
-  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
-  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (int r = check_heads(what, H, Hkv, dh, false)) return r;
   if (!pcy_attn_mq_covers(H, Hkv, dh, kv->Tmax)) return fail(1, "%s: the scores of %d suffix slots do not fit in LDS", what, kv->Tmax);
   return 0;
 }
@@ -1949,54 +2079,17 @@ int pcy_llama_decode_graph(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cac
 // epilogues.  The attention is the loop's stand-alone launch (all rows, *pos and the keep mask from device memory, shared-prefix caches).
 // The workspace is the decode carve: the pick / sampling launches behind the step find their partials where they expect them.
 
-// The many-queries attention (pcy_attn_mq.hip) on layer `layer` of a complete shared-prefix cache; ws: its score rows and partial
-// sums (mq_ws_bytes).  Built in ONE place for pcy_attn_decode_shared and the step of pcy_llama_decode_gemm_mq.
-static size_t mq_ws_bytes(const PcyMqPlan& p) { return align_up(p.sc_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
-static PcyMqAttnArgs mq_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
-                                  const bf16_t* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh, char* ws) {
-  const PcyMqPlan p = pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T);
-  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh, prefix_layer_stride = (size_t)kv->prefix_B * Hkv * kv->prefix_T * dh;
-  PcyMqAttnArgs a{};
-  a.qkv = qkv; a.ld = ld; a.k_own = (bf16_t*)kv->k + layer * layer_stride; a.v_own = (bf16_t*)kv->v + layer * layer_stride;
-  a.k_pre = (const bf16_t*)kv->prefix_k + layer * prefix_layer_stride; a.v_pre = (const bf16_t*)kv->prefix_v + layer * prefix_layer_stride;
-  a.Town = kv->Tmax; a.Tp = kv->prefix_T; a.rows_per_prefix = kv->rows_per_prefix; a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t;
-  a.keep = keep; a.ld_keep = kv_cap(kv); a.B = B; a.H = H; a.Hkv = Hkv; a.dh = dh; a.scale = 1.0f / sqrtf((float)dh);
-  Carver cv(ws);
-  a.sc = cv.take<bf16_t>(p.sc_bytes / sizeof(bf16_t)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
-  a.ntiles = p.ntiles; a.nchunk = p.nchunk; a.cblocks = p.cblocks; a.lds = p.lds;
-  return a;
-}
 // mq: the attention launch of every layer is the many-queries one, its buffers behind the decode carve (pcy_llama_decode_gemm_mq)
 // split: ... the split-key one, its buffers at split_ws_offset (pcy_llama_decode_gemm_split)
 static void enqueue_decode_gemm(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, bool mq, bool split = false) {
-  hipStream_t s = c->stream;
-  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
   const DecodeCx cx = decode_cx(c, m, kv, st, B);
-  char* mq_ws = c->ws + align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256);
-  char* split_ws = split ? c->ws + split_ws_offset(m, kv, B) : nullptr;
+  char* attn_ws = c->ws + (split ? split_ws_offset(m, kv, B) : align_up(decode_ws_bytes(m, B, kv_cap(kv)), 256));
   const DecodePlan p{};   // (the stand-alone attention: no key split, its own column cut)
-  pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
-  int xn_ready = 0;   // xn = RMSNorm(x) of the next projection already written by a K-split finish launch
-  for (int l = 0; l < m->n_layers; ++l) {
-    const pcy_llama_layer& L = m->layers[l];
-    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, B, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    linear(s, cx.xn, d, (const bf16_t*)L.wqkv, nullptr, nullptr, 0, cx.qkv, cx.qkvw, B, cx.qkvw, d, EPI_STORE, cx.sk_ws, cx.sk_bytes);
-    if (split) pcy_launch_attn_split(s, split_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin,
-                                                        st->keep, B, H, m->n_kv_heads, dh, split_ws));
-    else if (mq) pcy_launch_attn_mq(s, mq_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, st->keep,
-                                               B, H, m->n_kv_heads, dh, mq_ws));
-    else pcy_launch_attn_decode(s, attn_args(cx, p, l));
-    linear(s, cx.ao, H * dh, (const bf16_t*)L.wo, nullptr, cx.x, d, cx.x, d, B, d, H * dh, EPI_RESID, cx.sk_ws, cx.sk_bytes,
-           (const bf16_t*)L.ln2, cx.xn, &xn_ready, m->rms_eps, m->rms_cast, 1);   // (1: K splits that fill the chip at one or two row tiles)
-    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, B, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    linear(s, cx.xn, d, (const bf16_t*)L.wgu, nullptr, nullptr, 0, cx.act, F, B, 2 * F, d, EPI_SWIGLU);
-    linear(s, cx.act, F, (const bf16_t*)L.wdown, nullptr, cx.x, d, cx.x, d, B, d, F, EPI_RESID, cx.sk_ws, cx.sk_bytes,
-           (const bf16_t*)(l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm), cx.xn, &xn_ready, m->rms_eps, m->rms_cast, 1);
-  }
-  if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, B, d, m->rms_eps, m->rms_cast);
-  linear(s, cx.xn, d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)st->logits, m->vocab, B, m->vocab, d, EPI_STORE);
+  pcy_launch_embed_tokens_dev(c->stream, (const bf16_t*)m->embed, st->next_tok, cx.x, B, m->d);
+  int xn_ready = 0;
+  enqueue_layers(cx, p, BACKEND_GEMM, split ? ATTN_SPLIT : mq ? ATTN_MQ : ATTN_DECODE, attn_ws, 0, &xn_ready);
+  norm_if_needed(cx, true, m->final_norm, &xn_ready);
+  linear(c->stream, cx.xn, m->d, (const bf16_t*)m->lm_head, nullptr, nullptr, 0, (bf16_t*)st->logits, m->vocab, B, m->vocab, m->d, EPI_STORE);
   ++g_pcy_decode_gemm;
   if (mq) ++g_pcy_attn_mq;
   if (split) ++g_pcy_attn_split;
@@ -2006,21 +2099,16 @@ static int decode_gemm_entry(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_c
   PCY_STICKY(c);
   const char* what = split ? "pcy_llama_decode_gemm_split" : mq ? "pcy_llama_decode_gemm_mq" : "pcy_llama_decode_gemm";
   if (int r = check_step_args(m, kv, st, B, what)) return r;
-  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  const int H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim;
   if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
   if (kv_shared(kv) && kv->rows_per_prefix == 0) return fail(1, "%s: a grouped cache (rows_per_prefix == 0) is read by the extension entries only", what);
   if (int r = check_shared_cache(kv, B, what)) return r;
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (32/64/128)", what, dh);
-  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
-  if (d % 64 || F % 64 || (H * dh) % 64 || (Hkv * dh) % 64) return fail(1, "%s: d, ffn, H*dh, Hkv*dh must be multiples of 64", what);
+  if (int r = check_heads(what, H, Hkv, dh, true)) return r;
+  if (int r = check_widths(what, m, 64, false)) return r;
   size_t need = decode_ws_bytes(m, B, kv_cap(kv));
-  if (mq) {
+  if (mq || split) {   // (one set of cache and geometry rules for the two attentions on a shared prefix)
     if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
-    need = align_up(need, 256) + mq_ws_bytes(pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T));
-  }
-  if (split) {   // (the same cache and geometry rules as the many-queries attention)
-    if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
-    need = split_step_ws_bytes(m, kv, B);
+    need = split ? split_step_ws_bytes(m, kv, B) : align_up(need, 256) + attn_ws_bytes(ATTN_MQ, kv, B, H, Hkv, dh);
   }
   if (int r = c->reserve(need)) return r;
   enqueue_decode_gemm(c, m, kv, st, B, mq, split);
@@ -2044,17 +2132,9 @@ unsigned long long pcy_debug_decode_gemm_count(void) { return g_pcy_decode_gemm;
 unsigned long long pcy_debug_attn_mq_count(void) { return g_pcy_attn_mq; }
 
 // ---- the decode step that streams e4m3 weights: weight-only fp8 projections, 1..8 rows ----
-// One launch per stage, built the way enqueue_decode_gemm is: the four projections of a layer are pcy_launch_gemv_w8 launches (RMSNorm fused
+// One launch per stage, the layer loop on its e4m3 back-end: the four projections of a layer are pcy_launch_gemv_w8 launches (RMSNorm fused
 // into qkv and gate/up, residual epilogue on o and down), the attention is the loop's stand-alone launch, lm_head stays bf16 on the streaming
 // GEMV with the final norm fused.  The workspace is the decode carve.
-static PcyGemvW8Args w8_args(const void* W, const float* scale, const bf16_t* x, int K, bf16_t* y, int N, int B, int epi, const void* ln,
-                             const pcy_llama_desc* m) {
-  PcyGemvW8Args g{};
-  g.W = (const uint8_t*)W; g.scale = scale; g.x = x; g.y = y; g.N = N; g.K = K; g.B = B; g.ldx = K; g.ldy = N; g.epi = epi;
-  if (epi == EPI_RESID) g.resid = y;
-  else { g.rms_w = (const bf16_t*)ln; g.rms_eps = m->rms_eps; g.rms_cast = m->rms_cast; }
-  return g;
-}
 static uint64_t w8_fingerprint(const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8) {   // as layers_fingerprint
   uint64_t h = fnv1a(FNV_BASIS, {m->final_norm, m->lm_head, m->rope_cos, m->rope_sin});
   for (int l = 0; l < m->n_layers; ++l) {
@@ -2064,28 +2144,15 @@ static uint64_t w8_fingerprint(const pcy_llama_desc* m, const pcy_llama_layer_fp
   return h;
 }
 static void enqueue_decode_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
-  hipStream_t s = c->stream;
-  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
-  const DecodeCx cx = decode_cx(c, m, kv, st, B);
+  const DecodeCx cx = decode_cx(c, m, kv, st, B, w8);
   DecodePlan p{};   // (the stand-alone attention: no key split)
   // Its column cut is the one a ONE-row step gets, whatever B: the launcher otherwise widens the cut with Hkv * B, and the order of a row's
   // sums with it -- a row's bits would depend on the batch it sits in (head_dim 128; the other head sizes have one cut).
   p.force_ds = m->n_kv_heads >= 128 ? 128 : m->n_kv_heads >= 32 ? 64 : 16;
-  pcy_launch_embed_tokens_dev(s, (const bf16_t*)m->embed, st->next_tok, cx.x, B, d);
-  for (int l = 0; l < m->n_layers; ++l) {
-    const pcy_llama_layer& L = m->layers[l];
-    const pcy_llama_layer_fp8& Q = w8[l];
-    pcy_launch_gemv_w8(s, w8_args(Q.wqkv, Q.sqkv, cx.x, d, cx.qkv, cx.qkvw, B, EPI_STORE, L.ln1, m));
-    pcy_launch_attn_decode(s, attn_args(cx, p, l));
-    pcy_launch_gemv_w8(s, w8_args(Q.wo, Q.so, cx.ao, H * dh, cx.x, d, B, EPI_RESID, nullptr, m));
-    pcy_launch_gemv_w8(s, w8_args(Q.wgu, Q.sgu, cx.x, d, cx.act, F, B, EPI_SWIGLU, L.ln2, m));
-    pcy_launch_gemv_w8(s, w8_args(Q.wdown, Q.sdown, cx.act, F, cx.x, d, B, EPI_RESID, nullptr, m));
-  }
-  PcyGemvArgs h{};
-  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)st->logits; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
-  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = B; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
-  h.force_stream = 1;   // (the fused norm selects the streaming kernel anyway, rows in groups of <= 4: a row's bits do not depend on B)
-  pcy_launch_gemv(s, h);
+  pcy_launch_embed_tokens_dev(c->stream, (const bf16_t*)m->embed, st->next_tok, cx.x, B, m->d);
+  int xn_ready = 0;
+  enqueue_layers(cx, p, BACKEND_W8, ATTN_DECODE, nullptr, 0, &xn_ready);
+  enqueue_lm_head(cx, p, st->logits, xn_ready, true);
   ++g_pcy_decode_w8;
 }
 // everything pcy_llama_decode_w8 / pcy_llama_greedy_w8 refuse; reserves the workspace behind the checks
@@ -2102,9 +2169,8 @@ static int decode_w8_check(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_
   const int bmax = kv->B < 8 ? kv->B : 8;
   if (B < 1 || B > bmax) return fail(1, "%s: B=%d outside [1, min(8, cache rows %d)]", what, B, kv->B);
   if (kv_shared(kv)) return fail(1, "%s: a shared-prefix or grouped cache is not served by this step (plain caches only)", what);
-  if (dh != 32 && dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (32/64/128)", what, dh);
-  if (Hkv < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
-  if (d % 16 || F % 16 || (H * dh) % 16 || ((H + 2 * Hkv) * dh) % 16) return fail(1, "%s: d, ffn, H*dh, (H+2Hkv)*dh must be multiples of 16", what);
+  if (int r = check_heads(what, H, Hkv, dh, true)) return r;
+  if (int r = check_widths(what, m, 16, true)) return r;
   if ((size_t)d * 2 * 4 > 65536) return fail(1, "%s: d=%d: the fused final norm of lm_head needs 4 rows of x in 64 KiB of LDS", what, d);
   if (pcy_gemv_w8_rows_per_pass(d) < 1 || pcy_gemv_w8_rows_per_pass(F) < 1 || pcy_gemv_w8_rows_per_pass(H * dh) < 1)
     return fail(1, "%s: a row of x (d, ffn or H*dh elements) does not fit in LDS", what);
@@ -2397,65 +2463,26 @@ int pcy_gemv_w8(pcy_ctx* c, const void* W8, const float* scale, const void* x, i
 }
 
 // ---- the lookahead pass on the decode loop: W consecutive tokens of ONE cache row ----
-// The window attention (pcy_attn_win.hip) on layer `layer` of a plain one-row cache; ws: its roped queries, chunk statistics and partial sums
-// (win_ws_bytes).  Built in ONE place for pcy_attn_window and the step of pcy_llama_decode_window.
-static size_t win_ws_bytes(const PcyWinPlan& p) { return align_up(p.qr_bytes, 256) + align_up(p.stats_bytes, 256) + align_up(p.part_bytes, 256) + 256; }
-static PcyWinAttnArgs win_attn_args(const bf16_t* qkv, int ld, const pcy_kv_cache* kv, int layer, bf16_t* o, int ldo, const int32_t* pos, const bf16_t* cos_t,
-                                    const bf16_t* sin_t, int W, int H, int Hkv, int dh, char* ws) {
-  const PcyWinPlan p = pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax);
-  const size_t layer_stride = (size_t)kv->B * Hkv * kv->Tmax * dh;
-  PcyWinAttnArgs a{};
-  a.qkv = qkv; a.ld = ld; a.kcache = (bf16_t*)kv->k + layer * layer_stride; a.vcache = (bf16_t*)kv->v + layer * layer_stride;
-  a.o = o; a.ldo = ldo; a.pos_dev = pos; a.cos_t = cos_t; a.sin_t = sin_t; a.W = W; a.H = H; a.Hkv = Hkv; a.dh = dh; a.Tmax = kv->Tmax;
-  a.scale = 1.0f / sqrtf((float)dh);
-  Carver cv(ws);
-  a.qr = cv.take<bf16_t>(p.qr_bytes / sizeof(bf16_t)); a.stats = cv.take<float2>(p.stats_bytes / sizeof(float2)); a.part = cv.take<float>(p.part_bytes / sizeof(float));
-  a.nchunk = p.nchunk;
-  return a;
-}
 // what the operator refuses, for the operator entry and the step alike
 static int check_win_call(const pcy_kv_cache* kv, int W, int H, int Hkv, int dh, const char* what) {
   if (kv_shared(kv)) return fail(1, "%s: a shared-prefix or grouped cache is not served by the window attention (plain caches only)", what);
   if (kv->B != 1) return fail(1, "%s: the cache holds %d rows (the window is W tokens of ONE row: kv->B == 1)", what, kv->B);
   if (W < 2 || W > 32) return fail(1, "%s: W=%d outside [2, 32]", what, W);
-  if (dh != 64 && dh != 128) return fail(1, "%s: head_dim %d unsupported (64/128)", what, dh);
-  if (Hkv < 1 || H < 1 || H % Hkv || !(H / Hkv == 1 || H / Hkv == 2 || H / Hkv == 4 || H / Hkv == 8)) return fail(1, "%s: H/Hkv must be 1, 2, 4 or 8", what);
+  if (int r = check_heads(what, H, Hkv, dh, false)) return r;   // (H >= 1 follows from Hkv >= 1 and the ratio)
   if (kv->Tmax < W) return fail(1, "%s: the cache holds %d slots, fewer than the %d of a window", what, kv->Tmax, W);
   if (((uintptr_t)kv->k | (uintptr_t)kv->v) & 15) return fail(1, "%s: the cache must be 16-byte aligned", what);
   return 0;
 }
-// The loop of enqueue_decode at B = W (its helpers, unchanged: proj_args, the K-split finish with the fused next norm, SwiGLU, the final norm +
-// lm_head GEMV), never a fused step, with the window attention in the place of the decode attention and the GEMV's own finish launch.
+// The layer loop at B = W on the GEMV back-end, never a fused step, with the window attention in the place of the decode attention and the
+// GEMV's own finish launch; the final norm + lm_head GEMV.
 static void enqueue_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int W, void* logits_out) {
-  hipStream_t s = c->stream;
-  const int d = m->d, H = m->n_heads, dh = m->head_dim, F = m->ffn;
   const DecodeCx cx = decode_cx(c, m, kv, st, W);
-  char* win_ws = c->ws + align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256);
   DecodePlan p{};   // (the loop alone: no fused step, no deferred qkv finish, no rotated K order, no key split)
-  p.batched_head = W >= pcy_mfma_min_batch() && d % 128 == 0 && F % 128 == 0;
+  p.batched_head = W >= pcy_mfma_min_batch() && m->d % 128 == 0 && m->ffn % 128 == 0;
   p.batched = p.batched_head;
   int xn_ready = 0;
-  for (int l = 0; l < m->n_layers; ++l) {
-    const pcy_llama_layer& L = m->layers[l];
-    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln1, cx.xn, W, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    pcy_launch_gemv(s, proj_args(cx, p, L.wqkv, L.ln1, cx.x, d, cx.qkv, cx.qkvw, EPI_STORE, true, 0, nullptr));
-    pcy_launch_attn_window(s, win_attn_args(cx.qkv, cx.qkvw, kv, l, cx.ao, H * dh, st->pos, (const bf16_t*)m->rope_cos, (const bf16_t*)m->rope_sin, W, H,
-                                            m->n_kv_heads, dh, win_ws));
-    pcy_launch_gemv(s, proj_args(cx, p, L.wo, L.ln2, cx.ao, H * dh, cx.x, d, EPI_RESID, true, 0, &xn_ready));
-    if (p.batched && !xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)L.ln2, cx.xn, W, d, m->rms_eps, m->rms_cast);
-    xn_ready = 0;
-    pcy_launch_gemv(s, proj_args(cx, p, L.wgu, L.ln2, cx.x, d, cx.act, F, EPI_SWIGLU, false, 0, nullptr));
-    pcy_launch_gemv(s, proj_args(cx, p, L.wdown, l + 1 < m->n_layers ? m->layers[l + 1].ln1 : m->final_norm, cx.act, F, cx.x, d, EPI_RESID, true, 0, &xn_ready));
-  }
-  PcyGemvArgs h{};
-  h.W = (const bf16_t*)m->lm_head; h.x = cx.x; h.y = (bf16_t*)logits_out; h.rms_w = (const bf16_t*)m->final_norm; h.rms_eps = m->rms_eps;
-  h.rms_cast = m->rms_cast; h.N = m->vocab; h.K = d; h.B = W; h.ldx = d; h.ldy = m->vocab; h.epi = EPI_STORE;
-  if (p.batched_head) {
-    if (!xn_ready) pcy_launch_rmsnorm(s, cx.x, (const bf16_t*)m->final_norm, cx.xn, W, d, m->rms_eps, m->rms_cast);
-    h.x = cx.xn; h.rms_w = nullptr;
-  }
-  pcy_launch_gemv(s, h);
+  enqueue_layers(cx, p, BACKEND_GEMV, ATTN_WINDOW, c->ws + align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256), 0, &xn_ready);
+  enqueue_lm_head(cx, p, logits_out, xn_ready);
   ++g_pcy_decode_window;
 }
 int pcy_llama_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, const void* embeds, int W,
@@ -2465,10 +2492,10 @@ int pcy_llama_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_ca
   if (!m || !kv || !st || !kv->k || !kv->v || !st->pos || !m->layers || !embeds || !logits_out) return fail(1, "%s: model, cache, state, embeds or logits_out incomplete", what);
   if (st->keep) return fail(1, "%s: a keep mask is not supported (lookahead prompts are unpadded)", what);
   if (m->layers_fp8) return fail(1, "%s: fp8 projections are not supported on this step", what);
-  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
+  const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim;
   if (int r = check_win_call(kv, W, H, Hkv, dh, what)) return r;
-  if (d % 16 || F % 16 || (H * dh) % 16 || ((H + 2 * Hkv) * dh) % 16) return fail(1, "%s: d, ffn, H*dh, (H+2Hkv)*dh must be multiples of 16", what);
-  const size_t need = align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256) + win_ws_bytes(pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax));
+  if (int r = check_widths(what, m, 16, true)) return r;
+  const size_t need = align_up(decode_ws_bytes(m, W, kv_cap(kv)), 256) + attn_ws_bytes(ATTN_WINDOW, kv, W, H, Hkv, dh);
   if (int r = c->reserve(need)) return r;
   HIP_TRY(hipMemcpyAsync(carve_decode_ws(c->ws, m, W, kv_cap(kv)).x, embeds, (size_t)W * d * 2, hipMemcpyDeviceToDevice, c->stream));
   enqueue_decode_window(c, m, kv, st, W, logits_out);
@@ -2477,48 +2504,31 @@ int pcy_llama_decode_window(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_ca
 unsigned long long pcy_debug_decode_window_count(void) { return g_pcy_decode_window; }
 int pcy_attn_window_chunk(void) { return pcy_attn_win_chunk(); }
 
+// The operator entries of the attentions with a workspace of their own: what they share.  An entry states its kind -- the cache check, the
+// workspace size and the launcher follow from it (check_win_call / check_mq_cache, attn_ws_bytes, launch_attn).
+static int attn_op_entry(pcy_ctx* c, const char* what, AttnKind kind, AttnCall a) {
+  PCY_STICKY(c);
+  const pcy_kv_cache* kv = a.kv;
+  if (!a.qkv || !kv || !kv->k || !kv->v || !a.o || !a.pos || !a.cos_t || !a.sin_t || a.layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, a.layer);
+  if (kind != ATTN_WINDOW && (a.B < 1 || a.B > kv->B)) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, a.B, kv->B);   // (the window: W, below)
+  if (int r = kind == ATTN_WINDOW ? check_win_call(kv, a.B, a.H, a.Hkv, a.dh, what) : check_mq_cache(kv, a.B, a.H, a.Hkv, a.dh, what)) return r;
+  if (a.ld % 8 || a.ld < (a.H + 2 * a.Hkv) * a.dh || a.ldo % 8 || a.ldo < a.H * a.dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, a.ld, a.ldo);
+  if (int r = c->reserve(attn_ws_bytes(kind, kv, a.B, a.H, a.Hkv, a.dh))) return r;
+  a.ws = c->ws;
+  if (!launch_attn(c->stream, kind, a)) return fail(1, "%s: shape not covered", what);
+  return check_launch(what);
+}
 int pcy_attn_window(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
                     const void* sin_t, int W, int H, int Hkv, int dh) {
-  PCY_STICKY(c);
-  const char* what = "pcy_attn_window";
-  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
-  if (int r = check_win_call(kv, W, H, Hkv, dh, what)) return r;
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
-  if (int r = c->reserve(win_ws_bytes(pcy_attn_win_plan(W, H, Hkv, dh, kv->Tmax)))) return r;
-  if (!pcy_launch_attn_window(c->stream, win_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t,
-                                                       W, H, Hkv, dh, c->ws)))
-    return fail(1, "%s: shape not covered", what);
-  return check_launch(what);
+  return attn_op_entry(c, "pcy_attn_window", ATTN_WINDOW, AttnCall{(const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, nullptr, W, H, Hkv, dh, nullptr});
 }
-
 int pcy_attn_decode_shared(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
                            const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh) {
-  PCY_STICKY(c);
-  const char* what = "pcy_attn_decode_shared";
-  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
-  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
-  if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
-  if (int r = c->reserve(mq_ws_bytes(pcy_attn_mq_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T)))) return r;
-  if (!pcy_launch_attn_mq(c->stream, mq_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
-                                                  B, H, Hkv, dh, c->ws)))
-    return fail(1, "%s: shape not covered", what);
-  return check_launch(what);
+  return attn_op_entry(c, "pcy_attn_decode_shared", ATTN_MQ, AttnCall{(const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep, B, H, Hkv, dh, nullptr});
 }
-
 int pcy_attn_decode_split(pcy_ctx* c, void* qkv, int ld, const pcy_kv_cache* kv, int layer, void* o, int ldo, const int32_t* pos, const void* cos_t,
                           const void* sin_t, const uint8_t* keep, int B, int H, int Hkv, int dh) {
-  PCY_STICKY(c);
-  const char* what = "pcy_attn_decode_split";
-  if (!qkv || !kv || !kv->k || !kv->v || !o || !pos || !cos_t || !sin_t || layer < 0) return fail(1, "%s: qkv, cache, o, pos or rope tables missing (layer=%d)", what, layer);
-  if (B < 1 || B > kv->B) return fail(1, "%s: B=%d outside [1, cache rows %d]", what, B, kv->B);
-  if (int r = check_mq_cache(kv, B, H, Hkv, dh, what)) return r;
-  if (ld % 8 || ld < (H + 2 * Hkv) * dh || ldo % 8 || ldo < H * dh) return fail(1, "%s: ld=%d ldo=%d (rows must be 16-byte aligned and hold all heads)", what, ld, ldo);
-  if (int r = c->reserve(split_ws_bytes(pcy_attn_split_plan(B, kv->rows_per_prefix, H, Hkv, dh, kv->prefix_T)))) return r;
-  if (!pcy_launch_attn_split(c->stream, split_attn_args((const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep,
-                                                        B, H, Hkv, dh, c->ws)))
-    return fail(1, "%s: shape not covered", what);
-  return check_launch(what);
+  return attn_op_entry(c, "pcy_attn_decode_split", ATTN_SPLIT, AttnCall{(const bf16_t*)qkv, ld, kv, layer, (bf16_t*)o, ldo, pos, (const bf16_t*)cos_t, (const bf16_t*)sin_t, keep, B, H, Hkv, dh, nullptr});
 }
 
 int pcy_llama_decode_split(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B) {
