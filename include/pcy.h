@@ -62,10 +62,30 @@ int pcy_timer_start(pcy_ctx* ctx);
 int pcy_timer_stop(pcy_ctx* ctx, float* ms_out);
 
 /* ---- primitive ops (unit parity tests; also what the host composes for odd shapes) ---------- */
-/* C[M,N] = epi(A[M,K] . W[N,K]^T + bias); EPI_SWIGLU: W is [N,K] with 16-row gate/up interleave, C is [M,N/2] */
+/* C[M,N] = epi(A[M,K] . W[N,K]^T + bias); EPI_SWIGLU: W is [N,K] with 16-row gate/up interleave, C is [M,N/2] (bias and resid are not read).
+ * Rounding points: bf16(acc + bias), then bf16(. + resid) (EPI_RESID) or the bf16 -> bf16 activation; SwiGLU bf16(bf16(silu(bf16 g)) * bf16 u).
+ * Operands (all bf16; lda / ldr / ldc = elements between rows):
+ *   A [M, K] at stride lda, W [N, K] contiguous: read as 16-byte pieces of a row by LDS-DMA -- A and W 16-byte aligned, lda % 8 == 0,
+ *     lda >= K, K a positive multiple of 64.  Rows M.. of A and N.. of W are never read, nor columns K.. of a row of A.
+ *   C [M, N] at stride ldc >= N (N/2 for SwiGLU), resid [M, N] at stride ldr >= N (EPI_RESID only), bias [N] or NULL: any 2-byte aligned
+ *     address and any stride.  The kernels move them as 8- or 16-byte pieces where strides, N and the three addresses allow it and element
+ *     by element otherwise, with the same bits; only columns [0, N) of rows [0, M) are read or written.
+ *   resid may be C itself with ldr == ldc (in place: every element is read before it is written, by the same lane); any other overlap of
+ *     C with an input is outside the contract.
+ *   EPI_SWIGLU: N % 32 == 0, and the store is one 8-byte piece per four features with no element-wise form: C 8-byte aligned, ldc % 4 == 0.
+ * M == 0 or N == 0 returns 0 without a launch.  Refused with code 1 before any launch (C untouched): anything else -- an unknown epi, a NULL A /
+ * W / C, EPI_RESID without resid, a negative size, K, lda, ldc, ldr or an alignment outside the above. */
 int pcy_gemm(pcy_ctx*, const void* A, int lda, const void* W, const void* bias, const void* resid, int ldr,
              void* C, int ldc, int M, int N, int K, int epi);
-/* y[B,N] = epi(x[B,K] . W[N,K]^T); rms_w != NULL fuses RMSNorm(x)*rms_w in front (rms_cast 0: >=4.32, 1: 4.31) */
+/* y[B,N] = epi(x[B,K] . W[N,K]^T + bias); rms_w != NULL fuses RMSNorm(x)*rms_w in front (rms_cast 0: >=4.32, 1: 4.31; STORE / SWIGLU only,
+ * min(B, 4) rows of x within 64 KiB).  EPI_SWIGLU: N = features, W is [2N, K] in the 16-row gate/up interleave, bias and resid are not read.
+ * Operands (bf16): W [N, K] contiguous, x [B, K] at stride ldx, rms_w [K]: read as 16-byte pieces -- W, x, rms_w 16-byte aligned, K > 0,
+ *   K % 8 == 0, ldx % 8 == 0, ldx >= K.  y [B, N] and resid [B, N] (EPI_RESID only) BOTH at stride ldy >= N, bias [N] or NULL: any 2-byte
+ *   aligned address; 8-byte stores are used where ldy and y allow them, single elements otherwise, same bits.  resid may be y itself.
+ *   EPI_SWIGLU: N % 16 == 0, y 8-byte aligned and ldy % 4 == 0 (the MFMA kernels store four features as one piece, no other form).
+ * Only columns [0, N) of rows [0, B) of y are written.  N == 0 or B == 0 returns 0 without a launch; everything outside the above is refused
+ * with code 1 before any launch (y untouched).  A row's bits depend neither on the other rows nor, among calls served by one kernel
+ * (pcy_debug_gemv_route_count), on B; the streaming and the MFMA kernels add in different orders. */
 int pcy_gemv(pcy_ctx*, const void* W, const void* x, int ldx, const void* bias, const void* resid, void* y, int ldy,
              const void* rms_w, float rms_eps, int rms_cast, int N, int K, int B, int epi);
 /* One token through a Llama MLP, in place: x[d] += (silu(g) * u) . Wdown^T with [g; u] = (RMSNorm(x) * ln2) . Wgu^T
@@ -98,6 +118,14 @@ int pcy_attention(pcy_ctx*, const void* q, int ldq, int qcol0, const void* k, in
  * counts as kind 6 of pcy_debug_dispatch_count and under none of these.  Words of their own, as pcy_debug_look_count: the kinds of
  * pcy_debug_dispatch_count are pinned.  Kernels 2 and 3 give one sequence the same bits (same key-block order, same rounding points). */
 unsigned long long pcy_debug_attn_route_count(int which);
+/* Test instrumentation: launches of pcy_gemv (and of every other caller of its launcher: the launch-per-stage decode steps) since the library
+ * was loaded, by the kernel chosen, counted where the launch is decided -- 0: streaming, 2-row units; 1: streaming, 4-row units (N >= 8189);
+ * 2: chunked (min(B, 4) rows of x exceed 64 KiB of LDS); 3: MFMA, weights through registers (PCY_DISABLE=gemv_lds); 4: MFMA, weights by
+ * LDS-DMA, x one chunk ahead (PCY_DISABLE=gemv_mfma4); 5: MFMA, x and weights as pairs (B >= 4, K % 128 == 0, no fused norm); anything else
+ * reads 0.  One count per launch: a batch is served in passes of 4 rows (0 - 2) or 32 rows (3 - 5).  Words of their own, as
+ * pcy_debug_attn_route_count.  Kernels 3, 4 and 5 issue the same MFMAs in the same order (same bits); the streaming kernels add in another
+ * order. */
+unsigned long long pcy_debug_gemv_route_count(int which);
 /* Decode attention of ONE new token per row against the [B,Hkv,Tmax,dh] cache: ropes q and the new k at position
  * *pos (device scalar = cache length), appends K,V at slot *pos, attends slots [0,*pos] (keep: optional [B,Tmax]
  * key mask, NULL = the reference's unmasked decode, quirk Q1).  qkv [B,(H+2Hkv)*dh] un-roped projections.
@@ -166,7 +194,10 @@ size_t pcy_lm_head_xent_ws_bytes(int M, int V);
  * channel) and per call on activations (per token). */
 int pcy_quant_rows_fp8(pcy_ctx*, const void* x, int ldx, int rows, int K, void* q_out, float* scale_out);
 /* C[M,N] = epi( ((A8[M,K] . W8[N,K]^T) * sa[m]) * sw[n] ) on the MX-scaled 16x16x128 fp8 MFMA (unit block scales), fp32
- * accumulation, then the same bf16 rounding points as pcy_gemm.  epi in {STORE, RESID, SWIGLU}; K % 128 == 0. */
+ * accumulation, then the same bf16 rounding points as pcy_gemm.  epi in {STORE, RESID, SWIGLU}; K a positive multiple of 128.
+ * Operands: A8 [M, K] and W8 [N, K] contiguous e4m3 bytes, 16-byte aligned; sa [M], sw [N] fp32, 4-byte aligned (sw is read as 16-byte
+ * pieces where its address allows); C, resid, ldc, ldr, the in-place residual and the SwiGLU rule exactly as pcy_gemm; no bias.
+ * Refused with code 1 before any launch (C untouched): everything outside that, as pcy_gemm. */
 int pcy_gemm_fp8(pcy_ctx*, const void* A8, const float* sa, const void* W8, const float* sw, const void* resid, int ldr,
                  void* C, int ldc, int M, int N, int K, int epi);
 

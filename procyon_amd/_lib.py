@@ -21,6 +21,8 @@ DISPATCH_DECODE = dict(step_gqa=DISPATCH_DEC_STEP_GQA, step_mha=DISPATCH_DEC_STE
                        step_mb=DISPATCH_DEC_STEP_MB, loop_stream=DISPATCH_DEC_LOOP_STREAM, loop_mfma=DISPATCH_DEC_LOOP_MFMA)
 # pcy_debug_attn_route_count words: which two-pass prefill attention kernel the launcher chose
 ATTN_ROUTE_DH32, ATTN_ROUTE_DH64, ATTN_ROUTE_LDS128_1, ATTN_ROUTE_LDS128_2 = range(4)
+# pcy_debug_gemv_route_count words: which kernel pcy_launch_gemv chose
+GEMV_ROUTE_STREAM2, GEMV_ROUTE_STREAM4, GEMV_ROUTE_CHUNKED, GEMV_ROUTE_MFMA2, GEMV_ROUTE_MFMA3, GEMV_ROUTE_MFMA4 = range(6)
 
 vp = C.c_void_p
 i32 = C.c_int32
@@ -120,6 +122,7 @@ SIGNATURES = {
     "pcy_rope": (ci, [vp, vp, ci, ci, ci, ci, vp, vp, vp, ci, ci, C.c_float]),
     "pcy_attention": (ci, [vp, vp, ci, ci, vp, ci, ci, vp, ci, ci, vp, ci, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, C.c_float]),
     "pcy_debug_attn_route_count": (C.c_ulonglong, [ci]),
+    "pcy_debug_gemv_route_count": (C.c_ulonglong, [ci]),
     "pcy_attn_decode": (ci, [vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),
     "pcy_attn_extend_packed": (ci, [vp, vp, ci, C.POINTER(KvCache), ci, vp, ci, ci, vp, vp, vp, ci, ci, ci, ci, ci]),

@@ -957,6 +957,27 @@ void enqueue_kv_reorder(hipStream_t s, const pcy_llama_desc* m, const pcy_kv_cac
 
 }  // namespace
 
+// Operand contract of pcy_gemm / pcy_gemm_fp8 (include/pcy.h), checked before any launch.  row_align = elements per 16 bytes of A and W (8 bf16,
+// 16 e4m3): every kernel stages their rows as 16-byte LDS-DMA pieces.  C / resid / bias go through epilogues that test strides and bases
+// themselves and fall back to single elements -- except the SwiGLU epilogue of the natural row order, which always stores 8 bytes.
+static int check_gemm_operands(const char* who, const void* A, int lda, int row_align, const void* W, const void* bias, const void* resid, int ldr,
+                        void* C, int ldc, int M, int N, int K, int epi, int epi_max) {
+  if (epi < EPI_STORE || epi > epi_max) return fail(1, "%s: epilogue %d unknown", who, epi);
+  if (M < 0 || N < 0) return fail(1, "%s: M=%d N=%d", who, M, N);
+  if (M == 0 || N == 0) return 0;
+  if (!A || !W || !C) return fail(1, "%s: A, W and C are required", who);
+  if (lda < K || lda % row_align != 0 || ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(W)) & 15))
+    return fail(1, "%s: rows of A and W must be 16-byte aligned (lda=%d a multiple of %d), lda >= K=%d", who, lda, row_align, K);
+  const int Nout = epi == EPI_SWIGLU ? N / 2 : N;
+  if (ldc < Nout || (epi == EPI_RESID && ldr < N)) return fail(1, "%s: ldc=%d / ldr=%d must cover the %d output columns", who, ldc, ldr, Nout);
+  if ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(resid) | reinterpret_cast<uintptr_t>(bias)) & 1)
+    return fail(1, "%s: C, resid and bias hold bf16 elements (2-byte aligned)", who);
+  if (epi == EPI_RESID && resid == C && ldr != ldc) return fail(1, "%s: an in-place residual needs ldr == ldc (%d, %d)", who, ldr, ldc);
+  if (epi == EPI_SWIGLU && (ldc % 4 != 0 || (reinterpret_cast<uintptr_t>(C) & 7)))
+    return fail(1, "%s: SwiGLU needs ldc %% 4 == 0 (ldc=%d) and an 8-byte aligned C", who, ldc);
+  return 0;
+}
+
 // ====================================================================================== C ABI
 hipStream_t pcy_ctx_stream(pcy_ctx* c) { return c->stream; }
 void* pcy_ctx_reserve(pcy_ctx* c, size_t bytes) { return c->reserve(bytes) == 0 ? c->ws : nullptr; }
@@ -964,6 +985,7 @@ extern "C" {
 int pcy_abi_version(void) { return PCY_ABI_VERSION; }
 unsigned long long pcy_debug_dispatch_count(int kind) { return (kind >= 0 && kind < PCY_DISPATCH_N) ? g_pcy_dispatch[kind] : 0; }
 unsigned long long pcy_debug_attn_route_count(int which) { return (which >= 0 && which < PCY_ATTN_ROUTE_N) ? g_pcy_attn_route[which] : 0; }
+unsigned long long pcy_debug_gemv_route_count(int which) { return (which >= 0 && which < PCY_GEMV_ROUTE_N) ? g_pcy_gemv_route[which] : 0; }
 const char* pcy_last_error(void) { return g_err; }
 
 int pcy_ctx_create(int device_id, void* stream, pcy_ctx** out) {
@@ -1018,9 +1040,10 @@ int pcy_timer_stop(pcy_ctx* c, float* ms) {
 
 int pcy_gemm(pcy_ctx* c, const void* A, int lda, const void* W, const void* bias, const void* resid, int ldr, void* C,
              int ldc, int M, int N, int K, int epi) {
-  if (K % 64 != 0) return fail(1, "pcy_gemm: K=%d must be a multiple of 64", K);
+  if (K <= 0 || K % 64 != 0) return fail(1, "pcy_gemm: K=%d must be a positive multiple of 64", K);
   if (epi == EPI_SWIGLU && N % 32 != 0) return fail(1, "pcy_gemm: SwiGLU needs N %% 32 == 0");
   if (epi == EPI_RESID && !resid) return fail(1, "pcy_gemm: EPI_RESID without residual");
+  if (int r = check_gemm_operands("pcy_gemm", A, lda, 8, W, bias, resid, ldr, C, ldc, M, N, K, epi, EPI_SWIGLU)) return r;
   PcyGemmArgs a{};
   a.A = (const bf16_t*)A; a.W = (const bf16_t*)W; a.C = (bf16_t*)C; a.bias = (const bf16_t*)bias; a.resid = (const bf16_t*)resid;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldc = ldc; a.ldr = ldr; a.epi = epi;
@@ -1047,7 +1070,20 @@ int pcy_lm_head_xent(pcy_ctx* c, const void* x, int ldx, const void* W, int M, i
 
 int pcy_gemv(pcy_ctx* c, const void* W, const void* x, int ldx, const void* bias, const void* resid, void* y, int ldy,
              const void* rms_w, float rms_eps, int rms_cast, int N, int K, int B, int epi) {
-  if (K % 8 != 0 || ldx % 8 != 0) return fail(1, "pcy_gemv: K and ldx must be multiples of 8");
+  if (K <= 0 || K % 8 != 0 || ldx % 8 != 0) return fail(1, "pcy_gemv: K=%d and ldx=%d must be multiples of 8, K > 0", K, ldx);
+  if (epi < EPI_STORE || epi > EPI_SWIGLU) return fail(1, "pcy_gemv: epilogue %d unknown", epi);
+  if (N < 0 || B < 0) return fail(1, "pcy_gemv: N=%d B=%d", N, B);
+  if (N == 0 || B == 0) return 0;
+  if (!W || !x || !y) return fail(1, "pcy_gemv: W, x and y are required");
+  // every kernel reads W and x (and rms_w) as 16-byte pieces of a row, straight or through LDS-DMA
+  if (ldx < K || ((reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(rms_w)) & 15))
+    return fail(1, "pcy_gemv: rows of W, x and rms_w must be 16-byte aligned, ldx=%d >= K=%d", ldx, K);
+  if (ldy < N || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(resid) | reinterpret_cast<uintptr_t>(bias)) & 1))
+    return fail(1, "pcy_gemv: ldy=%d must cover N=%d; y, resid and bias hold bf16 elements (2-byte aligned)", ldy, N);
+  if (epi == EPI_RESID && !resid) return fail(1, "pcy_gemv: EPI_RESID without residual");
+  // the MFMA kernels store four SwiGLU outputs as one 8-byte piece, with no element-wise form
+  if (epi == EPI_SWIGLU && (N % 16 != 0 || ldy % 4 != 0 || (reinterpret_cast<uintptr_t>(y) & 7)))
+    return fail(1, "pcy_gemv: SwiGLU needs N %% 16 == 0 (N=%d), ldy %% 4 == 0 (ldy=%d) and an 8-byte aligned y", N, ldy);
   if (rms_w && !(epi == EPI_STORE || epi == EPI_SWIGLU)) return fail(1, "pcy_gemv: fused RMSNorm only with STORE/SWIGLU");
   if (rms_w && (size_t)K * 2 * (B < 4 ? B : 4) > 65536) return fail(1, "pcy_gemv: fused RMSNorm needs x to fit LDS");
   PcyGemvArgs g{};
@@ -1181,6 +1217,10 @@ int pcy_gemm_fp8(pcy_ctx* c, const void* A8, const float* sa, const void* W8, co
   if (K <= 0 || K % 128) return fail(1, "pcy_gemm_fp8: K=%d must be a multiple of 128", K);
   if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU) return fail(1, "pcy_gemm_fp8: epilogue %d unsupported", epi);
   if (epi == EPI_SWIGLU && N % 32) return fail(1, "pcy_gemm_fp8: SwiGLU needs N %% 32 == 0");
+  if (epi == EPI_RESID && !resid) return fail(1, "pcy_gemm_fp8: EPI_RESID without residual");
+  if (int r = check_gemm_operands("pcy_gemm_fp8", A8, K, 16, W8, nullptr, resid, ldr, C, ldc, M, N, K, epi, EPI_SWIGLU)) return r;
+  if (M > 0 && N > 0 && (!sa || !sw || ((reinterpret_cast<uintptr_t>(sa) | reinterpret_cast<uintptr_t>(sw)) & 3)))
+    return fail(1, "pcy_gemm_fp8: sa and sw are required, 4-byte aligned");
   PcyGemmArgs a{};
   a.A = (const bf16_t*)A8; a.W = (const bf16_t*)W8; a.C = (bf16_t*)C; a.resid = (const bf16_t*)resid;
   a.M = M; a.N = N; a.K = K; a.lda = K; a.ldc = ldc; a.ldr = ldr; a.epi = epi; a.fp8 = 1; a.sa = sa; a.sw = sw;

@@ -118,7 +118,10 @@ __device__ __forceinline__ void gemm_epilogue(const PcyGemmArgs& a, f32x4 (&acc)
   auto emit = [&](int m, int n, uint2 w) __attribute__((always_inline)) {
     *reinterpret_cast<uint2*>(a.C + (size_t)m * a.ldc + n) = w;
   };
-  const bool vec_ok = (a.ldc % 4 == 0) && (a.N % 4 == 0) && (a.resid == nullptr || a.ldr % 4 == 0);
+  // (8-byte pieces of C, resid and bias: row strides AND bases -- as gemm_epilogue_perm tests its 16-byte pieces; else element by element)
+  const bool vec_ok = (a.ldc % 4 == 0) && (a.N % 4 == 0) && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0 &&
+                      (a.resid == nullptr || (a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.resid) & 7) == 0)) &&
+                      (a.bias == nullptr || (reinterpret_cast<uintptr_t>(a.bias) & 7) == 0);
   if (EPI == EPI_SWIGLU) {
 #pragma unroll
     for (int j = 0; j < WTM; ++j) {

@@ -452,6 +452,8 @@ void launch_stream(hipStream_t s, const PcyGemvArgs& a) {
   int blocks, wpb;
   pick_grid(units, blocks, wpb);
   const size_t smem = (size_t)NB * a.K * 2 + 64;
+  static PcyLdsAttr lds;   // (x of exactly 64 KiB plus the reduction words is above the size a kernel may ask for unconfigured)
+  lds.ensure(&gemv_stream_kernel<NB, EPI, RMS, R>, smem);
   hipLaunchKernelGGL((gemv_stream_kernel<NB, EPI, RMS, R>), dim3(blocks), dim3(wpb * 64), smem, s, a, units);
 }
 
@@ -459,15 +461,18 @@ template <int NB, int EPI, bool RMS>
 void launch_nb(hipStream_t s, const PcyGemvArgs& a) {
   if ((size_t)NB * a.K * 2 <= XS_BYTES_MAX) {
     // few rows -> 2-row units so that the launch still spreads over ~2k waves
-    if ((a.N + 3) / 4 < GEMV_MAX_WAVES) launch_stream<NB, EPI, RMS, 2>(s, a);
-    else launch_stream<NB, EPI, RMS, 4>(s, a);
+    if ((a.N + 3) / 4 < GEMV_MAX_WAVES) { ++g_pcy_gemv_route[PCY_GEMV_ROUTE_STREAM2]; launch_stream<NB, EPI, RMS, 2>(s, a); }
+    else { ++g_pcy_gemv_route[PCY_GEMV_ROUTE_STREAM4]; launch_stream<NB, EPI, RMS, 4>(s, a); }
     return;
   }
+  ++g_pcy_gemv_route[PCY_GEMV_ROUTE_CHUNKED];
   int KC = a.K;
   if ((size_t)NB * KC * 2 > XS_BYTES_MAX) KC = (XS_BYTES_MAX / (NB * 2)) & ~511;
   const size_t smem = (size_t)NB * KC * 2 + 64;
   const int blocks = (a.N + 15) / 16;
   constexpr int UN = (EPI == EPI_SWIGLU) ? 2 : 4;
+  static PcyLdsAttr lds;   // (a full 64-KiB chunk plus the reduction words, as above)
+  lds.ensure(&gemv_kernel<NB, EPI, RMS, UN>, smem);
   hipLaunchKernelGGL((gemv_kernel<NB, EPI, RMS, UN>), dim3(blocks), dim3(GEMV_THREADS), smem, s, a, KC);
 }
 
@@ -678,7 +683,7 @@ __device__ __forceinline__ void mfma_gemv_epilogue(const PcyGemvArgs& a, f32x4 (
         if (EPI == EPI_GELU_ERF) v[r] = rbf(gelu_erf_f(v[r]));
         if (EPI == EPI_GELU_ESM) v[r] = gelu_esm_chain(v[r]);
       }
-      if (n + 3 < a.N && (a.ldy & 3) == 0) {
+      if (n + 3 < a.N && (a.ldy & 3) == 0 && (reinterpret_cast<uintptr_t>(a.y) & 7) == 0) {   // (8-byte store: row stride AND base)
         *reinterpret_cast<uint2*>(a.y + (size_t)b * a.ldy + n) = make_uint2(pack_bf(v[0], v[1]), pack_bf(v[2], v[3]));
       } else {
 #pragma unroll
@@ -1068,11 +1073,16 @@ void launch_mfma(hipStream_t s, const PcyGemvArgs& a) {
     // PCY_DISABLE=gemv_mfma4: the previous schedule (gemv_mfma3_kernel: x one chunk ahead); read per call, same bits
     const bool v4 = lds && (!pcy_off("gemv_mfma4") || kunit == 128) && a.K % (ksplit * 128) == 0;
     if (v4 && (a.B <= 16 ? launch_mfma4<EPI, 1>(s, a, bx, ksplit) : launch_mfma4<EPI, 2>(s, a, bx, ksplit))) {
+      ++g_pcy_gemv_route[PCY_GEMV_ROUTE_MFMA4];
     } else if (lds) {
+      ++g_pcy_gemv_route[PCY_GEMV_ROUTE_MFMA3];
       if (a.B <= 16) launch_mfma3<EPI, 1>(s, a, bx, ksplit);
       else launch_mfma3<EPI, 2>(s, a, bx, ksplit);
-    } else if (a.B <= 16) hipLaunchKernelGGL((gemv_mfma2_kernel<EPI, 1>), dim3(bx, ksplit), dim3(256), 0, s, a, ksplit);
-    else hipLaunchKernelGGL((gemv_mfma2_kernel<EPI, 2>), dim3(bx, ksplit), dim3(256), 0, s, a, ksplit);
+    } else {
+      ++g_pcy_gemv_route[PCY_GEMV_ROUTE_MFMA2];
+      if (a.B <= 16) hipLaunchKernelGGL((gemv_mfma2_kernel<EPI, 1>), dim3(bx, ksplit), dim3(256), 0, s, a, ksplit);
+      else hipLaunchKernelGGL((gemv_mfma2_kernel<EPI, 2>), dim3(bx, ksplit), dim3(256), 0, s, a, ksplit);
+    }
     if (a.defer_finish) *a.defer_finish = 0;
     if (ksplit > 1 && EPI == EPI_STORE && a.defer_finish && !a.bias) { *a.defer_finish = ksplit; return; }
     if (ksplit > 1) {
@@ -1148,6 +1158,9 @@ __global__ __launch_bounds__(256) void gemv_kwin4_kernel(PcyGemvArgs a) {
 }
 
 }  // namespace
+
+// launches per kernel, counted where the launch is decided (pcy_debug_gemv_route_count)
+unsigned long long g_pcy_gemv_route[PCY_GEMV_ROUTE_N] = {};
 
 bool pcy_launch_splitk_finish_norm(hipStream_t s, const float* ws, int splits, int rows, int N, const bf16_t* resid, bf16_t* y,
                                    const bf16_t* next_rms_w, bf16_t* next_xn, float rms_eps, int rms_cast) {

@@ -210,6 +210,16 @@ enum { PCY_ATTN_ROUTE_DH32 = 0,       // attn_kernel<32, 2>
        PCY_ATTN_ROUTE_LDS128_2 = 3,   // attn_lds_kernel<128, 2>
        PCY_ATTN_ROUTE_N = 4 };
 extern unsigned long long g_pcy_attn_route[PCY_ATTN_ROUTE_N];
+// which kernel pcy_launch_gemv chose (pcy_debug_gemv_route_count), one count per launch -- a batch above 4 (streaming / chunked) or 32 (MFMA)
+// rows counts once per pass.  Words of their own as well.
+enum { PCY_GEMV_ROUTE_STREAM2 = 0,    // gemv_stream_kernel, 2-row units
+       PCY_GEMV_ROUTE_STREAM4 = 1,    // gemv_stream_kernel, 4-row units
+       PCY_GEMV_ROUTE_CHUNKED = 2,    // gemv_kernel (x does not fit LDS: K in chunks)
+       PCY_GEMV_ROUTE_MFMA2 = 3,      // gemv_mfma2_kernel
+       PCY_GEMV_ROUTE_MFMA3 = 4,      // gemv_mfma3_kernel
+       PCY_GEMV_ROUTE_MFMA4 = 5,      // gemv_mfma4_kernel
+       PCY_GEMV_ROUTE_N = 6 };
+extern unsigned long long g_pcy_gemv_route[PCY_GEMV_ROUTE_N];
 
 // lm_head x cross-entropy without logits in memory (pcy_xent.hip): nll[m] = logsumexp_n(bf16(x[m] . W[n])) - bf16(x[m] . W[targets[m]]).
 // x [M, d] bf16 (ldx, rows 16-byte aligned), W [V, d], d % 64 == 0, targets [M] int32 in [0, V) (anything else: nll = NaN).  lse / row_max /

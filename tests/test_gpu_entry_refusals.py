@@ -35,6 +35,7 @@ def _counters():
     """every dispatch, route and step counter of the library"""
     lib = _lib()
     return ([int(lib.pcy_debug_dispatch_count(k)) for k in range(20)], [int(lib.pcy_debug_attn_route_count(k)) for k in range(4)],
+            [int(lib.pcy_debug_gemv_route_count(k)) for k in range(6)],
             [int(lib.pcy_debug_f32_select_count(k)) for k in range(2)], [int(lib.pcy_debug_look_count(k)) for k in range(2)],
             int(lib.pcy_debug_f32_stream_count()), int(lib.pcy_debug_attn_split_count()), int(lib.pcy_debug_decode_gemm_count()),
             int(lib.pcy_debug_attn_mq_count()), int(lib.pcy_debug_decode_w8_count()), int(lib.pcy_debug_decode_window_count()),
