@@ -382,6 +382,28 @@ typedef struct {
                               * always attended; bytes at and above *pos are not read */
   int32_t max_steps;
   int32_t logits_all_ld;     /* row stride of logits_all in elements; 0 = vocab.  A multiple of 8 enables 16-byte stores */
+  /* ---- EOS stop of the greedy and sampling picks; all zero / NULL = no stop: every entry launches what it
+   * launched without these fields and gives the same bits.  With finished != NULL the four picks (pcy_greedy_pick, pcy_sample_pick,
+   * pcy_f32_greedy_pick, pcy_f32_sample_pick, alone or inside pcy_llama_greedy / _sample / _greedy_w8 / pcy_f32_llama_greedy / _sample):
+   *   unfinished row: the selection, logprob increment, tokens_out[b][*step] and next_tok[b] of the entry without a stop, bit for bit; a
+   *     token equal to eos_id sets finished[b] (the EOS itself is emitted and its log-probability added);
+   *   finished row: tokens_out[b][*step] = next_tok[b] = eos_id, logprob[b] unchanged; its logits are not read for a selection (they may
+   *     hold anything, NaN included) and a sampling pick skips its histogram / radix passes unless a probs_out record is asked for; its
+   *     variate stays uniforms[step * B + b], so no other row's draw moves; the logits_all / probs_out rows are written as without a stop;
+   *   the launch that finishes the last unfinished row of [0, B) raises *done (and writes *n_steps_run) -- a count of the unfinished rows
+   *     behind the picks of a launch, no floating-point atomics;
+   *   a launch that finds *done set changes nothing: not *step, *pos, tokens_out, next_tok, logprob, finished nor the logits_all /
+   *     probs_out record (pcy_beam_step's rule).  The decode launches in front of it still run and rewrite K / V at slot *pos, which no
+   *     result anyone reads attends: steps enqueued past *done are harmless.
+   * Rows finish independently: a row's tokens up to and including its EOS and its logprob are bit-equal to the same call without a stop.
+   * Argument errors of every entry named above (code 1, nothing launched): finished != NULL with done == NULL; finished != NULL with eos_id
+   * outside [0, vocab).  A captured chain is keyed on all four fields: a state with a stop and one without never share a graph. */
+  int32_t* finished;         /* optional [B] device, zero-initialised: non-zero = the row has emitted eos_id.  NULL = no EOS stop */
+  int32_t* done;             /* device scalar, zero-initialised: raised by the pick that finishes the last unfinished row of [0, B).
+                              * Required when finished != NULL */
+  int32_t* n_steps_run;      /* optional device scalar: *step behind the pick that raised *done == the number of real rows of
+                              * tokens_out / logits_all (untouched while *done is 0) */
+  int32_t eos_id;            /* read only when finished != NULL */
 } pcy_gen_state;
 /* one decode step: next_tok -> logits (and K/V appended at slot *pos); does not pick or advance */
 int pcy_llama_decode(pcy_ctx*, const pcy_llama_desc*, const pcy_kv_cache*, const pcy_gen_state*, int B);
@@ -543,7 +565,11 @@ int pcy_look_draft(pcy_ctx*, const pcy_llama_desc*, const pcy_look_state*, const
  * drafts j with window[j+1] == argmax(row j); n = min(a + 1, max_steps - *step) tokens are committed: the argmaxes of rows 0..n-1 go to
  * tokens_out[*step..] and hist, their log-probabilities are added to logprob[0] in row order, rows 0..n-1 of the logits to rows *step.. of
  * logits_all (when kept; pinned host memory works), next_tok[0] = window[0] = the last of them, *pos += n, *step += n.  Deterministic.
- * The K / V of rejected rows stay in slots [*pos, ...) behind the new *pos; the next W-row pass rewrites them before any query reads them. */
+ * The K / V of rejected rows stay in slots [*pos, ...) behind the new *pos; the next W-row pass rewrites them before any query reads them.
+ * With the EOS stop of the state (finished != NULL, see pcy_gen_state; argument errors as there): the commit ends with the first committed
+ * token that equals eos_id -- n is cut there, the rows behind it count as rejected drafts, nothing of them reaches tokens_out, logprob, hist
+ * or the record -- and that launch sets finished[0], *done and *n_steps_run = the new *step; a launch that finds *done set commits nothing
+ * (last[1] = 0). */
 int pcy_look_verify(pcy_ctx*, const pcy_llama_desc*, const pcy_look_state*, const pcy_gen_state*, const void* logits);
 /* calls since the library was loaded -- 0: pcy_look_draft, 1: pcy_look_verify (= passes); anything else reads 0.  Words of their own, as
  * pcy_debug_extend_grouped_count: the kinds of pcy_debug_dispatch_count are pinned. */

@@ -86,7 +86,9 @@ class PrefixGroups(C.Structure):
 
 class GenState(C.Structure):
     _fields_ = [("pos", vp), ("step", vp), ("next_tok", vp), ("tokens_out", vp), ("logprob", vp), ("logits", vp),
-                ("logits_all", vp), ("keep", vp), ("max_steps", i32), ("logits_all_ld", i32)]
+                ("logits_all", vp), ("keep", vp), ("max_steps", i32), ("logits_all_ld", i32),
+                # (the trailing fields: the EOS stop of the greedy and sampling picks, all zero = no stop -- include/pcy.h)
+                ("finished", vp), ("done", vp), ("n_steps_run", vp), ("eos_id", i32)]
 
 
 class LookState(C.Structure):

@@ -452,10 +452,22 @@ __global__ __launch_bounds__(PICK_NT) void pick_stage1_kernel(const bf16_t* __re
 __global__ __launch_bounds__(256) void pick_stage2_kernel(const bf16_t* __restrict__ logits, int V, const PickPartial* __restrict__ part,
                                                           int32_t* __restrict__ next_tok, int32_t* __restrict__ tokens_out, int max_steps,
                                                           float* __restrict__ logprob, int32_t* __restrict__ step_dev, int32_t* __restrict__ pos_dev,
-                                                          int advance_pos, int B) {
+                                                          int advance_pos, int B, PcyStop stop) {
+  // EOS stop (stop.finished != nullptr; pcy.h): a launch that finds *done set changes nothing; a finished row emits eos_id and keeps its
+  // logprob; the rows still unfinished behind their picks are counted in LDS, and the launch that counts none raises *done
+  __shared__ int s_unfinished;
   const int l = threadIdx.x & 63;
+  if (stop.finished) {
+    if (*stop.done) return;   // (uniform: thread 0 writes the word behind the barrier below only)
+    if (threadIdx.x == 0) s_unfinished = 0;
+    __syncthreads();
+  }
   const int step = *step_dev;
   for (int b = threadIdx.x >> 6; b < B; b += 4) {
+    if (stop.finished && stop.finished[b]) {   // (wave-uniform)
+      if (l == 0) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + step] = stop.eos_id; }
+      continue;
+    }
     float best, se;
     int bi;
     pick_merge_row(part[b * PICK_NB + l], best, bi, se);
@@ -464,10 +476,21 @@ __global__ __launch_bounds__(256) void pick_stage2_kernel(const bf16_t* __restri
       logprob[b] += lsm;
       next_tok[b] = bi;
       tokens_out[(size_t)b * max_steps + step] = bi;
+      if (stop.finished) {
+        if (bi == stop.eos_id) stop.finished[b] = 1;
+        else atomicAdd(&s_unfinished, 1);
+      }
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0) { if (advance_pos) *pos_dev += 1; *step_dev = step + 1; }
+  if (threadIdx.x == 0) {
+    if (advance_pos) *pos_dev += 1;
+    *step_dev = step + 1;
+    if (stop.finished && s_unfinished == 0) {
+      if (stop.n_steps_run) *stop.n_steps_run = step + 1;
+      *stop.done = 1;
+    }
+  }
 }
 
 // ------------------------------------------------------------------ sampling / nucleus step (A8, model_unified.py:896-906)
@@ -546,9 +569,12 @@ __device__ __forceinline__ int block_excl_scan_i(int v, int* lds) {
 // on 64 CUs instead of the one that runs the selection.
 __global__ __launch_bounds__(PICK_NT) void sample_probs_kernel(const bf16_t* __restrict__ logits, int V, const float4* __restrict__ part,
                                                                float temperature, int nucleus, unsigned* __restrict__ hist,
-                                                               bf16_t* __restrict__ pbits) {
+                                                               bf16_t* __restrict__ pbits, PcyStop stop, int record) {
   __shared__ float s_ml[2];
   const int b = blockIdx.y, c = blockIdx.x, lane = threadIdx.x & 63;
+  // EOS stop: exactly the rows sample_stage2_kernel skips (it is what zeroes the histogram again) -- every row once *done is set, a finished
+  // row unless its probability vector is recorded.  Both words are written behind this launch only (stage 2 / the advance launch).
+  if (stop.finished && (*stop.done || (stop.finished[b] && !record))) return;
   if (threadIdx.x < 64) {   // merge the chunk partials (as sample_stage2_kernel does)
     const float4 pp = part[b * PICK_NB + lane];
     const float ms = wave_max(pp.z);
@@ -601,7 +627,7 @@ __global__ __launch_bounds__(SMP_NT) void sample_stage2_kernel(const bf16_t* __r
                                                                unsigned* __restrict__ hist, bf16_t* __restrict__ probs_out,
                                                                int32_t* __restrict__ next_tok, int32_t* __restrict__ tokens_out, int max_steps,
                                                                float* __restrict__ logprob, const int32_t* __restrict__ step_dev, int B,
-                                                               const bf16_t* __restrict__ pbits) {
+                                                               const bf16_t* __restrict__ pbits, PcyStop stop) {
   constexpr int NWV = SMP_NT / 64;
   __shared__ float fl[NWV];
   __shared__ int il[NWV];
@@ -610,6 +636,17 @@ __global__ __launch_bounds__(SMP_NT) void sample_stage2_kernel(const bf16_t* __r
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const bf16_t* lg = logits + (size_t)b * V;
   const int step = *step_dev;
+  // EOS stop (pcy.h): nothing once *done is set; a finished row emits eos_id, keeps its logprob and takes no pass over its probabilities
+  // unless they are recorded (probs_out) -- its variate uniforms[step * B + b] is simply not read, the other rows' indices do not move
+  bool was_finished = false;
+  if (stop.finished) {   // (workgroup-uniform; *done and finished[b] are written behind this point of the step only)
+    if (*stop.done) return;
+    was_finished = stop.finished[b] != 0;
+    if (was_finished && !probs_out) {
+      if (tid == 0) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + step] = stop.eos_id; }
+      return;
+    }
+  }
   if (tid < 64) {   // merge the chunk partials
     const float4 pp = part[b * PICK_NB + lane];
     const float mr = wave_max(pp.x), ms = wave_max(pp.z);
@@ -761,19 +798,38 @@ __global__ __launch_bounds__(SMP_NT) void sample_stage2_kernel(const bf16_t* __r
     if (lane == 0) atomicMax(&s_tok, tok);
   }
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0 && was_finished) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + step] = stop.eos_id; }
+  if (tid == 0 && !was_finished) {
     int tok = s_tok >= 0 ? s_tok : s_last;   // u * total landed on the very end of the CDF
     if (tok < 0) tok = 0;
     const float lsm = rbf((bf2f(lg[tok]) - m_raw) - logf(l_raw));   // bf16 log_softmax of the unscaled logits
     logprob[b] += lsm;
     next_tok[b] = tok;
     tokens_out[(size_t)b * max_steps + step] = tok;
+    if (stop.finished && tok == stop.eos_id) stop.finished[b] = 1;
   }
 #undef SMP_PB
 }
-// after every row has read *step_dev
-__global__ void sample_advance_kernel(int32_t* pos_dev, int32_t* step_dev, int advance_pos) {
-  if (threadIdx.x == 0) { if (advance_pos) *pos_dev += 1; *step_dev += 1; }
+// after every row has read *step_dev (and, with an EOS stop, written finished[b]: the count of the unfinished rows raises *done)
+// (one wave: lane l counts rows l, l + 64, ...; lane 0 writes)
+__global__ void sample_advance_kernel(int32_t* pos_dev, int32_t* step_dev, int advance_pos, PcyStop stop, int B) {
+  int unfinished = 0;
+  if (stop.finished) {
+    if (*stop.done) return;   // (uniform: lane 0 writes the word at the end only)
+    for (int b = threadIdx.x; b < B; b += 64) unfinished += stop.finished[b] == 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) unfinished += __shfl_xor(unfinished, o, 64);
+  }
+  if (threadIdx.x != 0) return;
+  if (advance_pos) *pos_dev += 1;
+  const int step = *step_dev + 1;
+  *step_dev = step;
+  if (stop.finished) {
+    if (unfinished == 0) {
+      if (stop.n_steps_run) *stop.n_steps_run = step;
+      *stop.done = 1;
+    }
+  }
 }
 
 // ------------------------------------------------------------------ F.normalize(x, dim=-1) on a bf16 tensor
@@ -1453,21 +1509,22 @@ void pcy_launch_pick_stage1(hipStream_t s, const bf16_t* logits, int rows, int V
   if (rows > 0) hipLaunchKernelGGL(pick_stage1_kernel, dim3(PICK_NB, rows), dim3(PICK_NT), 0, s, logits, V, reinterpret_cast<PickPartial*>(partials));
 }
 void pcy_launch_greedy_pick(hipStream_t s, const bf16_t* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out,
-                            int max_steps, float* logprob, int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials) {
+                            int max_steps, float* logprob, int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials,
+                            const PcyStop& stop) {
   hipLaunchKernelGGL(pick_stage1_kernel, dim3(PICK_NB, B), dim3(PICK_NT), 0, s, logits, V, reinterpret_cast<PickPartial*>(partials));
   hipLaunchKernelGGL(pick_stage2_kernel, dim3(1), dim3(256), 0, s, logits, V, reinterpret_cast<const PickPartial*>(partials), next_tok,
-                     tokens_out, max_steps, logprob, step_dev, pos_dev, advance_pos, B);
+                     tokens_out, max_steps, logprob, step_dev, pos_dev, advance_pos, B, stop);
 }
 int pcy_sample_max_vocab() { return SMP_NT * SMP_KMAX; }
 void pcy_launch_sample_step(hipStream_t s, const bf16_t* logits, int B, int V, float temperature, float nucleus_p, const float* uniforms,
                             unsigned* hist, bf16_t* probs_out, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
-                            int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials, bf16_t* pbits) {
+                            int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials, bf16_t* pbits, const PcyStop& stop) {
   hipLaunchKernelGGL(sample_stage1_kernel, dim3(PICK_NB, B), dim3(PICK_NT), 0, s, logits, V, temperature, reinterpret_cast<float4*>(partials));
   hipLaunchKernelGGL(sample_probs_kernel, dim3(PICK_NB, B), dim3(PICK_NT), 0, s, logits, V, reinterpret_cast<const float4*>(partials), temperature,
-                     nucleus_p > 0.f ? 1 : 0, hist, pbits);
+                     nucleus_p > 0.f ? 1 : 0, hist, pbits, stop, probs_out ? 1 : 0);
   hipLaunchKernelGGL(sample_stage2_kernel, dim3(B), dim3(SMP_NT), 0, s, logits, V, reinterpret_cast<const float4*>(partials), temperature,
-                     nucleus_p, uniforms, hist, probs_out, next_tok, tokens_out, max_steps, logprob, step_dev, B, pbits);
-  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(64), 0, s, pos_dev, step_dev, advance_pos);
+                     nucleus_p, uniforms, hist, probs_out, next_tok, tokens_out, max_steps, logprob, step_dev, B, pbits, stop);
+  hipLaunchKernelGGL(sample_advance_kernel, dim3(1), dim3(64), 0, s, pos_dev, step_dev, advance_pos, stop, B);
 }
 void pcy_launch_copy_rows(hipStream_t s, const bf16_t* src, int lds_, bf16_t* dst, int ldd, const int32_t* rows, int nrows, int d) {
   if (nrows > 0) hipLaunchKernelGGL(copy_rows_kernel, dim3(nrows), dim3(NT), 0, s, src, lds_, dst, ldd, rows, d);

@@ -101,6 +101,8 @@ struct DecodeGraphKey {
   int attn_split;                                  // 1: every layer's attention is the split-key one (pcy_attn_split.hip); never shares a graph with 0
   const void* uniforms;                            // KIND_F32_SAMPLE: the variates and the two parameters of the sampling pick
   uint32_t temperature_bits, nucleus_bits;
+  const void *stop_finished, *stop_done, *stop_n_steps_run;   // key_base: the EOS stop of the state (all zero: none); a chain with a stop and
+  int stop_eos_id;                                            // one without never share a graph
 };
 
 struct pcy_ctx {
@@ -823,7 +825,8 @@ void enqueue_decode(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
 // Row (step, b) starts at all + (step*B + b)*ld; with ld % 8 == 0 every row is 16-byte aligned and is written with 16-byte
 // stores (the source rows have the odd stride V, so they are gathered with 2-byte loads from L2).
 __global__ void store_logits_kernel(const bf16_t* __restrict__ logits, bf16_t* __restrict__ all, const int32_t* step_dev,
-                                    int B, int V, int ld) {
+                                    int B, int V, int ld, const int32_t* __restrict__ done) {
+  if (done && *done) return;   // EOS stop: a launch behind *done changes nothing (the word is written by the pick behind this launch only)
   const size_t step = (size_t)(*step_dev);
   const int chunks = (V + 7) / 8;
   const bool vec = (ld % 8 == 0) && ((reinterpret_cast<uintptr_t>(all) & 15) == 0);
@@ -841,13 +844,26 @@ __global__ void store_logits_kernel(const bf16_t* __restrict__ logits, bf16_t* _
   }
 }
 // the step's logits -> row (step, b) of `all` (nullptr: no record; ld <= 0: rows of V)
-void enqueue_store_logits(hipStream_t s, const void* logits, void* all, int ld, const int32_t* step_dev, int B, int V) {
-  if (all) hipLaunchKernelGGL(store_logits_kernel, dim3(B >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)logits, (bf16_t*)all, step_dev, B, V, ld > 0 ? ld : V);
+// (done: the word of an EOS stop, nullptr without one)
+void enqueue_store_logits(hipStream_t s, const void* logits, void* all, int ld, const int32_t* step_dev, int B, int V, const int32_t* done = nullptr) {
+  if (all) hipLaunchKernelGGL(store_logits_kernel, dim3(B >= 8 ? 256 : 64), dim3(256), 0, s, (const bf16_t*)logits, (bf16_t*)all, step_dev, B, V, ld > 0 ? ld : V, done);
+}
+// the EOS stop of a state as the pick launchers take it (pcy.h; without `finished` the other three fields are not read: all zero)
+PcyStop stop_of(const pcy_gen_state* st) {
+  return st->finished ? PcyStop{st->finished, st->done, st->n_steps_run, st->eos_id} : PcyStop{};
+}
+// ... and what every entry with a pick refuses about it, before anything is launched
+int check_stop(const pcy_gen_state* st, int vocab, const char* what) {
+  if (!st || !st->finished) return 0;
+  if (!st->done) return fail(1, "%s: an EOS stop (finished != NULL) needs the done word", what);
+  if (st->eos_id < 0 || st->eos_id >= vocab) return fail(1, "%s: eos_id %d outside [0, vocab %d)", what, st->eos_id, vocab);
+  return 0;
 }
 void enqueue_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos, int Tmax) {
-  enqueue_store_logits(c->stream, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab);
+  const PcyStop stop = stop_of(st);
+  enqueue_store_logits(c->stream, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab, stop.done);
   pcy_launch_greedy_pick(c->stream, (const bf16_t*)st->logits, B, m->vocab, st->next_tok, st->tokens_out, st->max_steps,
-                         st->logprob, st->pos, st->step, advance_pos, carve_decode_ws(c->ws, m, B, Tmax).partials);
+                         st->logprob, st->pos, st->step, advance_pos, carve_decode_ws(c->ws, m, B, Tmax).partials, stop);
 }
 
 // sampling / nucleus selection on state->logits (the non-greedy branch of `_generate_sampling`, model_unified.py:896-906)
@@ -856,10 +872,11 @@ void enqueue_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_gen_state* st
   hipStream_t s = c->stream;
   // the nucleus branch of the reference is softmax(logits) * mask -- the temperature is not applied there (model_unified.py:899-901)
   if (nucleus_p > 0.f) temperature = 1.0f;
-  enqueue_store_logits(s, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab);
+  const PcyStop stop = stop_of(st);
+  enqueue_store_logits(s, st->logits, st->logits_all, st->logits_all_ld, st->step, B, m->vocab, stop.done);
   void* partials = carve_decode_ws(c->ws, m, B, Tmax).partials;
   pcy_launch_sample_step(s, (const bf16_t*)st->logits, B, m->vocab, temperature, nucleus_p, uniforms, c->smp_hist, probs_out, st->next_tok,
-                         st->tokens_out, st->max_steps, st->logprob, st->pos, st->step, advance_pos, partials, c->smp_pbits);
+                         st->tokens_out, st->max_steps, st->logprob, st->pos, st->step, advance_pos, partials, c->smp_pbits, stop);
 }
 int ensure_sample_state(pcy_ctx* c, int B, int V) {
   if ((size_t)B * V > c->smp_pbits_elems) {
@@ -1873,6 +1890,7 @@ void key_base(DecodeGraphKey& k, GraphKind kind, int B, const M* m, const KV* kv
   k.model = m; k.layers = m->layers; k.embed = m->embed; k.kv_k = kv->k; k.kv_v = kv->v; k.Tmax = kv->Tmax; k.kv_B = kv->B;
   k.pos = st->pos; k.step = st->step; k.next_tok = st->next_tok; k.logits = st->logits;
   k.ws = c->ws; k.layers_fp = fp;
+  if (st->finished) { k.stop_finished = st->finished; k.stop_done = st->done; k.stop_n_steps_run = st->n_steps_run; k.stop_eos_id = st->eos_id; }
 }
 // ... and what enqueue_decode reads on top (call after ensure_decode_state: the context's buffers are final)
 void decode_graph_key(DecodeGraphKey& k, const pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, GraphKind kind, const PcySwitches& sw) {
@@ -2049,6 +2067,7 @@ int pcy_llama_decode_layers(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_ca
 
 int pcy_greedy_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos) {
   PCY_STICKY(c);
+  if (int r = check_stop(st, m->vocab, "pcy_greedy_pick")) return r;
   if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   enqueue_pick(c, m, st, B, advance_pos, kv_cap(kv));
   return check_launch("pcy_greedy_pick");
@@ -2081,8 +2100,9 @@ int pcy_look_verify(pcy_ctx* c, const pcy_llama_desc* m, const pcy_look_state* l
   PcyLookArgs a;
   if (int r = look_args("pcy_look_verify", ls, st, &a)) return r;
   if (!logits) return fail(1, "pcy_look_verify: logits is NULL");
+  if (int r = check_stop(st, m->vocab, "pcy_look_verify")) return r;
   if (int r = c->reserve(pcy_look_verify_ws_bytes(a.W))) return r;
-  pcy_launch_look_verify(c->stream, a, (const bf16_t*)logits, m->vocab, (bf16_t*)st->logits_all, st->logits_all_ld, c->ws);
+  pcy_launch_look_verify(c->stream, a, (const bf16_t*)logits, m->vocab, (bf16_t*)st->logits_all, st->logits_all_ld, c->ws, stop_of(st));
   ++g_pcy_look[1];
   return check_launch("pcy_look_verify");
 }
@@ -2093,6 +2113,7 @@ int pcy_llama_greedy(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
                      int use_graph) {
   PCY_STICKY(c);
   PcySwitches sw;
+  if (m) if (int r = check_stop(st, m->vocab, "pcy_llama_greedy")) return r;
   if (int r = decode_prologue(c, m, kv, st, B, "pcy_llama_greedy", step_ws_bytes, &sw)) return r;
   DecodeGraphKey key;
   decode_graph_key(key, c, m, kv, st, B, KIND_GREEDY, sw);
@@ -2225,6 +2246,7 @@ int pcy_llama_decode_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_lay
 int pcy_llama_greedy_w8(pcy_ctx* c, const pcy_llama_desc* m, const pcy_llama_layer_fp8* w8, const pcy_kv_cache* kv, const pcy_gen_state* st, int B,
                         int n_steps, int use_graph) {
   PCY_STICKY(c);
+  if (m) if (int r = check_stop(st, m->vocab, "pcy_llama_greedy_w8")) return r;
   if (int r = decode_w8_check(c, m, w8, kv, st, B, "pcy_llama_greedy_w8")) return r;
   if (!st->step || !st->tokens_out || !st->logprob) return fail(1, "pcy_llama_greedy_w8: generation state incomplete");
   // (this step reads no switch and none of the fused steps' buffers: the base key, whose fingerprint holds ln1 / ln2 of every layer, the keep
@@ -2298,7 +2320,7 @@ static void enqueue_decode_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pc
 }
 static void enqueue_pick_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos) {
   pcy_launch_f32_pick(c->stream, (const float*)st->logits, B, m->vocab, st->next_tok, st->tokens_out, st->max_steps, st->logprob, st->pos, st->step,
-                      advance_pos, (float*)st->logits_all, st->logits_all_ld);
+                      advance_pos, (float*)st->logits_all, st->logits_all_ld, stop_of(st));
 }
 // everything the fp32 step entries refuse; reserves the workspace behind the checks
 static int f32_stream_check(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, bool pick, const char* what) {
@@ -2306,6 +2328,7 @@ static int f32_stream_check(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f
       !m->rope_cos || !m->rope_sin)
     return fail(1, "%s: model, cache or state incomplete", what);
   if (pick && (!st->step || !st->tokens_out || !st->logprob || st->max_steps < 1)) return fail(1, "%s: generation state incomplete", what);
+  if (pick) if (int r = check_stop(st, m->vocab, what)) return r;
   if (st->keep) return fail(1, "%s: keep must be NULL (the fp32 step attends every slot, as the reference does after the prefill)", what);
   const int d = m->d, H = m->n_heads, Hkv = m->n_kv_heads, dh = m->head_dim, F = m->ffn;
   if (m->n_layers < 1 || m->vocab < 1 || d < 4 || F < 4) return fail(1, "%s: geometry incomplete", what);
@@ -2346,6 +2369,7 @@ int pcy_f32_greedy_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_k
   if (!m || !st || !st->logits || !st->pos || !st->step || !st->next_tok || !st->tokens_out || !st->logprob || st->max_steps < 1)
     return fail(1, "pcy_f32_greedy_pick: generation state incomplete");
   if (B < 1 || B > 65535 || m->vocab < 1 || (kv && B > kv->B)) return fail(1, "pcy_f32_greedy_pick: B=%d", B);
+  if (int r = check_stop(st, m->vocab, "pcy_f32_greedy_pick")) return r;
   enqueue_pick_f32(c, m, st, B, advance_pos);
   return check_launch("pcy_f32_greedy_pick");
 }
@@ -2446,10 +2470,11 @@ int pcy_f32_llama_beam_steps(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_
 static void enqueue_sample_f32(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_gen_state* st, int B, int advance_pos, float temperature,
                                float nucleus_prob, const float* uniforms, float* probs_out) {
   hipStream_t s = c->stream;
-  pcy_launch_f32_record(s, (const float*)st->logits, (float*)st->logits_all, st->step, B, m->vocab, st->logits_all_ld);
+  const PcyStop stop = stop_of(st);
+  pcy_launch_f32_record(s, (const float*)st->logits, (float*)st->logits_all, st->step, B, m->vocab, st->logits_all_ld, stop.done);
   pcy_launch_f32_sample_step(s, (const float*)st->logits, B, m->vocab, nucleus_prob > 0.f ? 1.0f : temperature, nucleus_prob, uniforms, probs_out,
-                             st->next_tok, st->tokens_out, st->max_steps, st->logprob, st->step, c->ws + f32_select_ws_offset(m, B));
-  pcy_launch_f32_advance(s, st->step, st->pos, advance_pos);
+                             st->next_tok, st->tokens_out, st->max_steps, st->logprob, st->step, c->ws + f32_select_ws_offset(m, B), stop);
+  pcy_launch_f32_advance(s, st->step, st->pos, advance_pos, stop, B);
 }
 int pcy_f32_sample_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_kv_cache* kv, const pcy_gen_state* st, int B, int advance_pos,
                         float temperature, float nucleus_prob, const float* uniforms, float* probs_out) {
@@ -2458,6 +2483,7 @@ int pcy_f32_sample_pick(pcy_ctx* c, const pcy_f32_llama_desc* m, const pcy_f32_k
     return fail(1, "pcy_f32_sample_pick: generation state incomplete");
   if (B < 1 || B > 65535 || (kv && B > kv->B)) return fail(1, "pcy_f32_sample_pick: B=%d", B);
   if (int r = check_sample_args("pcy_f32_sample_pick", m->vocab, 163840, temperature, nucleus_prob, uniforms)) return r;
+  if (int r = check_stop(st, m->vocab, "pcy_f32_sample_pick")) return r;
   if (int r = c->reserve(f32_select_ws_offset(m, B) + pcy_f32_sample_ws_bytes(B, m->vocab))) return r;
   enqueue_sample_f32(c, m, st, B, advance_pos, temperature, nucleus_prob, uniforms, probs_out);
   ++g_pcy_f32_select[1];
@@ -2583,6 +2609,7 @@ int pcy_sample_pick(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv,
                     float temperature, float nucleus_prob, const float* uniforms, void* probs_out) {
   PCY_STICKY(c);
   if (int r = check_sample_args("pcy_sample_pick", m->vocab, pcy_sample_max_vocab(), temperature, nucleus_prob, uniforms)) return r;
+  if (int r = check_stop(st, m->vocab, "pcy_sample_pick")) return r;
   if (int r = c->reserve(decode_ws_bytes(m, B, kv_cap(kv)))) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;
   enqueue_sample(c, m, st, B, advance_pos, kv_cap(kv), temperature, nucleus_prob, uniforms, (bf16_t*)probs_out);
@@ -2595,6 +2622,7 @@ int pcy_llama_sample(pcy_ctx* c, const pcy_llama_desc* m, const pcy_kv_cache* kv
   const char* what = "pcy_llama_sample";
   if (int r = check_step_args(m, kv, st, B, what)) return r;   // (ahead of the prologue: the sampling arguments are refused before anything is allocated)
   if (int r = check_sample_args(what, m->vocab, pcy_sample_max_vocab(), temperature, nucleus_prob, uniforms)) return r;
+  if (int r = check_stop(st, m->vocab, what)) return r;
   PcySwitches sw;
   if (int r = decode_prologue(c, m, kv, st, B, what, step_ws_bytes, &sw)) return r;
   if (int r = ensure_sample_state(c, B, m->vocab)) return r;

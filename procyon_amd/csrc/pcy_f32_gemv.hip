@@ -344,7 +344,8 @@ __global__ __launch_bounds__(E_NT) void rmsnorm_stream_f32_kernel(const float* _
 }
 // row (*step, b) of the record <- the step's logits
 __global__ __launch_bounds__(E_NT) void record_f32_kernel(const float* __restrict__ logits, float* __restrict__ all, const int32_t* __restrict__ step_dev,
-                                                          int B, int V, int ld) {
+                                                          int B, int V, int ld, const int32_t* __restrict__ done) {
+  if (done && *done) return;   // EOS stop: a launch behind *done changes nothing (written by the advance launch only)
   const int b = blockIdx.y;
   const float* src = logits + (size_t)b * V;
   float* dst = all + ((size_t)(*step_dev) * B + b) * ld;
@@ -353,11 +354,20 @@ __global__ __launch_bounds__(E_NT) void record_f32_kernel(const float* __restric
 constexpr int P_NT = 1024;
 // one workgroup per row: argmax (lowest index on ties), sum exp(x - max), logprob += (x[tok] - max) - log(sum)
 __global__ __launch_bounds__(P_NT) void pick_f32_kernel(const float* __restrict__ logits, int V, int32_t* __restrict__ next_tok, int32_t* __restrict__ tokens_out,
-                                                        int max_steps, float* __restrict__ logprob, const int32_t* __restrict__ step_dev) {
+                                                        int max_steps, float* __restrict__ logprob, const int32_t* __restrict__ step_dev, PcyStop stop) {
   __shared__ float redv[P_NT / 64];
   __shared__ int redi[P_NT / 64];
   __shared__ float red[P_NT / 64];
   const int b = blockIdx.x;
+  // EOS stop (pcy.h; workgroup-uniform, both words are written behind this point of the step only): nothing once *done is set; a finished
+  // row emits eos_id, keeps its logprob and does not read its logits
+  if (stop.finished) {
+    if (*stop.done) return;
+    if (stop.finished[b]) {
+      if (threadIdx.x == 0) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + *step_dev] = stop.eos_id; }
+      return;
+    }
+  }
   const float* lg = logits + (size_t)b * V;
   float best = -INFINITY;
   int bi = 0x7fffffff;
@@ -384,11 +394,29 @@ __global__ __launch_bounds__(P_NT) void pick_f32_kernel(const float* __restrict_
     logprob[b] += (lg[bi] - best) - logf(se);
     next_tok[b] = bi;
     tokens_out[(size_t)b * max_steps + *step_dev] = bi;
+    if (stop.finished && bi == stop.eos_id) stop.finished[b] = 1;
   }
 }
-__global__ void advance_f32_kernel(int32_t* step_dev, int32_t* pos_dev, int advance_pos) {
-  *step_dev += 1;
+// (with an EOS stop: behind the picks of every row -- the count of the rows of [0, B) still unfinished raises *done at zero)
+// One thread without a stop; with one, a wave: lane l counts rows l, l + 64, ..., lane 0 writes.
+__global__ void advance_f32_kernel(int32_t* step_dev, int32_t* pos_dev, int advance_pos, PcyStop stop, int B) {
+  int unfinished = 0;
+  if (stop.finished) {
+    if (*stop.done) return;   // (uniform: lane 0 writes the word at the end only)
+    for (int b = threadIdx.x; b < B; b += 64) unfinished += stop.finished[b] == 0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) unfinished += __shfl_xor(unfinished, o, 64);
+  }
+  if (threadIdx.x != 0) return;
+  const int step = *step_dev + 1;
+  *step_dev = step;
   if (advance_pos) *pos_dev += 1;
+  if (stop.finished) {
+    if (unfinished == 0) {
+      if (stop.n_steps_run) *stop.n_steps_run = step;
+      *stop.done = 1;
+    }
+  }
 }
 
 int launch_ok(const char* what) {
@@ -434,20 +462,20 @@ void pcy_launch_f32_embed_dev(hipStream_t s, const float* table, const int32_t* 
 void pcy_launch_f32_rmsnorm(hipStream_t s, const float* x, const float* w, float* y, int rows, int d, float eps) {
   hipLaunchKernelGGL(rmsnorm_stream_f32_kernel, dim3(rows), dim3(E_NT), 0, s, x, w, y, d, eps);
 }
-void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld) {
+void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld, const int32_t* done) {
   if (!logits_all) return;
   int nb = (V + E_NT - 1) / E_NT;
   nb = nb < 64 ? nb : 64;
-  hipLaunchKernelGGL(record_f32_kernel, dim3(nb, B), dim3(E_NT), 0, s, logits, logits_all, step_dev, B, V, ld > 0 ? ld : V);
+  hipLaunchKernelGGL(record_f32_kernel, dim3(nb, B), dim3(E_NT), 0, s, logits, logits_all, step_dev, B, V, ld > 0 ? ld : V, done);
 }
-void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos) {
-  hipLaunchKernelGGL(advance_f32_kernel, dim3(1), dim3(1), 0, s, step_dev, pos_dev, advance_pos);
+void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos, const PcyStop& stop, int B) {
+  hipLaunchKernelGGL(advance_f32_kernel, dim3(1), dim3(stop.finished ? 64 : 1), 0, s, step_dev, pos_dev, advance_pos, stop, B);
 }
 void pcy_launch_f32_pick(hipStream_t s, const float* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
-                         int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld) {
-  pcy_launch_f32_record(s, logits, logits_all, step_dev, B, V, logits_all_ld);
-  hipLaunchKernelGGL(pick_f32_kernel, dim3(B), dim3(P_NT), 0, s, logits, V, next_tok, tokens_out, max_steps, logprob, step_dev);
-  pcy_launch_f32_advance(s, step_dev, pos_dev, advance_pos);
+                         int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld, const PcyStop& stop) {
+  pcy_launch_f32_record(s, logits, logits_all, step_dev, B, V, logits_all_ld, stop.finished ? stop.done : nullptr);
+  hipLaunchKernelGGL(pick_f32_kernel, dim3(B), dim3(P_NT), 0, s, logits, V, next_tok, tokens_out, max_steps, logprob, step_dev, stop);
+  pcy_launch_f32_advance(s, step_dev, pos_dev, advance_pos, stop, B);
 }
 
 extern "C" {

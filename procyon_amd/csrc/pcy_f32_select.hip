@@ -212,11 +212,24 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_f32_kernel(const float* 
                                                                    const float* __restrict__ uniforms, const float4* __restrict__ part,
                                                                    const float* __restrict__ pbuf, float* __restrict__ probs_out,
                                                                    int32_t* __restrict__ next_tok, int32_t* __restrict__ tokens_out, int max_steps,
-                                                                   float* __restrict__ logprob, const int32_t* __restrict__ step_dev, int B) {
+                                                                   float* __restrict__ logprob, const int32_t* __restrict__ step_dev, int B,
+                                                                   PcyStop stop) {
   __shared__ SelShared sh;
   const int tid = threadIdx.x, b = blockIdx.x;
   const int step = *step_dev;
   if (step < 0 || step >= max_steps) return;             // outside tokens_out and the variates: nothing is written
+  // EOS stop (pcy.h; workgroup-uniform, both words are written behind this point of the step only): nothing once *done is set; a finished
+  // row emits eos_id, keeps its logprob and takes no pass over its probabilities unless they are recorded (probs_out) -- its variate
+  // uniforms[step * B + b] is simply not read, the other rows' indices do not move
+  bool was_finished = false;
+  if (stop.finished) {
+    if (*stop.done) return;
+    was_finished = stop.finished[b] != 0;
+    if (was_finished && !probs_out) {
+      if (tid == 0) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + step] = stop.eos_id; }
+      return;
+    }
+  }
   const float4* p4 = reinterpret_cast<const float4*>(pbuf + (size_t)b * Vp);
   const int n4 = Vp / 4;
   // ---- what is kept: patterns above kstar, and of the tokens with pattern kstar (probability qstar in fixed point) the nstar-th in token
@@ -304,7 +317,8 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_f32_kernel(const float* 
     if (last >= 0) atomicMax(&sh.last, last);
     __syncthreads();
   }
-  if (tid == 0) {
+  if (tid == 0 && was_finished) { next_tok[b] = stop.eos_id; tokens_out[(size_t)b * max_steps + step] = stop.eos_id; }
+  if (tid == 0 && !was_finished) {
     int tok = sh.found ? sh.token : sh.last;
     tok = tok < 0 ? 0 : tok >= V ? V - 1 : tok;
     float m, se, ss;
@@ -312,6 +326,7 @@ __global__ __launch_bounds__(SEL_NT) void sample_select_f32_kernel(const float* 
     logprob[b] += (logits[(size_t)b * V + tok] - m) - logf(se);
     next_tok[b] = tok;
     tokens_out[(size_t)b * max_steps + step] = tok;
+    if (stop.finished && tok == stop.eos_id) stop.finished[b] = 1;
   }
 }
 
@@ -337,12 +352,12 @@ size_t pcy_f32_sample_ws_bytes(int B, int V) {
 }
 void pcy_launch_f32_sample_step(hipStream_t s, const float* logits, int B, int V, float temperature, float nucleus_p, const float* uniforms,
                                 float* probs_out, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob, const int32_t* step_dev,
-                                void* ws) {
+                                void* ws, const PcyStop& stop) {
   const int Vp = (V + 3) / 4 * 4;
   float4* part = reinterpret_cast<float4*>(ws);
   float* pbuf = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + ((size_t)B * S_NCH * sizeof(float4) + 255) / 256 * 256);
   hipLaunchKernelGGL(sample_stats_f32_kernel, dim3(S_NCH, B), dim3(S_NT), 0, s, logits, V, temperature, part);
   hipLaunchKernelGGL(sample_probs_f32_kernel, dim3(S_NCH, B), dim3(S_NT), 0, s, logits, V, Vp, temperature, part, pbuf);
   hipLaunchKernelGGL(sample_select_f32_kernel, dim3(B), dim3(SEL_NT), 0, s, logits, V, Vp, temperature, nucleus_p, uniforms, part, pbuf, probs_out,
-                     next_tok, tokens_out, max_steps, logprob, step_dev, B);
+                     next_tok, tokens_out, max_steps, logprob, step_dev, B, stop);
 }

@@ -64,6 +64,8 @@ struct PcyF32GemvArgs {
   float* y;             // [B,N] (ldy)
   int N, K, B, ldx, ldr, ldy, epi;   // epi in STORE / RESID / SWIGLU
 };
+// EOS stop of a greedy / sampling pick (pcy.h, the trailing fields of pcy_gen_state); finished == nullptr: no stop, nothing below is read
+struct PcyStop { int32_t* finished; int32_t* done; int32_t* n_steps_run; int32_t eos_id; };
 bool pcy_launch_f32_gemv(hipStream_t s, const PcyF32GemvArgs& a);   // false = the device refused the LDS size (nothing launched)
 size_t pcy_f32_attn_pos_lds(int H, int Hkv, int dh, int Tmax);      // dynamic LDS of the launch below, bytes
 bool pcy_launch_f32_attn_decode_pos(hipStream_t s, const float* qkv, int ld, float* kc, float* vc, int ldkv, int Tmax, float* o, int ldo,
@@ -72,12 +74,15 @@ void pcy_launch_f32_embed_dev(hipStream_t s, const float* table, const int32_t* 
 void pcy_launch_f32_rmsnorm(hipStream_t s, const float* x, const float* w, float* y, int rows, int d, float eps);
 // record row *step of logits_all (optional), then the pick and the counters (pcy.h, the fp32 greedy pick)
 void pcy_launch_f32_pick(hipStream_t s, const float* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
-                         int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld);
+                         int32_t* pos_dev, int32_t* step_dev, int advance_pos, float* logits_all, int logits_all_ld, const PcyStop& stop = PcyStop{});
 
 // the two ends of that chain on their own (the sampling and beam steps of pcy_f32_select.hip put another selection between them):
 // row (*step, b) of the record <- logits (logits_all == nullptr: nothing; ld <= 0: rows of V); ++*step and, on request, ++*pos
-void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld);
-void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos);
+// (done != nullptr and *done set: the record launch writes nothing; stop.finished != nullptr: the advance launch counts the unfinished rows
+// of [0, B), raises *stop.done at zero and leaves the counters alone when it finds *stop.done set)
+void pcy_launch_f32_record(hipStream_t s, const float* logits, float* logits_all, const int32_t* step_dev, int B, int V, int ld,
+                           const int32_t* done = nullptr);
+void pcy_launch_f32_advance(hipStream_t s, int32_t* step_dev, int32_t* pos_dev, int advance_pos, const PcyStop& stop = PcyStop{}, int B = 0);
 
 // fp32 selection on the device (pcy_f32_select.hip; the beam step itself is pcy_launch_f32_beam_step below)
 // K / V reorder of the token-major fp32 caches [L][Bcache][Tmax][kw]: row b of rows [0, B) takes slots [t0, t) of row src_rows[b], in place,
@@ -92,7 +97,7 @@ void pcy_launch_f32_kv_copy_rows(hipStream_t s, float* dk, float* dv, int Bdst, 
 size_t pcy_f32_sample_ws_bytes(int B, int V);
 void pcy_launch_f32_sample_step(hipStream_t s, const float* logits, int B, int V, float temperature, float nucleus_p, const float* uniforms,
                                 float* probs_out, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob, const int32_t* step_dev,
-                                void* ws);
+                                void* ws, const PcyStop& stop = PcyStop{});
 
 // Rotated K order of the batched GEMVs (round 6).  Every workgroup of these kernels walks ITS K range front to back in step with all the
 // others, so at any moment every wave of the chip reads the same 256-byte window of its rows -- and with a power-of-two row stride (K = 4096:
@@ -510,7 +515,7 @@ void pcy_launch_pool(hipStream_t s, const bf16_t* h, int d, const int32_t* seg, 
 // next_tok[b], then (one thread) ++*step and, if advance_pos, ++*pos.
 void pcy_launch_greedy_pick(hipStream_t s, const bf16_t* logits, int B, int V, int32_t* next_tok, int32_t* tokens_out,
                             int max_steps, float* logprob, int32_t* pos_dev, int32_t* step_dev, int advance_pos,
-                            void* partials /* B*64*16 bytes of scratch */);
+                            void* partials /* B*64*16 bytes of scratch */, const PcyStop& stop = PcyStop{});
 // stage 1 of the pick alone: the 64 chunk partials of every row of logits [rows, V] -> partials (rows * 64 * 16 bytes)
 void pcy_launch_pick_stage1(hipStream_t s, const bf16_t* logits, int rows, int V, void* partials);
 // Greedy decoding with lookahead (pcy_lookahead.hip; pcy.h, pcy_look_state + the scalars of the pcy_gen_state it works beside): device pointers
@@ -522,7 +527,7 @@ struct PcyLookArgs {
 size_t pcy_look_verify_ws_bytes(int W);
 void pcy_launch_look_draft(hipStream_t s, const PcyLookArgs& a, const bf16_t* embed, int V, int d, bf16_t* embeds_out /* [W, d] */);
 void pcy_launch_look_verify(hipStream_t s, const PcyLookArgs& a, const bf16_t* logits /* [W, V] */, int V, bf16_t* logits_all, int logits_all_ld,
-                            void* partials /* pcy_look_verify_ws_bytes(W) */);
+                            void* partials /* pcy_look_verify_ws_bytes(W) */, const PcyStop& stop = PcyStop{});
 // sampling / nucleus selection of one step (model_unified.py:896-906): token ~ multinomial(probs) by inverse CDF with the caller's
 // uniform variate uniforms[step * B + b]; nucleus_p <= 0: plain temperature sampling.  hist: [B][65536] uint32, zero on entry / exit;
 // partials: B * 64 * 16 bytes; probs_out: optional [B,V] record of the pre-sampling probability vector
@@ -533,7 +538,7 @@ int pcy_sample_max_vocab();   // largest vocabulary the selection workgroup of t
 void pcy_launch_sample_step(hipStream_t s, const bf16_t* logits, int B, int V, float temperature, float nucleus_p, const float* uniforms,
                             unsigned* hist, bf16_t* probs_out, int32_t* next_tok, int32_t* tokens_out, int max_steps, float* logprob,
                             int32_t* pos_dev, int32_t* step_dev, int advance_pos, void* partials /* 64 x float4 per row */,
-                            bf16_t* pbits /* [B][V] scratch: the probabilities' bits */);
+                            bf16_t* pbits /* [B][V] scratch: the probabilities' bits */, const PcyStop& stop = PcyStop{});
 // device-side state of the diverse beam search (pcy_beam_step); every pointer is device memory, BB = B * beam rows
 struct PcyBeamState {
   int32_t* out; int32_t max_len;   // [2][BB][max_len] token histories, buffer (step & 1) is current

@@ -85,7 +85,10 @@ __global__ __launch_bounds__(LOOK_NT) void look_draft_kernel(PcyLookArgs a, cons
 
 // Rows 0..W-1 have their 64 chunk partials (pick_stage1_kernel); wave w merges rows w, w + 4, ... exactly as pick_stage2_kernel does, then one
 // thread compares with the drafts and commits.
-__global__ __launch_bounds__(LOOK_NT) void look_verify_kernel(PcyLookArgs a, const bf16_t* __restrict__ logits, int V, const PickPartial* __restrict__ part) {
+// EOS stop (stop.finished != nullptr; pcy.h): the commit ends with the first committed token that equals eos_id -- the rows behind it are
+// treated as rejected drafts -- and raises *done; a launch that finds *done set commits nothing (last[1] = 0).
+__global__ __launch_bounds__(LOOK_NT) void look_verify_kernel(PcyLookArgs a, const bf16_t* __restrict__ logits, int V, const PickPartial* __restrict__ part,
+                                                              PcyStop stop) {
   __shared__ int tok[LOOK_WMAX];
   __shared__ float lsm[LOOK_WMAX];
   const int l = threadIdx.x & 63;
@@ -104,6 +107,12 @@ __global__ __launch_bounds__(LOOK_NT) void look_verify_kernel(PcyLookArgs a, con
   while (acc < a.W - 1 && a.window[acc + 1] == tok[acc]) ++acc;
   int n = a.max_steps - step;
   n = n < 0 ? 0 : (n > acc + 1 ? acc + 1 : n);
+  bool eos = false;
+  if (stop.finished) {
+    if (*stop.done) n = 0;
+    for (int i = 0; i < n && !eos; ++i)
+      if (tok[i] == stop.eos_id) { n = i + 1; eos = true; }
+  }
   float lp = a.logprob[0];
   for (int i = 0; i < n; ++i) {
     a.tokens_out[step + i] = tok[i];
@@ -121,6 +130,11 @@ __global__ __launch_bounds__(LOOK_NT) void look_verify_kernel(PcyLookArgs a, con
   a.counters[0] += 1;
   a.counters[1] += n;
   a.counters[2 + n - 1] += 1;
+  if (eos) {
+    stop.finished[0] = 1;
+    if (stop.n_steps_run) *stop.n_steps_run = step + n;
+    *stop.done = 1;
+  }
 }
 
 // rows [0, last[1]) of the pass's logits -> rows last[2].. of the record (one prompt: row stride ld); `all` may be pinned host memory.
@@ -153,9 +167,10 @@ void pcy_launch_look_draft(hipStream_t s, const PcyLookArgs& a, const bf16_t* em
   hipLaunchKernelGGL(look_draft_kernel, dim3(a.W), dim3(LOOK_NT), 0, s, a, embed, V, d, embeds_out);
 }
 
-void pcy_launch_look_verify(hipStream_t s, const PcyLookArgs& a, const bf16_t* logits, int V, bf16_t* logits_all, int logits_all_ld, void* partials) {
+void pcy_launch_look_verify(hipStream_t s, const PcyLookArgs& a, const bf16_t* logits, int V, bf16_t* logits_all, int logits_all_ld, void* partials,
+                            const PcyStop& stop) {
   pcy_launch_pick_stage1(s, logits, a.W, V, partials);
-  hipLaunchKernelGGL(look_verify_kernel, dim3(1), dim3(LOOK_NT), 0, s, a, logits, V, reinterpret_cast<const PickPartial*>(partials));
+  hipLaunchKernelGGL(look_verify_kernel, dim3(1), dim3(LOOK_NT), 0, s, a, logits, V, reinterpret_cast<const PickPartial*>(partials), stop);
   if (logits_all)
     hipLaunchKernelGGL(look_store_kernel, dim3(a.W >= 8 ? 256 : 64), dim3(LOOK_NT), 0, s, logits, logits_all, a.last, V, logits_all_ld > 0 ? logits_all_ld : V);
 }

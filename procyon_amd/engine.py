@@ -647,8 +647,90 @@ def disabled_switches():
     return frozenset(n.strip() for n in os.environ.get("PCY_DISABLE", "").split(",") if n.strip())
 
 
-class GenState:
-    def __init__(self, B, vocab, max_steps, device, keep_logits=False, keep=None, pos=None, next_tok=None):   # pos, next_tok: see BeamState.gen_state
+STOP_CHUNK = 8      # decode steps enqueued between two looks at `done` (generate_beam's number)
+
+
+class EosStop:
+    """The EOS stop of a generation state (the trailing fields of pcy_gen_state), shared by GenState and
+    engine_f32.GenStateF32.  eos_id=None: no stop -- nothing is allocated and the four fields of the C struct stay zero.  Otherwise
+    `finished` [B], `done` and `n_steps_run` (device int32 scalars), all zero-initialised, and a pinned host row that takes one copy of
+    `done` per chunk of steps."""
+
+    def _init_stop(self, B, eos_id, device, max_steps):
+        self.eos_id = None if eos_id is None else int(eos_id)
+        self.finished = self.done = self.n_steps_run = self._done_host = None
+        self._n_looks = 0
+        if eos_id is not None:
+            self.finished = torch.zeros(B, dtype=torch.int32, device=device)
+            self.done = torch.zeros(1, dtype=torch.int32, device=device)
+            self.n_steps_run = torch.zeros(1, dtype=torch.int32, device=device)
+            self._done_host = torch.zeros(max_steps // STOP_CHUNK + 3, dtype=torch.int32, pin_memory=True)
+
+    def _stop_args(self):
+        if self.eos_id is None:
+            return (None, None, None, 0)
+        return (self.finished.data_ptr(), self.done.data_ptr(), self.n_steps_run.data_ptr(), self.eos_id)
+
+    @property
+    def steps_run(self):
+        """rows of tokens_out / of the logits record that a pick has written (reads *step back: synchronises).  Without a stop, or when no
+        launch raised `done`: every step that was enqueued.  With a stop: the step of the last row's EOS + 1, exactly -- the picks behind
+        `done` change nothing, *step included."""
+        return int(self.step)
+
+    def look_at_done(self):
+        """an asynchronous copy of `done` to the host behind what the stream holds now -> a callable that waits for THAT copy only (not for
+        what is enqueued after it) and returns the flag"""
+        slot = self._done_host[self._n_looks % self._done_host.numel():][:1]
+        self._n_looks += 1
+        slot.copy_(self.done, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+
+        def flag():
+            ev.synchronize()
+            return bool(int(slot))
+        return flag
+
+
+def steps_until_done(st, total, enqueue, first_look=None):
+    """`total` decode steps of a state with an EOS stop, enqueued by `enqueue(n)` in chunks of STOP_CHUNK, until a look at `done` says that
+    every row has emitted its EOS.  The look at the chunk before is read while the latest chunk runs: one chunk at most is in flight ahead
+    of the read, and the stream never drains.  Worst case: the flag raised by the first step of a chunk is read after the next chunk was
+    enqueued -- 2 * STOP_CHUNK - 1 = 15 decode steps behind the finishing one, each followed by a pick that changes nothing.  first_look: the
+    look behind whatever the caller ran in front (the pick on the prefill's logits).  Returns the steps enqueued."""
+    pending, i = first_look, 0
+    while i < total:
+        n = min(STOP_CHUNK, total - i)
+        enqueue(n)
+        i += n
+        look = st.look_at_done()
+        if pending is not None and pending():
+            break
+        pending = look
+    return i
+
+
+def finish_stop(st, la):
+    """What a driver with an EOS stop hands out, behind a synchronisation: (tokens [B, max_steps] int64 with eos_id in every slot behind a
+    row's EOS -- the steps never run included --, the logits record cut to [B, steps_run, V])"""
+    n = st.steps_run
+    tok = st.tokens_out.long()
+    tok[:, n:] = st.eos_id
+    return tok, (None if la is None else la[:, :n])
+
+
+def check_stop_arg(stop_on_eos, vocab, what):
+    """What a driver's `stop_on_eos=None | eos_id` means: None, or the id as an int inside the vocabulary (ValueError otherwise)"""
+    if stop_on_eos is None:
+        return None
+    if isinstance(stop_on_eos, bool) or not isinstance(stop_on_eos, int) or not 0 <= stop_on_eos < vocab:
+        raise ValueError(f"{what}: stop_on_eos={stop_on_eos!r}: None or a token id in [0, {vocab})")
+    return stop_on_eos
+
+
+class GenState(EosStop):
+    def __init__(self, B, vocab, max_steps, device, keep_logits=False, keep=None, pos=None, next_tok=None, eos_id=None):   # pos, next_tok: see BeamState.gen_state
         self.pos = torch.zeros(1, dtype=torch.int32, device=device) if pos is None else pos
         self.step = torch.zeros(1, dtype=torch.int32, device=device)
         self.next_tok = torch.zeros(B, dtype=torch.int32, device=device) if next_tok is None else next_tok
@@ -667,10 +749,11 @@ class GenState:
             else:
                 self.logits_all = torch.empty(max_steps, B, vocab, dtype=BF16, device=device)
         self.keep = keep
+        self._init_stop(B, eos_id, device, max_steps)
         self.c = L.GenState(self.pos.data_ptr(), self.step.data_ptr(), self.next_tok.data_ptr(), self.tokens_out.data_ptr(),
                             self.logprob.data_ptr(), self.logits.data_ptr(),
                             0 if self.logits_all is None else self.logits_all.data_ptr(),
-                            0 if keep is None else keep.data_ptr(), max_steps, ld)
+                            0 if keep is None else keep.data_ptr(), max_steps, ld, *self._stop_args())
 
 
 class BeamState:
@@ -1148,38 +1231,51 @@ class LlamaEngine:
         L.check(self.ctx.lib.pcy_llama_sample(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B, n_steps, float(temperature),
                                               -1.0 if nucleus_prob is None else float(nucleus_prob), _p(uniforms)), "pcy_llama_sample")
 
-    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, keep=None):
+    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, keep=None, eos_id=None):
         """How greedy and sampling open: a cache of T + max_len slots, the state, the prompts prefilled, their last-row logits in st.logits, pos = T."""
         B, T, _ = embeds.shape
         cache = self.new_cache(B, T + max_len)
-        st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, keep)
+        st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, keep, eos_id=eos_id)
         logits, _ = self.prefill(embeds, attn_mask, cache, "last")
         st.logits.copy_(logits)
         st.pos.fill_(T)
         return cache, st
 
     def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, decode_gemm=False,
-                          decode_w8=False):
+                          decode_w8=False, stop_on_eos=None):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) entirely on the device: prefill, then per step the
         decode launches + the sampling kernels (pcy_llama_sample); the uniform variates of all steps are drawn up front from
         torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state).
         decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + sample_pick per step.
-        decode_w8 (False | True): the steps on the e4m3 weight stream, one decode_w8 + sample_pick per step."""
+        decode_w8 (False | True): the steps on the e4m3 weight stream, one decode_w8 + sample_pick per step.
+        stop_on_eos (None | eos_id): as in `generate_greedy` -- the sampling pick raises `done`, the variates keep their positions
+        uniforms[step * B + b], so a row's draws are those of the call without a stop."""
         B = embeds.shape[0]
         w8 = self._use_decode_w8(decode_w8, B, decode_gemm)
         gemm = self._use_decode_gemm(decode_gemm, B)
+        eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_sampling")
         u = torch.rand(max_len * B, device=self.device, dtype=torch.float32) if uniforms is None else uniforms.to(self.device, torch.float32).contiguous()
-        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, eos_id=eos)
         self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
         if gemm or w8:
             step = self.decode_w8 if w8 else self.decode_gemm
-            for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
-                step(cache, st, B)
-                self.sample_pick(cache, st, B, True, u, temperature, nucleus_prob)
+
+            def eager(n):      # no host synchronisation inside: the step reads the token and the position from the device
+                for _ in range(n):
+                    step(cache, st, B)
+                    self.sample_pick(cache, st, B, True, u, temperature, nucleus_prob)
+            run = eager
+        else:
+            run = lambda n: self.sample_steps(cache, st, B, n, u, temperature, nucleus_prob)
+        if max_len > 1 and eos is None:
+            run(max_len - 1)
         elif max_len > 1:
-            self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob)
+            steps_until_done(st, max_len - 1, run, st.look_at_done())
         self.ctx.sync()       # the record may live in host memory; and a watchdog of the fused decode launches must fail THIS call
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        if eos is not None:
+            tok, la = finish_stop(st, la)
+            return tok, st.logprob, la, (st, cache, u)
         return st.tokens_out.long(), st.logprob, la, (st, cache, u)
 
     def kv_reorder(self, cache, src_rows, t, t0=0):
@@ -1188,33 +1284,48 @@ class LlamaEngine:
         L.check(self.ctx.lib.pcy_kv_reorder_range(self.ctx.h, C.byref(self.desc), C.byref(cache.c), _p(src), src.numel(), int(t0), t), "pcy_kv_reorder")
 
     def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, clean_decode_mask=False, use_graph=True, decode_gemm=False,
-                        decode_w8=False):
+                        decode_w8=False, stop_on_eos=None):
         """`_generate_sampling(greedy=True)` (model_unified.py:861-921): prefill, then max_len-1 cached decode
-        steps with no mask and position = cache length (Q1/Q2); no EOS stop.  Everything stays on the device;
-        returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,max_len,V] bf16 | None, state).
+        steps with no mask and position = cache length (Q1/Q2); by default no EOS stop: all max_len steps run.  Everything stays on the
+        device; returns (tokens [B,max_len] int64, logprob [B] fp32, logits [B,steps_run,V] bf16 | None, state), steps_run == max_len
+        without a stop.
         decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + pick per step.
-        decode_w8 (False | True): the steps on the e4m3 weight stream (`use_graph` as for the default step)."""
+        decode_w8 (False | True): the steps on the e4m3 weight stream (`use_graph` as for the default step).
+        stop_on_eos (None | eos_id): the pick marks a row that emits eos_id as finished, freezes its logprob, and raises
+        `done` on the device once every row has; the steps are enqueued in chunks of STOP_CHUNK with one look at `done` per chunk
+        (`steps_until_done`: at most 2 * STOP_CHUNK - 1 decode steps are enqueued behind the finishing one, and their picks change nothing).
+        A row's tokens up to its EOS, its logprob and its record rows up to that step are bit-equal to the call without a stop (behind its
+        EOS a row of a batch that goes on is fed the EOS: other logits); every slot behind a row's EOS holds eos_id; the state (first of the tuple) exposes `steps_run` <= max_len, the rows of the record."""
         B, T, _ = embeds.shape
         w8 = self._use_decode_w8(decode_w8, B, decode_gemm)
         gemm = self._use_decode_gemm(decode_gemm, B)
+        eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_greedy")
         keep = None
         if clean_decode_mask and attn_mask is not None:
             keep = torch.ones(B, T + max_len, dtype=torch.uint8, device=self.device)
             keep[:, :T] = (attn_mask != 0).to(self.device, torch.uint8)
-        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, keep)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, keep, eos_id=eos)
         self.pick(cache, st, B, advance_pos=False)
         if gemm:
-            for _ in range(max_len - 1):      # no host synchronisation inside: the step reads the token and the position from the device
-                self.decode_gemm(cache, st, B)
-                self.pick(cache, st, B, advance_pos=True)
-        elif max_len > 1 and w8:
-            self.greedy_steps_w8(cache, st, B, max_len - 1, use_graph)
+            def run(n):      # no host synchronisation inside: the step reads the token and the position from the device
+                for _ in range(n):
+                    self.decode_gemm(cache, st, B)
+                    self.pick(cache, st, B, advance_pos=True)
+        elif w8:
+            run = lambda n: self.greedy_steps_w8(cache, st, B, n, use_graph)
+        else:
+            run = lambda n: self.greedy_steps(cache, st, B, n, use_graph)
+        if max_len > 1 and eos is None:
+            run(max_len - 1)
         elif max_len > 1:
-            self.greedy_steps(cache, st, B, max_len - 1, use_graph)
+            steps_until_done(st, max_len - 1, run, st.look_at_done())
         # complete before anything is handed out: the logits record may live in host memory, and a watchdog that fired inside a
         # fused decode launch (workgroups not all resident) must fail THIS call, not a later one (pcy_ctx_sync reads the sticky word)
         self.ctx.sync()
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        if eos is not None:
+            tok, la = finish_stop(st, la)
+            return tok, st.logprob, la, (st, cache)
         return st.tokens_out.long(), st.logprob, la, (st, cache)
 
     def decode_window(self, cache: KVCache, st: GenState, embeds, logits):
@@ -1236,11 +1347,11 @@ class LlamaEngine:
         _chk_bf16(logits)
         L.check(self.ctx.lib.pcy_look_verify(self.ctx.h, C.byref(self.desc), C.byref(look.c), C.byref(st.c), _p(logits)), "pcy_look_verify")
 
-    def generate_lookahead(self, embeds, input_ids, max_len, window, ngram=(3, 1), forced=None, keep_logits=False, step="extend"):
+    def generate_lookahead(self, embeds, input_ids, max_len, window, ngram=(3, 1), forced=None, keep_logits=False, step="extend", stop_on_eos=None):
         """Greedy generation of ONE prompt with `window - 1` drafted tokens checked per pass over the weights: prefill, token 0
         from its logits as in `generate_greedy`, then passes of draft (prompt lookup over `input_ids` + the text so far, pcy_look_draft) ->
-        `extend` of exactly `window` rows at the cache length -> verify + commit (pcy_look_verify) until max_len tokens are committed; no EOS
-        stop.  embeds [1,T,d] bf16 of an unpadded prompt; input_ids [T] its token ids, negative where a slot holds no text token (soft
+        `extend` of exactly `window` rows at the cache length -> verify + commit (pcy_look_verify) until max_len tokens are committed; by
+        default no EOS stop.  embeds [1,T,d] bf16 of an unpadded prompt; input_ids [T] its token ids, negative where a slot holds no text token (soft
         tokens: never matched, never drafted); ngram = (longest, shortest) n-gram looked up; forced: optional [max_len] ints, forced[i] >= 0
         replaces the draft of output token i (tests, measurements).  Returns what `generate_greedy` returns: (tokens [1,max_len] int64,
         logprob [1] fp32, logits [1,max_len,V] bf16 | None, (state, cache, look state)).
@@ -1248,7 +1359,11 @@ class LlamaEngine:
         are NOT promised bit-equal to `generate_greedy` (a window-row pass and a one-row decode step are different arithmetic).
         step: what a pass runs on -- "extend" (the default: `extend`, the prefill's launch-per-stage loop) or "window" (`decode_window`, the
         batched decode loop with the window attention; the position is then read on the device).  The two are different
-        arithmetic: each is independent of the drafts, they are not promised bit-equal to each other."""
+        arithmetic: each is independent of the drafts, they are not promised bit-equal to each other.
+        stop_on_eos (None | eos_id): the commit of a pass ends with the first committed token that is eos_id (on the device:
+        tokens, logprob and record are those of the call without a stop up to and including the EOS), and the loop, which reads a few bytes
+        back per pass anyway, ends with that pass: no pass runs behind the EOS.  Tokens behind the EOS are eos_id, the record is cut to
+        [1, steps_run, V], the state exposes `steps_run`."""
         if step not in ("extend", "window"):
             raise ValueError(f"generate_lookahead: step={step!r}: 'extend' or 'window'")
         if embeds.dim() != 3 or embeds.shape[0] != 1:
@@ -1275,10 +1390,11 @@ class LlamaEngine:
             if fz.numel() != max_len or int(fz.max()) >= self.cfg.vocab:
                 raise ValueError(f"generate_lookahead: forced holds {fz.numel()} entries for max_len {max_len}, largest {int(fz.max())} (vocab {self.cfg.vocab})")
         dev, V, d = self.device, self.cfg.vocab, self.cfg.d
+        eos = check_stop_arg(stop_on_eos, V, "generate_lookahead")
         # a pass ALWAYS has W rows, also when fewer tokens remain (the projections' tile / K-split choices depend on the row count): the last
         # pass may write up to W - 1 slots beyond the last committed token, hence the spare slots
         cache = self.new_cache(1, T + max_len + W - 1)
-        st = GenState(1, V, max_len, dev, keep_logits)
+        st = GenState(1, V, max_len, dev, keep_logits, eos_id=eos)
         logits0, _ = self.prefill(embeds, None, cache, "last")
         st.logits.copy_(logits0)
         st.pos.fill_(T)
@@ -1292,7 +1408,8 @@ class LlamaEngine:
         logits = torch.empty(W, V, dtype=BF16, device=dev)
         on_window = step == "window"      # (`step` counts the committed tokens from here on)
         pos, step = T, 1
-        while step < max_len:
+        ended = eos is not None and max_len > 1 and bool(int(st.done))      # (token 0 may be the EOS)
+        while step < max_len and not ended:
             self.look_draft(look, st, emb)
             # rows of rejected drafts left K / V in slots [pos, pos + W - 1 - accepted) of the previous pass's range: this pass starts at pos,
             # has W rows and so rewrites every one of them before any of its queries reads it (a query at slot p reads [0, p] only)
@@ -1303,12 +1420,18 @@ class LlamaEngine:
             self.look_verify(look, st, logits)
             # the one host read of a pass: `extend` takes t_past from the host, and either step needs `step` to know when to stop
             # 
-            _, n, step0, pos0 = look.last.tolist()
+            if eos is None:
+                _, n, step0, pos0 = look.last.tolist()
+            else:
+                _, n, step0, pos0, ended = torch.cat([look.last, st.done]).tolist()
             if n < 1:
                 raise L.PcyError(f"generate_lookahead: a pass committed nothing at step {step0}")
             pos, step = pos0 + n, step0 + n
         self.ctx.sync()       # the record may live in host memory (as in generate_greedy)
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        if eos is not None:
+            tok, la = finish_stop(st, la)
+            return tok, st.logprob, la, (st, cache, look)
         return st.tokens_out.long(), st.logprob, la, (st, cache, look)
 
     def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new, decode_gemm=False,

@@ -30,7 +30,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import BeamState, Context, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, score_plan, uniform_keep
+from .engine import (BeamState, Context, EosStop, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, check_stop_arg, finish_stop,
+                     score_plan, steps_until_done, uniform_keep)
 
 F32 = torch.float32
 
@@ -332,12 +333,13 @@ class KVCacheF32:
             c[:, moved, :t] = c[:, idx[moved], :t]       # (advanced indexing on the right gathers into a temporary first: sources are read before any write)
 
 
-class GenStateF32:
+class GenStateF32(EosStop):
     """device state of the fp32 stream step (a pcy_gen_state whose logits hold fp32): pos / step int32 scalars, next_tok [B], tokens_out
     [B, max_steps], logprob [B], logits [B, V], optionally the record logits_all [max_steps, B, V].  pos / next_tok: arrays to share
-    instead of new ones (a beam search: the step reads what the beam step writes, as engine.BeamState.gen_state does for bf16)"""
+    instead of new ones (a beam search: the step reads what the beam step writes, as engine.BeamState.gen_state does for bf16).  eos_id: the
+    EOS stop of the greedy and sampling picks (engine.EosStop; None: no stop, nothing allocated)"""
 
-    def __init__(self, B, vocab, max_steps, device, keep_logits=False, pos=None, next_tok=None):
+    def __init__(self, B, vocab, max_steps, device, keep_logits=False, pos=None, next_tok=None, eos_id=None):
         i32 = dict(dtype=torch.int32, device=device)
         self.B, self.vocab, self.max_steps = B, vocab, max_steps
         self.pos, self.step = torch.zeros(1, **i32) if pos is None else pos, torch.zeros(1, **i32)
@@ -346,8 +348,9 @@ class GenStateF32:
         self.logprob = torch.zeros(B, dtype=F32, device=device)
         self.logits = torch.zeros(B, vocab, dtype=F32, device=device)
         self.logits_all = torch.zeros(max_steps, B, vocab, dtype=F32, device=device) if keep_logits else None
+        self._init_stop(B, eos_id, device, max_steps)
         self.c = L.GenState(_p(self.pos), _p(self.step), _p(self.next_tok), _p(self.tokens_out), _p(self.logprob), _p(self.logits), _p(self.logits_all),
-                            None, max_steps, 0)
+                            None, max_steps, 0, *self._stop_args())
 
     def set(self, pos=None, step=None, next_tok=None):
         """device-side writes only (a fill / a copy on the stream: nothing is read back)"""
@@ -432,8 +435,8 @@ class LlamaEngineF32:
                                          self.sin.data_ptr(), arr)
         return self._sdesc
 
-    def new_gen_state(self, B, max_steps, keep_logits=False):
-        return GenStateF32(B, self.cfg.vocab, max_steps, self.device, keep_logits)
+    def new_gen_state(self, B, max_steps, keep_logits=False, eos_id=None):
+        return GenStateF32(B, self.cfg.vocab, max_steps, self.device, keep_logits, eos_id=eos_id)
 
     @staticmethod
     def _stream_cache(cache):
@@ -554,27 +557,70 @@ class LlamaEngineF32:
         self.ops.ctx.sync()
         return tokens, scores, out_logits
 
-    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, graph=True):
+    def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, graph=True, stop_on_eos=None):
+        """`_generate_sampling(greedy=True)` (model_unified.py:861-921) of an fp32 model entirely on the device: the prefill, one pick on its
+        logits, then max_len - 1 x (step + pick) without a host synchronisation (`greedy_steps`).  Returns what `LlamaEngine.generate_greedy`
+        returns: (tokens [B, max_len] int64, logprob [B], logits [B, steps_run, V] fp32 | None, (state, cache)).
+        stop_on_eos (None | eos_id): as in `LlamaEngine.generate_greedy` -- chunks of engine.STOP_CHUNK steps, one look at
+        `done` per chunk, at most 2 * STOP_CHUNK - 1 decode steps behind the finishing one; steps_run == max_len without a stop."""
+        B, T, _ = embeds.shape
+        Tmax = self._generation_capacity(T, max_len, max_len)
+        eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_greedy")
+        cache = self.new_cache(B, Tmax)
+        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits, eos_id=eos)
+        logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
+        st.logits.copy_(logits)
+        st.set(pos=T, step=0)
+        return self.greedy_from_logits(cache, st, B, max_len, graph=graph) + ((st, cache),)
+
+    def greedy_from_logits(self, cache: KVCacheF32, st: GenStateF32, B, max_len, graph=True):
+        """the greedy loop behind a prefill -- st.logits holds its last-row logits, *st.pos the prompt length, *st.step 0: the pick on them,
+        max_len - 1 x (step + pick), all at once or, with the state's EOS stop, in chunks (engine.steps_until_done), a synchronisation ->
+        (tokens [B, max_len] int64, logprob [B], logits [B, steps_run, V] | None).  The one driver of `generate_greedy` and of the model's
+        decode_f32="stream" / "device" greedy path."""
+        self.greedy_pick(cache, st, B, advance_pos=False)
+        run = lambda n: self.greedy_steps(cache, st, B, n, graph=graph)
+        if max_len > 1 and st.eos_id is None:
+            run(max_len - 1)
+        elif max_len > 1:
+            steps_until_done(st, max_len - 1, run, st.look_at_done())
+        self.ops.ctx.sync()
+        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        if st.eos_id is not None:
+            tok, la = finish_stop(st, la)
+            return tok, st.logprob, la
+        return st.tokens_out.long(), st.logprob, la
+
+    def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, graph=True,
+                          stop_on_eos=None):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) of an fp32 model entirely on the device: the prefill, one pick on its
         logits, then max_len - 1 x (step + pick) without a host synchronisation (`sample_steps`).  The uniform variates of all steps come
         from ONE `torch.rand` on the device generator unless `uniforms` [max_len * B] injects them.  Returns what
         `LlamaEngine.generate_sampling` returns: (tokens [B, max_len] int64, logprob [B], logits [B, max_len, V] fp32 | None, (state, cache,
-        variates)).  ValueError before any decode step when max_len tokens do not fit the cache."""
+        variates)).  ValueError before any decode step when max_len tokens do not fit the cache.
+        stop_on_eos (None | eos_id): as in `generate_greedy`; the variates keep their positions uniforms[step * B + b]."""
         B, T, _ = embeds.shape
         Tmax = self._generation_capacity(T, max_len, max_len)
+        eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_sampling")
         u = torch.rand(max_len * B, device=self.device, dtype=F32) if uniforms is None else uniforms.to(self.device, F32).contiguous()
         if u.numel() < max_len * B:
             raise ValueError(f"generate_sampling: {u.numel()} uniform variates for {max_len} steps x {B} rows")
         cache = self.new_cache(B, Tmax)
-        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits)
+        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits, eos_id=eos)
         logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
         st.logits.copy_(logits)
         st.set(pos=T, step=0)
         self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
-        if max_len > 1:
-            self.sample_steps(cache, st, B, max_len - 1, u, temperature, nucleus_prob, graph=graph)
+        run = lambda n: self.sample_steps(cache, st, B, n, u, temperature, nucleus_prob, graph=graph)
+        if max_len > 1 and eos is None:
+            run(max_len - 1)
+        elif max_len > 1:
+            steps_until_done(st, max_len - 1, run, st.look_at_done())
         self.ops.ctx.sync()
         la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+        if eos is not None:
+            tok, la = finish_stop(st, la)
+            return tok, st.logprob, la, (st, cache, u)
         return st.tokens_out.long(), st.logprob, la, (st, cache, u)
 
     def _rows(self, spec, B, T):

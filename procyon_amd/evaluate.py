@@ -18,7 +18,9 @@ once whatever the row count -- a DataLoader batch of 16 prompts x beam 10 is 160
 prompt against one pass over the K / V they share; DESIGN.md 4.3d -- or "split": the split-key attention in every beam-search step, with or
 without "decode_gemm"), "decode_f32" (caption plugin; "ops", "stream" or "device", default "ops": `generate`'s option of the same name --
 "stream" runs the cached steps of an fp32 model on the device-resident fp32 step; "device" the beam / sampling selection on
-the device as well; a ValueError on a bf16 model)."""
+the device as well; a ValueError on a bf16 model), "stop_on_eos" (caption plugin; False or True, default False: with a greedy or
+sampling "generation_method", `generate`'s option of the same name -- the generation ends on the device where the last text ends, DESIGN.md
+4.11; with "beam", which has its own EOS stop, nothing is passed on)."""
 from collections import defaultdict
 from collections.abc import Mapping
 
@@ -164,6 +166,9 @@ class ProcyonCaptionEval:
         self.decode_gemm = model_config.get("decode_gemm", False)
         self.shared_attn = model_config.get("shared_attn", False)
         self.decode_f32 = model_config.get("decode_f32", "ops")
+        self.stop_on_eos = model_config.get("stop_on_eos", False)
+        if not (self.stop_on_eos is False or self.stop_on_eos is True):
+            raise ValueError(f"model_config['stop_on_eos']={self.stop_on_eos!r}: False or True")
 
     @torch.no_grad()
     def get_predictions(self, data_loader):
@@ -176,7 +181,8 @@ class ProcyonCaptionEval:
                                                     beam_group_size=self.beam_group_size, truncate_on_eos=True,
                                                     **({"decode_gemm": self.decode_gemm} if self.decode_gemm else {}),
                                                     **({"shared_attn": self.shared_attn} if self.shared_attn else {}),
-                                                    **({"decode_f32": self.decode_f32} if self.decode_f32 != "ops" else {}))
+                                                    **({"decode_f32": self.decode_f32} if self.decode_f32 != "ops" else {}),
+                                                    **({"stop_on_eos": True} if self.stop_on_eos and self.method != "beam" else {}))
             for i, indices in enumerate(model_inputs["reference_indices"]["input"]["seq"]):
                 for j in range(self.num_captions):
                     aaseq_indices.append(indices[-1])

@@ -926,11 +926,13 @@ class UnifiedProCyon:
 
     @torch.no_grad()
     def _generate_sampling(self, input_embeds, attn_masks, max_len=64, num_text_per_instance=1, temperature=1.0,
-                           greedy=False, nucleus_prob=None, decode_gemm=False, decode_w8=False):
+                           greedy=False, nucleus_prob=None, decode_gemm=False, decode_w8=False, stop_on_eos=None, steps_out=None):
         """`_generate_sampling` (model_unified.py:861-921).  Greedy runs entirely on the device (hipGraph-replayed
         decode steps, fused argmax + log-prob), and so does sampling: `pcy_llama_sample` forms the reference's pre-sampling
         probability vector (`_sampling_probs` below is its torch restatement) and draws by inverse CDF with uniform variates
-        taken from torch's device generator."""
+        taken from torch's device generator.
+        stop_on_eos (None | eos_id): the engines' EOS stop; steps_out: a list that takes `steps_run` of every text.  Records
+        of several texts per instance are padded with zeros to the longest."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
         eng = self.text_encoder.engine
         B = len(input_embeds)
@@ -938,13 +940,19 @@ class UnifiedProCyon:
         for _ in range(num_text_per_instance):
             # the whole loop on the device: decode launches + the pick (greedy: argmax; sampling: softmax, nucleus mask by histogram, inverse-CDF
             # draw with uniform variates from torch's device generator); the logits record goes to the host as it is produced
-            w8 = {"decode_w8": True} if decode_w8 else {}
-            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm, **w8) if greedy else \
+            opts = {"decode_w8": True} if decode_w8 else {}
+            if stop_on_eos is not None:
+                opts["stop_on_eos"] = stop_on_eos
+            tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm, **opts) if greedy else \
                 eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True,
-                                      decode_gemm=decode_gemm, **w8)
+                                      decode_gemm=decode_gemm, **opts)
             out_list.append(tok.cpu())
             lp_list.append(lp.cpu().clone())
             logit_list.append(lg.cpu())
+            if steps_out is not None:
+                steps_out.append(lg.shape[1])
+        if stop_on_eos is not None:
+            logit_list = self._pad_records(logit_list)
         # one text per instance (every caller in the reference): a view instead of a host-to-host copy of the [B, max_len, V] record
         # (4.2 GB at batch 32 x 512 tokens)
         logits_out = logit_list[0].unsqueeze(1) if len(logit_list) == 1 else torch.stack(logit_list, dim=1)
@@ -969,6 +977,12 @@ class UnifiedProCyon:
                                         **({"shared_attn": shared_attn} if shared_attn else {}))
         return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
 
+    @staticmethod
+    def _pad_records(recs):
+        """logits records [B, steps_i, V] of several texts per instance, padded with zeros to the longest (they differ only under an EOS stop)"""
+        n = max(r.shape[1] for r in recs)
+        return [r if r.shape[1] == n else torch.nn.functional.pad(r, (0, 0, 0, n - r.shape[1])) for r in recs]
+
     @contextmanager
     def _room_for(self, max_len):
         """the text encoder's caches hold at least max_len generated tokens inside the block (max_new_tokens raised, then put back)"""
@@ -985,13 +999,17 @@ class UnifiedProCyon:
     # on the device-resident step of DESIGN.md 4.10 (greedy: the whole loop on the device)
     @torch.no_grad()
     def _generate_sampling_f32(self, input_embeds, attn_masks, max_len=64, num_text_per_instance=1, temperature=1.0, greedy=False,
-                               nucleus_prob=None, decode_f32="ops"):
+                               nucleus_prob=None, decode_f32="ops", stop_on_eos=None, steps_out=None):
         """`_generate_sampling` (model_unified.py:861-921) in fp32: prefill, then max_len - 1 cached steps; greedy argmax, or multinomial
         on softmax(logits / temperature) / the un-renormalised nucleus-masked softmax; chosen log-probabilities summed; no EOS stop.
         decode_f32="stream": the cached steps on the device-resident step -- greedy entirely on the device
         (`LlamaEngineF32.greedy_steps`), sampling with this loop's host-side selection around the replayed graph.
-        decode_f32="device": greedy as "stream"; sampling entirely on the device too (`LlamaEngineF32.generate_sampling`)."""
+        decode_f32="device": greedy as "stream"; sampling entirely on the device too (`LlamaEngineF32.generate_sampling`).
+        stop_on_eos (None | eos_id): the device-resident loops take the engines' EOS stop; the host-driven loop ("ops", and
+        the sampling of "stream") checks the tokens it reads anyway -- a finished row emits eos_id and keeps its sum, the loop ends with the
+        step in which the last row finishes.  steps_out: a list that takes `steps_run` of every text."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
+        stop = {} if stop_on_eos is None else {"stop_on_eos": stop_on_eos}
         enc = self.text_encoder
         B = len(input_embeds)
         stream = decode_f32 in ("stream", "device")
@@ -1002,23 +1020,23 @@ class UnifiedProCyon:
                 total = torch.zeros(B, device=self.device)
                 if decode_f32 == "device" and not greedy:
                     tok, lp, lg, _ = enc.engine_f32.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature,
-                                                                      nucleus_prob=nucleus_prob, keep_logits=True)
+                                                                      nucleus_prob=nucleus_prob, keep_logits=True, **stop)
                     outs.append(tok.cpu()); lps.append(lp.cpu()); lgs.append(lg.cpu())
                     continue
                 if stream and greedy:
                     eng = enc.engine_f32
                     o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1))
                     past = o.past_key_values
-                    st = eng.new_gen_state(B, max_len, keep_logits=True)
+                    st = eng.new_gen_state(B, max_len, keep_logits=True, **({} if stop_on_eos is None else {"eos_id": stop_on_eos}))
                     st.logits.copy_(o.logits[:, -1, :])
                     st.set(pos=past.t, step=0)
-                    eng.greedy_pick(past.cache, st, B, advance_pos=False)       # the prefill's logits: token 0, the position stays
-                    if max_len > 1:
-                        if past.t + max_len - 1 > past.cache.Tmax:
-                            raise ValueError(f"KV cache capacity {past.cache.Tmax} exhausted; raise max_new_tokens")
-                        eng.greedy_steps(past.cache, st, B, max_len - 1, graph=True)
-                    outs.append(st.tokens_out.long().cpu()); lps.append(st.logprob.cpu()); lgs.append(st.logits_all.transpose(0, 1).cpu())
+                    if max_len > 1 and past.t + max_len - 1 > past.cache.Tmax:
+                        raise ValueError(f"KV cache capacity {past.cache.Tmax} exhausted; raise max_new_tokens")
+                    # the prefill's logits: token 0, the position stays; then the steps (LlamaEngineF32.greedy_from_logits)
+                    tok, lp, lg = eng.greedy_from_logits(past.cache, st, B, max_len, graph=True)
+                    outs.append(tok.cpu()); lps.append(lp.cpu()); lgs.append(lg.cpu())
                     continue
+                fin = None if stop_on_eos is None else torch.zeros(B, dtype=torch.bool, device=self.device)
                 for i in range(max_len):
                     o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1)) \
                         if i == 0 else enc(input_ids=toks[:, -1:], use_cache=True, past_key_values=past)
@@ -1029,9 +1047,21 @@ class UnifiedProCyon:
                     rec.append(logits.cpu())
                     lsm = logits.log_softmax(-1)
                     nxt = logits.argmax(-1, keepdim=True) if greedy else torch.multinomial(self._sampling_probs(logits, temperature, nucleus_prob), 1)
-                    total += lsm.gather(1, nxt)[:, 0]
+                    if stop_on_eos is None:
+                        total += lsm.gather(1, nxt)[:, 0]
+                    else:      # a finished row emits the EOS and keeps its sum; the row that emits it now still adds its log-probability
+                        nxt = torch.where(fin[:, None], torch.full_like(nxt, stop_on_eos), nxt)
+                        total = torch.where(fin, total, total + lsm.gather(1, nxt)[:, 0])
+                        fin = fin | (nxt[:, 0] == stop_on_eos)
                     toks = nxt if toks is None else torch.cat([toks, nxt], -1)
+                    if stop_on_eos is not None and bool(fin.all()):      # (the loop reads the tokens on the host anyway)
+                        toks = torch.nn.functional.pad(toks, (0, max_len - toks.shape[1]), value=stop_on_eos)
+                        break
                 outs.append(toks.cpu()); lps.append(total.cpu()); lgs.append(torch.stack(rec, 1))
+            if steps_out is not None:
+                steps_out.extend(lg.shape[1] for lg in lgs)
+            if stop_on_eos is not None:
+                lgs = self._pad_records(lgs)
         return torch.stack(outs, 1), torch.stack(lps).T, torch.stack(lgs, 1)
 
     @torch.no_grad()
@@ -1094,7 +1124,7 @@ class UnifiedProCyon:
                  num_text_per_instance=1, return_all_internals=False, beam_size=5, beam_group_size=5,
                  diversity_penalty=0.8, exclude_protein_structure=False, nucleus_prob=0.9, truncate_on_eos=True,
                  lookahead=0, lookahead_ngram=(3, 1), decode_gemm=False, shared_attn=False, decode_w8=False, lookahead_step="extend",
-                 decode_f32="ops"):
+                 decode_f32="ops", stop_on_eos=False):
         """`generate` (model_unified.py:924-1027).  The non-beam call site of the reference mis-binds its positional
         arguments (:998-1005, quirk Q8); the evident intent -- the same names bound by keyword -- is implemented, which
         means `nucleus_prob` (default 0.9) reaches `_generate_sampling` for every non-beam method, as written there;
@@ -1136,7 +1166,19 @@ class UnifiedProCyon:
         chain per step), sampling / temperature / nucleus `LlamaEngineF32.generate_sampling` (pcy_f32_sample_pick; the draw is the inverse
         CDF on uniform variates from torch's device generator, not torch.multinomial's stream), greedy exactly the "stream" path.  Same
         return values and shapes; beam_size <= 32.  ValueError for any other value, for "stream" / "device" on a bf16 model and for
-        beam_size > 32 with "device": never a fallback."""
+        beam_size > 32 with "device": never a fallback.
+        stop_on_eos=True (not in the reference; False, the default, is today's code: every method runs max_len steps and truncate_on_eos cuts
+        the text on the host): the greedy and sampling methods end where the text ends -- the picks mark a row that emits
+        the tokenizer's EOS as finished and raise a flag on the device once every row has, the host enqueues the steps in chunks of 8 and
+        stops at the flag (at most 15 decode steps behind the finishing one; lookahead: none; the host-driven fp32 loops: none).  On every
+        decode path: bf16 and fp32 ("ops", "stream", "device"), lookahead, decode_gemm, decode_w8.  A row's tokens up to its EOS and its
+        log-probability are those of stop_on_eos=False bit for bit, every slot behind an EOS holds the EOS, the logits record is cut to
+        [B, texts, steps_run, V], `text` under truncate_on_eos is the same, and return_all_internals gains "steps_run" (a list, one entry
+        per text of an instance).  ValueError with method="beam" (beam search has its own stop) and for anything but False / True."""
+        if not (stop_on_eos is False or stop_on_eos is True):
+            raise ValueError(f"generate: stop_on_eos={stop_on_eos!r}: False or True")
+        if stop_on_eos and method == "beam":
+            raise ValueError("generate: stop_on_eos ends greedy and sampling generation; method='beam' has its own EOS stop")
         if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream", "device")):
             raise ValueError(f"generate: decode_f32={decode_f32!r}: 'ops', 'stream' or 'device'")
         if decode_f32 != "ops" and not self._f32:
@@ -1197,6 +1239,8 @@ class UnifiedProCyon:
         gt_text = [inputs["data"]["text"][i] for i in inputs["target"]["text"]] if inputs["target"]["text"] is not None else None
         batch_size = input_embeds.shape[0]
         look_stats = None
+        steps_run = []
+        stop = {"stop_on_eos": int(self.tokenizer.eos_token_id)} if stop_on_eos else {}
         if lookahead:
             if method == "beam" or not greedy:
                 raise ValueError("generate(lookahead=W) verifies drafts against the argmax: it needs a greedy method (method='greedy' or greedy=True)")
@@ -1207,7 +1251,9 @@ class UnifiedProCyon:
             for i in (self.prot_replacement_idx, self.struct_idx, self.drug_idx):
                 hist_ids[hist_ids == i] = -1
             tok, lp, lg, (_, _, look) = self.text_encoder.engine.generate_lookahead(input_embeds, hist_ids, max_len, lookahead, ngram=lookahead_ngram,
-                                                                                    keep_logits=True, **({} if lookahead_step == "extend" else {"step": lookahead_step}))
+                                                                                    keep_logits=True, **({} if lookahead_step == "extend" else {"step": lookahead_step}),
+                                                                                    **stop)
+            steps_run.append(lg.shape[1])
             tokens, log_probs, logits = tok.cpu().unsqueeze(1), lp.cpu().clone().unsqueeze(0).T, lg.cpu().unsqueeze(1)
             # ("step" is named only where it was chosen: the default call returns the dictionary it always returned)
             look_stats = look.stats() if lookahead_step == "extend" else dict(look.stats(), step=lookahead_step)
@@ -1220,7 +1266,8 @@ class UnifiedProCyon:
             tokens, log_probs, logits = (self._generate_sampling_f32 if self._f32 else self._generate_sampling)(
                 input_embeds, attn_masks, max_len=max_len, num_text_per_instance=num_text_per_instance,
                 temperature=temperature, greedy=greedy, nucleus_prob=nucleus_prob, **({"decode_gemm": decode_gemm} if decode_gemm else {}),
-                **({"decode_w8": True} if decode_w8 else {}), **({"decode_f32": decode_f32} if decode_f32 != "ops" else {}))
+                **({"decode_w8": True} if decode_w8 else {}), **({"decode_f32": decode_f32} if decode_f32 != "ops" else {}),
+                **(dict(stop, steps_out=steps_run) if stop else {}))
         flattened = torch.flatten(tokens, start_dim=0, end_dim=1)
         text = self.tokenizer.batch_decode(flattened)
         if truncate_on_eos:
@@ -1233,5 +1280,7 @@ class UnifiedProCyon:
                    "seq_references": [inputs["reference_indices"]["input"]["seq"][j][-1] for j, _ in enumerate(inputs["input"]["seq"])]}
             if look_stats is not None:
                 out["lookahead"] = look_stats
+            if stop_on_eos:
+                out["steps_run"] = steps_run
             return out
         return tokens, log_probs, logits, text

@@ -66,7 +66,7 @@ def _merge_dedup(inputs: List[dict]) -> dict:
 def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_dataset: str = "uniprot", prompt_relation: str = "all",
                  max_len: int = 200, beam_size: int = 10, diversity_penalty: float = 0.8, save_path: Optional[str] = None,
                  batch_size: int = 8, save_frequency: int = 5, device=None, decode_gemm=False,
-                 shared_attn=False, decode_f32="ops") -> pd.DataFrame:
+                 shared_attn=False, decode_f32="ops", stop_on_eos=False) -> pd.DataFrame:
     """-> DataFrame(uniprot_id, response0 .. response{beam_size // 2 - 1}); `save_path` receives the running table as a pickle
     whenever the one-by-one loop would have written it (after protein i for every i % save_frequency == 0, i > 0) and the final
     table as CSV (caption_bulk.py:99-148).  decode_gemm (False | True | "auto"): `generate`'s option of the same name -- batch_size x beam_size
@@ -75,11 +75,17 @@ def caption_bulk(model, model_args, data_args, uniprot_ids: List[str], prompt_da
     "split": the split-key attention in every step, with or without decode_gemm (4.3f).  decode_f32 ("ops" | "stream" | "device"): `generate`'s option of
     the same name; "stream" keeps the model in fp32 AS LOADED (no cast here) and runs every cached step of the beam search on the
     device-resident fp32 step (4.10), "device" the whole search on the device as well (4.10a: one prefill per protein, the beam step and the
-    K / V reorder as kernels) -- a model that was cast to bf16 before is `generate`'s ValueError."""
+    K / V reorder as kernels) -- a model that was cast to bf16 before is `generate`'s ValueError.  stop_on_eos (False | True): end every
+    generation where its text ends.  The captions here come from method="beam", whose search already ends on the device once
+    every beam holds an EOS, so `generate`'s option of the same name (greedy and sampling methods only: a ValueError with beam search) has
+    nothing to add and is not passed on: the table is the one without the option.  Anything but False / True is a ValueError."""
     from procyon.data.inference_utils import create_caption_input_simple, uniprot_id_to_index
     assert "drug" not in prompt_dataset, "DrugBank not supported in this script"
     if not (isinstance(decode_f32, str) and decode_f32 in ("ops", "stream", "device")):
         raise ValueError(f"caption_bulk: decode_f32={decode_f32!r}: 'ops', 'stream' or 'device'")
+    if not (stop_on_eos is False or stop_on_eos is True):
+        raise ValueError(f"caption_bulk: stop_on_eos={stop_on_eos!r}: False or True")
+    # (validated above and NOT passed on: every generation below is a beam search, which generate() refuses together with the option)
     model.eval()
     if decode_f32 == "ops":
         model.bfloat16()

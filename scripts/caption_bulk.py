@@ -42,7 +42,8 @@ def main(args):
     start, end = chunk_rows(table.shape[0], args.num_chunks, args.chunk_idx, "caption_bulk")
     df = caption_bulk(model, model_args, data_args, table["uniprot_id"].iloc[start:end].tolist(), args.prompt_dataset, args.prompt_relation,
                       args.max_len, args.beam_size, args.diversity_penalty, args.save_path, args.batch_size, device=device,
-                      **({"decode_f32": "device"} if args.fp32_device else {"decode_f32": "stream"} if args.fp32_stream else {}))
+                      **({"decode_f32": "device"} if args.fp32_device else {"decode_f32": "stream"} if args.fp32_stream else {}),
+                      **({"stop_on_eos": True} if args.stop_on_eos else {}))
     print(df)
 
 
@@ -63,5 +64,7 @@ if __name__ == "__main__":
                                                               "(generate(decode_f32='stream'), DESIGN.md 4.10)")
     p.add_argument("--fp32_device", action="store_true", help="keep fp32 and run the beam search entirely on the device: the fp32 step and the "
                                                               "selection (generate(decode_f32='device'), DESIGN.md 4.10a)")
+    p.add_argument("--stop_on_eos", action="store_true", help="end every generation where its text ends (caption_bulk(stop_on_eos=True), "
+                                                              "DESIGN.md 4.11; the beam search of this script already does)")
     p.add_argument("--batch_size", default=8, type=int, help="proteins per engine call (the reference script: 1)")
     main(p.parse_args())
