@@ -647,7 +647,7 @@ def disabled_switches():
     return frozenset(n.strip() for n in os.environ.get("PCY_DISABLE", "").split(",") if n.strip())
 
 
-STOP_CHUNK = 8      # decode steps enqueued between two looks at `done` (generate_beam's number)
+STOP_CHUNK = 8      # decode steps enqueued between two looks at `done`: steps_until_done's and beam_steps_until_done's number
 
 
 class EosStop:
@@ -718,6 +718,75 @@ def finish_stop(st, la):
     tok = st.tokens_out.long()
     tok[:, n:] = st.eos_id
     return tok, (None if la is None else la[:, :n])
+
+
+def hand_out(st):
+    """What a greedy, sampling or lookahead driver returns from a state that is ALREADY synchronised: (tokens [B, max_steps] int64,
+    logprob [B], the logits record [B, steps_run, V] | None) -- with an EOS stop `finish_stop`'s tokens and record, without one every slot."""
+    la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
+    tok, la = (st.tokens_out.long(), la) if st.eos_id is None else finish_stop(st, la)
+    return tok, st.logprob, la
+
+
+def run_generation(st, max_len, first_pick, enqueue, sync):
+    """The loop behind a prefill of every greedy and sampling driver: `first_pick()` on the prefill's logits; the max_len - 1 steps, by
+    `enqueue(n)` = n x (decode step + pick) without a host synchronisation, at once or under the state's EOS stop in chunks; `sync()` (the
+    record may live in host memory, and a watchdog that fired inside a fused launch must fail THIS call); then `hand_out`."""
+    first_pick()
+    if max_len > 1 and st.eos_id is None:
+        enqueue(max_len - 1)
+    elif max_len > 1:
+        steps_until_done(st, max_len - 1, enqueue, st.look_at_done())
+    sync()
+    return hand_out(st)
+
+
+def sampling_variates(uniforms, max_len, B, device):
+    """The variates uniforms[step * B + b] of a sampling call, float32 and contiguous on `device`: ONE `torch.rand` of max_len * B, or the
+    caller's `uniforms` -- more are accepted, fewer are a ValueError (the picks would read beyond the allocation)."""
+    n = int(max_len) * int(B)
+    if uniforms is None:
+        return torch.rand(n, device=device, dtype=torch.float32)
+    if uniforms.numel() < n:
+        raise ValueError(f"generate_sampling: {uniforms.numel()} uniform variates for {max_len} steps x {B} rows: {n} are needed")
+    return uniforms.to(device, torch.float32).contiguous()
+
+
+def beam_parent_index(anc):
+    """anc [steps, BB]: the parent slot of every slot at every step -> idx [steps, BB] int64, the slot that held at step s what slot r holds
+    after the last step (the record of step s is re-indexed by the parents of every step >= s).  Pure."""
+    steps, BB = anc.shape
+    anc = anc.long()
+    slot = torch.arange(BB, device=anc.device)
+    idx = torch.empty(steps, BB, dtype=torch.long, device=anc.device)
+    for s in range(steps - 1, -1, -1):
+        slot = anc[s][slot]
+        idx[s] = slot
+    return idx
+
+
+def beam_hand_out(bs, rec, max_len, sync):
+    """What a device-side beam search returns from its state and its per-slot record rec [max_len, BB, V]: (tokens [BB, max_len] int64, zeros
+    behind an early EOS stop, and scores [BB] on the host, logits [BB, steps, V] along the parent chain: gathered on the device, then ONE copy
+    into pinned host memory -- a pageable destination moves a beam-10 record at a few GB/s, ~1 ms per generated token).  sync() comes last."""
+    out, steps = bs.tokens()                                   # synchronises
+    idx = beam_parent_index(bs.anc[:steps])
+    BB, V = rec.shape[1:]
+    rec_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
+    out_logits = torch.empty(rec_dev.shape, dtype=rec.dtype, pin_memory=True)
+    out_logits.copy_(rec_dev, non_blocking=True)
+    tokens, scores = torch.nn.functional.pad(out.cpu(), (0, max_len - steps)), bs.cur.cpu()
+    sync()
+    return tokens, scores, out_logits
+
+
+def beam_steps_until_done(bs, max_len, advance):
+    """Steps 1 .. max_len - 1 of a beam search: `advance(i, n_max)` enqueues 1..n_max steps from step i and returns how many; n_max never
+    crosses the next multiple of STOP_CHUNK or max_len, and `bs.done` is read (a synchronisation) only where i is such a multiple."""
+    i = 1
+    while i < max_len and not (i % STOP_CHUNK == 0 and int(bs.done)):
+        i += advance(i, min(STOP_CHUNK - i % STOP_CHUNK, max_len - i))
+    return i
 
 
 def check_stop_arg(stop_on_eos, vocab, what):
@@ -1231,10 +1300,11 @@ class LlamaEngine:
         L.check(self.ctx.lib.pcy_llama_sample(self.ctx.h, C.byref(self.desc), C.byref(cache.c), C.byref(st.c), B, n_steps, float(temperature),
                                               -1.0 if nucleus_prob is None else float(nucleus_prob), _p(uniforms)), "pcy_llama_sample")
 
-    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, keep=None, eos_id=None):
-        """How greedy and sampling open: a cache of T + max_len slots, the state, the prompts prefilled, their last-row logits in st.logits, pos = T."""
+    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, keep=None, eos_id=None, spare_slots=0):
+        """How greedy, sampling and lookahead open: a cache of T + max_len (+ spare_slots) slots, the state, the prompts prefilled, their
+        last-row logits in st.logits, pos = T."""
         B, T, _ = embeds.shape
-        cache = self.new_cache(B, T + max_len)
+        cache = self.new_cache(B, T + max_len + spare_slots)
         st = GenState(B, self.cfg.vocab, max_len, self.device, keep_logits, keep, eos_id=eos_id)
         logits, _ = self.prefill(embeds, attn_mask, cache, "last")
         st.logits.copy_(logits)
@@ -1245,7 +1315,8 @@ class LlamaEngine:
                           decode_w8=False, stop_on_eos=None):
         """`_generate_sampling(greedy=False)` (model_unified.py:861-921) entirely on the device: prefill, then per step the
         decode launches + the sampling kernels (pcy_llama_sample); the uniform variates of all steps are drawn up front from
-        torch's device generator (one `torch.rand`).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state).
+        torch's device generator (one `torch.rand`) unless `uniforms` [>= max_len * B] injects them (`sampling_variates`: fewer are a ValueError
+        before the prefill).  Returns (tokens [B,max_len] int64, logprob [B], logits | None, state).
         decode_gemm (False | True | "auto"): the steps on the one-pass GEMM step, one decode_gemm + sample_pick per step.
         decode_w8 (False | True): the steps on the e4m3 weight stream, one decode_w8 + sample_pick per step.
         stop_on_eos (None | eos_id): as in `generate_greedy` -- the sampling pick raises `done`, the variates keep their positions
@@ -1254,29 +1325,19 @@ class LlamaEngine:
         w8 = self._use_decode_w8(decode_w8, B, decode_gemm)
         gemm = self._use_decode_gemm(decode_gemm, B)
         eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_sampling")
-        u = torch.rand(max_len * B, device=self.device, dtype=torch.float32) if uniforms is None else uniforms.to(self.device, torch.float32).contiguous()
+        u = sampling_variates(uniforms, max_len, B, self.device)
         cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, eos_id=eos)
-        self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
         if gemm or w8:
             step = self.decode_w8 if w8 else self.decode_gemm
 
-            def eager(n):      # no host synchronisation inside: the step reads the token and the position from the device
+            def run(n):      # no host synchronisation inside: the step reads the token and the position from the device
                 for _ in range(n):
                     step(cache, st, B)
                     self.sample_pick(cache, st, B, True, u, temperature, nucleus_prob)
-            run = eager
         else:
             run = lambda n: self.sample_steps(cache, st, B, n, u, temperature, nucleus_prob)
-        if max_len > 1 and eos is None:
-            run(max_len - 1)
-        elif max_len > 1:
-            steps_until_done(st, max_len - 1, run, st.look_at_done())
-        self.ctx.sync()       # the record may live in host memory; and a watchdog of the fused decode launches must fail THIS call
-        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
-        if eos is not None:
-            tok, la = finish_stop(st, la)
-            return tok, st.logprob, la, (st, cache, u)
-        return st.tokens_out.long(), st.logprob, la, (st, cache, u)
+        first = lambda: self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
+        return run_generation(st, max_len, first, run, self.ctx.sync) + ((st, cache, u),)
 
     def kv_reorder(self, cache, src_rows, t, t0=0):
         """cache[:, b] = cache[:, src_rows[b]] over slots [t0, t) (t0 > 0: the rows are known to hold the same contents below t0)"""
@@ -1293,7 +1354,7 @@ class LlamaEngine:
         decode_w8 (False | True): the steps on the e4m3 weight stream (`use_graph` as for the default step).
         stop_on_eos (None | eos_id): the pick marks a row that emits eos_id as finished, freezes its logprob, and raises
         `done` on the device once every row has; the steps are enqueued in chunks of STOP_CHUNK with one look at `done` per chunk
-        (`steps_until_done`: at most 2 * STOP_CHUNK - 1 decode steps are enqueued behind the finishing one, and their picks change nothing).
+        (`run_generation` on `steps_until_done`: at most 2 * STOP_CHUNK - 1 decode steps are enqueued behind the finishing one, and their picks change nothing).
         A row's tokens up to its EOS, its logprob and its record rows up to that step are bit-equal to the call without a stop (behind its
         EOS a row of a batch that goes on is fed the EOS: other logits); every slot behind a row's EOS holds eos_id; the state (first of the tuple) exposes `steps_run` <= max_len, the rows of the record."""
         B, T, _ = embeds.shape
@@ -1305,7 +1366,6 @@ class LlamaEngine:
             keep = torch.ones(B, T + max_len, dtype=torch.uint8, device=self.device)
             keep[:, :T] = (attn_mask != 0).to(self.device, torch.uint8)
         cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, keep, eos_id=eos)
-        self.pick(cache, st, B, advance_pos=False)
         if gemm:
             def run(n):      # no host synchronisation inside: the step reads the token and the position from the device
                 for _ in range(n):
@@ -1315,18 +1375,8 @@ class LlamaEngine:
             run = lambda n: self.greedy_steps_w8(cache, st, B, n, use_graph)
         else:
             run = lambda n: self.greedy_steps(cache, st, B, n, use_graph)
-        if max_len > 1 and eos is None:
-            run(max_len - 1)
-        elif max_len > 1:
-            steps_until_done(st, max_len - 1, run, st.look_at_done())
-        # complete before anything is handed out: the logits record may live in host memory, and a watchdog that fired inside a
-        # fused decode launch (workgroups not all resident) must fail THIS call, not a later one (pcy_ctx_sync reads the sticky word)
-        self.ctx.sync()
-        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
-        if eos is not None:
-            tok, la = finish_stop(st, la)
-            return tok, st.logprob, la, (st, cache)
-        return st.tokens_out.long(), st.logprob, la, (st, cache)
+        # (the runner's sync is pcy_ctx_sync: it reads the sticky watchdog word of the fused launches, workgroups not all resident)
+        return run_generation(st, max_len, lambda: self.pick(cache, st, B, advance_pos=False), run, self.ctx.sync) + ((st, cache),)
 
     def decode_window(self, cache: KVCache, st: GenState, embeds, logits):
         """one lookahead pass on the batched decode loop (pcy_llama_decode_window): embeds [W, d] (or [1, W, d]) bf16 -> logits
@@ -1393,11 +1443,7 @@ class LlamaEngine:
         eos = check_stop_arg(stop_on_eos, V, "generate_lookahead")
         # a pass ALWAYS has W rows, also when fewer tokens remain (the projections' tile / K-split choices depend on the row count): the last
         # pass may write up to W - 1 slots beyond the last committed token, hence the spare slots
-        cache = self.new_cache(1, T + max_len + W - 1)
-        st = GenState(1, V, max_len, dev, keep_logits, eos_id=eos)
-        logits0, _ = self.prefill(embeds, None, cache, "last")
-        st.logits.copy_(logits0)
-        st.pos.fill_(T)
+        cache, st = self._prefill_for_generation(embeds, None, max_len, keep_logits, eos_id=eos, spare_slots=W - 1)
         self.pick(cache, st, 1, advance_pos=False)
         look = LookState(ids, max_len, W, (g_hi, g_lo), dev, fz)
         look.hist[T:T + 1] = st.next_tok
@@ -1428,11 +1474,7 @@ class LlamaEngine:
                 raise L.PcyError(f"generate_lookahead: a pass committed nothing at step {step0}")
             pos, step = pos0 + n, step0 + n
         self.ctx.sync()       # the record may live in host memory (as in generate_greedy)
-        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
-        if eos is not None:
-            tok, la = finish_stop(st, la)
-            return tok, st.logprob, la, (st, cache, look)
-        return st.tokens_out.long(), st.logprob, la, (st, cache, look)
+        return hand_out(st) + ((st, cache, look),)
 
     def generate_beam(self, embeds, attn_mask, max_len, beam_size, group_size, diversity_penalty, eos_id, max_new, decode_gemm=False,
                       shared_attn=False):
@@ -1491,40 +1533,25 @@ class LlamaEngine:
         rec[0].copy_(logits)
         self.beam_step(logits, bs, group_size, diversity_penalty)
         self.kv_reorder(cache, bs.src, T, t0=kv_t0)
-        i = 1
-        while i < max_len and not ((i & 7) == 0 and int(bs.done)):
+        def advance(i, n_max):
             if T + i > cache.capacity:
                 raise ValueError(f"KV cache capacity {cache.capacity} exhausted; raise max_new_tokens")
-            if gemm or "beam_graph" in off:
-                n = 1
-                if gemm:
-                    self.decode_gemm(cache, st, BB, **({"shared_attn": shared_attn} if shared_attn else {}))
-                elif split:
-                    self.decode_split(cache, st, BB)
-                else:
-                    self.decode_graph(cache, st, BB)
-                rec[i].copy_(st.logits)
-                self.beam_step(st.logits, bs, group_size, diversity_penalty)
-                self.kv_reorder(cache, bs.src, T + i, t0=kv_t0)
-            else:
-                n = min(8 - (i & 7), max_len - i, cache.capacity - T - i + 1)
+            if not (gemm or "beam_graph" in off):
+                n = min(n_max, cache.capacity - T - i + 1)
                 self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=kv_t0, **({"split": True} if split else {}))
-            i += n
-        out, steps = bs.tokens()                                   # synchronises
-        anc = bs.anc[:steps].long()
-        slot = torch.arange(BB, device=dev)
-        idx = torch.empty(steps, BB, dtype=torch.long, device=dev)
-        for s_ in range(steps - 1, -1, -1):                        # the record of step s is re-indexed by the parents of steps >= s
-            slot = anc[s_][slot]
-            idx[s_] = slot
-        # [BB, steps, V] on the device, then ONE copy into pinned host memory (a pageable destination moves the 2.5 MB per step
-        # and beam-10 record at a few GB/s: ~1 ms per generated token)
-        out_logits_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
-        out_logits = torch.empty(out_logits_dev.shape, dtype=out_logits_dev.dtype, pin_memory=True)
-        out_logits.copy_(out_logits_dev, non_blocking=True)
-        tokens, scores = torch.nn.functional.pad(out.cpu(), (0, max_len - steps)), bs.cur.cpu()      # (zeros behind an early EOS stop)
-        self.ctx.sync()      # stream complete + the sticky watchdog word of the fused launches checked (raises PcyError)
-        return tokens, scores, out_logits
+                return n
+            if gemm:
+                self.decode_gemm(cache, st, BB, **({"shared_attn": shared_attn} if shared_attn else {}))
+            elif split:
+                self.decode_split(cache, st, BB)
+            else:
+                self.decode_graph(cache, st, BB)
+            rec[i].copy_(st.logits)
+            self.beam_step(st.logits, bs, group_size, diversity_penalty)
+            self.kv_reorder(cache, bs.src, T + i, t0=kv_t0)
+            return 1
+        beam_steps_until_done(bs, max_len, advance)
+        return beam_hand_out(bs, rec, max_len, self.ctx.sync)      # (the sync raises PcyError for a watchdog of the fused launches)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -30,8 +30,8 @@ import ctypes as C
 import torch
 
 from . import _lib as L
-from .engine import (BeamState, Context, EosStop, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, check_stop_arg, finish_stop,
-                     score_plan, steps_until_done, uniform_keep)
+from .engine import (BeamState, Context, EosStop, EsmConfig, EsmEngine, LlamaConfig, _h2d_many, batched_split_long_seq, beam_hand_out,
+                     beam_steps_until_done, check_stop_arg, run_generation, sampling_variates, score_plan, uniform_keep)
 
 F32 = torch.float32
 
@@ -538,24 +538,23 @@ class LlamaEngineF32:
         rec = torch.empty(max_len, BB, V, dtype=F32, device=dev)
         rec[0].copy_(logits)
         self.beam_step(logits, bs, group_size, diversity_penalty)      # (no reorder: every beam of a prompt still holds its prompt rows only)
-        i = 1
-        while i < max_len and not ((i & 7) == 0 and int(bs.done)):
-            n = min(8 - (i & 7), max_len - i)
+
+        def advance(i, n):
             self.beam_steps(cache, st, bs, group_size, diversity_penalty, rec, n, kv_t0=T)
-            i += n
-        out, steps = bs.tokens()                                       # synchronises
-        anc = bs.anc[:steps].long()
-        slot = torch.arange(BB, device=dev)
-        idx = torch.empty(steps, BB, dtype=torch.long, device=dev)
-        for s_ in range(steps - 1, -1, -1):                            # the record of step s is re-indexed by the parents of steps >= s
-            slot = anc[s_][slot]
-            idx[s_] = slot
-        out_logits_dev = rec[:steps].gather(1, idx[:, :, None].expand(steps, BB, V)).transpose(0, 1).contiguous()
-        out_logits = torch.empty(out_logits_dev.shape, dtype=F32, pin_memory=True)
-        out_logits.copy_(out_logits_dev, non_blocking=True)
-        tokens, scores = torch.nn.functional.pad(out.cpu(), (0, max_len - steps)), bs.cur.cpu()      # (zeros behind an early EOS stop)
-        self.ops.ctx.sync()
-        return tokens, scores, out_logits
+            return n
+        beam_steps_until_done(bs, max_len, advance)
+        return beam_hand_out(bs, rec, max_len, self.ops.ctx.sync)
+
+    def _prefill_for_generation(self, embeds, attn_mask, max_len, keep_logits, eos_id=None):
+        """How greedy and sampling open (as LlamaEngine._prefill_for_generation): the capacity check, a cache, the state, the prompts
+        prefilled, their last-row logits in st.logits, pos = T, step = 0."""
+        B, T, _ = embeds.shape
+        cache = self.new_cache(B, self._generation_capacity(T, max_len, max_len))
+        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits, eos_id=eos_id)
+        logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
+        st.logits.copy_(logits)
+        st.set(pos=T, step=0)
+        return cache, st
 
     def generate_greedy(self, embeds, attn_mask, max_len, keep_logits=False, graph=True, stop_on_eos=None):
         """`_generate_sampling(greedy=True)` (model_unified.py:861-921) of an fp32 model entirely on the device: the prefill, one pick on its
@@ -563,33 +562,17 @@ class LlamaEngineF32:
         returns: (tokens [B, max_len] int64, logprob [B], logits [B, steps_run, V] fp32 | None, (state, cache)).
         stop_on_eos (None | eos_id): as in `LlamaEngine.generate_greedy` -- chunks of engine.STOP_CHUNK steps, one look at
         `done` per chunk, at most 2 * STOP_CHUNK - 1 decode steps behind the finishing one; steps_run == max_len without a stop."""
-        B, T, _ = embeds.shape
-        Tmax = self._generation_capacity(T, max_len, max_len)
         eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_greedy")
-        cache = self.new_cache(B, Tmax)
-        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits, eos_id=eos)
-        logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
-        st.logits.copy_(logits)
-        st.set(pos=T, step=0)
-        return self.greedy_from_logits(cache, st, B, max_len, graph=graph) + ((st, cache),)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, eos)
+        return self.greedy_from_logits(cache, st, embeds.shape[0], max_len, graph=graph) + ((st, cache),)
 
     def greedy_from_logits(self, cache: KVCacheF32, st: GenStateF32, B, max_len, graph=True):
         """the greedy loop behind a prefill -- st.logits holds its last-row logits, *st.pos the prompt length, *st.step 0: the pick on them,
-        max_len - 1 x (step + pick), all at once or, with the state's EOS stop, in chunks (engine.steps_until_done), a synchronisation ->
+        max_len - 1 x (step + pick), all at once or, with the state's EOS stop, in chunks, a synchronisation (engine.run_generation) ->
         (tokens [B, max_len] int64, logprob [B], logits [B, steps_run, V] | None).  The one driver of `generate_greedy` and of the model's
         decode_f32="stream" / "device" greedy path."""
-        self.greedy_pick(cache, st, B, advance_pos=False)
-        run = lambda n: self.greedy_steps(cache, st, B, n, graph=graph)
-        if max_len > 1 and st.eos_id is None:
-            run(max_len - 1)
-        elif max_len > 1:
-            steps_until_done(st, max_len - 1, run, st.look_at_done())
-        self.ops.ctx.sync()
-        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
-        if st.eos_id is not None:
-            tok, la = finish_stop(st, la)
-            return tok, st.logprob, la
-        return st.tokens_out.long(), st.logprob, la
+        return run_generation(st, max_len, lambda: self.greedy_pick(cache, st, B, advance_pos=False),
+                              lambda n: self.greedy_steps(cache, st, B, n, graph=graph), self.ops.ctx.sync)
 
     def generate_sampling(self, embeds, attn_mask, max_len, temperature=1.0, nucleus_prob=None, keep_logits=False, uniforms=None, graph=True,
                           stop_on_eos=None):
@@ -599,29 +582,13 @@ class LlamaEngineF32:
         `LlamaEngine.generate_sampling` returns: (tokens [B, max_len] int64, logprob [B], logits [B, max_len, V] fp32 | None, (state, cache,
         variates)).  ValueError before any decode step when max_len tokens do not fit the cache.
         stop_on_eos (None | eos_id): as in `generate_greedy`; the variates keep their positions uniforms[step * B + b]."""
-        B, T, _ = embeds.shape
-        Tmax = self._generation_capacity(T, max_len, max_len)
+        B = embeds.shape[0]
         eos = check_stop_arg(stop_on_eos, self.cfg.vocab, "generate_sampling")
-        u = torch.rand(max_len * B, device=self.device, dtype=F32) if uniforms is None else uniforms.to(self.device, F32).contiguous()
-        if u.numel() < max_len * B:
-            raise ValueError(f"generate_sampling: {u.numel()} uniform variates for {max_len} steps x {B} rows")
-        cache = self.new_cache(B, Tmax)
-        st = GenStateF32(B, self.cfg.vocab, max_len, self.device, keep_logits, eos_id=eos)
-        logits, _ = self.prefill(embeds, attn_mask, "last", cache=cache)
-        st.logits.copy_(logits)
-        st.set(pos=T, step=0)
-        self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob)
-        run = lambda n: self.sample_steps(cache, st, B, n, u, temperature, nucleus_prob, graph=graph)
-        if max_len > 1 and eos is None:
-            run(max_len - 1)
-        elif max_len > 1:
-            steps_until_done(st, max_len - 1, run, st.look_at_done())
-        self.ops.ctx.sync()
-        la = None if st.logits_all is None else st.logits_all.transpose(0, 1)
-        if eos is not None:
-            tok, la = finish_stop(st, la)
-            return tok, st.logprob, la, (st, cache, u)
-        return st.tokens_out.long(), st.logprob, la, (st, cache, u)
+        u = sampling_variates(uniforms, max_len, B, self.device)
+        cache, st = self._prefill_for_generation(embeds, attn_mask, max_len, keep_logits, eos)
+        return run_generation(st, max_len, lambda: self.sample_pick(cache, st, B, False, u, temperature, nucleus_prob),
+                              lambda n: self.sample_steps(cache, st, B, n, u, temperature, nucleus_prob, graph=graph),
+                              self.ops.ctx.sync) + ((st, cache, u),)
 
     def _rows(self, spec, B, T):
         """flat token rows b*T+t (int64, on the device) of a logit_rows argument: "last", "all", None or a tensor"""

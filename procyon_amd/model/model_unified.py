@@ -935,28 +935,16 @@ class UnifiedProCyon:
         of several texts per instance are padded with zeros to the longest."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
         eng = self.text_encoder.engine
-        B = len(input_embeds)
-        out_list, lp_list, logit_list = [], [], []
+        texts = []
         for _ in range(num_text_per_instance):
             # the whole loop on the device: decode launches + the pick (greedy: argmax; sampling: softmax, nucleus mask by histogram, inverse-CDF
             # draw with uniform variates from torch's device generator); the logits record goes to the host as it is produced
-            opts = {"decode_w8": True} if decode_w8 else {}
-            if stop_on_eos is not None:
-                opts["stop_on_eos"] = stop_on_eos
+            opts = dict({"decode_w8": True} if decode_w8 else {}, **({} if stop_on_eos is None else {"stop_on_eos": stop_on_eos}))
             tok, lp, lg, _ = eng.generate_greedy(input_embeds, attn_masks, max_len, keep_logits=True, decode_gemm=decode_gemm, **opts) if greedy else \
                 eng.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob, keep_logits=True,
                                       decode_gemm=decode_gemm, **opts)
-            out_list.append(tok.cpu())
-            lp_list.append(lp.cpu().clone())
-            logit_list.append(lg.cpu())
-            if steps_out is not None:
-                steps_out.append(lg.shape[1])
-        if stop_on_eos is not None:
-            logit_list = self._pad_records(logit_list)
-        # one text per instance (every caller in the reference): a view instead of a host-to-host copy of the [B, max_len, V] record
-        # (4.2 GB at batch 32 x 512 tokens)
-        logits_out = logit_list[0].unsqueeze(1) if len(logit_list) == 1 else torch.stack(logit_list, dim=1)
-        return torch.stack(out_list, dim=1), torch.stack(lp_list).T, logits_out
+            texts.append((tok.cpu(), lp.cpu().clone(), lg.cpu()))
+        return self._stack_texts(texts, steps_out)
 
     @torch.no_grad()
     def _generate_beam_search(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5,
@@ -978,10 +966,18 @@ class UnifiedProCyon:
         return tuple(x.unflatten(0, (input_embeds.shape[0], beam_size)) for x in flat)
 
     @staticmethod
-    def _pad_records(recs):
-        """logits records [B, steps_i, V] of several texts per instance, padded with zeros to the longest (they differ only under an EOS stop)"""
+    def _stack_texts(texts, steps_out=None):
+        """What `_generate_sampling` and its fp32 twin return from the (tokens [B, max_len], log-prob [B], record [B, steps, V]) of every text of
+        an instance, all on the host: (tokens [B, texts, max_len], log-probs [B, texts], records [B, texts, steps, V], padded with zeros to the
+        longest: they differ only under an EOS stop).  steps_out takes the `steps` of every text."""
+        toks, lps, recs = zip(*texts)
+        if steps_out is not None:
+            steps_out.extend(r.shape[1] for r in recs)
         n = max(r.shape[1] for r in recs)
-        return [r if r.shape[1] == n else torch.nn.functional.pad(r, (0, 0, 0, n - r.shape[1])) for r in recs]
+        recs = [r if r.shape[1] == n else torch.nn.functional.pad(r, (0, 0, 0, n - r.shape[1])) for r in recs]
+        # one text per instance (every caller in the reference): a view instead of a host-to-host copy of the [B, max_len, V] record
+        # (4.2 GB at batch 32 x 512 tokens)
+        return torch.stack(toks, 1), torch.stack(lps).T, recs[0].unsqueeze(1) if len(recs) == 1 else torch.stack(recs, 1)
 
     @contextmanager
     def _room_for(self, max_len):
@@ -1009,60 +1005,58 @@ class UnifiedProCyon:
         the sampling of "stream") checks the tokens it reads anyway -- a finished row emits eos_id and keeps its sum, the loop ends with the
         step in which the last row finishes.  steps_out: a list that takes `steps_run` of every text."""
         assert nucleus_prob is None or (0 < nucleus_prob < 1)
-        stop = {} if stop_on_eos is None else {"stop_on_eos": stop_on_eos}
         enc = self.text_encoder
         B = len(input_embeds)
         stream = decode_f32 in ("stream", "device")
+        prefill = lambda: enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True,
+                              logit_positions=torch.full((B,), input_embeds.shape[1] - 1))
+
+        def device_sampling():
+            tok, lp, lg, _ = enc.engine_f32.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature, nucleus_prob=nucleus_prob,
+                                                              keep_logits=True, **({} if stop_on_eos is None else {"stop_on_eos": stop_on_eos}))
+            return tok.cpu(), lp.cpu(), lg.cpu()
+
+        def device_greedy():      # the prefill through the text encoder: it sizes the cache by max_new_tokens
+            eng = enc.engine_f32
+            o = prefill()
+            past = o.past_key_values
+            st = eng.new_gen_state(B, max_len, keep_logits=True, **({} if stop_on_eos is None else {"eos_id": stop_on_eos}))
+            st.logits.copy_(o.logits[:, -1, :])
+            st.set(pos=past.t, step=0)
+            if max_len > 1 and past.t + max_len - 1 > past.cache.Tmax:
+                raise ValueError(f"KV cache capacity {past.cache.Tmax} exhausted; raise max_new_tokens")
+            # the prefill's logits: token 0, the position stays; then the steps (LlamaEngineF32.greedy_from_logits)
+            tok, lp, lg = eng.greedy_from_logits(past.cache, st, B, max_len, graph=True)
+            return tok.cpu(), lp.cpu(), lg.cpu()
+
+        def host_loop():
+            toks, past, rec = None, None, []
+            total = torch.zeros(B, device=self.device)
+            fin = None if stop_on_eos is None else torch.zeros(B, dtype=torch.bool, device=self.device)
+            for i in range(max_len):
+                o = prefill() if i == 0 else enc(input_ids=toks[:, -1:], use_cache=True, past_key_values=past)
+                past = o.past_key_values
+                if stream and past.state is None:
+                    past.state = enc.engine_f32.new_gen_state(B, max_len)
+                logits = o.logits[:, -1, :]
+                rec.append(logits.cpu())
+                lsm = logits.log_softmax(-1)
+                nxt = logits.argmax(-1, keepdim=True) if greedy else torch.multinomial(self._sampling_probs(logits, temperature, nucleus_prob), 1)
+                if stop_on_eos is None:
+                    total += lsm.gather(1, nxt)[:, 0]
+                else:      # a finished row emits the EOS and keeps its sum; the row that emits it now still adds its log-probability
+                    nxt = torch.where(fin[:, None], torch.full_like(nxt, stop_on_eos), nxt)
+                    total = torch.where(fin, total, total + lsm.gather(1, nxt)[:, 0])
+                    fin = fin | (nxt[:, 0] == stop_on_eos)
+                toks = nxt if toks is None else torch.cat([toks, nxt], -1)
+                if stop_on_eos is not None and bool(fin.all()):      # (the loop reads the tokens on the host anyway)
+                    toks = torch.nn.functional.pad(toks, (0, max_len - toks.shape[1]), value=stop_on_eos)
+                    break
+            return toks.cpu(), total.cpu(), torch.stack(rec, 1)
+
+        one_text = device_sampling if decode_f32 == "device" and not greedy else device_greedy if stream and greedy else host_loop
         with self._room_for(max_len):
-            outs, lps, lgs = [], [], []
-            for _ in range(num_text_per_instance):
-                toks, past, rec = None, None, []
-                total = torch.zeros(B, device=self.device)
-                if decode_f32 == "device" and not greedy:
-                    tok, lp, lg, _ = enc.engine_f32.generate_sampling(input_embeds, attn_masks, max_len, temperature=temperature,
-                                                                      nucleus_prob=nucleus_prob, keep_logits=True, **stop)
-                    outs.append(tok.cpu()); lps.append(lp.cpu()); lgs.append(lg.cpu())
-                    continue
-                if stream and greedy:
-                    eng = enc.engine_f32
-                    o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1))
-                    past = o.past_key_values
-                    st = eng.new_gen_state(B, max_len, keep_logits=True, **({} if stop_on_eos is None else {"eos_id": stop_on_eos}))
-                    st.logits.copy_(o.logits[:, -1, :])
-                    st.set(pos=past.t, step=0)
-                    if max_len > 1 and past.t + max_len - 1 > past.cache.Tmax:
-                        raise ValueError(f"KV cache capacity {past.cache.Tmax} exhausted; raise max_new_tokens")
-                    # the prefill's logits: token 0, the position stays; then the steps (LlamaEngineF32.greedy_from_logits)
-                    tok, lp, lg = eng.greedy_from_logits(past.cache, st, B, max_len, graph=True)
-                    outs.append(tok.cpu()); lps.append(lp.cpu()); lgs.append(lg.cpu())
-                    continue
-                fin = None if stop_on_eos is None else torch.zeros(B, dtype=torch.bool, device=self.device)
-                for i in range(max_len):
-                    o = enc(input_embeds=input_embeds, attn_masks=attn_masks, use_cache=True, logit_positions=torch.full((B,), input_embeds.shape[1] - 1)) \
-                        if i == 0 else enc(input_ids=toks[:, -1:], use_cache=True, past_key_values=past)
-                    past = o.past_key_values
-                    if stream and past.state is None:
-                        past.state = enc.engine_f32.new_gen_state(B, max_len)
-                    logits = o.logits[:, -1, :]
-                    rec.append(logits.cpu())
-                    lsm = logits.log_softmax(-1)
-                    nxt = logits.argmax(-1, keepdim=True) if greedy else torch.multinomial(self._sampling_probs(logits, temperature, nucleus_prob), 1)
-                    if stop_on_eos is None:
-                        total += lsm.gather(1, nxt)[:, 0]
-                    else:      # a finished row emits the EOS and keeps its sum; the row that emits it now still adds its log-probability
-                        nxt = torch.where(fin[:, None], torch.full_like(nxt, stop_on_eos), nxt)
-                        total = torch.where(fin, total, total + lsm.gather(1, nxt)[:, 0])
-                        fin = fin | (nxt[:, 0] == stop_on_eos)
-                    toks = nxt if toks is None else torch.cat([toks, nxt], -1)
-                    if stop_on_eos is not None and bool(fin.all()):      # (the loop reads the tokens on the host anyway)
-                        toks = torch.nn.functional.pad(toks, (0, max_len - toks.shape[1]), value=stop_on_eos)
-                        break
-                outs.append(toks.cpu()); lps.append(total.cpu()); lgs.append(torch.stack(rec, 1))
-            if steps_out is not None:
-                steps_out.extend(lg.shape[1] for lg in lgs)
-            if stop_on_eos is not None:
-                lgs = self._pad_records(lgs)
-        return torch.stack(outs, 1), torch.stack(lps).T, torch.stack(lgs, 1)
+            return self._stack_texts([one_text() for _ in range(num_text_per_instance)], steps_out)
 
     @torch.no_grad()
     def _generate_beam_search_f32(self, input_embeds, attn_mask, max_len=64, beam_size=5, beam_group_size=5, diversity_penalty=0.8, decode_f32="ops"):

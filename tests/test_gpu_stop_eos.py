@@ -443,6 +443,24 @@ def test_bf16_sampling_stops(path, B, shared):
     _check_sampling(eng, path, B, shared, run, replay_state, u)
 
 
+def test_bf16_sampling_refuses_too_few_variates(monkeypatch):
+    """the pick of step s reads uniforms[s * B + b]: fewer than max_len * B variates are refused before the prefill (as the fp32 family
+    refuses them); exactly as many, and more, are the same call"""
+    from procyon_amd.engine import LlamaEngine
+    eng = _engine(False)
+    B, max_len = 2, 4
+    emb, mask = eng.embed_tokens(_prompts(B, False)), torch.ones(B, T_PROMPT)
+    u = torch.rand(12, generator=torch.Generator().manual_seed(5)).cuda()
+    prefills, prefill = [], LlamaEngine.prefill
+    monkeypatch.setattr(LlamaEngine, "prefill", lambda self, *a, **k: (prefills.append(1), prefill(self, *a, **k))[1])
+    with pytest.raises(ValueError, match="7 uniform variates"):
+        eng.generate_sampling(emb, mask, max_len, temperature=0.7, uniforms=u[:7])
+    assert prefills == []
+    tok8 = eng.generate_sampling(emb, mask, max_len, temperature=0.7, uniforms=u[:8])[0]
+    tok12 = eng.generate_sampling(emb, mask, max_len, temperature=0.7, uniforms=u)[0]
+    assert len(prefills) == 2 and tok8.shape == (B, max_len) and torch.equal(tok8, tok12)
+
+
 @pytest.mark.parametrize("step", ["extend", "window"])
 def test_lookahead_stops(step):
     """the commit of the pass that holds the EOS ends with it (tokens, logprob and record of the run without a stop up to there), and no
